@@ -1,18 +1,25 @@
 """Headline benchmark: EfficientDet-D0 640x640 forward+backward (one full train_step) images/sec.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run with one rank per GPU; started WITHOUT it, `--gpus N` spawns the N ranks
   itself through `python -m torch.distributed.run --standalone`-style arguments on 127.0.0.1)
 
 One step = forward (training BatchNorm), focal+Huber loss, backward, L2, clip, [gradient all-reduce
 SUM over RCCL], SGD-momentum + EMA update on a synthetic COCO-shaped batch already resident in HBM
 (BASELINE.json configs[2]; weak scaling: 128 images per GPU).  By default the timed steps REPLAY the step
-captured as a hipGraph (--graph 0 / EDET_GRAPH=0: eager launches).  Rank 0 prints ONE JSON line with
-`roofline` (dominant kernel family, algorithmic bytes per SURVEY.md section 8d, per-launch HIP events on the
-launch stream: inside the timed region in eager mode, over the same K steps repeated eagerly right after it in
-graph mode -- a replayed graph has no host-side launch to bracket; `traffic` from the committed PMC passes
-under profiles/) and, at N = 1, `cpu_baseline` (the fp32 CPU oracle -- a port, not the reference's TensorFlow
-binary, which cannot be installed here -- on a bounded sample of the same workload).
+captured as a hipGraph (--graph 0 / EDET_GRAPH=0: eager launches).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly K steps and prints the line (`value`, `ms_per_step`, `config`).
+--dump-outputs DIR also writes what the last timed step handed its caller (loss values, updated variables) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+--full adds the side measurements, each of which costs runs of its own: one eager, fully profiled step in front of
+the timed region (dominant kernel family, --dump_launches table) and `roofline` (algorithmic bytes per SURVEY.md
+section 8d, per-launch HIP events on the launch stream: inside the timed region in eager mode, over the same K steps
+repeated eagerly right after it in graph mode -- a replayed graph has no host-side launch to bracket; `traffic` from
+the committed PMC passes under profiles/); at N = 1 `cpu_baseline` (the fp32 CPU oracle -- a port, not the
+reference's TensorFlow binary, which cannot be installed here -- on a bounded sample of the same workload) with the
+`parity` block, and `other_configs` (--no_cpu_baseline / --no_other_configs leave those out).
 """
 import argparse
 import json
@@ -92,6 +99,25 @@ def synth_batch(config, batch, size, seed, device, tdtype):
   labels['mean_num_positives'] = torch.full((batch,), 100.0, device=device)
   labels['normalizer'] = 100.0 * batch + 1.0     # host copy of sum(mean_num_positives)+1: no device sync
   return images, labels
+
+
+DUMP_BYTES = 60 * 10**6     # --dump-outputs writes at most this much (plus the .npy headers)
+
+
+def dump_outputs(dirname, eng):
+  """What a caller of the timed train step holds after its last step, as DIR/<name>.npy: the loss values train_step
+  returns (float64 scalars) and the variables the step updated (float32 flat arenas: weights, EMA shadows, momentum,
+  BatchNorm moving statistics).  Past DUMP_BYTES in all, every array is cut to the same seeded sample of its elements
+  (sorted indices of numpy.random.default_rng(0).choice(size, k, replace=False))."""
+  arrays = {k: np.float64(v) for k, v in eng.loss_values().items()}
+  for name, t in (('params', eng.params_flat), ('ema', eng.ema), ('velocity', eng.velocity), ('bn_state', eng.state_flat)):
+    arrays[name] = t.detach().float().cpu().numpy()
+  total = sum(a.nbytes for a in arrays.values())
+  os.makedirs(dirname, exist_ok=True)
+  for name, a in arrays.items():
+    if total > DUMP_BYTES and a.size > 1:
+      a = a[np.sort(np.random.default_rng(0).choice(a.size, a.size * DUMP_BYTES // total, replace=False))]
+    np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def physical_cores():
@@ -376,10 +402,15 @@ def main():
   ap.add_argument('--image_size', type=int, default=640)
   ap.add_argument('--model', default='efficientdet-d0')
   ap.add_argument('--dtype', default='bf16')
-  ap.add_argument('--no_cpu_baseline', action='store_true', help='skip the cpu_baseline and parity legs')
+  ap.add_argument('--full', action='store_true',
+                  help='also the side measurements: profiled step + roofline, cpu_baseline / parity, other_configs')
+  ap.add_argument('--dump-outputs', dest='dump_outputs', default='', metavar='DIR',
+                  help='write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB)')
+  ap.add_argument('--no_cpu_baseline', action='store_true', help='--full without the cpu_baseline and parity legs')
   ap.add_argument('--no_other_configs', action='store_true',
-                  help='skip the V2-S / D7x side measurements (they run at N = 1 on the headline workload only)')
-  ap.add_argument('--dump_launches', default='', help='write the per-(kernel, shape) launch table of one step here')
+                  help='--full without the V2-S / D7x side measurements (they run at N = 1 on the headline workload only)')
+  ap.add_argument('--dump_launches', default='',
+                  help='(--full) write the per-(kernel, shape) launch table of the profiled step here')
   ap.add_argument('--force_dist', action='store_true',
                   help='world size 1 through the data-parallel path all the same: RCCL communicator, the gradient '
                        'all-reduce between the two captured graphs (rehearsal of the multi-GPU launch structure on one GPU)')
@@ -391,6 +422,10 @@ def main():
   ap.add_argument('--graph', type=int, default=int(os.environ.get('EDET_GRAPH', '1')),
                   help='1: the timed steps replay the step captured as a hipGraph; 0: eager launches')
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
+  if args.dump_launches and not args.full:
+    ap.error('--dump_launches comes from the profiled step of --full')
 
   rank = int(os.environ.get('RANK', '0'))
   local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -434,34 +469,35 @@ def main():
     net.train_step((images, lb), sync_loss=False)
 
   # ---- warm-up (graph mode: step 1 eager, step 2 captures, then replays; at least 3 so that the timed
-  # region only replays), then one eager, fully profiled step to find the dominant kernel family
+  # region only replays), then (--full) one eager, fully profiled step to find the dominant kernel family
   for i in range(max(args.warmup, 3) if args.graph else args.warmup):
     step()
   if args.graph:      # from here on the synthetic batch lives in the captured step's own input buffers
     images, labels = net.input_buffers()
   torch.cuda.synchronize()
-  net.use_graph = False
-  _lib.profiler = _lib.Profiler(None)
-  step()
-  torch.cuda.synchronize()
-  net.use_graph = bool(args.graph)
-  full = _lib.profiler.summary()
-  if args.dump_launches and rank == 0:
-    rows = sorted(_lib.profiler.by_shape().items(), key=lambda kv: -kv[1][1])
-    with open(args.dump_launches, 'w') as f:
-      f.write('%-22s %-22s %5s %10s %10s %9s\n' % ('entry point', 'shape', 'calls', 'total_ms', 'MB/call', 'GB/s'))
-      for (name, tag), (n, ms, b) in rows:
-        f.write('%-22s %-22s %5d %10.3f %10.1f %9.1f\n' % (name, tag, n, ms, b / n / 1e6,
-                                                            b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0))
-      f.write('TOTAL kernel ms %.3f\n' % sum(v[1] for v in full.values()))
-  _lib.profiler = None
-  dominant = max(full.items(), key=lambda kv: kv[1][1])[0]
-  kernel_ms_total = sum(v[1] for v in full.values())
+  if args.full:
+    net.use_graph = False
+    _lib.profiler = _lib.Profiler(None)
+    step()
+    torch.cuda.synchronize()
+    net.use_graph = bool(args.graph)
+    full = _lib.profiler.summary()
+    if args.dump_launches and rank == 0:
+      rows = sorted(_lib.profiler.by_shape().items(), key=lambda kv: -kv[1][1])
+      with open(args.dump_launches, 'w') as f:
+        f.write('%-22s %-22s %5s %10s %10s %9s\n' % ('entry point', 'shape', 'calls', 'total_ms', 'MB/call', 'GB/s'))
+        for (name, tag), (n, ms, b) in rows:
+          f.write('%-22s %-22s %5d %10.3f %10.1f %9.1f\n' % (name, tag, n, ms, b / n / 1e6,
+                                                              b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0))
+        f.write('TOTAL kernel ms %.3f\n' % sum(v[1] for v in full.values()))
+    _lib.profiler = None
+    dominant = max(full.items(), key=lambda kv: kv[1][1])[0]
+    kernel_ms_total = sum(v[1] for v in full.values())
 
-  # ---- timed region: exactly K steps between barrier + synchronize.  Eager mode: the dominant kernel is
-  # HIP-event timed inside this region.  Graph mode: a replayed graph has no per-launch host call to bracket,
+  # ---- timed region: exactly K steps between barrier + synchronize.  --full, eager mode: the dominant kernel is
+  # HIP-event timed inside this region.  --full, graph mode: a replayed graph has no per-launch host call to bracket,
   # so the same K steps are repeated eagerly right after the timed region for the roofline leg.
-  _lib.profiler = None if args.graph else _lib.Profiler({dominant})
+  _lib.profiler = _lib.Profiler({dominant}) if args.full and not args.graph else None
   if dist is not None:
     dist.barrier()
   torch.cuda.synchronize()
@@ -483,8 +519,10 @@ def main():
   if net.collective_timer:
     allreduce_ms = [a.elapsed_time(b) for a, b in net.collective_timer]
   net.collective_timer = None
+  if args.dump_outputs and rank == 0:      # before anything else steps the network again
+    dump_outputs(args.dump_outputs, eng)
   eager_ms_per_step = None
-  if args.graph:
+  if args.full and args.graph:
     net.use_graph = False
     _lib.profiler = _lib.Profiler({dominant})
     torch.cuda.synchronize()
@@ -493,7 +531,7 @@ def main():
       step()
     torch.cuda.synchronize()
     eager_ms_per_step = (time.perf_counter() - t1) / args.steps * 1e3
-  prof = _lib.profiler.summary()
+  prof = _lib.profiler.summary() if args.full else None
   _lib.profiler = None
   ranks_seen = 1
   rank_ms = [local_elapsed / args.steps * 1e3] * 2      # slowest / fastest rank's own ms per step
@@ -514,11 +552,8 @@ def main():
   if rank == 0:
     ms_per_step = elapsed / args.steps * 1e3
     value = args.batch * world * args.steps / elapsed
-    n_l, ms_l, bytes_l = prof[dominant]
-    achieved = bytes_l / (ms_l * 1e-3) / 1e9
     is_headline = args.model == 'efficientdet-d0' and args.image_size == 640 and args.batch == 128 and \
         args.dtype == 'bf16' and args.clip_gradients_norm is None
-    traffic, traffic_src = pmc_traffic(dominant, n_l / args.steps) if is_headline else (None, None)
     out = {
         'metric': 'images/sec %s %dx%d fwd+bwd (whole job; per-GPU = value / n_gpus)' % (
             args.model.replace('efficientdet-d', 'EfficientDet-D'), args.image_size, args.image_size),
@@ -550,32 +585,36 @@ def main():
                                               'bytes': int(eng.grads_flat.numel()) * 4}
                                              if allreduce_ms else None),
                    'eager_ms_per_step': eager_ms_per_step},
-        'roofline': {
-            'bound': 'hbm', 'kernel': dominant, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-            'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
-            'traffic_source': traffic_src,
-            'launches_per_step': n_l / args.steps, 'avg_launch_ms': ms_l / n_l,
-            'timed_over': ('%d eager steps run right after the timed (graph replay) region' % args.steps)
-            if args.graph else 'the timed region',
-            'algorithmic_bytes_per_launch': bytes_l / n_l,
-            'kernel_time_share': full[dominant][1] / kernel_ms_total,
-            'whole_step_hbm_frac': (ALG_MB_PER_IMG * 1e6 * args.batch / (ms_per_step * 1e-3) / 1e9) / HBM_PEAK_GBS
-            if (args.model == 'efficientdet-d0' and args.image_size == 640) else None,
-            'whole_step_mfma_frac': (ALG_GFLOP_PER_IMG * 1e9 * args.batch / (ms_per_step * 1e-3) / 2.5e15)
-            if (args.model == 'efficientdet-d0' and args.image_size == 640) else None,
-            'per_kernel_ms': {k: round(v[1], 3) for k, v in sorted(full.items(), key=lambda kv: -kv[1][1])[:12]},
-        },
     }
-    if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
-      out['cpu_baseline'] = cpu_baseline(config, args.image_size)
-      if is_headline:
-        out['parity'] = parity_block(config, args.image_size)
-    if is_headline and world == 1 and not args.no_other_configs:
-      net._graph, net.engine = None, None      # release the headline workload's 36 GB of activation buffers
-      net._engines.clear()
-      eng._bufs.clear()
-      torch.cuda.empty_cache()
-      out['other_configs'] = other_configs()
+    if args.full:
+      n_l, ms_l, bytes_l = prof[dominant]
+      achieved = bytes_l / (ms_l * 1e-3) / 1e9
+      traffic, traffic_src = pmc_traffic(dominant, n_l / args.steps) if is_headline else (None, None)
+      out['roofline'] = {
+          'bound': 'hbm', 'kernel': dominant, 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+          'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
+          'traffic_source': traffic_src,
+          'launches_per_step': n_l / args.steps, 'avg_launch_ms': ms_l / n_l,
+          'timed_over': ('%d eager steps run right after the timed (graph replay) region' % args.steps)
+          if args.graph else 'the timed region',
+          'algorithmic_bytes_per_launch': bytes_l / n_l,
+          'kernel_time_share': full[dominant][1] / kernel_ms_total,
+          'whole_step_hbm_frac': (ALG_MB_PER_IMG * 1e6 * args.batch / (ms_per_step * 1e-3) / 1e9) / HBM_PEAK_GBS
+          if (args.model == 'efficientdet-d0' and args.image_size == 640) else None,
+          'whole_step_mfma_frac': (ALG_GFLOP_PER_IMG * 1e9 * args.batch / (ms_per_step * 1e-3) / 2.5e15)
+          if (args.model == 'efficientdet-d0' and args.image_size == 640) else None,
+          'per_kernel_ms': {k: round(v[1], 3) for k, v in sorted(full.items(), key=lambda kv: -kv[1][1])[:12]},
+      }
+      if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores)
+        out['cpu_baseline'] = cpu_baseline(config, args.image_size)
+        if is_headline:
+          out['parity'] = parity_block(config, args.image_size)
+      if is_headline and world == 1 and not args.no_other_configs:
+        net._graph, net.engine = None, None      # release the headline workload's 36 GB of activation buffers
+        net._engines.clear()
+        eng._bufs.clear()
+        torch.cuda.empty_cache()
+        out['other_configs'] = other_configs()
     print(json.dumps(out))
   if dist is not None:
     dist.barrier()

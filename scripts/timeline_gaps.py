@@ -1,9 +1,9 @@
 """Kernel timeline of one REPLAYED step out of a scripts/gpu_trace.sh trace: per queue the busy time and the holes between
 consecutive kernels (attributed to the kernel that starts after the hole), and the union of the busy intervals of all queues.
 
-usage: python scripts/timeline_gaps.py gpurun_out/TAG_trace.csv.gz [rows_per_queue]
+usage: python scripts/timeline_gaps.py out/TAG_trace.csv.gz [rows_per_queue]
 
-A bench.py run is: eager / capture / replay warm-up steps, one eager fully profiled step, the timed replays, then as many
+A `bench.py --full` run is: eager / capture / replay warm-up steps, one eager fully profiled step, the timed replays, then as many
 EAGER steps with HIP events around the dominant entry point (the roofline leg).  The steps are delimited by the stem kernel;
 the shortest one is a replay (the eager legs carry host gaps and event barriers) and is the one analysed."""
 import collections

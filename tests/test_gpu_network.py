@@ -863,7 +863,7 @@ def test_bench_spawns_two_ranks_and_reports_them(tmp_path):
   for graph, extra in (('1', []), ('0', []), ('0', ['--clip_gradients_norm', '0']),
                        ('0', ['--clip_gradients_norm', '0', '--overlap_reduce'])):
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--batch', '8', '--steps', '3',
-                        '--warmup', '1', '--image_size', '256', '--graph', graph, '--no_cpu_baseline',
+                        '--warmup', '1', '--image_size', '256', '--graph', graph, '--full', '--no_cpu_baseline',
                         '--no_other_configs'] + extra, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, (graph, r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -898,7 +898,7 @@ def test_rccl_path_on_the_device_at_world_size_one(tmp_path):
     sk.bind(('127.0.0.1', 0))
     port = sk.getsockname()[1]
   common = [os.path.join(root, 'bench.py'), '--gpus', '1', '--batch', '8', '--steps', '3', '--warmup', '3',
-            '--image_size', '256', '--no_cpu_baseline', '--no_other_configs']
+            '--image_size', '256', '--full', '--no_cpu_baseline', '--no_other_configs']
   lines = {}
   launcher = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
               '--master-addr', '127.0.0.1', '--master-port', str(port)]
@@ -941,3 +941,40 @@ def test_rccl_path_on_the_device_at_world_size_one(tmp_path):
     assert 0 < c['per_rank_ms_per_step']['min'] <= c['per_rank_ms_per_step']['max'] <= 1.001 * line['ms_per_step'], c
     assert 0 < c['host_enqueue_ms_min'] <= c['host_enqueue_ms_first_step'], c
     assert c['host_enqueue_ms_min'] <= c['host_enqueue_ms_per_step'] * 1.001, c
+
+
+def test_bench_plain_run_dumps_what_its_last_step_computed(tmp_path):
+  """A plain `bench.py` run (no --full) times exactly --steps steps and reports none of the side measurements;
+  --dump-outputs DIR writes what its last timed step left for the caller: the loss values (float64) the line reports
+  and the variables (float32) whose crc32 the line reports.  The inputs are seeded and the step is bit-reproducible,
+  so a second run with the same arguments writes the same arrays bit for bit."""
+  import json
+  import os
+  import subprocess
+  import sys
+  import zlib
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  env = dict(os.environ)
+  for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'EDET_BENCH_SAME_DEVICE', 'EDET_BENCH_BACKEND'):
+    env.pop(k, None)
+  runs = []
+  for i in range(2):
+    out = tmp_path / ('out%d' % i)
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--batch', '8', '--steps', '4',
+                        '--warmup', '1', '--image_size', '256', '--dump-outputs', str(out)],
+                       env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line['steps'] == 4 and line['ms_per_step'] > 0 and abs(line['value'] - 8 * 1e3 / line['ms_per_step']) < 1e-6 * line['value']
+    assert not {'roofline', 'cpu_baseline', 'parity', 'other_configs'} & set(line), sorted(line)
+    arrays = {p.stem: np.load(p) for p in out.glob('*.npy')}
+    assert {'params', 'ema', 'velocity', 'bn_state', 'loss', 'cls_loss', 'box_loss', 'gradient_norm'} <= set(arrays), sorted(arrays)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(p.stat().st_size for p in out.glob('*.npy')) <= 64 * 10**6
+    assert zlib.crc32(arrays['params'].tobytes()) & 0xffffffff == line['config']['param_crc32']
+    assert float(arrays['loss']) == line['config']['loss'] and np.isfinite(arrays['gradient_norm'])
+    runs.append(arrays)
+  for k, a in runs[0].items():
+    assert np.array_equal(a, runs[1][k]), k

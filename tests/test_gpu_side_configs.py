@@ -1,6 +1,6 @@
 """-m gpu: parity of the bf16 paths AT THE SIZES OF BASELINE.json configs[1] AND configs[4].
 
-bench.py times two more configurations next to the headline one (`other_configs`): EfficientNetV2-S 224x224 batch 256
+`bench.py --full` times two more configurations next to the headline one (`other_configs`): EfficientNetV2-S 224x224 batch 256
 forward (configs[1]) and the per-GPU leg of EfficientDet-D7x 1536x1536 batch 8 (configs[4]).  This module puts both
 under the discipline tests/test_gpu_bench_shapes.py applies to the headline configuration:
 
