@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/edet_hip.h"
@@ -266,6 +267,13 @@ int edet_reduce_partials2(const float* ws, int P, int64_t n, float* dst_a, int64
 
 // workgroups of kernel `fn` (block size `threads`, `lds` bytes of dynamic LDS) the device holds at once; 0 = unknown
 int edet_resident_wgs(const void* fn, int threads, size_t lds);
+
+// The implementation selectors the parity tests set to reach a reference path, read per call:
+// the integer value of environment variable `name`, or `dflt` when it is unset or empty
+static inline int edet_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return (e && e[0]) ? atoi(e) : dflt;
+}
 
 static inline hipStream_t to_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -342,8 +342,7 @@ int cvh_try_conv_fwd(const edet_tview_t* in, const void* wt, int ldw, int k, int
   // channels (63 KiB of halo, one workgroup per CU) 0.126 -> 0.138 ms: stays on the implicit GEMM
   if (s == 2 && cin > 32) return 0;
   if (in->ld % 8 != 0 || ldw % 8 != 0 || ldo % 8 != 0 || ldo < (cout + 7) / 8 * 8) return 0;
-  const char* e = getenv("EDET_CONV_HALO");
-  if (e && e[0] == '0') return 0;           // lab switch: the implicit GEMM for every shape
+  if (edet_env_int("EDET_CONV_HALO", 1) == 0) return 0;     // selector: the implicit GEMM for every shape
   Args a;
   memset(&a, 0, sizeof(a));
   a.tv = *in;

@@ -90,7 +90,7 @@ struct Args {
   int nch, ngroups;     // channel chunks (of CPT) per workgroup, channel groups
   int TX, TY;           // tile: TX columns (one per thread) x TY rows of the marched space
   int tiles_x, tiles_y, ntiles, P;
-  int xcd;              // 0: block b = (p, g) = (b / ngroups, b % ngroups); 1, 2: XCD-aware maps (lane_setup)
+  int xcd;              // 0: block b = (p, g) = (b / ngroups, b % ngroups); 1: the XCD-aware map (lane_setup)
 };
 
 struct Lane {
@@ -116,13 +116,10 @@ __device__ __forceinline__ Lane lane_setup(const Args& a, int C) {
     l.g = j % a.ngroups;
     const int ph = j / a.ngroups;
     l.p = ph * 8 + x;
-    l.tile0 = l.p;
-    if (a.xcd == 2) {
-      // ... and XCD x owns a contiguous range of tiles, its P / 8 resident slots walk it side by side: the column /
-      // row halos of neighbouring tiles come from the same L2 too
-      const int t8 = (a.ntiles + 7) / 8;
-      l.tile0 = x * t8 + ph; l.tstep = a.P / 8; l.tend = min(a.ntiles, (x + 1) * t8);
-    }
+    // ... and XCD x owns a contiguous range of tiles, its P / 8 resident slots walk it side by side: the column /
+    // row halos of neighbouring tiles come from the same L2 too
+    const int t8 = (a.ntiles + 7) / 8;
+    l.tile0 = x * t8 + ph; l.tstep = a.P / 8; l.tend = min(a.ntiles, (x + 1) * t8);
   }
   l.c = (l.g * a.nch + l.chunk) * CPT;
   l.active = l.px < a.TX && l.c < C;
@@ -1169,14 +1166,9 @@ inline int pick_nch(int nvec, int maxch) {
 }
 
 // XCD-aware (tile slot, channel group) -> block map (lane_setup): needs a whole number of slots per XCD.
-// EDET_DWM_XCD=0|1|2 overrides (lab switch).
 inline void xcd_map(Args& a) {
-  const char* e = getenv("EDET_DWM_XCD");
-  const int mode = (e && e[0]) ? atoi(e) : 2;
-  a.xcd = 0;
-  if (mode == 0 || a.P < 8 || (mode == 1 && a.ngroups == 1)) return;
-  a.P -= a.P % 8;
-  a.xcd = mode;
+  a.xcd = a.P >= 8;
+  if (a.xcd) a.P -= a.P % 8;
 }
 
 // space_w / space_h: extent of the marched tile space (output pixels; for dgrad the q / oy step space)
@@ -1186,9 +1178,7 @@ inline void plan(Args& a, int C, int n, int space_w, int space_h, int max_p, int
   // <= 128 contiguous bytes per pixel and workgroup.  (r02t lab: 64- or 32-byte channel groups for the two-channel
   // kernels -- wider column tiles, half the column halo -- are slower: backward 11.04 -> 11.40 / 12.01 ms, forward
   // 4.77 -> 4.87 / 5.01 ms over the 15 layer shapes.)
-  const char* gb_env = getenv("EDET_DWM_GB");      // lab switch: bytes of one pixel's channel group per workgroup
-  const int gb = (gb_env && gb_env[0]) ? atoi(gb_env) : 128;
-  a.nch = pick_nch(nvec, gb / (CPT * 2));
+  a.nch = pick_nch(nvec, 128 / (CPT * 2));
   a.ngroups = (nvec + a.nch - 1) / a.nch;
   a.TX = THREADS / a.nch;
   {
@@ -1206,15 +1196,14 @@ inline void plan(Args& a, int C, int n, int space_w, int space_h, int max_p, int
   a.tiles_x = (space_w + a.TX - 1) / a.TX;
   a.tiles_y = (space_h + a.TY - 1) / a.TY;
   a.ntiles = n * a.tiles_x * a.tiles_y;
-  // Persistent workgroups x channel groups.  r03d lab (scripts/kernel_lab.py --ab EDET_DWM_P=4096,2048,8192, the 15
-  // depthwise layer shapes of D0 640x640 batch 128): the 3x3 layers on the 160 / 320-row maps want many short-lived
+  // Persistent workgroups x channel groups.  r03d lab (targets of 4096 / 2048 / 8192 workgroups, the 15 depthwise layer
+  // shapes of D0 640x640 batch 128): the 3x3 layers on the 160 / 320-row maps want many short-lived
   // workgroups (8192: 320x320x32 fused backward 1.00 -> 0.86 ms, forward 0.61 -> 0.52 ms), every other layer fewer,
   // longer-lived ones (2048: 40x40x480 k5 backward 0.65 -> 0.54, 20x20x1152 k5 0.46 -> 0.38 ms); over the 15 shapes
   // backward 11.21 -> 10.52 ms, forward 4.84 -> 4.67 ms against round 2's 4096 everywhere.  r06l lab, the round-6 kernels:
   // the forward (four waves per SIMD now) wants 4096 on those layers (3.39 -> 3.34 ms over the 15 shapes, 20x20x1152 k3 0.071
-  // -> 0.064 ms), the one-pass backward keeps 2048 (7.14 / 7.16 / 7.35 ms at default / 2048 / 4096).  EDET_DWM_P overrides.
-  const char* p_env = getenv("EDET_DWM_P");
-  int P = ((p_env && p_env[0]) ? atoi(p_env) : ((k == 3 && a.in.h >= 160) ? 8192 : p_small)) / a.ngroups;
+  // -> 0.064 ms), the one-pass backward keeps 2048 (7.14 / 7.16 / 7.35 ms at default / 2048 / 4096).
+  int P = ((k == 3 && a.in.h >= 160) ? 8192 : p_small) / a.ngroups;
   if (P < 64) P = 64;
   if (P > max_p) P = max_p;
   if (P > a.ntiles) P = a.ntiles;
@@ -1239,9 +1228,8 @@ int dwm_try_fwd(const edet_tview_t* in, const float* weight, int k, int s, void*
   // 3x3: four channels per thread on the large maps, two (six rows of loads in flight, more waves) from 40 x 40 OUTPUT
   // pixels down -- r04 lab, D0 640x640 batch 128: 40x40x64 0.0340 (4) / 0.0278 ms (2), 40x40x480 0.162 / 0.140, 80x80x240
   // stride 2 0.166 / 0.142, 20x20x1152 0.097 / 0.089, but 80x80x64 0.057 / 0.068 and 320x320x32 0.43 / 0.56.  By the map,
-  // not the batch.  EDET_DWM_FWD_CPT=4|2 overrides (lab switch).
-  const char* fc = getenv("EDET_DWM_FWD_CPT");
-  const bool c2 = (fc && fc[0]) ? fc[0] == '2' : a.oh * a.ow <= 40 * 40;
+  // not the batch.
+  const bool c2 = a.oh * a.ow <= 40 * 40;
   const int actm = in->act == EDET_ACT_NONE ? 0 : (in->act == EDET_ACT_SWISH ? 1 : 2);
 #define DWM_FWD2(K_, S_, CPT_)                                                            \
   do {                                                                                    \
@@ -1269,12 +1257,7 @@ int dwm_try_fwd(const edet_tview_t* in, const float* weight, int k, int s, void*
 // channels per thread of the 3x3 stride-2 gradient kernels: 4 on the large maps, 2 (deeper load FIFO, more waves) up to
 // 80 x 80 input pixels -- r04 lab, D0 640x640 batch 128, data + weight gradient: 320x320x96 2.55 (4) / 2.77 ms (2),
 // 80x80x240 0.529 (4) / 0.460 ms (2).  By the map, not the batch (the parity runs launch what the batch-128 step launches).
-// EDET_DWM_S2_CPT="<dgrad><wgrad>" (e.g. "24") overrides (lab switch).
-static int s2_cpt(int which, int hw) {
-  const char* e = getenv("EDET_DWM_S2_CPT");
-  if (!e || strlen(e) < 2) return hw > 80 * 80 ? 4 : 2;
-  return e[which] == '2' ? 2 : 4;
-}
+static int s2_cpt(int hw) { return hw > 80 * 80 ? 4 : 2; }
 
 int dwm_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, int k, int s, float* dweight, void* workspace,
                   size_t workspace_bytes, hipStream_t st) {
@@ -1301,7 +1284,7 @@ int dwm_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, int k, int s, 
     else { if (oact) edet_launch(k_wgrad_lx<K_, S_, CPT_, false, true>, grid, block, lds + ring, st, a); else edet_launch(k_wgrad_lx<K_, S_, CPT_, false, false>, grid, block, lds + ring, st, a); }             \
   } while (0)
   if (k == 3 && s == 1) DWM_WG(3, 1, 4);
-  else if (k == 3 && s == 2 && s2_cpt(1, in->h * in->w) == 2) DWM_WG(3, 2, 2);
+  else if (k == 3 && s == 2 && s2_cpt(in->h * in->w) == 2) DWM_WG(3, 2, 2);
   else if (k == 3 && s == 2) DWM_WG(3, 2, 4);
   else if (k == 5 && s == 1) DWM_WG(5, 1, 2);
   else if (k == 5 && s == 2) DWM_WG(5, 2, 2);
@@ -1334,7 +1317,7 @@ int dwm_try_dgrad(const edet_gview_t* dy, const float* weight, int k, int s, con
     else { if (oact) edet_launch(k_dgrad_lx<K_, S_, CPT_, false, true>, grid, block, lds + ring, st, a); else edet_launch(k_dgrad_lx<K_, S_, CPT_, false, false>, grid, block, lds + ring, st, a); }             \
   } while (0)
   if (k == 3 && s == 1) DWM_DG(3, 1, 4);
-  else if (k == 3 && s == 2 && s2_cpt(0, in->h * in->w) == 2) DWM_DG(3, 2, 2);
+  else if (k == 3 && s == 2 && s2_cpt(in->h * in->w) == 2) DWM_DG(3, 2, 2);
   else if (k == 3 && s == 2) DWM_DG(3, 2, 4);
   else if (k == 5 && s == 1) DWM_DG(5, 1, 2);
   else if (k == 5 && s == 2) DWM_DG(5, 2, 2);
@@ -1354,10 +1337,7 @@ int dwm_try_bwd_fused(const edet_gview_t* dy, const float* weight, int k, int s,
   // k = 3, stride 1: 4 channels per thread (8-byte loads, 2 waves/SIMD) wins on the large maps, 2 channels per thread
   // (3-4 waves/SIMD) on the small ones (r02: 320x320x32 1.08 vs 1.55 ms, 40x40x64 1.25 vs 1.05 ms; r04, 64 channels:
   // 80x80 0.147 (2) -> 0.137 ms (4), 40x40 0.0485 -> 0.0480 with the threshold at 80x80, 0.057 with 4 channels there too)
-  const char* c4_env = getenv("EDET_DWM_C4_MINHW");      // lab switch
-  const bool k3c4 = (int64_t)in->h * in->w >= (c4_env && c4_env[0] ? atoi(c4_env) : 80 * 80);
-  const char* one_env = getenv("EDET_DWM_ONE");          // lab switch: 0 = the two-kernel path (k_wgrad_lx, k_dgrad_lx)
-  if (one_env && one_env[0] == '0') return 0;
+  const bool k3c4 = (int64_t)in->h * in->w >= 80 * 80;
   if ((s != 1 && s != 2) || (k != 3 && k != 5) || in->gate || epi->dgate || in->c % 8 != 0 || !workspace) return 0;
   if ((int64_t)in->h * in->w * in->ld * 2 >= 0x7fffffffLL) return 0;      // the kernel's 32-bit offsets inside one image
   Args a;

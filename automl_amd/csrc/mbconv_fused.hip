@@ -67,7 +67,6 @@ struct Args {
   int ngroups, TY, tiles_x, tiles_y, ntiles, P;
   int ngb;                    // channel blocks (workgroups) per tile slot: cexp / (48 NGR)
   long long M;                // k_exp_stats: pixels
-  int dbg;                    // lab switch EDET_MBF_DBG (1: the stores of the expanded tensor are dropped)
 };
 
 __device__ __forceinline__ bf16x8 zero_frag() { return __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u)); }
@@ -221,7 +220,7 @@ template <int K, int S, typename SH> struct Geo {
 // ACTM: 1 swish, 2 relu / relu6 / hswish / mish / srelu
 // (Three waves per SIMD: at four, the 3x3 stride-2 instantiations fit 128 VGPRs only with 1-7 spilled registers, and the
 // six-wave one then stored wrong values in the first row of a tile -- zeros in two of a lane's four MFMA results, r06
-// scripts/mbf_debug.py; no instantiation may spill: tests/test_abi.py checks the build's resource report.)
+// lab; no instantiation may spill: tests/test_abi.py checks the build's resource report.)
 template <int K, int S, int ACTM, bool STORE_E, typename SH>
 __global__ __launch_bounds__(SH::NT, 3) void k_exp_dw_fwd(const Args a) {
   using G = Geo<K, S, SH>;
@@ -307,7 +306,7 @@ __global__ __launch_bounds__(SH::NT, 3) void k_exp_dw_fwd(const Args a) {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int ixs = wc0 + spx[it];
-      const bool eok = STORE_E && a.dbg != 1 && tid + NT * it < WINC * ECH && ixs >= 0 && ixs < W &&
+      const bool eok = STORE_E && tid + NT * it < WINC * ECH && ixs >= 0 && ixs < W &&
                        (spx[it] < TXV * S || tx == a.tiles_x - 1);
       eoff[it] = eok ? (uint32_t)ixs * (uint32_t)(a.lde * 2) + (uint32_t)(cb * 2 + 16 * spart[it]) : OOB;
     }
@@ -395,8 +394,8 @@ __global__ __launch_bounds__(SH::NT, 3) void k_exp_dw_fwd(const Args a) {
             // stores -- fetches its data registers late: the compiler put a VALU write of the store's FIRST data register
             // (v_cndmask of the next store's offset) two instructions behind the store, and on the device lanes 12-15 of
             // every 16-lane row then stored the new value as their first dword: wrong first channels of a chunk in the
-            // expanded tensor, on some rows of the batch-128 run only, the depthwise output untouched (r06,
-            // scripts/mbf_debug2.py; LLVM guards this store-data hazard only for MUBUF stores WITHOUT a register soffset).
+            // expanded tensor, on some rows of the batch-128 run only, the depthwise output untouched (r06
+            // lab; LLVM guards this store-data hazard only for MUBUF stores WITHOUT a register soffset).
             // Two separated 8-byte buffer stores are correct but cost 12-20 % of the kernel.
             u32x4 v; v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
             if (est && eoff[it] != OOB) *reinterpret_cast<u32x4*>(e_row + eoff[it]) = v;
@@ -496,16 +495,11 @@ __global__ __launch_bounds__(SH::NT, 3) void k_exp_dw_fwd(const Args a) {
 
 // Tile slots (= workgroups = statistic partial rows, <= EDET_MAX_PARTS): at most ONE round of resident workgroups (r06
 // lab, 160x160x24->144: 768 six-wave workgroups on a chip that holds 512 ran a second, half-empty round: +30 %), and a
-// whole number of tiles per slot on every XCD.  EDET_MBF_P overrides the cap (lab switch).
+// whole number of tiles per slot on every XCD.
 inline void pick_slots(Args& a, const void* fn, int threads, size_t lds) {
-  const char* p_env = getenv("EDET_MBF_P");
   int pmax = EDET_MAX_PARTS;
-  if (p_env && p_env[0]) pmax = atoi(p_env);
-  else {
-    const int res = edet_resident_wgs(fn, threads, lds);
-    if (res / a.ngb >= 8 && res / a.ngb < pmax) pmax = res / a.ngb;
-  }
-  if (pmax < 8) pmax = 8;
+  const int res = edet_resident_wgs(fn, threads, lds);
+  if (res / a.ngb >= 8 && res / a.ngb < pmax) pmax = res / a.ngb;
   const int t8 = (a.ntiles + 7) / 8;
   const int rounds = (t8 + pmax / 8 - 1) / (pmax / 8);
   a.P = 8 * ((t8 + rounds - 1) / rounds);
@@ -587,9 +581,8 @@ extern "C" int edet_mbconv_expand_dw_fwd(const edet_tview_t* in, const void* wt,
   // that each write 96 of a pixel's 192 bytes).  Otherwise four-wave workgroups of 48 channels over a 64-column window:
   // fewest recomputed halo columns, no barrier across more than four waves (160x160x24->144, six-wave whole-pixel shape
   // against three workgroups per window: training 0.78 / 0.56 vs 0.64 / 0.54 ms for k3s1 / k5s2, inference 0.60 / 0.50 vs
-  // 0.46 / 0.31).  EDET_MBF_SHAPE=1|2 forces the per-group / whole-pixel shape (lab switch).
-  const char* sh_env = getenv("EDET_MBF_SHAPE");
-  const bool whole = (sh_env && sh_env[0]) ? sh_env[0] == '2' : (se && a.ngroups == 2);
+  // 0.46 / 0.31).
+  const bool whole = se && a.ngroups == 2;
   const int ngr = (whole && a.ngroups > 1) ? a.ngroups : 1;
   a.ngb = a.ngroups / ngr;
   const int winc = ngr == 1 ? 64 : 32;      // Shape<1,4>, Shape<2,2>, Shape<3,2>
@@ -602,7 +595,6 @@ extern "C" int edet_mbconv_expand_dw_fwd(const edet_tview_t* in, const void* wt,
   a.tiles_x = (a.ow + txv - 1) / txv;
   a.tiles_y = (a.oh + a.TY - 1) / a.TY;
   a.ntiles = in->n * a.tiles_x * a.tiles_y;
-  { const char* d = getenv("EDET_MBF_DBG"); a.dbg = (d && d[0]) ? atoi(d) : 0; }
   hipStream_t st = to_stream(stream);
   const bool sw = act == EDET_ACT_SWISH;
 #define MBF_GO2(K_, S_, SH_)                                                                    \

@@ -917,13 +917,8 @@ inline bool big_lds_ok(const void* kern) {
 
 }  // namespace pwb
 
-// consecutive row tiles per workgroup: as few as the partial-row limit allows; EDET_BIG_TPW = a minimum (lab switch)
-static int big_tpw(int ntm) {
-  int t = (ntm + EDET_MAX_PARTS - 1) / EDET_MAX_PARTS;
-  const char* e = getenv("EDET_BIG_TPW");
-  if (e && e[0] && atoi(e) > t) t = atoi(e);
-  return t;
-}
+// consecutive row tiles per workgroup: as few as the partial-row limit allows
+static int big_tpw(int ntm) { return (ntm + EDET_MAX_PARTS - 1) / EDET_MAX_PARTS; }
 
 // the LDS-DMA forward kernel (pw_glds.hip); same return convention
 int pwg_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
@@ -932,8 +927,7 @@ int pwg_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bi
 // r06al); it ties or loses a few per cent on the others.  EDET_PW_GLDS = 0: never; 2: every shape of its envelope (read
 // per call: lab switch and the bit-equality test).  The two kernels give the same bits, so the rule is free to change.
 static bool glds_wanted(const edet_tview_t* in) {
-  const char* e = getenv("EDET_PW_GLDS");
-  const int mode = e && e[0] ? atoi(e) : 1;
+  const int mode = edet_env_int("EDET_PW_GLDS", 1);
   return mode == 2 || (mode == 1 && in->gate != nullptr);
 }
 
@@ -1072,13 +1066,11 @@ int pwb_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, float* dweight
   const int ntile = a.ntk * a.ntn;
   const int64_t kn = (int64_t)K * N;
   // Workgroup target, at least 4 steps of 64 rows each, bounded by the workspace.  Every split writes a K x N fp32
-  // partial that edet_reduce_partials reads back, so more splits are not free: r03c lab (scripts/kernel_lab.py
-  // --entry pw_bwd_weight --layers mid --ab EDET_WGRAD_WGS=2048,1024,512,256, D0 640x640 batch 128): the 16 mid-size
-  // layers take 2.96 ms at 2048 workgroups (round 2), 2.59 ms with 512 for K*N < 64 K and 1024 above -- at 2048 the
-  // partials of 1152 x 320 (76 splits, 112 MB written and read back) outweigh the 183 MB the kernel streams.
-  // EDET_WGRAD_WGS overrides (lab switch, read per call).
-  const char* wgs_env = getenv("EDET_WGRAD_WGS");
-  const int wg_target = wgs_env ? atoi(wgs_env) : (kn >= 65536 ? 1024 : 512);
+  // partial that edet_reduce_partials reads back, so more splits are not free: r03c lab (targets of 2048 / 1024 / 512 /
+  // 256 workgroups, D0 640x640 batch 128): the 16 mid-size layers take 2.96 ms at 2048 workgroups (round 2), 2.59 ms
+  // with 512 for K*N < 64 K and 1024 above -- at 2048 the partials of 1152 x 320 (76 splits, 112 MB written and read
+  // back) outweigh the 183 MB the kernel streams.
+  const int wg_target = kn >= 65536 ? 1024 : 512;
   // rounded DOWN: two workgroups of this kernel are resident per compute unit (512 at a time), and a grid of 513 or
   // 1026 (288 x 48: 3 tiles x 171 splits; 1152 x 320: 27 x 38) runs a last round for one or two stragglers
   // (r03e: efficientdet-d7x 384x384x288->48 went from 0.93 to 1.19 ms per call when the target dropped to 512)

@@ -692,6 +692,20 @@ static bool pw_prefers_big(int op, int64_t rows, int cin, int cout) {
   return kn >= minkn[op] && rows >= 1024;
 }
 
+// The bf16 routing of one op: the tiled kernels first where pw_prefers_big says so, else the streaming kernels, then the
+// tiled kernels for any cin*cout >= 4096 the streaming kernels declined; EDET_PW_IMPL narrows it to one family.
+// Returns what the kernel that took the call returned: 0 = none did (the caller runs the generic kernel).
+template <typename TryBig, typename TryStream>
+static int pw_route(int op, int64_t rows, int cin, int cout, TryBig try_big, TryStream try_stream) {
+  const int impl = pw_impl_env();
+  const bool big_first = impl == PW_BIG || (impl == PW_AUTO && pw_prefers_big(op, rows, cin, cout));
+  int rc = 0;
+  if (big_first) rc = try_big();
+  if (rc == 0 && impl != PW_TILED && impl != PW_BIG) rc = try_stream();
+  if (rc == 0 && !big_first && impl == PW_AUTO && (int64_t)cin * cout >= 4096) rc = try_big();
+  return rc;
+}
+
 // streaming bf16 kernels (pw_stream.hip); return 1 = handled, 0 = shape outside their envelope
 int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
                 int ldo, float* stat_partials, int* nparts_out, hipStream_t st);
@@ -714,14 +728,10 @@ extern "C" int edet_pw_fwd(const edet_tview_t* in, const void* wt, int ldw, cons
   a.M = in->n * in->h * in->w; a.R = in->c; a.J = cout; a.hw = in->h * in->w;
   a.bias = bias; a.out = out; a.ldo = ldo; a.stat_partials = stat_partials;
   if (dtype == EDET_BF16) {
-    const int impl = pw_impl_env();
-    const bool big_first = impl == PW_BIG || (impl == PW_AUTO && pw_prefers_big(PW_OP_FWD, a.M, in->c, cout));
-    int rc = 0;
-    if (big_first) rc = pwb_try_fwd(in, wt, ldw, bias, out, cout, ldo, stat_partials, nparts_out, to_stream(stream));
-    if (rc == 0 && impl != PW_TILED && impl != PW_BIG)
-      rc = pws_try_fwd(in, wt, ldw, bias, out, cout, ldo, stat_partials, nparts_out, to_stream(stream));
-    if (rc == 0 && !big_first && impl == PW_AUTO && (int64_t)in->c * cout >= 4096)
-      rc = pwb_try_fwd(in, wt, ldw, bias, out, cout, ldo, stat_partials, nparts_out, to_stream(stream));
+    const int rc = pw_route(
+        PW_OP_FWD, a.M, in->c, cout,
+        [&] { return pwb_try_fwd(in, wt, ldw, bias, out, cout, ldo, stat_partials, nparts_out, to_stream(stream)); },
+        [&] { return pws_try_fwd(in, wt, ldw, bias, out, cout, ldo, stat_partials, nparts_out, to_stream(stream)); });
     if (rc != 0) return rc < 0 ? rc : 0;
     return launch_gemm<bf16_t, false>(a, nparts_out, to_stream(stream));
   }
@@ -760,19 +770,15 @@ extern "C" int edet_pw_bwd_data(const edet_gview_t* dy, const void* w, int ldw,
   a.M = in->n * in->h * in->w; a.R = dy->c; a.J = in->c; a.hw = in->h * in->w;
   a.epi = *epi; a.stat_partials = epi->stat_partials;
   if (dtype == EDET_BF16) {
-    const int impl = pw_impl_env();
-    const bool big_first = impl == PW_BIG || (impl == PW_AUTO && pw_prefers_big(PW_OP_DGRAD, a.M, in->c, dy->c));
-    int rc = 0;
     // SE-gated input: the tuned kernels store the gradient of the gated value and leave the gate-gradient sums to
     // k_gate_sums below (one writer per element; r06: their own sums were floating-point atomics, the last of the bf16
     // training step) -- the generic kernel (launch_gemm) does the same on its own
     edet_bwd_epi_t e2 = *epi;
     if (epi->dgate) e2.flags |= EDET_EPI_GATE_SUMS_LATER;
-    if (big_first) rc = pwb_try_dgrad(dy, w, ldw, in, &e2, nparts_out, to_stream(stream));
-    if (rc == 0 && impl != PW_TILED && impl != PW_BIG)
-      rc = pws_try_dgrad(dy, w, ldw, in, &e2, nparts_out, to_stream(stream));
-    if (rc == 0 && !big_first && impl == PW_AUTO && (int64_t)in->c * dy->c >= 4096)
-      rc = pwb_try_dgrad(dy, w, ldw, in, &e2, nparts_out, to_stream(stream));
+    const int rc = pw_route(
+        PW_OP_DGRAD, a.M, in->c, dy->c,
+        [&] { return pwb_try_dgrad(dy, w, ldw, in, &e2, nparts_out, to_stream(stream)); },
+        [&] { return pws_try_dgrad(dy, w, ldw, in, &e2, nparts_out, to_stream(stream)); });
     if (rc > 0 && epi->dgate) {
       edet_launch(k_gate_sums<bf16_t>, dim3(a.tv.n * cdiv(a.J, 64)), dim3(THREADS), 0, to_stream(stream), a);
       EDET_LAUNCH_CHECK("edet_pw_bwd_data (gate sums)");
@@ -797,14 +803,10 @@ extern "C" int edet_pw_bwd_weight(const edet_tview_t* in, const edet_gview_t* dy
   a.M = in->n * in->h * in->w; a.hw = in->h * in->w;
   a.dw = dweight;
   if (dtype == EDET_BF16) {
-    const int impl = pw_impl_env();
-    const bool big_first = impl == PW_BIG || (impl == PW_AUTO && pw_prefers_big(PW_OP_WGRAD, a.M, in->c, dy->c));
-    int rc = 0;
-    if (big_first) rc = pwb_try_wgrad(in, dy, dweight, workspace, workspace_bytes, to_stream(stream));
-    if (rc == 0 && impl != PW_TILED && impl != PW_BIG)
-      rc = pws_try_wgrad(in, dy, dweight, workspace, workspace_bytes, to_stream(stream));
-    if (rc == 0 && !big_first && impl == PW_AUTO && (int64_t)in->c * dy->c >= 4096)
-      rc = pwb_try_wgrad(in, dy, dweight, workspace, workspace_bytes, to_stream(stream));
+    const int rc = pw_route(
+        PW_OP_WGRAD, a.M, in->c, dy->c,
+        [&] { return pwb_try_wgrad(in, dy, dweight, workspace, workspace_bytes, to_stream(stream)); },
+        [&] { return pws_try_wgrad(in, dy, dweight, workspace, workspace_bytes, to_stream(stream)); });
     if (rc != 0) return rc < 0 ? rc : 0;
     return launch_wgrad<bf16_t>(a, workspace, workspace_bytes, to_stream(stream));
   }
@@ -837,9 +839,8 @@ extern "C" int edet_pw_bwd(const edet_gview_t* dy, const void* w, int ldw, const
                                        to_stream(stream));
       if (rc != 0) return rc < 0 ? rc : 0;
     }
-    // the one-pass tiled kernel (pw_tile_bwd.hip): cout <= 128; EDET_PWT=0 switches it off (lab / test switch, read per call)
-    const char* pwt_env = getenv("EDET_PWT");
-    if (impl == PW_AUTO && !(pwt_env && pwt_env[0] == '0')) {
+    // the one-pass tiled kernel (pw_tile_bwd.hip): cout <= 128; EDET_PWT=0 switches it off (test selector, read per call)
+    if (impl == PW_AUTO && edet_env_int("EDET_PWT", 1) != 0) {
       const int rc = pwt_try_bwd(dy, w, ldw, in, epi, nparts_out, dweight, workspace, workspace_bytes, to_stream(stream));
       if (rc != 0) return rc < 0 ? rc : 0;
     }

@@ -1517,12 +1517,6 @@ __global__ __launch_bounds__(256) void k_noy_apply(const float* __restrict__ psu
   dweight[i] += ga[n] * psum[i] + gb[n] * t + gc[n] * psum[(size_t)KO * R + (size_t)KO * KO + k];
 }
 
-// lab switches (read per call): integer environment variable or the default
-inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && e[0]) ? atoi(e) : dflt;
-}
-
 template <typename KernelT>
 inline bool allow_big_lds(KernelT kern, size_t lds) {
   if (lds <= 64 * 1024) return true;
@@ -1570,7 +1564,7 @@ int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bi
     if (lds == 0 || a.NWC != a.Npad) lds = plan_lds(a.Npad, a.pst * a.ck.rp, a.SA, a.SW, 150 * 1024, &a.NWC, &a.SC);
     if (lds == 0) return 0;
   }
-  if (!oact_ && env_int("EDET_PWS_FWD_EXACT", 1)) {
+  if (!oact_) {
     // the instantiation with the fewest passes that covers the super-tile; its passes are all issued (rows beyond the
     // super-tile are the wave's next rows) and staged, so the LDS tile holds NS * rp rows
     static const int exact_ns[] = {4, 6, 7, 8, 11, 16};
@@ -1587,8 +1581,7 @@ int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bi
   if (a.nwc > 2) return 0;   // the big operand would be re-read too often: leave it to the tiled kernel
   const int nst = (a.M + TR * a.G - 1) / (TR * a.G);
   // >= 4 super-tiles per wave (r03d lab, 24 pointwise layer shapes: 2 / 4 / 8 / 16 -> forward 4.85 / 4.79 / 4.82 / 4.87 ms)
-  const int spw_min = env_int("EDET_PWS_SPW", 4);
-  int grid = (nst + WAVES * spw_min - 1) / (WAVES * spw_min);
+  int grid = (nst + WAVES * 4 - 1) / (WAVES * 4);
   // One round: at most as many workgroups as the chip holds at once (3 per compute unit for the 8-pass kernel, 2 for the
   // 16-pass one).  r03h lab, caps of 1024 (the partial-row limit, round 2) / 768 / 512: 320x320x16->96 0.92 / 0.81 / 0.83
   // ms, 160x160x24->144 0.39 / 0.33 / 0.36, 320x320x32->16 0.46 / 0.40 / 0.48, 80x80x64->64 62 / 55 / 60 us; the
@@ -1605,8 +1598,7 @@ int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bi
     default: kfn = oact_ ? reinterpret_cast<const void*>(&k_pw_fwd<16, false, true>) : reinterpret_cast<const void*>(&k_pw_fwd<16, false, false>); break;
   }
   const int slots_fwd = edet_resident_wgs(kfn, THREADS, lds);
-  const int cap_fwd = env_int("EDET_PWS_FWD_CAP", slots_fwd > 0 ? slots_fwd : EDET_MAX_PARTS);     // lab switch overrides
-  if (grid > cap_fwd) grid = cap_fwd;
+  if (slots_fwd > 0 && grid > slots_fwd) grid = slots_fwd;
   if (grid > EDET_MAX_PARTS) grid = EDET_MAX_PARTS;
   if (grid < 1) grid = 1;
   a.spw = (nst + grid * WAVES - 1) / (grid * WAVES);
@@ -1664,10 +1656,8 @@ int pws_try_dgrad(const edet_gview_t* dy, const void* w, int ldw, const edet_tvi
   }
   if (lds > 150 * 1024) return 0;
   const int nst = (a.M + TR * a.G - 1) / (TR * a.G);
-  const int spw_min = env_int("EDET_PWS_SPW", 4);      // r03d lab: 2 / 4 / 8 -> backward 16.62 / 16.49 / 16.45 ms over 24 shapes
-  int grid = (nst + WAVES * spw_min - 1) / (WAVES * spw_min);
-  const int cap_bwd = env_int("EDET_PWS_BWD_CAP", EDET_MAX_PARTS);     // lab switch
-  if (grid > cap_bwd) grid = cap_bwd;
+  // >= 4 super-tiles per wave (r03d lab: 2 / 4 / 8 -> backward 16.62 / 16.49 / 16.45 ms over 24 shapes)
+  int grid = (nst + WAVES * 4 - 1) / (WAVES * 4);
   if (grid > EDET_MAX_PARTS) grid = EDET_MAX_PARTS;
   if (grid < 1) grid = 1;
   a.spw = (nst + grid * WAVES - 1) / (grid * WAVES);
@@ -1705,7 +1695,7 @@ int pws_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, float* dweight
   while (a.cpwV < nvecV) a.cpwV <<= 1;
   // row splits: ~2048 waves in total, at least 8 steps of 32 rows each, bounded by the workspace
   const int64_t kn = (int64_t)K * N;
-  int S = env_int("EDET_PWS_WG_TARGET", 2048) / a.nus;
+  int S = 2048 / a.nus;
   const int max_by_rows = (a.M + 8 * TR - 1) / (8 * TR);
   if (S > max_by_rows) S = max_by_rows;
   const int64_t max_by_ws = (int64_t)(workspace_bytes / sizeof(float)) / kn;
@@ -1752,12 +1742,12 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
   // ms, 160x160x24->144 1.45 -> 0.73 ms.  Class B (r03): at most 64 output channels -- the project layers (dW <= 3 x 9
   // tiles) and the 64 -> 64 layers (4 x 4) -- which the round-2 kernel ran slower than the two-kernel path because it
   // issued 5-8x the gradient loads a tile needs (every instantiated pass) and paid 16-48 LDS atomics per tile for the
-  // per-channel sums; EDET_PWS_FUSED_WIDE=0 keeps class A only (lab switch, read per call).
+  // per-channel sums; EDET_PWS_FUSED_WIDE=0 keeps class A only (test selector, read per call).
   const int tmin = a.TK < a.TN ? a.TK : a.TN, tmax = a.TK < a.TN ? a.TN : a.TK;
   const bool class_a = R >= 2 * KO && a.TK <= 2 && a.TN <= 9;
   int ft = 0;                                           // class B tile grid: 44 = 4 x 4, 39 = 3 x 9
   if (!class_a) {
-    if (env_int("EDET_PWS_FUSED_WIDE", 1) == 0) return 0;
+    if (edet_env_int("EDET_PWS_FUSED_WIDE", 1) == 0) return 0;
     // project shape only.  r03m: the 64 -> 64 layers of the BiFPN / heads (plain input view, no chain epilogue) take
     // 0.181 ms one-pass against 0.169 ms for the two tiled kernels at 80x80, and a kernel that owns every register of
     // a CU shuts out the small pyramid levels' chain on the second stream (the step did not move: 64.6 ms)
@@ -1767,19 +1757,16 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
     // 640x640 batch 128: 160x160x96->24 0.436 against 0.582 ms here, 80x80x144->40 0.226 / 0.274, 160x160x144->24 0.803 /
     // 0.796 (a tie, and the tiled kernel has no atomics); 320x320x32->16 stays here (0.787 against 0.841 ms).
     // EDET_PWT=0 (the tiled kernel off) restores the round-3 envelope.
-    {
-      const char* pwt_env = getenv("EDET_PWT");
-      // ... and every SE-gated projection: this kernel adds its gate-gradient sums into dgate with global atomics, the
-      // tiled kernel in a fixed order (320x320x32->16: 0.84 against 0.79 ms here -- the price of a reproducible step)
-      if ((KO > 32 || in->gate) && !(pwt_env && pwt_env[0] == '0')) return 0;
-    }
+    // ... and every SE-gated projection: this kernel adds its gate-gradient sums into dgate with global atomics, the
+    // tiled kernel in a fixed order (320x320x32->16: 0.84 against 0.79 ms here -- the price of a reproducible step)
+    if ((KO > 32 || in->gate) && edet_env_int("EDET_PWT", 1) != 0) return 0;
     if (in->gate && a.hw % TR != 0) return 0;   // ... and take every 32-row tile to lie in one image where a gate is involved
     if (tmax <= 4 && KO <= 64) ft = 44;
     else if (tmin <= 3 && tmax <= 9) ft = 39;
     else return 0;
     // r03k lab, 64 -> 64: 80x80 (819 K rows) 0.219 -> 0.165 ms, 40x40 (205 K rows) 0.071 -> 0.070, 20x20 0.030 -> 0.054:
     // the prologue, the LDS reduction of dW and one wave per SIMD need ~250 K rows to pay off
-    if (a.M < env_int("EDET_PWS_FUSED_MINROWS", 262144)) return 0;
+    if (a.M < edet_env_int("EDET_PWS_FUSED_MINROWS", 262144)) return 0;
   }
   a.cr = make_colmap(R);
   a.cx = make_colmap(KO);
@@ -1794,21 +1781,20 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
   const bool gbn = dy->a != nullptr;
   // NOY: BatchNorm backward without the saved convolution output (see the kernel's header): dy carries a BatchNorm
   // backward, the input is a plain stored tensor (x~ = x; no chain epilogue), whole 16-byte chunks of dz.
-  // EDET_PW_NOY=0 keeps the form that reads y (lab switch, read per call).  r03c, first version (column sums of x through
+  // EDET_PW_NOY=0 keeps the form that reads y (test selector, read per call).  r03c, first version (column sums of x through
   // 16 LDS atomics per tile): SLOWER than reading y, 320x320x16->96 1.86 -> 2.31 ms -- the kernel runs one wave per SIMD
   // with one tile of loads in flight and is bound by that latency, not by bytes.  r03d, sums kept in registers across the
   // tiles: 1.90 -> 1.75 ms, 160x160x24->144 0.76 -> 0.68 ms (-8 / -10 %), with 43 % less traffic.
-  const char* noy_env = getenv("EDET_PW_NOY");
   const bool noy = class_a && gbn && (epi->flags & EDET_EPI_Y_IS_CONV_OF_INPUT) && dy->b && dy->cc && !in->scale && !in->gate &&
                    in->act == EDET_ACT_NONE &&
-                   !epi->stat_partials && !epi->dgate && R % 8 == 0 && KO <= 32 && !(noy_env && noy_env[0] == '0');
+                   !epi->stat_partials && !epi->dgate && R % 8 == 0 && KO <= 32 && edet_env_int("EDET_PW_NOY", 1) != 0;
   a.SG = frag_stride(a.KOpad, false);
   a.kxsteps = (KO + 15) / 16;
   const size_t part = (size_t)KO * R + (noy ? (size_t)KO * KO + KO : 0);      // floats per workgroup partial
   // Rows in flight: G tiles of 32 rows per step, as many as an instantiated (NSR, NSX) pair of load passes covers
   // without loading more than ~30 % past the step, the LDS (150 KB) and a budget of ~24 KB of loads per wave allow (the
-  // kernel runs one wave per SIMD: the bytes in flight per wave ARE the latency hiding).  EDET_PWS_FUSED_G caps it
-  // (lab switch).  r03j, D0 640x640 batch 128: 320x320x32->16 1.87 / 1.57 / 1.43 ms at G = 1 / 2 / 4.
+  // kernel runs one wave per SIMD: the bytes in flight per wave ARE the latency hiding).  r03j, D0 640x640 batch 128:
+  // 320x320x32->16 1.87 / 1.57 / 1.43 ms at G = 1 / 2 / 4.
   static const int pairs_noy[][2] = {{13, 2}, {22, 4}};
   static const int pairs_a[][2] = {{12, 4}};
   static const int pairs_44[][2] = {{4, 8}};
@@ -1816,15 +1802,13 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
   const int (*pairs)[2] = class_a ? (noy ? pairs_noy : pairs_a) : (ft == 44 ? pairs_44 : pairs_39);
   const int npairs = class_a ? (noy ? 2 : 1) : (ft == 44 ? 1 : 3);
   const int rbytes = ((gbn && !noy) ? 2 : 1) * Rp * 2, xbytes = (epi->beta ? 2 : 1) * KO * 2;
-  const int g_cap = env_int("EDET_PWS_FUSED_G", 4);
-  const int inflight = env_int("EDET_PWS_FUSED_INFLIGHT", 24 * 1024);
   size_t lds = 0;
   int pick = -1;
   double pick_waste = 1e30;
   a.G = 0;
-  for (int g = g_cap < 4 ? (g_cap < 1 ? 1 : g_cap) : 4; g >= 1; --g) {
+  for (int g = 4; g >= 1; --g) {
     const int nsr = (TR * g + a.cr.rp - 1) / a.cr.rp, nsx = (TR * g + a.cx.rp - 1) / a.cx.rp;
-    if (g > 1 && TR * g * (rbytes + xbytes) > inflight) continue;
+    if (g > 1 && TR * g * (rbytes + xbytes) > 24 * 1024) continue;
     const size_t l = (size_t)a.KOpad * a.SW + (size_t)4 * a.KOpad * 4 +
                      (noy ? (size_t)a.KOpad * 4 + (size_t)a.KOpad * a.SG : 0) +
                      (size_t)WAVES * ((size_t)TR * g * a.SA + (size_t)(epi->beta ? 2 : 1) * TR * g * a.SX +
@@ -1845,7 +1829,7 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
   // one workgroup per compute unit, a single round (r03d lab: grids of 1024 / 512 / 256 -> 320x320x16->96 1.90 / 1.83 /
   // 1.81 ms, 160x160x24->144 0.69 / 0.64 / 0.61 ms: every workgroup pays the prologue and the dW partial once); at
   // least 2 steps per wave, partials bounded by the workspace
-  int grid = env_int("EDET_PWS_FUSED_GRID", 256);
+  int grid = 256;
   const int64_t max_by_ws = (int64_t)(workspace_bytes / sizeof(float)) / (int64_t)part - (noy ? 1 : 0);
   if (grid > max_by_ws) grid = (int)max_by_ws;
   if (grid > EDET_MAX_PARTS) grid = EDET_MAX_PARTS;

@@ -540,11 +540,6 @@ __global__ __launch_bounds__(256) void k_gate_finish(const float* __restrict__ g
   dgate[idx] += tot;
 }
 
-inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && e[0]) ? atoi(e) : dflt;
-}
-
 template <int KT, int NT, bool GBN, int XM, bool OACT, int NSL = 1, int PF = 1>
 int launch(Args& a, int* nparts_out, size_t workspace_bytes, hipStream_t st) {
   auto kern = k_pw_bwd_tile<KT, NT, GBN, XM, OACT, NSL, PF>;
@@ -554,23 +549,20 @@ int launch(Args& a, int* nparts_out, size_t workspace_bytes, hipStream_t st) {
   if (!lds_ok) return 0;
   static const int resident = edet_resident_wgs(reinterpret_cast<const void*>(kern), THREADS, lds);
   a.nsl = (a.K + KT - 1) / KT;
-  // Row splits: one round of resident workgroups (EDET_PWT_ROUNDS rounds), at least EDET_PWT_MINSTEPS steps each,
-  // bounded by the statistic partial rows and the workspace.  Every split writes a K x N fp32 partial that
-  // edet_reduce_partials reads back.
+  // Row splits: the rounds of resident workgroups below, at least 4 steps each, bounded by the statistic partial rows and
+  // the workspace.  Every split writes a K x N fp32 partial that edet_reduce_partials reads back.
   // Rounds of resident workgroups.  One round everywhere except where K is cut into MANY slices (r06 lab, D0 640x640 batch
-  // 128, EDET_PWT_ROUNDS = 1 / 2 / 3 / 4): 40x40x672->112 (11 slices) 0.355 / 0.299 / 0.259 / 0.274 ms, 20x20x672->192 0.179 /
+  // 128, 1 / 2 / 3 / 4 rounds): 40x40x672->112 (11 slices) 0.355 / 0.299 / 0.259 / 0.274 ms, 20x20x672->192 0.179 /
   // 0.164 / 0.144 / 0.163, 20x20x1152->192 (18 slices, two column slices) 0.284 / 0.210 / 0.261 / 0.230, 20x20x1152->320
   // (18 slices, three column slices, one workgroup per CU) 0.608 / 0.496 / 0.454 / 0.390; every layer with <= 8 slices
   // loses 3-30 % beyond one round.  The slices of a row split re-read the same (dz, y) rows and only share them through
   // the L2 while they walk in step: nothing synchronises them, and the longer the split the further they drift apart.
-  int rounds = env_int("EDET_PWT_ROUNDS", 0);
   // (efficientdet-d7x, 384 -> 384 BiFPN / tower layers: 6 slices, three column slices: 96x96 0.239 / 0.214 / 0.162 / 0.183 ms,
   // 48x48 0.094 / 0.077 / 0.076 / 0.076)
-  if (rounds <= 0) rounds = NSL >= 3 ? (a.nsl >= 16 ? 4 : (a.nsl >= 4 ? 3 : 1)) : (a.nsl >= 16 ? 2 : (a.nsl >= 10 ? 3 : 1));
+  const int rounds = NSL >= 3 ? (a.nsl >= 16 ? 4 : (a.nsl >= 4 ? 3 : 1)) : (a.nsl >= 16 ? 2 : (a.nsl >= 10 ? 3 : 1));
   const int slots = (resident > 0 ? resident : 512) * rounds;
-  int S = env_int("EDET_PWT_SPLITS", slots / a.nsl);
-  const int minsteps = env_int("EDET_PWT_MINSTEPS", 4);
-  if (S > a.T / minsteps) S = a.T / minsteps;
+  int S = slots / a.nsl;
+  if (S > a.T / 4) S = a.T / 4;
   if (S > EDET_MAX_PARTS) S = EDET_MAX_PARTS;
   if (S < 1) S = 1;
   const bool gated = a.tv.gate != nullptr && a.epi.dgate != nullptr;
@@ -622,12 +614,11 @@ int pwt_try_bwd(const edet_gview_t* dy, const void* w, int ldw, const edet_tview
   // per compute unit (103 KB of LDS) and loses -- 672->112 0.435 against 0.652 ms, 480->112 0.225 / 0.240, 480->80 0.217 /
   // 0.232, 240->80 0.119 / 0.129 --; with N <= 64 the wide slice wins on the large maps (80x80x240->40 0.296 against
   // 0.357 ms) and is a wash on the small ones (20x20x320->64 0.0287 / 0.0270): wide from 80 x 80 pixels per image up.
-  // EDET_PWT_KT overrides (lab switch).
   const int nt = N <= 64 ? 64 : 128;
   // (decided by the map, not by the batch: the 2-image parity runs then launch the instantiations of the batch-128 step)
-  const int kt = K <= 64 ? 64 : env_int("EDET_PWT_KT", (nt == 64 && in->h * in->w >= 3200) ? 128 : 64);
+  const int kt = K > 64 && nt == 64 && in->h * in->w >= 3200 ? 128 : 64;
   int rc = 0;
-  const bool xgate = in->gate && epi->dgate && !epi->stat_partials && env_int("EDET_PWT_XGATE", 1);
+  const bool xgate = in->gate && epi->dgate && !epi->stat_partials;
   // (PF = 2, two steps of loads in flight, is not instantiated: r04n lab, +-1 % on every layer shape -- these kernels
   // are not short of bytes in flight)
 #define PWT_GO(KT_, NT_, GBN_, XM_, OACT_) rc = launch<KT_, NT_, GBN_, XM_, OACT_>(a, nparts_out, workspace_bytes, st)
@@ -646,9 +637,9 @@ int pwt_try_bwd(const edet_gview_t* dy, const void* w, int ldw, const edet_tview
   } while (0)
   if (N > 128) {
     // column-sliced instantiations (KT = 64, slices of 128): plain or SE-gated input, swish / linear; 7 slices only for
-    // the class-predict layers (no BatchNorm behind them).  EDET_PWT_NSL=0 switches them off (lab switch).
+    // the class-predict layers (no BatchNorm behind them).
     const int nsl = (N + 127) / 128;
-    if (oact || (xgen && !xgate) || !env_int("EDET_PWT_NSL", 1)) return 0;
+    if (oact || (xgen && !xgate)) return 0;
     // Every K slice re-reads the whole N-wide gradient pair: with more than two slices that only pays on the small maps,
     // where the re-reads come out of the L2 / MALL (r04k, efficientdet-d7x 1536x1536 batch 8: 384->384 at 192x192 10.4 ->
     // 14.7 ms over 18 layers, at 96x96 4.0 -> 5.8, at 24x24 0.92 -> 0.78; D0 20x20x1152->192 0.417 -> 0.284 ms): up to 8192
@@ -658,17 +649,16 @@ int pwt_try_bwd(const edet_gview_t* dy, const void* w, int ldw, const edet_tview
     // r06: with 2-4 rounds of row splits (launch) the sliced kernel also wins on efficientdet-d7x's 96 x 96 projections --
     // 1344->224 0.92 -> 0.32 ms, 960->160 0.69 -> 0.23 ms per call at batch 8 -- which the round-4 limit of 8192 pixels
     // left to the two-kernel path; and on its 192 x 192 BiFPN layers (384 -> 384: 0.64 -> 0.48 ms)
-    if (K > 128 && hw > env_int("EDET_PWT_NSL_MAXHW", 65536)) return 0;
-    const bool wide_expand = nsl > 3 && nsl <= 6 && gbn && !xgen && K <= 128 && env_int("EDET_PWT_WIDE", 1);
+    if (K > 128 && hw > 65536) return 0;
+    const bool wide_expand = nsl > 3 && nsl <= 6 && gbn && !xgen && K <= 128;
     // 7 slices (class predict): up to two K slices (efficientdet-d0 .. d2: 64 / 88 / 112 filters) -- every further slice
     // re-reads the 810-column gradient --, and any K on the small maps, where the two-kernel path would run the generic
     // weight gradient (fp32 atomics) and the re-reads cost nothing (maps up to 8192 pixels per image)
-    if (nsl > 3 && !wide_expand && (nsl > 7 || gbn || xgen || (K > 128 && hw > env_int("EDET_PWT_NSL_MAXHW", 65536)))) return 0;
+    if (nsl > 3 && !wide_expand && (nsl > 7 || gbn || xgen)) return 0;
     // r04d lab (D0 640x640 batch 128): 80x80x40->240 0.437 -> 0.210 ms, 40x40x40->240 0.109 -> 0.055, 20x20x1152->192 0.417 ->
     // 0.284, 20x20x672->192 0.266 -> 0.180; three slices hold one workgroup per compute unit (94 KB of LDS) and LOSE on
     // the gated 20x20x1152->320 (0.571 -> 0.612 ms) -- kept all the same: the two-kernel path adds the SE gate-gradient
-    // sums with global atomics, this one in a fixed order (EDET_PWT_NSL3=0 switches it off)
-    if (nsl == 3 && xgate && !env_int("EDET_PWT_NSL3", 1)) return 0;
+    // sums with global atomics, this one in a fixed order
 #define PWT_N(NSL_, GBN_, XM_) rc = launch<64, 128, GBN_, XM_, false, NSL_>(a, nparts_out, workspace_bytes, st)
 #define PWT_NX(NSL_)                                   \
   do {                                                 \
@@ -686,8 +676,7 @@ int pwt_try_bwd(const edet_gview_t* dy, const void* w, int ldw, const edet_tview
 #undef PWT_N
   } else if (kt == 64 && nt == 64) PWT_G(64, 64);
   else if (kt == 64) PWT_G(64, 128);
-  else if (nt == 64) PWT_G(128, 64);
-  else PWT_G(128, 128);
+  else PWT_G(128, 64);      // (kt = 128 only with nt = 64)
 #undef PWT_G
 #undef PWT_X
 #undef PWT_GO

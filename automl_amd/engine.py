@@ -17,7 +17,6 @@ import contextlib
 import ctypes
 import re
 import math
-import os
 
 import numpy as np
 import torch
@@ -286,9 +285,9 @@ class Engine(object):
     self._build_params(params, seed, arena)
     cmax = max([p.shape[0] for p in self.spec.params if len(p.shape) == 1] + [64])
     self._cmax = cmax
-    # batched weight-gradient reductions (see _ws): EDET_DEFER_REDUCE=0 = one reduction launch per layer, as in round 3
-    self.defer_reduce = os.environ.get('EDET_DEFER_REDUCE', '1') != '0'
-    self.fuse_wfold = os.environ.get('EDET_FUSE_WFOLD', '1') != '0'
+    # batched weight-gradient reductions (see _ws); False = one reduction launch per layer, as in round 3 (the tests
+    # compare both forms)
+    self.defer_reduce = True
     self._deferring = False
     self._defer_streams = set()
     ws_floats = (64 if self.defer_reduce else 16) * 1024 * 1024      # 256 MiB with deferral (64 MiB: the round-3 scratch)
@@ -314,13 +313,7 @@ class Engine(object):
     self._cast_items = {}      # weight name -> descriptors of its compute copies (filled by the first pass)
     self._cast_table = None
     self.batched_casts = True    # every compute copy of a step in one edet_cast_batch launch
-    # inference forward with bf16 storage: the class / box logits are stored as fp32 (edet_pw_fwd_f32out) -- rounding them to
-    # bf16 is 3e-3 of their range and the whole of what separated the path from the 1e-3 of north_star
-    # (scripts/precision_sweep.py, DESIGN section 4); the training step keeps bf16 logits (they only feed the loss)
-    self.logits_f32 = os.environ.get('EDET_LOGITS_F32', '1') != '0'
     self._f32_island = False
-    self.fuse_merge_identity = os.environ.get('EDET_FUSE_MERGE', '1') != '0'   # BiFPN backward: see Engine.fuse
-    self.overlap_s2_wgrad = os.environ.get('EDET_S2_OVERLAP', '0') == '1'
     # bucketed gradient all-reduce overlapped with the backward pass (set_overlap_reduce): None = off
     self._overlap_reduce = None
     self._reduce_marks = {}
@@ -328,10 +321,9 @@ class Engine(object):
     self._bucket_no = 0
     # head of an MBConv block (expansion -> BatchNorm -> activation -> depthwise) in one kernel where the library has one
     # (mbconv_fused.hip: bf16, <= 32 block-input channels): the expanded tensor is not read back by the depthwise
-    # convolution -- and never stored at all in inference.  EDET_MBCONV_FUSED=0: the two-kernel path (lab switch)
-    self.fused_mbconv_head = os.environ.get('EDET_MBCONV_FUSED', '1') != '0'
+    # convolution -- and never stored at all in inference (always on; bench.py reports it)
+    self.fused_mbconv_head = True
     self.fused_heads = set()     # block scopes whose head ran fused in the last forward pass (inference: no ':exp' tensor)
-    self.fused_dw_bwd = True     # one edet_dw_bwd call per layer (bf16: ONE kernel for both gradients, any stride)
     self.fused_pw_bwd = True     # one edet_pw_bwd call per pointwise layer whose input needs a gradient
     # cross-replica BatchNorm (utils.SyncBatchNormalization / TpuBatchNormalization, utils.py:166-241):
     # (all_reduce_fn, world_size) or None.  Set by train_lib when sync_bn=True.
@@ -657,7 +649,7 @@ class Engine(object):
   # ------------------------------------------------------------------ layers
   def pw(self, key, vin, wname, cout, bias=None, bn=None, act=ACT_NONE, ld=None, f32out=False, bias_grad=False):
     """1x1 conv (+bias) [-> BN -> act as a view].  f32out (inference, bf16 storage): the output is stored as fp32 --
-    the class / box logits, whose bf16 rounding alone is 3e-3 of their range (Engine.logits_f32)."""
+    the class / box logits, whose bf16 rounding alone is 3e-3 of their range (Engine._head_level)."""
     r = vin.raw
     cin = r.c
     wt, ldk, w, ldn = self._pw_copies(wname, cin, cout)
@@ -807,45 +799,19 @@ class Engine(object):
     g = self._gview(vout)
     nb = (vin.raw.rows + vout.raw.rows) * vin.raw.c * self.esize
     tag = '%dx%dx%d k%ds%d' % (vin.raw.h, vin.raw.w, vin.raw.c, k, stride)
-    if vin.raw.needs_grad and self.fused_dw_bwd:
-      epi, fused = self._epi(vin)
-      call('edet_dw_bwd', ctypes.byref(g), ptr(self.param(wname)), k, stride, ctypes.byref(vin.tview()),
-           ctypes.byref(epi), ctypes.byref(self._nparts), ptr(self.grad(wname)), *self._ws(), self.dtype, self.stream, nbytes=2 * nb, tag=tag)
-      self._ws_mark()
-      vin.raw.grad_written = True
-      if fused:
-        self._bn_bwd_finalize(vin.bn, self._nparts.value)
-      return
-    gptr = ptr(self.grad(wname))
-
-    def wgrad():
-      call('edet_dw_bwd_weight', ctypes.byref(vin.tview()), ctypes.byref(g), k, stride, gptr,
+    if not vin.raw.needs_grad:
+      call('edet_dw_bwd_weight', ctypes.byref(vin.tview()), ctypes.byref(g), k, stride, ptr(self.grad(wname)),
            *self._ws(), self.dtype, self.stream, nbytes=nb, tag=tag)
       self._ws_mark()
-
-    def dgrad():
-      epi, fused = self._epi(vin)
-      call('edet_dw_bwd_data', ctypes.byref(g), ptr(self.param(wname)), k, stride, ctypes.byref(vin.tview()),
-           ctypes.byref(epi), ctypes.byref(self._nparts), self.dtype, self.stream, nbytes=nb, tag=tag)
-      vin.raw.grad_written = True
-      if fused:
-        self._bn_bwd_finalize(vin.bn, self._nparts.value)
-
-    if vin.raw.needs_grad and self.overlap_s2_wgrad and self.training and self.sync_bn is None and self._branch is self._main:
-      # Stride-2 layer: the weight-gradient kernel (nothing on the chain waits for it) on the side stream NEXT TO the
-      # data-gradient kernel -- both march over the same (dz, y, x), the second reader finds them in the L2 / MALL
-      # (Engine.overlap_s2_wgrad; the side chain records its reduction on its own stream and flushes before the join)
-      def side_job():
-        self._defer_begin()
-        try:
-          wgrad()
-        finally:
-          self._defer_end()
-      self._fork_join(dgrad, side_job)
       return
-    wgrad()
-    if vin.raw.needs_grad:
-      dgrad()
+    # both gradients in one call (bf16: ONE kernel, any stride)
+    epi, fused = self._epi(vin)
+    call('edet_dw_bwd', ctypes.byref(g), ptr(self.param(wname)), k, stride, ctypes.byref(vin.tview()),
+         ctypes.byref(epi), ctypes.byref(self._nparts), ptr(self.grad(wname)), *self._ws(), self.dtype, self.stream, nbytes=2 * nb, tag=tag)
+    self._ws_mark()
+    vin.raw.grad_written = True
+    if fused:
+      self._bn_bwd_finalize(vin.bn, self._nparts.value)
 
   def se(self, key, v, scope, se_filters):
     """Squeeze-and-excitation: returns the gated view of v (efficientnet_model.py:183-195)."""
@@ -969,8 +935,9 @@ class Engine(object):
     method = (2 if wm in ('attn', 'channel_attn') else 0) if wnames else 1
     wp = [ptr(self.param(w)) for w in wnames] + [None] * (3 - len(wnames)) if wnames else [None] * 3
     # scalar fusion variables: normalised inside the fusion kernel, their gradient inside the ordered finish of dwn (no
-    # edet_fuse_weights / edet_fuse_weights_bwd launches: 50 of them per D0 step; EDET_FUSE_WFOLD=0: separate launches)
-    wfold = self.fuse_wfold and wc == 1
+    # edet_fuse_weights / edet_fuse_weights_bwd launches: 50 of them per D0 step); per-channel weight vectors still take
+    # those launches
+    wfold = wc == 1
     wraw = (ctypes.c_void_p * 3)(*wp) if wfold else None
     if not wfold:
       call('edet_fuse_weights', wp[0], wp[1], wp[2], nin, method, ptr(wn), wc, self.stream)
@@ -995,7 +962,7 @@ class Engine(object):
         tvp2 = [ctypes.byref(t) for t in tv2] + [None] * (3 - nin)
         # identity inputs that need a gradient: written by the fusion kernel itself (no edet_fuse_bwd_input launch, no
         # second read of ds); ds is stored only when a resampled input still has to read it
-        merged = [self.fuse_merge_identity and modes[i] == RS_IDENTITY and v.raw.needs_grad for i, v in enumerate(inputs)]
+        merged = [modes[i] == RS_IDENTITY and v.raw.needs_grad for i, v in enumerate(inputs)]
         gin = (ctypes.c_void_p * 3)()
         gbeta = (ctypes.c_int * 3)()
         for i, v in enumerate(inputs):
@@ -1167,7 +1134,7 @@ class Engine(object):
                        survival_prob=sps[b.index] if sps else None)
 
   def _mbconv_head_fusable(self, vin, cexp, k, stride):
-    if not self.fused_mbconv_head or self.dtype != EDET_BF16 or self.act == ACT_NONE:
+    if self.dtype != EDET_BF16 or self.act == ACT_NONE:
       return False
     return _lib.load().edet_mbconv_fused_supported(ctypes.byref(vin.tview()), cexp, k, stride, self.dtype) == 1
 
@@ -1276,7 +1243,7 @@ class Engine(object):
         x = y
     s = '%s/%s-predict' % (net, prefix)
     key = '%s:l%d' % (s, level)
-    if net == 'box_net' and self.logits_f32 and not self.training and self.dtype == EDET_BF16:
+    if net == 'box_net' and not self.training and self.dtype == EDET_BF16:
       # Inference, bf16 storage: the BOX-predict layer (depthwise 3x3 + 64 -> 36 pointwise) runs in fp32.  Error budget
       # of the box logits against the fp32 oracle (scripts/precision_sweep.py, d0 640x640): bf16 matrix-core operands of
       # this one layer 1.1e-3 of the range, its depthwise output stored as bf16 6.1e-4, everything else together 3e-4
@@ -1284,8 +1251,11 @@ class Engine(object):
       with self._fp32_island():
         d = self.dw(key + ':dw:f32', self._to_f32(key + ':x:f32', x), s + '/depthwise_kernel', 3, 1)
         return self.pw(key + ':pw:f32', d, s + '/pointwise_kernel', out_ch, bias=s + '/bias')
+    # inference forward with bf16 storage: the class / box logits are stored as fp32 (edet_pw_fwd_f32out) -- rounding them to
+    # bf16 is 3e-3 of their range and the whole of what separated the path from the 1e-3 of north_star
+    # (scripts/precision_sweep.py, DESIGN section 4); the training step keeps bf16 logits (they only feed the loss)
     d = self.dw(key + ':dw', x, s + '/depthwise_kernel', 3, 1)
-    return self.pw(key + ':pw', d, s + '/pointwise_kernel', out_ch, bias=s + '/bias', f32out=self.logits_f32)
+    return self.pw(key + ':pw', d, s + '/pointwise_kernel', out_ch, bias=s + '/bias', f32out=True)
 
   def _head(self, feats, net, prefix, out_ch):
     return [self._head_level(feat, self.config.min_level + li, net, prefix, out_ch) for li, feat in enumerate(feats)]
@@ -1301,7 +1271,7 @@ class Engine(object):
       for i in range(c.box_class_repeats):
         self._pw_copies('%s/%s-%d/pointwise_kernel' % (net, prefix, i), c.fpn_num_filters, c.fpn_num_filters)
       self._pw_copies('%s/%s-predict/pointwise_kernel' % (net, prefix), c.fpn_num_filters, out_ch)
-    if self.logits_f32 and not self.training and self.dtype == EDET_BF16:
+    if not self.training and self.dtype == EDET_BF16:
       # ... and the fp32 copies of the box-predict kernel (_head_level's fp32 island): the chain that casts them first would
       # otherwise do so on ITS stream while the other chain reads the same buffer with no event in between
       with self._fp32_island():

@@ -1,10 +1,11 @@
 """Kernel lab: HIP-event timing of single C-ABI entry points at the layer shapes of EfficientDet-D0 640x640 batch 128
-(bf16), with in-process A/B over the environment switches that the library reads per call.
+(bf16), with in-process A/B over the implementation selectors that the library reads per call
+(INTEGRATION.md section 10).
 
 The whole-step bench (bench.py) costs ~40 s of GPU time per variant; a kernel-level A/B here costs a few seconds:
 
   python scripts/kernel_lab.py --entry pw_bwd_weight --layers mid --ab EDET_PW_IMPL=auto,big,stream
-  python scripts/kernel_lab.py --entry pw_bwd_data --shape 128x20x20x1152x192 --ab EDET_PW_BIG_MINKN=2048,1000000
+  python scripts/kernel_lab.py --entry pw_bwd --shape 128x80x80x64x64 --ab EDET_PWT=1,0
   python scripts/kernel_lab.py --entry dw_bwd --layers all --reps 5
   python scripts/kernel_lab.py --list                                      # the layer tables, no GPU needed
 

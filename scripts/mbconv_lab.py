@@ -1,6 +1,6 @@
 """Lab: the fused MBConv head (edet_mbconv_expand_stats + edet_mbconv_expand_dw_fwd) against the two-kernel path
 (edet_pw_fwd + edet_dw_fwd) at the three layer shapes of EfficientDet-D0 640x640 batch 128 that the engine fuses.
-HIP-event time per call; environment switches of the library (EDET_MBF_*) are read per call.
+HIP-event time per call.
 
   python scripts/mbconv_lab.py [--batch 128] [--reps 10]
 """

@@ -48,6 +48,33 @@ def test_struct_layouts_match_header():
   assert ctypes.sizeof(_lib.BwdEpi) == 7 * 8                  # int beta and int flags padded
 
 
+def test_environment_variables_are_documented():
+  """The EDET_* variables the library reads (automl_amd/csrc: getenv / edet_env_int) are exactly the rows of the table in
+  INTEGRATION.md section 10, and every EDET_* variable the Python package reads is described somewhere in INTEGRATION.md."""
+  csrc = os.path.join(ROOT, 'automl_amd', 'csrc')
+  lib_reads = set()
+  for name in os.listdir(csrc):
+    path = os.path.join(csrc, name)
+    if os.path.isfile(path):
+      lib_reads |= set(re.findall(r'\b(?:getenv|edet_env_int)\(\s*"(EDET_\w+)"', open(path).read()))
+  doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+  section = doc.split('\n## 10.', 1)[1].split('\n## ', 1)[0]
+  table = set()
+  for line in section.splitlines():
+    if line.startswith('| `EDET_'):
+      table |= set(re.findall(r'EDET_\w+', line.split('|')[1]))
+  assert lib_reads and lib_reads == table, ('read but not in the table', lib_reads - table, 'in the table but not read',
+                                            table - lib_reads)
+  pkg = os.path.join(ROOT, 'automl_amd')
+  py_reads = set()
+  for name in os.listdir(pkg):
+    if name.endswith('.py'):
+      py_reads |= set(re.findall(r"os\.environ\.get\(\s*['\"](EDET_\w+)['\"]", open(os.path.join(pkg, name)).read()))
+  assert py_reads, 'no environment reads found in automl_amd/*.py'
+  missing = sorted(n for n in py_reads if n not in doc)
+  assert not missing, missing
+
+
 def test_missing_library_fails_loudly(monkeypatch):
   monkeypatch.setattr(_lib, '_lib', None)
   monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libedet_hip.so')

@@ -499,8 +499,8 @@ def test_model_backward_bf16_deferred_reductions_equal_immediate_ones():
   """bf16 storage (EffNetV2Model's default): the weight-gradient partial sums of a layer wait in the workspace for
   the batched reduction (Engine._ws / _ws_mark), so every later call -- the stem's weight gradient is the last one --
   has to work BEHIND them (V2Engine.stem_bwd handed the stem kernel the workspace BASE, on top of the first
-  recorded layer's partial rows).  The same backward pass with one reduction launch per layer (EDET_DEFER_REDUCE=0
-  semantics, nothing waits in the workspace) must give the same gradients up to the summation order of the partial rows
+  recorded layer's partial rows).  The same backward pass with one reduction launch per layer (Engine.defer_reduce
+  = False, nothing waits in the workspace) must give the same gradients up to the summation order of the partial rows
   (the batched kernel adds them in another fixed order than the immediate one: <= 1e-4 of a tensor's largest element, where
   an overwritten partial row is an error of order one), and each mode is bit-reproducible on its own."""
   model_name, size, over, batch = 'efficientnetv2-b0', 64, 'num_classes=24,survival_prob=0,dropout_rate=0', 4

@@ -399,7 +399,6 @@ def test_pw_bwd_tile(shape, mode, gbn, monkeypatch):
   if 384 < shape[4] <= 768 and not gbn:
     pytest.skip('4 / 6 slices: instantiated for the MBConv expansions only (BatchNorm behind the convolution)')
   monkeypatch.setenv('EDET_PWS_FUSED_WIDE', '0')      # keep the wave-private one-pass kernel to its expand shapes
-  monkeypatch.setenv('EDET_PWT_NSL3', '1')            # the three-slice gated instantiation is off by default (slower)
   _lib.launch_log_start()
   try:
     first = pw_bwd_case(bf16, shape, mode, gbn, 'auto', one_call=True, conv_y=False)
