@@ -55,6 +55,18 @@ struct Named {
   uint64_t off, bytes;
 };
 
+// One entry of the plan's variable table: `off` / `count` are ELEMENTS inside the variable's fp32 arena ("params" and the
+// slot arenas of the same layout for a trainable variable, "bn_state" for a moving statistic).
+struct Var {
+  std::string name;
+  int trainable = 0;
+  int rank = 0;
+  int64_t dims[4] = {0, 0, 0, 0};
+  uint64_t off = 0, count = 0;
+};
+constexpr int NUM_SLOTS = 4;
+const char* const kSlotNames[NUM_SLOTS] = {"value", "ema", "momentum", "adam_v"};
+
 }  // namespace
 
 struct edet_net {
@@ -68,6 +80,12 @@ struct edet_net {
   std::vector<hipEvent_t> events;
   std::vector<std::vector<unsigned char>*> blobs;
   bool use_graph = false;
+  std::vector<Var> vars;                 // the variable table, in the Python arena's creation order
+  std::map<std::string, int64_t> var_index;
+  bool has_vars = false;
+  int optimizer = -1;                    // property "optimizer": 0 sgd, 1 adam; -1 = a plan without it
+  int64_t iterations = 0;
+  double beta1 = 0.0, beta2 = 0.0;       // Adam plans
   edet_allreduce_fn allreduce = nullptr;
   void* allreduce_ctx = nullptr;
 };
@@ -364,6 +382,64 @@ extern "C" int edet_create(const char* plan_path, edet_net_t** net_out) {
     }
     NET_CHECK(r.ok, "edet_create: truncated plan (program '%s')", prog.name.c_str());
   }
+  // the variable table (optional section behind the last program; layout: automl_amd/plan.py)
+  if (net->props.count("num_variables")) {
+    char vmagic[8];
+    NET_CHECK(fread(vmagic, 1, 8, f) == 8 && memcmp(vmagic, "EDETVARS", 8) == 0,
+              "edet_create: the plan announces a variable table and holds none");
+    const uint32_t nvars = r.get<uint32_t>();
+    NET_CHECK(r.ok && (int64_t)nvars == net->props["num_variables"], "edet_create: bad variable table (count)");
+    auto arena_elems = [&](const char* arena) -> int64_t {
+      auto it = net->names.find(arena);
+      return it == net->names.end() ? -1 : (int64_t)(it->second.bytes / 4);
+    };
+    const int64_t cap_train = arena_elems("params"), cap_state = arena_elems("bn_state");
+    for (const char* slot : {"ema", "velocity", "adam_v"}) {
+      const int64_t c = arena_elems(slot);
+      NET_CHECK(c < 0 || c == cap_train, "edet_create: bad variable table (the '%s' arena is not of the size of 'params')", slot);
+    }
+    net->vars.reserve(nvars < 65536 ? nvars : 65536);
+    for (uint32_t i = 0; i < nvars; ++i) {
+      Var v;
+      v.name = r.str();
+      v.trainable = r.get<uint8_t>() ? 1 : 0;
+      v.rank = r.get<uint8_t>();
+      NET_CHECK(r.ok && v.rank <= 4, "edet_create: bad variable table (entry %u)", i);
+      uint64_t prod = 1;
+      bool fits = true;
+      for (int d = 0; d < v.rank; ++d) {
+        const uint64_t dim = r.get<uint64_t>();
+        fits = fits && dim <= (1ull << 40) && (dim == 0 || prod <= (1ull << 40) / dim);
+        if (fits) prod *= dim;
+        v.dims[d] = (int64_t)dim;
+      }
+      v.off = r.get<uint64_t>();
+      v.count = r.get<uint64_t>();
+      const int64_t cap = v.trainable ? cap_train : cap_state;
+      NET_CHECK(r.ok && fits && v.count == prod && cap >= 0 && v.count <= (uint64_t)cap && v.off <= (uint64_t)cap - v.count,
+                "edet_create: bad variable table (variable '%s' does not fit its arena)", v.name.c_str());
+      NET_CHECK(net->var_index.emplace(v.name, (int64_t)i).second, "edet_create: bad variable table ('%s' twice)", v.name.c_str());
+      net->vars.push_back(v);
+    }
+    net->has_vars = true;
+  }
+  {
+    auto prop = [&](const char* name, int64_t fallback) {
+      auto it = net->props.find(name);
+      return it == net->props.end() ? fallback : it->second;
+    };
+    net->optimizer = (int)prop("optimizer", -1);
+    net->iterations = prop("iterations", 0);
+    NET_CHECK(net->optimizer >= -1 && net->optimizer <= 1 && net->iterations >= 0, "edet_create: bad optimizer properties");
+    if (net->optimizer == 1) {
+      NET_CHECK(net->props.count("adam_beta1_bits") && net->props.count("adam_beta2_bits"),
+                "edet_create: an Adam plan without its beta properties");
+      const int64_t b1 = net->props["adam_beta1_bits"], b2 = net->props["adam_beta2_bits"];
+      memcpy(&net->beta1, &b1, 8);
+      memcpy(&net->beta2, &b2, 8);
+      NET_CHECK(net->beta1 >= 0.0 && net->beta1 < 1.0 && net->beta2 >= 0.0 && net->beta2 < 1.0, "edet_create: bad Adam betas");
+    }
+  }
   // initial contents, through one pinned staging buffer
   {
     const size_t CH = 64u << 20;
@@ -458,11 +534,244 @@ extern "C" int edet_train_step(edet_net_t* net, float learning_rate, float ema_d
   EDET_CHECK(it != net->names.end() && it->second.bytes >= 8, "edet_train_step: the plan names no 'hyper' buffer");
   // per-step scalars of the schedule: a stream-ordered copy from pageable memory (staged by the runtime before it
   // returns), in front of -- never inside -- the replayed graph, as Engine.set_hyper does
-  const float h[2] = {learning_rate, ema_decay};
+  float h[2] = {learning_rate, ema_decay};
+  if (net->optimizer == 1) {
+    // tf.keras Adam's bias-corrected rate of THIS step, in the operation order of Engine.set_hyper (engine.py):
+    // lr * sqrt(1 - beta2 ** t) / (1 - beta1 ** t) in double, rounded to float once
+#pragma clang fp contract(off)
+    const double t = (double)(net->iterations + 1);
+    const double alpha = (double)learning_rate * sqrt(1.0 - pow(net->beta2, t)) / (1.0 - pow(net->beta1, t));
+    h[0] = (float)alpha;
+  }
   const hipError_t e = hipMemcpyAsync((char*)net->bufs[it->second.buf] + it->second.off, h, sizeof(h), hipMemcpyHostToDevice,
                                       reinterpret_cast<hipStream_t>(stream));
   EDET_CHECK(e == hipSuccess, "edet_train_step: hipMemcpyAsync: %s", hipGetErrorString(e));
-  return run_program(net, "train_step", stream);
+  const int rc = run_program(net, "train_step", stream);
+  if (rc == 0) ++net->iterations;
+  return rc;
+}
+
+// ---- variables by name ------------------------------------------------------------------------------------------------
+namespace {
+
+// Device address of a variable's slot, or nullptr with the error text set (the message names the variable).
+float* slot_ptr(edet_net* net, const Var& v, int slot, const char* who) {
+  if (slot < 0 || slot >= NUM_SLOTS) {
+    edet_set_error("%s: variable '%s': unknown slot %d", who, v.name.c_str(), slot);
+    return nullptr;
+  }
+  if (slot != EDET_SLOT_VALUE && !v.trainable) {
+    edet_set_error("%s: variable '%s' is not trainable: it has no %s slot", who, v.name.c_str(), kSlotNames[slot]);
+    return nullptr;
+  }
+  const char* arena = slot == EDET_SLOT_VALUE ? (v.trainable ? "params" : "bn_state")
+                      : slot == EDET_SLOT_EMA ? "ema" : slot == EDET_SLOT_MOMENTUM ? "velocity" : "adam_v";
+  auto it = net->names.find(arena);
+  if (it == net->names.end() || (slot == EDET_SLOT_ADAM_V && net->optimizer != 1)) {
+    edet_set_error("%s: variable '%s' has no %s slot in this plan%s", who, v.name.c_str(), kSlotNames[slot],
+                   slot == EDET_SLOT_ADAM_V ? " (its optimizer is not Adam)" : "");
+    return nullptr;
+  }
+  return (float*)((char*)net->bufs[it->second.buf] + it->second.off) + v.off;      // bounds: checked by edet_create
+}
+
+bool has_slot(edet_net* net, const Var& v, int slot) {
+  if (slot == EDET_SLOT_VALUE) return true;
+  if (!v.trainable) return false;
+  if (slot == EDET_SLOT_ADAM_V) return net->optimizer == 1 && net->names.count("adam_v");
+  return net->names.count(slot == EDET_SLOT_EMA ? "ema" : "velocity") != 0;
+}
+
+const Var* find_var(edet_net* net, const char* name, const char* who) {
+  if (!net || !name) {
+    edet_set_error("%s: null argument", who);
+    return nullptr;
+  }
+  if (!net->has_vars) {
+    edet_set_error("%s: variable '%s': the plan was recorded without a variable table", who, name);
+    return nullptr;
+  }
+  auto it = net->var_index.find(name);
+  if (it == net->var_index.end()) {
+    edet_set_error("%s: the plan has no variable '%s'", who, name);
+    return nullptr;
+  }
+  return &net->vars[(size_t)it->second];
+}
+
+}  // namespace
+
+extern "C" int edet_net_num_variables(edet_net_t* net, int64_t* count) {
+  EDET_CHECK(net && count, "edet_net_num_variables: null argument");
+  EDET_CHECK(net->has_vars, "edet_net_num_variables: the plan was recorded without a variable table");
+  *count = (int64_t)net->vars.size();
+  return 0;
+}
+
+extern "C" int edet_net_variable_info(edet_net_t* net, int64_t index, edet_var_info* out) {
+  EDET_CHECK(net && out, "edet_net_variable_info: null argument");
+  EDET_CHECK(net->has_vars, "edet_net_variable_info: the plan was recorded without a variable table");
+  EDET_CHECK(index >= 0 && index < (int64_t)net->vars.size(), "edet_net_variable_info: index %lld of %lld variables",
+             (long long)index, (long long)net->vars.size());
+  const Var& v = net->vars[(size_t)index];
+  out->name = v.name.c_str();
+  out->rank = v.rank;
+  out->trainable = v.trainable;
+  for (int d = 0; d < 4; ++d) out->dims[d] = v.dims[d];
+  out->count = (int64_t)v.count;
+  return 0;
+}
+
+extern "C" int edet_net_find_variable(edet_net_t* net, const char* name, int64_t* index) {
+  EDET_CHECK(index, "edet_net_find_variable: null argument");
+  const Var* v = find_var(net, name, "edet_net_find_variable");
+  if (!v) return -1;
+  *index = (int64_t)(v - net->vars.data());
+  return 0;
+}
+
+extern "C" int edet_get_variable(edet_net_t* net, const char* name, int slot, float* host, int64_t capacity) {
+  const Var* v = find_var(net, name, "edet_get_variable");
+  if (!v) return -1;
+  EDET_CHECK(host && capacity >= (int64_t)v->count, "edet_get_variable: variable '%s' has %lld elements, the capacity is %lld",
+             name, (long long)v->count, (long long)capacity);
+  float* p = slot_ptr(net, *v, slot, "edet_get_variable");
+  if (!p) return -1;
+  return edet_copy_to_host(host, p, (size_t)v->count * 4);
+}
+
+extern "C" int edet_set_variable(edet_net_t* net, const char* name, int slot, const float* host, int64_t count) {
+  const Var* v = find_var(net, name, "edet_set_variable");
+  if (!v) return -1;
+  EDET_CHECK(host && count == (int64_t)v->count, "edet_set_variable: variable '%s' has %lld elements, got %lld", name,
+             (long long)v->count, (long long)count);
+  float* p = slot_ptr(net, *v, slot, "edet_set_variable");
+  if (!p) return -1;
+  if (edet_copy_to_device(p, host, (size_t)v->count * 4) != 0) return -1;
+  // until the first optimizer step the moving average follows the variable (ParamArena.set_params)
+  if (slot == EDET_SLOT_VALUE && v->trainable && net->iterations == 0 && has_slot(net, *v, EDET_SLOT_EMA)) {
+    float* e = slot_ptr(net, *v, EDET_SLOT_EMA, "edet_set_variable");
+    if (!e || edet_copy_to_device(e, host, (size_t)v->count * 4) != 0) return -1;
+  }
+  return 0;
+}
+
+extern "C" int edet_net_get_iterations(edet_net_t* net, int64_t* iterations) {
+  EDET_CHECK(net && iterations, "edet_net_get_iterations: null argument");
+  *iterations = net->iterations;
+  return 0;
+}
+
+extern "C" int edet_net_set_iterations(edet_net_t* net, int64_t iterations) {
+  EDET_CHECK(net, "edet_net_set_iterations: null network");
+  EDET_CHECK(iterations >= 0, "edet_net_set_iterations: negative iteration count %lld", (long long)iterations);
+  net->iterations = iterations;
+  return 0;
+}
+
+// State files (layout: include/edet_net.h).
+extern "C" int edet_net_save_state(edet_net_t* net, const char* path) {
+  EDET_CHECK(net && path, "edet_net_save_state: null argument");
+  EDET_CHECK(net->has_vars, "edet_net_save_state: the plan was recorded without a variable table");
+  uint32_t nrec = 0;
+  for (const Var& v : net->vars)
+    for (int slot = 0; slot < NUM_SLOTS; ++slot) nrec += has_slot(net, v, slot) ? 1 : 0;
+  FILE* f = fopen(path, "wb");
+  EDET_CHECK(f, "edet_net_save_state: cannot open %s", path);
+  const uint32_t version = 1;
+  bool good = fwrite("EDETSTAT", 1, 8, f) == 8 && fwrite(&version, 4, 1, f) == 1 && fwrite(&nrec, 4, 1, f) == 1 &&
+              fwrite(&net->iterations, 8, 1, f) == 1;
+  std::vector<float> host;
+  int rc = 0;
+  for (size_t i = 0; good && rc == 0 && i < net->vars.size(); ++i) {
+    const Var& v = net->vars[i];
+    for (int slot = 0; good && rc == 0 && slot < NUM_SLOTS; ++slot) {
+      if (!has_slot(net, v, slot)) continue;
+      float* p = slot_ptr(net, v, slot, "edet_net_save_state");
+      host.resize((size_t)v.count + 1);
+      rc = p ? edet_copy_to_host(host.data(), p, (size_t)v.count * 4) : -1;
+      const uint16_t len = (uint16_t)v.name.size();
+      const uint8_t s8 = (uint8_t)slot, r8 = (uint8_t)v.rank;
+      good = fwrite(&len, 2, 1, f) == 1 && fwrite(v.name.data(), 1, len, f) == len && fwrite(&s8, 1, 1, f) == 1 &&
+             fwrite(&r8, 1, 1, f) == 1;
+      for (int d = 0; good && d < v.rank; ++d) {
+        const uint64_t dim = (uint64_t)v.dims[d];
+        good = fwrite(&dim, 8, 1, f) == 1;
+      }
+      good = good && fwrite(&v.count, 8, 1, f) == 1 && fwrite(host.data(), 4, (size_t)v.count, f) == (size_t)v.count;
+    }
+  }
+  good = (fclose(f) == 0) && good;
+  if (rc != 0) return rc;
+  EDET_CHECK(good, "edet_net_save_state: could not write %s", path);
+  return 0;
+}
+
+extern "C" int edet_net_load_state(edet_net_t* net, const char* path) {
+  EDET_CHECK(net && path, "edet_net_load_state: null argument");
+  EDET_CHECK(net->has_vars, "edet_net_load_state: the plan was recorded without a variable table");
+  FILE* f = fopen(path, "rb");
+  EDET_CHECK(f, "edet_net_load_state: cannot open %s", path);
+  struct Rec { const Var* v; int slot; std::vector<float> data; };
+  std::vector<Rec> recs;
+  std::vector<char> seen(net->vars.size() * NUM_SLOTS, 0);
+  Reader r{f};
+  char magic[8];
+  int64_t iterations = 0;
+  // pass 1: read and check everything; nothing on the device changes unless the whole file is good
+#define STATE_CHECK(cond, ...)       \
+  do {                               \
+    if (!(cond)) {                   \
+      edet_set_error(__VA_ARGS__);   \
+      fclose(f);                     \
+      return -1;                     \
+    }                                \
+  } while (0)
+  STATE_CHECK(fread(magic, 1, 8, f) == 8 && memcmp(magic, "EDETSTAT", 8) == 0, "edet_net_load_state: %s is not a state file", path);
+  const uint32_t version = r.get<uint32_t>(), nrec = r.get<uint32_t>();
+  iterations = r.get<int64_t>();
+  STATE_CHECK(r.ok && version == 1, "edet_net_load_state: state file version %u (this library reads version 1)", version);
+  STATE_CHECK(iterations >= 0 && nrec <= seen.size(), "edet_net_load_state: %s holds %u records, the plan has %llu variable "
+              "slots", path, nrec, (unsigned long long)seen.size());
+  recs.reserve(nrec);
+  for (uint32_t i = 0; i < nrec; ++i) {
+    const std::string name = r.str();
+    const int slot = r.get<uint8_t>(), rank = r.get<uint8_t>();
+    STATE_CHECK(r.ok && rank <= 4, "edet_net_load_state: truncated or bad record %u", i);
+    uint64_t dims[4] = {0, 0, 0, 0};
+    for (int d = 0; d < rank; ++d) dims[d] = r.get<uint64_t>();
+    const uint64_t count = r.get<uint64_t>();
+    STATE_CHECK(r.ok, "edet_net_load_state: truncated state file (variable '%s')", name.c_str());
+    auto it = net->var_index.find(name);
+    STATE_CHECK(it != net->var_index.end(), "edet_net_load_state: the plan has no variable '%s'", name.c_str());
+    const Var& v = net->vars[(size_t)it->second];
+    STATE_CHECK(slot < NUM_SLOTS && has_slot(net, v, slot), "edet_net_load_state: variable '%s' has no slot %d in this plan",
+                name.c_str(), slot);
+    STATE_CHECK(count == v.count, "edet_net_load_state: variable '%s' has %llu elements, the file holds %llu", name.c_str(),
+                (unsigned long long)v.count, (unsigned long long)count);
+    bool same = rank == v.rank;
+    for (int d = 0; same && d < rank; ++d) same = dims[d] == (uint64_t)v.dims[d];
+    STATE_CHECK(same, "edet_net_load_state: variable '%s': the shape in the file differs from the plan's", name.c_str());
+    char& mark = seen[(size_t)it->second * NUM_SLOTS + slot];
+    STATE_CHECK(!mark, "edet_net_load_state: variable '%s' comes twice in slot %s", name.c_str(), kSlotNames[slot]);
+    mark = 1;
+    recs.push_back(Rec{&v, slot, std::vector<float>((size_t)count)});      // count == v.count: bounded by the arena
+    STATE_CHECK(count == 0 || fread(recs.back().data.data(), 4, (size_t)count, f) == (size_t)count,
+                "edet_net_load_state: truncated state file (variable '%s')", name.c_str());
+  }
+  STATE_CHECK(fgetc(f) == EOF, "edet_net_load_state: %s carries bytes after its last record", path);
+  for (size_t i = 0; i < net->vars.size(); ++i)
+    for (int slot = 0; slot < NUM_SLOTS; ++slot)
+      STATE_CHECK(seen[i * NUM_SLOTS + slot] || !has_slot(net, net->vars[i], slot),
+                  "edet_net_load_state: %s does not hold the %s of variable '%s'", path, kSlotNames[slot], net->vars[i].name.c_str());
+#undef STATE_CHECK
+  fclose(f);
+  for (const Rec& rec : recs) {
+    float* p = slot_ptr(net, *rec.v, rec.slot, "edet_net_load_state");
+    if (!p || edet_copy_to_device(p, rec.data.data(), rec.data.size() * 4) != 0) return -1;
+  }
+  net->iterations = iterations;
+  return 0;
 }
 
 extern "C" int edet_dp_init(edet_net_t* net, edet_allreduce_fn fn, void* ctx) {

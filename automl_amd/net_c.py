@@ -23,10 +23,26 @@ NET_SIGNATURES = {
     'edet_detect': [ctypes.c_void_p, ctypes.c_void_p],
     'edet_train_step': [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p],
     'edet_dp_init': [ctypes.c_void_p, ALLREDUCE_FN, ctypes.c_void_p],
+    'edet_net_num_variables': [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)],
+    'edet_net_variable_info': [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p],
+    'edet_net_find_variable': [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)],
+    'edet_get_variable': [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64],
+    'edet_set_variable': [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64],
+    'edet_net_get_iterations': [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)],
+    'edet_net_set_iterations': [ctypes.c_void_p, ctypes.c_int64],
+    'edet_net_save_state': [ctypes.c_void_p, ctypes.c_char_p],
+    'edet_net_load_state': [ctypes.c_void_p, ctypes.c_char_p],
     'edet_anchors': [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_double,
                      ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
 }
 _bound = False
+SLOT_VALUE, SLOT_EMA, SLOT_MOMENTUM, SLOT_ADAM_V = 0, 1, 2, 3      # EDET_SLOT_* of edet_net.h
+
+
+class VarInfo(ctypes.Structure):
+  """edet_var_info."""
+  _fields_ = [('name', ctypes.c_char_p), ('rank', ctypes.c_int32), ('trainable', ctypes.c_int32),
+              ('dims', ctypes.c_int64 * 4), ('count', ctypes.c_int64)]
 
 
 def _lib_net():
@@ -140,3 +156,49 @@ class CNet(object):
     p, n = self.buffer(name)
     assert a.nbytes == n, (name, a.nbytes, n)
     _check(self.lib, self.lib.edet_copy_to_device(p, a.ctypes.data, n), 'edet_copy_to_device')
+
+  # ---- variables by name ------------------------------------------------------------------------------------------------
+  def variables(self):
+    """[(name, shape, trainable)] in the creation order of the Python arena."""
+    n = ctypes.c_int64()
+    _check(self.lib, self.lib.edet_net_num_variables(self.h, ctypes.byref(n)), 'edet_net_num_variables')
+    out = []
+    info = VarInfo()
+    for i in range(n.value):
+      _check(self.lib, self.lib.edet_net_variable_info(self.h, i, ctypes.byref(info)), 'edet_net_variable_info')
+      out.append((info.name.decode(), tuple(info.dims[d] for d in range(info.rank)), bool(info.trainable)))
+    return out
+
+  def _info(self, name):
+    idx = ctypes.c_int64()
+    _check(self.lib, self.lib.edet_net_find_variable(self.h, name.encode(), ctypes.byref(idx)), 'edet_net_find_variable')
+    info = VarInfo()
+    _check(self.lib, self.lib.edet_net_variable_info(self.h, idx.value, ctypes.byref(info)), 'edet_net_variable_info')
+    return info
+
+  def get_variable(self, name, slot=SLOT_VALUE):
+    """fp32 array in the reference layout (synchronises the device)."""
+    info = self._info(name)
+    out = np.empty(tuple(info.dims[d] for d in range(info.rank)), np.float32)
+    _check(self.lib, self.lib.edet_get_variable(self.h, name.encode(), slot, out.ctypes.data, out.size), 'edet_get_variable')
+    return out
+
+  def set_variable(self, name, value, slot=SLOT_VALUE):
+    a = np.ascontiguousarray(value, dtype=np.float32)
+    _check(self.lib, self.lib.edet_set_variable(self.h, name.encode(), slot, a.ctypes.data, a.size), 'edet_set_variable')
+
+  @property
+  def iterations(self):
+    v = ctypes.c_int64()
+    _check(self.lib, self.lib.edet_net_get_iterations(self.h, ctypes.byref(v)), 'edet_net_get_iterations')
+    return v.value
+
+  @iterations.setter
+  def iterations(self, value):
+    _check(self.lib, self.lib.edet_net_set_iterations(self.h, int(value)), 'edet_net_set_iterations')
+
+  def save_state(self, path):
+    _check(self.lib, self.lib.edet_net_save_state(self.h, path.encode()), 'edet_net_save_state')
+
+  def load_state(self, path):
+    _check(self.lib, self.lib.edet_net_load_state(self.h, path.encode()), 'edet_net_load_state')

@@ -26,7 +26,20 @@ File layout (little endian), version 1:
     0 CALL   u16 fn, u8 nargs, args: u8 type { 0 int64 | 1 double | 2 devptr u32 buf u64 off (buf 0xffffffff = NULL)
                                                 | 3 stream u32 idx | 4 host blob u32 nbytes, bytes, u16 nreloc x {u32 at, u32 buf, u64 off} | 5 NULL }
     1 EVENT_RECORD u32 event u32 stream      2 STREAM_WAIT u32 stream u32 event      3 ALLREDUCE_SUM_F32 u32 buf u64 off u64 count u32 stream
+  [variable table, optional: present exactly when the names section holds the integer property 'num_variables']
+    'EDETVARS' u32 nvars, nvars x { u16 len, name, u8 trainable, u8 rank (<= 4), rank x u64 dim, u64 offset, u64 count }
+    one entry per variable of ParamArena.offsets, in its order: the reference name, the shape in the reference layout, and
+    the ELEMENT offset / count inside its fp32 arena -- trainable variables in 'params' (and, at the same offset, in the
+    slots 'ema', 'velocity' and, for Adam, 'adam_v'), BatchNorm moving statistics in 'bn_state'.  It follows the last
+    program, in front of the padding, where a reader that knows nothing of it never looks; the properties 'optimizer'
+    (0 sgd, 1 adam), 'iterations' (optimizer steps behind the state the plan starts from) and, for Adam, 'adam_beta1_bits' /
+    'adam_beta2_bits' / 'adam_epsilon_bits' (the doubles' bit patterns) go with it.
   initial contents, 256-byte aligned, at the offsets the buffer table names.
+
+State files (edet_net_save_state / edet_net_load_state, read_state / write_state below), little endian, version 1:
+  'EDETSTAT' u32 version u32 nrecords i64 iterations
+  nrecords x { u16 len, name, u8 slot (0 value | 1 ema | 2 momentum | 3 adam_v), u8 rank (<= 4), rank x u64 dim, u64 count,
+               count x f32 }
 """
 import bisect
 import ctypes
@@ -42,6 +55,11 @@ from automl_amd import _lib
 MAGIC = b'EDETPLAN'
 VERSION = 1
 NULL_BUF = 0xffffffff
+VARS_MAGIC = b'EDETVARS'
+STATE_MAGIC = b'EDETSTAT'
+STATE_VERSION = 1
+STATE_SLOTS = ('variables', 'ema', 'momentum', 'adam_v')      # slot id = index (EDET_SLOT_* of edet_net.h)
+MAX_RANK = 4
 _HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'edet_hip.h')
 
 
@@ -94,6 +112,7 @@ class Recorder(object):
     self.names = {}             # name -> (pointer, bytes)
     self.props = {}             # name -> integer property of the network (batch, image size, levels, ...)
     self.dev_relocs = []        # (address of an 8-byte slot in device memory, device pointer stored there)
+    self.variables = []         # (name, shape, trainable, element offset, element count) inside the variable's arena
     self._stream_pos = stream_arg_index()
     self._keep = []             # tensors that must stay allocated until the plan is written
 
@@ -189,20 +208,26 @@ class Recorder(object):
     out.sort()
     return out
 
-  def snapshot_initial_state(self, persistent, max_bytes=32 << 20):
+  def snapshot_initial_state(self, persistent, max_bytes=32 << 20, without=()):
     """Copies to the host what the replay must start from: every live block that holds a `persistent` tensor, and every
-    other live block of at most max_bytes (tables, scalars, inputs).  Call AFTER a warm-up pass (all buffers exist) and
-    BEFORE the recorded passes."""
+    other live block of at most max_bytes (tables, scalars, inputs).  The blocks of the tensors in `without` (inputs the
+    host writes before it runs anything) get no initial contents whatever their size.  Call AFTER a warm-up pass (all
+    buffers exist) and BEFORE the recorded passes."""
     torch.cuda.synchronize()
     blocks = self.live_blocks()
     starts = [a for a, _ in blocks]
-    must = set()
-    for t in persistent:
+
+    def block_of(t):
       i = bisect.bisect_right(starts, t.data_ptr()) - 1
       assert i >= 0 and t.data_ptr() < blocks[i][0] + blocks[i][1], 'persistent tensor outside the allocator'
-      must.add(i)
+      return i
+    must = {block_of(t) for t in persistent}
+    skip = {block_of(t) for t in without}
+    assert not (must & skip), 'an input shares its allocation with persistent state'
     self._initial = {}
     for i, (a, n) in enumerate(blocks):
+      if i in skip:
+        continue
       if i in must or n <= max_bytes:
         from automl_amd import net_c
         self._initial[a] = net_c.copy_to_host(a, n)
@@ -262,7 +287,10 @@ class Recorder(object):
     for n, (p, nbytes) in sorted(self.names.items()):
       b, off = resolve(p)
       names.append((n, b, off, nbytes))
-    for n, v in sorted(self.props.items()):
+    props = dict(self.props)
+    if self.variables:
+      props['num_variables'] = len(self.variables)
+    for n, v in sorted(props.items()):
       names.append((n, NULL_BUF, int(v), 0))
     devrel = []
     for at, p in self.dev_relocs:
@@ -285,6 +313,12 @@ class Recorder(object):
       head += struct.pack('<IQIQ', b, at, tb, toff)
     for pname, nops, body in progs:
       head += s16(pname) + struct.pack('<I', nops) + body
+    if self.variables:
+      head += VARS_MAGIC + struct.pack('<I', len(self.variables))
+      for name, shape, trainable, off, count in self.variables:
+        shape = tuple(int(d) for d in shape)
+        assert len(shape) <= MAX_RANK, (name, shape)
+        head += s16(name) + struct.pack('<BB%dQQQ' % len(shape), 1 if trainable else 0, len(shape), *shape, int(off), int(count))
     pos = (len(head) + 255) // 256 * 256
     table = bytearray()
     payload = []
@@ -307,8 +341,7 @@ class Recorder(object):
             'entry_points': len(fn_ids), 'streams': len(self.streams), 'events': self.nevents}
 
 
-def read_summary(path):
-  """Header of a plan file (CPU: the format test and `python -m automl_amd.plan FILE`)."""
+def _read_header(path):
   with open(path, 'rb') as f:
     raw = f.read(8 + 32)
     assert raw[:8] == MAGIC, 'not a plan file'
@@ -327,13 +360,25 @@ def read_summary(path):
           'events': nevents, 'programs': nprog, 'device_relocations': ndevreloc}
 
 
+def read_summary(path):
+  """Header of a plan file (CPU: the format test and `python -m automl_amd.plan FILE`); 'variables': the variable table
+  (see read_plan), empty for a plan written without one."""
+  out = _read_header(path)
+  out['variables'] = read_plan(path)['variables'] if 'num_variables' in out['names'] else []
+  return out
+
+
 def read_plan(path):
   """The whole plan decoded (CPU; the mirror of csrc/net_runtime.cpp's loader): summary + 'ops': program -> list of
   ('call', entry point, [args]) / ('evrec', event, stream) / ('wait', stream, event) / ('allreduce', buf, off, count, stream);
-  args: ('i', v) ('f', v) ('p', buf, off) ('s', idx) ('b', bytes, [(at, buf, off)]) ('n',)."""
-  out = read_summary(path)
+  args: ('i', v) ('f', v) ('p', buf, off) ('s', idx) ('b', bytes, [(at, buf, off)]) ('n',); 'variables': the variable table
+  as [{'name', 'shape', 'trainable', 'offset', 'count'}] (offset / count in elements of the variable's arena), empty for
+  a plan written without one."""
+  out = _read_header(path)
   with open(path, 'rb') as f:
-    data = f.read()
+    # everything in front of the initial contents (which start at the smallest offset the buffer table names)
+    first = min([b[1] for b in out['buffers'] if b[1]] or [0])
+    data = f.read(first) if first else f.read()
   pos = [8 + 32]
 
   def take(fmt):
@@ -391,6 +436,88 @@ def read_plan(path):
     progs[name] = ops
   out['ops'] = progs
   out['device_relocation_table'] = devrel
+  variables = []
+  if 'num_variables' in out['names']:
+    if data[pos[0]:pos[0] + 8] != VARS_MAGIC:
+      raise ValueError('%s: the plan announces a variable table and holds none' % path)
+    pos[0] += 8
+    nvars = take('I')
+    if nvars != out['names']['num_variables'][1]:
+      raise ValueError('%s: variable table of %d entries, property num_variables = %d' % (path, nvars, out['names']['num_variables'][1]))
+    for _ in range(nvars):
+      name = s16()
+      trainable, rank = take('BB')
+      if rank > MAX_RANK:
+        raise ValueError('%s: variable %s of rank %d' % (path, name, rank))
+      shape = tuple(take('Q') for _ in range(rank))
+      off, count = take('QQ')
+      variables.append({'name': name, 'shape': shape, 'trainable': bool(trainable), 'offset': off, 'count': count})
+  out['variables'] = variables
+  return out
+
+
+def write_state(path, variables, ema=None, momentum=None, adam_v=None, iterations=0):
+  """Writes a state file (the format edet_net_save_state writes and edet_net_load_state reads): name -> fp32 array in the
+  reference layout per slot -- the variables' values, the EMA shadows, the momentum slots (Adam: first moments), Adam's
+  second moments -- and the optimizer's iteration count.  Pure numpy."""
+  records = []
+  for slot, values in enumerate((variables, ema, momentum, adam_v)):
+    for name, v in (values or {}).items():
+      a = np.asarray(v, dtype='<f4')      # (ascontiguousarray would turn a 0-d variable into [1]; tobytes is C order)
+      if a.ndim > MAX_RANK:
+        raise ValueError('variable %s: rank %d (at most %d)' % (name, a.ndim, MAX_RANK))
+      raw = name.encode()
+      records.append(struct.pack('<H', len(raw)) + raw + struct.pack('<BB%dQQ' % a.ndim, slot, a.ndim, *a.shape, a.size)
+                     + a.tobytes())
+  with open(path, 'wb') as f:
+    f.write(STATE_MAGIC + struct.pack('<IIq', STATE_VERSION, len(records), int(iterations)))
+    for r in records:
+      f.write(r)
+
+
+def read_state(path):
+  """-> {'variables': {name: array}, 'ema': {...}, 'momentum': {...}, 'adam_v': {...}, 'iterations': n} of a state file;
+  ValueError for a file that is not one, is truncated or carries bytes after its last record."""
+  with open(path, 'rb') as f:
+    data = f.read()
+  if data[:8] != STATE_MAGIC:
+    raise ValueError('%s is not a state file' % path)
+  pos = [8]
+
+  def take(fmt, what):
+    n = struct.calcsize('<' + fmt)
+    if n > len(data) - pos[0]:
+      raise ValueError('%s: truncated state file (%s)' % (path, what))
+    vals = struct.unpack_from('<' + fmt, data, pos[0])
+    pos[0] += n
+    return vals if len(vals) > 1 else vals[0]
+  version, nrec, iterations = take('IIq', 'header')
+  if version != STATE_VERSION:
+    raise ValueError('%s: state file version %d (this reader knows version %d)' % (path, version, STATE_VERSION))
+  out = {k: {} for k in STATE_SLOTS}
+  for _ in range(nrec):
+    n = take('H', 'name')
+    if n > len(data) - pos[0]:
+      raise ValueError('%s: truncated state file (name)' % path)
+    name = data[pos[0]:pos[0] + n].decode()
+    pos[0] += n
+    slot, rank = take('BB', name)
+    if slot >= len(STATE_SLOTS) or rank > MAX_RANK:
+      raise ValueError('%s: variable %s: bad slot %d / rank %d' % (path, name, slot, rank))
+    shape = tuple(take('Q', name) for _ in range(rank))
+    count = take('Q', name)
+    want = 1
+    for d in shape:
+      want *= d
+    if count != want or count > (len(data) - pos[0]) // 4:
+      raise ValueError('%s: truncated state file or bad count (variable %s, %d elements)' % (path, name, count))
+    if name in out[STATE_SLOTS[slot]]:
+      raise ValueError('%s: variable %s twice in slot %s' % (path, name, STATE_SLOTS[slot]))
+    out[STATE_SLOTS[slot]][name] = np.frombuffer(data, '<f4', count, pos[0]).reshape(shape).copy()
+    pos[0] += 4 * count
+  if pos[0] != len(data):
+    raise ValueError('%s: %d bytes after the last record' % (path, len(data) - pos[0]))
+  out['iterations'] = iterations
   return out
 
 
@@ -461,9 +588,6 @@ class _Detect(object):
     self.compact = None      # per level (cls, box) without padding columns: made by the first pass (needs the views)
     self.clip_hw = utils.parse_image_size((self.oh, self.ow))
 
-  def persistent(self):
-    return [self.raw, self.anchors, self.scales]
-
   def run(self):
     eng = self.eng
     st = eng.stream
@@ -506,7 +630,7 @@ class _Detect(object):
 
 
 def record_network(net, images, labels=None, path='efficientdet.plan', learning_rate=0.01, ema_decay=0.0,
-                   max_init_bytes=32 << 20, detect_raw_hw=None, raw_images=None):
+                   max_init_bytes=32 << 20, detect_raw_hw=None, raw_images=None, keep_inputs=True):
   """Records `forward` (EfficientDetNet.call, inference BatchNorm) and -- with labels -- `train_step` of a network
   (efficientdet_net.EfficientDetNet / train_lib.EfficientDetNetTrain) on device tensors `images` [B,H,W,3] and the label
   dictionary of train_step, and writes the plan.  Returns (summary, expected): `expected` holds what the Python host
@@ -514,6 +638,12 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
 
   detect_raw_hw = (H, W): also records `detect` (EfficientDetModel.call on raw uint8 images of that size: preprocessing,
   network, global-NMS post-processing; edet_detect); raw_images [B,H,W,3] uint8 are the recorded inputs (default zeros).
+
+  keep_inputs=False: "images", the target buffers and "raw_images" get no initial contents (zero-filled at edet_create; the
+  host writes them before it runs a program), and the file loses their bytes.
+
+  The plan also holds the variable table (one entry per variable of ParamArena.offsets: what edet_get_variable /
+  edet_set_variable / edet_net_save_state address by name) and the optimizer's kind, constants and iteration count.
 
   The state the plan starts from is the network's state after one un-recorded warm-up pass of each program.
   """
@@ -540,14 +670,25 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
   torch.cuda.synchronize()
   rec = Recorder()
   persistent = [eng.params_flat, eng.velocity, eng.ema, eng.state_flat, eng.seg_flags, eng.seg_offsets, eng.seg_factor,
-                eng.hyper, images]
+                eng.hyper]
+  inputs = [images]
   if dl is not None:
-    persistent += [t for t in dl.values() if torch.is_tensor(t)]
+    inputs += [t for t in dl.values() if torch.is_tensor(t)]
   if getattr(eng.arena, 'adam_v', None) is not None:
     persistent.append(eng.arena.adam_v)
   if det is not None:
-    persistent += det.persistent()
-  rec.snapshot_initial_state(persistent, max_init_bytes)
+    persistent += [det.anchors, det.scales]
+    inputs.append(det.raw)
+  if keep_inputs:
+    rec.snapshot_initial_state(persistent + inputs, max_init_bytes)
+  else:
+    rec.snapshot_initial_state(persistent, max_init_bytes, without=inputs)
+  rec.variables = [(name, shape, tr, off, n) for name, (off, n, shape, tr) in eng.arena.offsets.items()]
+  rec.props.update({'optimizer': 1 if eng.adam else 0, 'iterations': int(eng.arena.step_count)})
+  if eng.adam:
+    for key, v in (('adam_beta1_bits', float(eng.config.momentum)), ('adam_beta2_bits', eng.ADAM_BETA2),
+                   ('adam_epsilon_bits', eng.ADAM_EPSILON)):
+      rec.props[key] = struct.unpack('<Q', struct.pack('<d', v))[0]
   expected = {}
   # every program re-makes the compute copies of the variables (and, in inference, the BatchNorm vectors): a replayed step
   # follows other replayed steps, whose updates the host-side version counter of this engine has not seen
@@ -603,6 +744,8 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
     expected['velocity'] = eng.velocity.cpu().numpy().copy()
     expected['bn_state'] = eng.state_flat.cpu().numpy().copy()
     expected['loss_sums'] = eng.loss_sums.cpu().numpy().copy()
+    if eng.adam:
+      expected['adam_v'] = eng.arena.adam_v.cpu().numpy().copy()
     for k, t in dl.items():
       if torch.is_tensor(t):
         rec.name_buffer(k, t)
@@ -610,6 +753,8 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
   rec.name_buffer('params', eng.params_flat)
   rec.name_buffer('ema', eng.ema)
   rec.name_buffer('velocity', eng.velocity)
+  if eng.adam and getattr(eng.arena, 'adam_v', None) is not None:
+    rec.name_buffer('adam_v', eng.arena.adam_v)
   rec.name_buffer('bn_state', eng.state_flat)
   rec.name_buffer('loss_sums', eng.loss_sums)
   rec.name_buffer('hyper', eng.hyper)
@@ -624,4 +769,5 @@ if __name__ == '__main__':
   s = read_summary(sys.argv[1])
   s['buffers'] = {'count': len(s['buffers']), 'bytes': sum(b[0] for b in s['buffers']),
                   'initialised_bytes': sum(b[0] for b in s['buffers'] if b[1])}
+  s['variables'] = len(s['variables'])
   print(json.dumps(s, indent=1))

@@ -31,16 +31,20 @@ extern "C" {
 typedef struct edet_net edet_net_t;
 
 /* Loads a plan: allocates its buffers on the current HIP device, uploads the initial contents, relocates the pointers.
- * The network starts in the state the plan was recorded from (variables, optimizer slots, moving statistics, and the
- * recorded inputs in "images" / the target buffers).  */
+ * A plan is recorded once by the Python engine (automl_amd/plan.py: record_network) per (config, batch, image size,
+ * storage type); it fixes the model, the optimizer and the optimizer's constants.  The network starts in the state the
+ * plan was recorded from: variables, optimizer slots, moving statistics, iteration count, and the recorded inputs in
+ * "images" / the target buffers (zero-filled in a plan recorded with keep_inputs=False: write them before the first
+ * pass).  What changes afterwards is reached by name through the variable functions and the state files below.  A plan
+ * whose variable table does not fit its buffers is refused.  */
 int edet_create(const char* plan_path, edet_net_t** net_out);
 int edet_destroy(edet_net_t* net);
 
 /* Named device buffers of the network: "images" [B,H,W,3] in the storage type; "cls_outputs_<L>" / "box_outputs_<L>"
  * [B,h,w,ld] per pyramid level (the first `channels` elements of a pixel are the logits; properties
  * "<name>.channels/.ld/.height/.width/.elem_bytes"); training: "cls_targets_<L>" int32 [B,h,w,A], "box_targets_<L>" fp32
- * [B,h,w,4A], "mean_num_positives" fp32 [B]; state: "params", "ema", "velocity" (flat fp32 arenas), "bn_state" (moving
- * statistics), "loss_sums" fp32[4] (class, box, L2, -: sums of the last step), "hyper" fp32[4]; "drop_mask:<block>"
+ * [B,h,w,4A], "mean_num_positives" fp32 [B]; state: "params", "ema", "velocity" (flat fp32 arenas; Adam plans: "velocity" is the first
+ * moment, "adam_v" the second), "bn_state" (moving statistics), "loss_sums" fp32[4] (class, box, L2, -: sums of the last step), "hyper" fp32[4]; "drop_mask:<block>"
  * fp32 [B,C] stochastic-depth scales floor(p + u) / p that the host refreshes per step (utils.drop_connect).  */
 int edet_net_buffer(edet_net_t* net, const char* name, void** device_ptr, size_t* bytes);
 int edet_net_num_buffers(edet_net_t* net);
@@ -72,10 +76,54 @@ int edet_forward(edet_net_t* net, void* stream);
 int edet_detect(edet_net_t* net, void* stream);
 
 /* One training step over "images" and the target buffers (EfficientDetNetTrain.train_step: forward with batch
- * statistics, focal + Huber loss, backward, L2, per-tensor and global-norm clip, [gradient exchange], SGD momentum + EMA).
- * learning_rate / ema_decay are this step's values of the schedule (train_lib.py:37-173, :193-197; ema_decay 0 = the
- * plan was recorded without a moving average).  */
+ * statistics, focal + Huber loss, backward, L2, per-tensor and global-norm clip, [gradient exchange], the update + EMA).
+ * The optimizer is the plan's (property "optimizer": 0 = SGD with momentum, 1 = Adam; train_lib.py:176-199).
+ * learning_rate / ema_decay are this step's RAW values of the schedule (train_lib.py:37-173, :193-197; ema_decay 0 = the
+ * plan was recorded without a moving average).  Adam plans: the runtime forms tf.keras Adam's bias-corrected rate itself,
+ * alpha = learning_rate * sqrt(1 - beta2^t) / (1 - beta1^t) with t = iterations + 1, in double arithmetic, rounded to
+ * float, from the betas the plan holds -- exactly what the Python engine hands its update kernel.  Every step that
+ * returns 0 advances the iteration count by one.  An Adam plan written before plans carried the "optimizer" property
+ * replays as it always did: learning_rate goes to the update kernel as it is, so the caller passes alpha.  */
 int edet_train_step(edet_net_t* net, float learning_rate, float ema_decay, void* stream);
+
+/* ---- variables by name --------------------------------------------------------------------------------------------------
+ * The plan's variable table: one entry per variable of the model, in the creation order of the Python host's arena, under
+ * the reference's names ("class_net/class-predict/bias", "efficientnet-b0/stem/conv2d/kernel", ...), shapes in the
+ * reference's layouts.  Values are fp32.  A trainable variable has the slots VALUE, EMA (the moving-average shadow),
+ * MOMENTUM (SGD: the momentum accumulator; Adam: the first moment) and -- in Adam plans only -- ADAM_V (the second
+ * moment); a BatchNorm moving statistic has VALUE only.  Every function refuses a plan recorded without the table.  */
+enum { EDET_SLOT_VALUE = 0, EDET_SLOT_EMA = 1, EDET_SLOT_MOMENTUM = 2, EDET_SLOT_ADAM_V = 3 };
+typedef struct {
+  const char* name;      /* owned by the network, valid until edet_destroy */
+  int32_t rank;          /* 0..4 */
+  int32_t trainable;
+  int64_t dims[4];
+  int64_t count;         /* elements = product of dims (1 for rank 0) */
+} edet_var_info;
+int edet_net_num_variables(edet_net_t* net, int64_t* count);
+int edet_net_variable_info(edet_net_t* net, int64_t index, edet_var_info* out);
+int edet_net_find_variable(edet_net_t* net, const char* name, int64_t* index);
+/* Synchronous, like edet_copy_to_host / _to_device: they wait for the device first.  capacity / count in elements; get
+ * wants capacity >= the variable's count, set wants count == it.  Refused, with the variable's name in the message: an
+ * unknown name, a wrong count, a slot the variable does not have.  Setting VALUE of a trainable variable while the
+ * iteration count is 0 also seeds its EMA shadow (the average starts from the variable, as on the Python host).  */
+int edet_get_variable(edet_net_t* net, const char* name, int slot, float* host, int64_t capacity);
+int edet_set_variable(edet_net_t* net, const char* name, int slot, const float* host, int64_t count);
+/* Optimizer steps applied to the variables: starts at the plan's "iterations" property (0 without it), +1 per successful
+ * edet_train_step.  It drives Adam's bias correction; a host's learning-rate schedule reads it.  */
+int edet_net_get_iterations(edet_net_t* net, int64_t* iterations);
+int edet_net_set_iterations(edet_net_t* net, int64_t iterations);
+
+/* State files: everything a training run needs to resume -- every variable's VALUE, every slot that exists, and the
+ * iteration count.  Little endian:
+ *   'EDETSTAT'  u32 version (1)  u32 nrecords  i64 iterations
+ *   nrecords x { u16 len, name,  u8 slot (EDET_SLOT_*),  u8 rank,  rank x u64 dim,  u64 count,  count x f32 }
+ * edet_net_load_state restores by name.  It refuses -- and changes nothing -- when the file names a variable or slot the
+ * plan does not have, a record's element count differs from the variable's, a record comes twice, or a variable / slot
+ * of the plan is missing from the file.  automl_amd/plan.py read_state / write_state are the same format in numpy: the
+ * bridge to the Python host and, through util_keras.save_ckpt / restore_ckpt, to the reference's checkpoints.  */
+int edet_net_save_state(edet_net_t* net, const char* path);
+int edet_net_load_state(edet_net_t* net, const char* path);
 
 /* Data parallelism (one process per GPU): `fn` is called where the reference's optimizer all-reduces the clipped
  * gradients (train_lib.py:675-683), with the flat fp32 gradient arena, to be summed IN PLACE over the replicas on
