@@ -687,3 +687,187 @@ extern "C" int edet_loss_normalizer(const float* mean_num_positives, int n, floa
   EDET_LAUNCH_CHECK("edet_loss_normalizer");
   return 0;
 }
+
+// ---- EfficientNetV2 classifier training (efficientnetv2/main_tf2.py:36-117,199-207) ------------------------------------
+namespace {
+constexpr int XENT_ROWS = THREADS / 64;       // one wave per row
+
+// tf.keras.losses.CategoricalCrossentropy(label_smoothing, from_logits=True), mean over the batch, with its gradient and the
+// TopKCategoricalAccuracy(1 / 5) counts in one pass over the logits.  Per row: m = max x, lse = m + log sum exp(x - m),
+// y_c = (1 - s) [c == label] + s / nc, loss = lse - sum_c y_c x_c, d x_c = (softmax_c - y_c) * grad_scale / B.  A wave owns a
+// row (8-element chunks strided over the lanes, xor butterflies: a fixed tree); the waves of a workgroup add their rows in
+// wave order, workgroups write [loss / B | top1 | top5] rows that edet_reduce_partials2 adds in order -- no atomics.
+// A label outside [0, nc) is refused by the host wrapper's callers (it cannot be seen here without a synchronisation); the
+// kernel reads nothing out of bounds for one: such a row has no hot class and counts for neither metric.
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_softmax_xent(const T* __restrict__ logits, int ld, const int32_t* __restrict__ labels,
+                                                         int batch, int nc, float ls, float gscale, float inv_b,
+                                                         T* __restrict__ dlogits, float* sums, float* part) {
+  __shared__ float sh[XENT_ROWS][3];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float uni = ls / (float)nc, hot = 1.f - ls;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int row = blockIdx.x * XENT_ROWS + wv; row < batch; row += gridDim.x * XENT_ROWS) {
+    const T* x = logits + (size_t)row * ld;
+    const int lab = labels[row];
+    const bool lab_ok = lab >= 0 && lab < nc;
+    const float xl = lab_ok ? to_f<T>(x[lab]) : 0.f;
+    float m = -INFINITY;
+    for (int c0 = lane * 8; c0 < nc; c0 += 64 * 8) {
+      float v[8];
+      load8<T>(x + c0, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) if (c0 + e < nc) m = fmaxf(m, v[e]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    float r[3] = {0.f, 0.f, 0.f};      // sum exp(x - m), sum x, logits strictly greater than the label's
+    for (int c0 = lane * 8; c0 < nc; c0 += 64 * 8) {
+      float v[8];
+      load8<T>(x + c0, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (c0 + e < nc) {
+          r[0] += __expf(v[e] - m);
+          r[1] += v[e];
+          r[2] += v[e] > xl ? 1.f : 0.f;
+        }
+      }
+    }
+    wave_group_sum(r, 1);
+    const float inv_se = 1.f / r[0];
+    const float lse = m + __logf(r[0]);
+    acc[0] += (lse - hot * xl - uni * r[1]) * inv_b;
+    acc[1] += (lab_ok && r[2] < 1.f) ? 1.f : 0.f;
+    acc[2] += (lab_ok && r[2] < 5.f) ? 1.f : 0.f;
+    T* dx = dlogits + (size_t)row * ld;
+    for (int c0 = lane * 8; c0 < ld; c0 += 64 * 8) {
+      float v[8], g[8];
+      load8<T>(x + c0, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = c0 + e;
+        const float y = uni + ((lab_ok && c == lab) ? hot : 0.f);
+        g[e] = c < nc ? (__expf(v[e] - m) * inv_se - y) * gscale : 0.f;      // padding columns: zeros
+      }
+      store8<T>(dx + c0, g);
+    }
+  }
+  if (lane == 0) {
+    sh[wv][0] = acc[0]; sh[wv][1] = acc[1]; sh[wv][2] = acc[2];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    float t = 0.f;
+    for (int w = 0; w < XENT_ROWS; ++w) t += sh[w][threadIdx.x];
+    if (part) part[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
+    else sums[threadIdx.x] += t;          // (no partial buffer: the kernel runs as ONE workgroup)
+  }
+}
+
+// out = cast(src * mask): the head dropout (effnetv2_model.py:464-467,483-484) folded into the cast of the pooled sums;
+// mask == NULL is edet_cast.  In place (dst == src, fp32) for the backward pass.
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_dropout_cast(const float* src, const float* __restrict__ mask, T* dst, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * THREADS;
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += stride)
+    dst[i] = from_f<T>(mask ? src[i] * mask[i] : src[i]);
+}
+
+// TensorFlow's ApplyRMSProp with momentum (what tf.keras.optimizers.RMSprop runs): ms += (1 - rho)(g^2 - ms);
+// mom = momentum mom + lr g / sqrt(ms + eps); w -= mom; TFA MovingAverage on top as for the other optimizers
+__device__ __forceinline__ void rms1(float g, float& ms, float& mom, float& w, float& em, float lr, float rho, float momentum,
+                                     float eps, float decay, bool has_ema) {
+  ms += (g * g - ms) * (1.f - rho);
+  mom = momentum * mom + (lr * g) / sqrtf(ms + eps);
+  w -= mom;
+  if (has_ema) em -= (1.f - decay) * (em - w);
+}
+
+__global__ __launch_bounds__(THREADS) void k_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
+                                                        const int64_t* seg_off, const float* seg_factor,
+                                                        const int32_t* seg_flags, const float* hyper, float rho, float momentum,
+                                                        float eps) {
+  const int s = blockIdx.x;
+  int64_t b, e;
+  if (!slice_range(seg_off, s, blockIdx.y, b, e)) return;
+  if (seg_flags && (seg_flags[s] & EDET_SEG_FROZEN)) return;      // not in the optimizer's variable list
+  const float f = seg_factor ? seg_factor[s] : 1.f;
+  const float lr = hyper[0], decay = hyper[1];
+  const bool has_ema = ema != nullptr;
+  if ((b & 3) == 0) {
+    const int64_t nv = (e - b) >> 2;
+    const float4* g4 = reinterpret_cast<const float4*>(grads + b);
+    float4* s4 = reinterpret_cast<float4*>(ms + b);
+    float4* m4 = reinterpret_cast<float4*>(mom + b);
+    float4* w4 = reinterpret_cast<float4*>(params + b);
+    float4* e4 = has_ema ? reinterpret_cast<float4*>(ema + b) : nullptr;
+    for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
+      const float4 g = g4[i];
+      float4 q = s4[i], v = m4[i], w = w4[i], em = has_ema ? e4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      rms1(g.x * f, q.x, v.x, w.x, em.x, lr, rho, momentum, eps, decay, has_ema);
+      rms1(g.y * f, q.y, v.y, w.y, em.y, lr, rho, momentum, eps, decay, has_ema);
+      rms1(g.z * f, q.z, v.z, w.z, em.z, lr, rho, momentum, eps, decay, has_ema);
+      rms1(g.w * f, q.w, v.w, w.w, em.w, lr, rho, momentum, eps, decay, has_ema);
+      s4[i] = q;
+      m4[i] = v;
+      w4[i] = w;
+      if (has_ema) e4[i] = em;
+    }
+    b += nv << 2;
+  }
+  for (int64_t i = b + threadIdx.x; i < e; i += THREADS) {
+    float q = ms[i], v = mom[i], w = params[i], em = has_ema ? ema[i] : 0.f;
+    rms1(grads[i] * f, q, v, w, em, lr, rho, momentum, eps, decay, has_ema);
+    ms[i] = q;
+    mom[i] = v;
+    params[i] = w;
+    if (has_ema) ema[i] = em;
+  }
+}
+}  // namespace
+
+extern "C" int edet_softmax_xent(const void* logits, int ld, const int32_t* labels, int batch, int num_classes,
+                                 float label_smoothing, float grad_scale, void* dlogits, float* sums, void* workspace,
+                                 size_t workspace_bytes, int dtype, void* stream) {
+  EDET_CHECK(logits && labels && dlogits && sums, "edet_softmax_xent: null pointer");
+  EDET_CHECK(batch > 0 && num_classes >= 1, "edet_softmax_xent: batch %d, num_classes %d", batch, num_classes);
+  EDET_CHECK(ld % 8 == 0 && ld >= num_classes, "edet_softmax_xent: bad ld %d (num_classes %d)", ld, num_classes);
+  EDET_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "edet_softmax_xent: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  int g = (batch + XENT_ROWS - 1) / XENT_ROWS;
+  if (g > 1024) g = 1024;
+  // ordered partial rows [g][3] when the workspace holds them (else: one workgroup walks every row)
+  float* part = (g > 1 && workspace && workspace_bytes >= (size_t)g * 3 * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
+  if (!part) g = 1;
+  const float inv_b = 1.f / (float)batch;
+  if (dtype == EDET_BF16)
+    edet_launch(k_softmax_xent<bf16_t>, dim3(g), dim3(THREADS), 0, to_stream(stream), (const bf16_t*)logits, ld, labels, batch, num_classes, label_smoothing, grad_scale * inv_b, inv_b, (bf16_t*)dlogits, sums, part);
+  else if (dtype == EDET_F32)
+    edet_launch(k_softmax_xent<float>, dim3(g), dim3(THREADS), 0, to_stream(stream), (const float*)logits, ld, labels, batch, num_classes, label_smoothing, grad_scale * inv_b, inv_b, (float*)dlogits, sums, part);
+  else EDET_CHECK(false, "edet_softmax_xent: bad dtype %d", dtype);
+  if (part && edet_reduce_partials2(part, g, 3, nullptr, 0, sums, to_stream(stream)) != 0) return -2;
+  EDET_LAUNCH_CHECK("edet_softmax_xent");
+  return 0;
+}
+
+extern "C" int edet_dropout_cast(const float* src, const float* mask, void* dst, int64_t count, int dtype, void* stream) {
+  EDET_CHECK(src && dst, "edet_dropout_cast: null pointer");
+  if (count <= 0) return 0;
+  int64_t grid = (count + THREADS - 1) / THREADS;
+  if (grid > 2048) grid = 2048;
+  if (dtype == EDET_BF16) edet_launch(k_dropout_cast<bf16_t>, dim3((unsigned)grid), dim3(THREADS), 0, to_stream(stream), src, mask, (bf16_t*)dst, count);
+  else if (dtype == EDET_F32) edet_launch(k_dropout_cast<float>, dim3((unsigned)grid), dim3(THREADS), 0, to_stream(stream), src, mask, (float*)dst, count);
+  else EDET_CHECK(false, "edet_dropout_cast: bad dtype %d", dtype);
+  EDET_LAUNCH_CHECK("edet_dropout_cast");
+  return 0;
+}
+
+extern "C" int edet_opt_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
+                                    const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
+                                    const float* hyper_dev, float rho, float momentum, float epsilon, void* stream) {
+  EDET_CHECK(params && grads && ms && mom && seg_offsets && hyper_dev && nseg > 0, "edet_opt_rmsprop_ema: bad arguments");
+  edet_launch(k_rmsprop_ema, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, grads, ms, mom, ema, seg_offsets,
+              seg_factor, seg_flags, hyper_dev, rho, momentum, epsilon);
+  EDET_LAUNCH_CHECK("edet_opt_rmsprop_ema");
+  return 0;
+}

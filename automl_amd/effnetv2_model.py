@@ -8,8 +8,11 @@ Variable names follow the Keras model (model name as prefix, ``blocks_%d``, per-
 
 Scope: the forward pass in both BatchNorm modes and the backward
 pass of the whole graph (``backward(d_outputs)``: Fused-MBConv dense convolutions, MBConv, SE, stochastic depth,
-head, dense layer).  The classifier's loss / optimizer / dropout are outside the detection hot path:
-``training=True`` refuses dropout (pass ``model_config='dropout_rate=0'``).
+head, dense layer).  The classifier's training step -- softmax cross-entropy with label smoothing, head dropout, the
+RMSprop / momentum / Adam update (``efficientnetv2/main_tf2.py``) -- is ``effnetv2_train.TrainableModel`` on the
+V2Engine methods at the end of this file (``softmax_loss``, ``update_local`` / ``update_apply``, ``head_dropout``).
+``EffNetV2Model.__call__(training=True)`` itself still refuses dropout (pass ``model_config='dropout_rate=0'``): it has
+no labels to train with, and only the trainer owns the draws.  ``conv_dropout`` is not built anywhere.
 """
 import collections
 import ctypes
@@ -143,6 +146,10 @@ class V2Engine(engine_lib.Engine):
       params = {**init_params(spec, seed), **(params or {})}      # a partial set keeps the other initial values
     super().__init__(spec.mconfig, batch_size, image_size, dtype=dtype, device=device, seed=seed,
                      params=params, spec=spec, arena=arena)
+    # head dropout (effnetv2_model.py:464-467,483-484): set by effnetv2_train.TrainableModel only -- 0 = the plain cast
+    self.head_dropout = 0.0
+    self.dropout_mask = None      # fp32 [B, feature_size] in {0, 1 / (1 - rate)}, redrawn by refresh_drop_masks
+    self.cls_sums = self.zbuf('cls_sums', (4,))      # mean loss, top-1 rows, top-5 rows, L2 loss (zeroed every pass)
 
   def forward(self, images, training=False, update_moving=True):
     """images: device tensor [B,H,W,3] in the engine dtype.  Fills self.endpoints / self.outputs."""
@@ -197,9 +204,20 @@ class V2Engine(engine_lib.Engine):
     self.pooled_sum, self.pooled_inv_hw = pooled, 1.0 / (r.h * r.w)
     self.head_view = hv
     self.logits = None
+    self._dlogits_ready = False
+    self._dropout_on = False
     if spec.num_classes:
       pv = engine_lib.Raw(self, 'head:pooled', n, 1, 1, r.c, needs_grad=False)
-      call('edet_cast', ptr(pooled), ptr(pv.data), n * r.c, self.dtype, self.stream)
+      self._dropout_on = bool(training and self.head_dropout)
+      if self._dropout_on:
+        if self.dropout_mask is None:
+          self.dropout_mask = self.buf('head:dropmask', (n, r.c), torch.float32)
+          if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the head-dropout mask must exist before the step is captured (run one eager step)')
+          self._draw_dropout_mask()
+        call('edet_dropout_cast', ptr(pooled), ptr(self.dropout_mask), ptr(pv.data), n * r.c, self.dtype, self.stream)
+      else:
+        call('edet_cast', ptr(pooled), ptr(pv.data), n * r.c, self.dtype, self.stream)
       inv = self.buf('head:inv_hw', (2, r.c), torch.float32)
       inv[0].fill_(self.pooled_inv_hw)
       inv[1].zero_()
@@ -214,25 +232,29 @@ class V2Engine(engine_lib.Engine):
       self._fc = (pv, tv, inv)
     return self.logits
 
-  def backward(self, d_out):
+  def backward(self, d_out=None):
     """Gradients of every variable for a given gradient of the model output (after forward(training=True)):
     d_out = d(logits) [B, num_classes] with include_top, else d(pooled features) [B, feature_size].  Fills
-    grads_flat (get_grads()).  The loss itself -- softmax cross-entropy with label smoothing in the reference's
-    classifier training, efficientnetv2/main.py -- stays with the caller: classifier training is outside the
-    detection hot path, the backward of the Fused-MBConv / MBConv / SE / head graph is what is built here."""
+    grads_flat (get_grads()).  d_out = None: d(logits) is what softmax_loss() left in the 'head:dlogits' buffer (the
+    classifier's training step, effnetv2_train.TrainableModel)."""
     spec = self.spec
     assert self.training, 'run forward(training=True) first'
     name = spec.name
     hv = self.head_view
     r = hv.raw
     n, c = r.n, r.c
-    d_out = torch.as_tensor(d_out).to(device=self.device, dtype=torch.float32).reshape(n, -1)
+    if d_out is None:
+      assert spec.num_classes and self._dlogits_ready, 'backward() without d_out needs softmax_loss() after this forward pass'
+    else:
+      d_out = torch.as_tensor(d_out).to(device=self.device, dtype=torch.float32).reshape(n, -1)
     if spec.num_classes:
       pv, tv, inv = self._fc
       ncls = spec.num_classes
       dl = engine_lib.Raw(self, 'head:dlogits', n, 1, 1, ncls, needs_grad=False)
-      dl.data.zero_()
-      dl.data.reshape(n, -1)[:, :ncls] = d_out.to(self.tdtype)
+      if d_out is not None:
+        dl.data.zero_()
+        dl.data.reshape(n, -1)[:, :ncls] = d_out.to(self.tdtype)
+      self._dlogits_ready = False
       g = _lib.GView(ptr(dl.data), None, None, None, None, n, 1, 1, ncls, dl.ld)
       wname = name + '/head/dense/kernel'
       _, _, wcopy, ldn = self._pw_copies(wname, c, ncls)
@@ -250,6 +272,8 @@ class V2Engine(engine_lib.Engine):
     # global average pooling backward: every pixel receives d_mean / (H*W); through swish' and the head BatchNorm
     dpool = self.buf('head:dpool', (n, c), torch.float32)
     dpool.copy_(d_mean * self.pooled_inv_hw)
+    if spec.num_classes and self._dropout_on:      # the forward pass's mask on d(pooled), in place
+      call('edet_dropout_cast', ptr(dpool), ptr(self.dropout_mask), ptr(dpool), n * c, _lib.EDET_F32, self.stream)
     gbuf = r.ensure_grad()
     gbuf.zero_()
     ones = self.buf('ones:%d:%d' % (n, c), (n, c), torch.float32)
@@ -260,6 +284,85 @@ class V2Engine(engine_lib.Engine):
     self._bn_bwd_finalize(hv.bn, self._nparts.value)
     r.grad_written = True
     super().backward()
+
+  # ---- classifier training (efficientnetv2/main_tf2.py:36-117): loss, dropout draws, update ----------------------------
+  RMSPROP_RHO, RMSPROP_MOMENTUM, RMSPROP_EPSILON = 0.9, 0.9, 0.001      # build_tf2_optimizer, main_tf2.py:36-52
+  ADAM_BETA1 = 0.9                                                      # tf.keras.optimizers.Adam(learning_rate) defaults
+
+  def _draw_dropout_mask(self):
+    """tf.keras.layers.Dropout(rate): keep with probability 1 - rate, kept values scaled by 1 / (1 - rate); one draw per
+    (image, feature).  From the engine's generator, like the stochastic-depth masks."""
+    keep = 1.0 - float(self.head_dropout)
+    u = torch.rand(self.dropout_mask.shape, device=self.device, generator=self._rng)
+    self.dropout_mask.copy_((u + keep).floor() / keep)
+
+  def refresh_drop_masks(self):
+    """New stochastic-depth draws and a new head-dropout mask (device-side, OUTSIDE any captured graph: the masks live in
+    static buffers that a replayed step reads)."""
+    super().refresh_drop_masks()
+    if self.dropout_mask is not None:
+      self._draw_dropout_mask()
+
+  def softmax_loss(self, labels, label_smoothing=0.0, grad_scale=1.0):
+    """CategoricalCrossentropy(label_smoothing, from_logits=True) of the logits of the last forward pass against sparse
+    int32 device labels [B] (main_tf2.py:199-207): adds the mean loss and the top-1 / top-5 row counts to cls_sums[0:3]
+    and, after a training forward pass, leaves d(logits) for backward().  The caller has checked the label range."""
+    out = self.logits
+    assert out is not None, 'softmax_loss needs a model with a classifier head (include_top)'
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == self.batch
+    ncls = self.spec.num_classes
+    dl = engine_lib.Raw(self, 'head:dlogits', out.n, 1, 1, ncls, needs_grad=False)
+    call('edet_softmax_xent', ptr(out.data), out.ld, ptr(labels), out.n, ncls, float(label_smoothing), float(grad_scale),
+         ptr(dl.data), ptr(self.cls_sums), *self._ws(), self.dtype, self.stream)
+    self._dlogits_ready = self.training
+
+  def set_update_hyper(self, lr, ema_decay, optimizer):
+    """hyper[0] = the step's learning rate (Adam: bias-corrected for t = iterations + 1, as Engine.set_hyper), hyper[1] =
+    EMA decay; outside the captured step."""
+    if optimizer == 'adam':
+      t = self.arena.step_count + 1
+      lr = lr * math.sqrt(1.0 - self.ADAM_BETA2 ** t) / (1.0 - self.ADAM_BETA1 ** t)
+    self.hyper[:2].copy_(torch.tensor([lr, ema_decay or 0.0], dtype=torch.float32), non_blocking=True)
+
+  def update_local(self, weight_decay):
+    """TrainableModel._reg_l2_loss (main_tf2.py:80-87: the detection trainer's regular expression, so the arena's L2
+    flags) added to the gradient and to cls_sums[3]; no clipping (gclip = 0, hparams.py:261) -- clip 0 yields the
+    gradient norm and factors of one.  The update values come from the trainer: the model config has no training keys."""
+    st = self.stream
+    call('edet_opt_l2_norms', ptr(self.grads_flat), ptr(self.params_flat), ptr(self.seg_offsets), ptr(self.seg_flags),
+         self.nseg, float(weight_decay), ptr(self.seg_sqnorm), st)
+    call('edet_opt_clip_factors', ptr(self.seg_sqnorm), self.nseg, 0.0, ptr(self.seg_factor), ptr(self.gnorm),
+         ptr(self.cls_sums[3:]), st)
+
+  def l2_loss_eval(self, weight_decay):
+    """The same L2 term for an evaluation pass (test_step, main_tf2.py:105-117), added to cls_sums[3] WITHOUT touching the
+    gradient arena, the clip factors or the gradient norm (update_local adds weight_decay * w to the gradients): per-segment
+    sums of squares by torch.segment_reduce, weighted by the arena's L2 flags.  Not on the training path."""
+    a = self.arena
+    if getattr(a, '_l2_weights', None) is None:
+      a._seg_lengths = (a.seg_offsets[1:] - a.seg_offsets[:-1]).contiguous()
+      a._l2_weights = (a.seg_flags == _lib.SEG_L2).to(torch.float32)
+    sq = torch.segment_reduce(self.params_flat * self.params_flat, 'sum', lengths=a._seg_lengths, unsafe=True)
+    self.cls_sums[3:4].add_((0.5 * float(weight_decay)) * (sq * a._l2_weights).sum().reshape(1))
+
+  def update_apply(self, optimizer, momentum, use_ema):
+    """build_tf2_optimizer (main_tf2.py:36-59): 'rmsprop' (rho 0.9, momentum 0.9, epsilon 0.001), 'momentum' / 'sgd'
+    (Keras SGD, `momentum` = 0 for 'sgd'), 'adam' (Keras defaults); lr / EMA decay from self.hyper."""
+    a = self.arena
+    common = (ptr(self.ema) if use_ema else None, ptr(self.seg_offsets), None, ptr(self.seg_flags), self.nseg, ptr(self.hyper))
+    if optimizer == 'rmsprop':
+      call('edet_opt_rmsprop_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(a.second_moment()), ptr(self.velocity),
+           *common, self.RMSPROP_RHO, float(momentum), self.RMSPROP_EPSILON, self.stream)
+    elif optimizer == 'adam':
+      call('edet_opt_adam_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(self.velocity), ptr(a.second_moment()),
+           *common, self.ADAM_BETA1, self.ADAM_BETA2, self.ADAM_EPSILON, self.stream)
+    elif optimizer in ('momentum', 'sgd'):
+      call('edet_opt_sgd_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(self.velocity), *common, float(momentum),
+           self.stream)
+    else:
+      raise ValueError('unknown optimizer %r' % (optimizer,))
+    a.version += 1
+    a.step_count += 1
 
   def _fused_mbconv(self, xin, b, scope):
     """FusedMBConvBlock.call (effnetv2_model.py:373-406)."""

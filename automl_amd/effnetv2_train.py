@@ -1,0 +1,247 @@
+"""EfficientNetV2 classifier training on one MI355X: the reference's TF2 trainer on the HIP kernels.
+
+Mirror of ``efficientnetv2/main_tf2.py``: ``TrainableModel`` (:62-117, ``train_step`` / ``test_step``) on top of
+``EffNetV2Model``, ``build_tf2_optimizer`` (:36-59: RMSprop(rho 0.9, momentum 0.9, epsilon 0.001) by default,
+hparams.py:249; 'momentum', 'sgd', 'adam'), the compiled loss ``CategoricalCrossentropy(label_smoothing,
+from_logits=True)`` with the ``acc_top1`` / ``acc_top5`` metrics (:199-207), and ``WarmupLearningRateSchedule``
+(``efficientnetv2/utils.py:78-131``).
+
+One step = forward(training) with stochastic depth and head dropout -> ``edet_softmax_xent`` (loss, d logits and the
+metric counts in one pass) -> ``V2Engine.backward`` -> ``edet_opt_l2_norms`` / ``edet_opt_clip_factors`` (the L2 term of
+``_reg_l2_loss`` and the gradient norm; the reference clips nothing, gclip = 0) -> ``edet_opt_rmsprop_ema`` (or the SGD /
+Adam kernel).  The BatchNorm moving statistics move in the forward pass.  With ``use_graph`` the step is captured once
+into a hipGraph and replayed; the learning rate travels through a device vector and the dropout / stochastic-depth masks
+are redrawn outside the graph.
+
+Single GPU.  Not built, and raising or absent rather than ignored: data-parallel classifier training, mixup / cutmix
+and soft labels (both 0 in hparams.py:282-283), ``conv_dropout``, progressive resizing, the TF1 trainer's
+EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
+reference's TF2 trainer, keeps none).
+"""
+import math
+
+import numpy as np
+import torch
+
+from automl_amd import effnetv2_model
+
+OPTIMIZERS = ('rmsprop', 'momentum', 'sgd', 'adam')
+
+
+class WarmupLearningRateSchedule(object):
+  """efficientnetv2/utils.py:78-131, evaluated on the host for an integer step."""
+
+  def __init__(self, initial_lr, steps_per_epoch=None, lr_decay_type='exponential', decay_factor=0.97, decay_epochs=2.4,
+               total_steps=None, warmup_epochs=5, minimal_lr=0):
+    if lr_decay_type not in ('exponential', 'cosine', 'linear', 'constant'):
+      raise ValueError('Unknown lr_decay_type : %s' % lr_decay_type)
+    self.initial_lr = initial_lr
+    self.steps_per_epoch = steps_per_epoch
+    self.lr_decay_type = lr_decay_type
+    self.decay_factor = decay_factor
+    self.decay_epochs = decay_epochs
+    self.total_steps = total_steps
+    self.warmup_epochs = warmup_epochs
+    self.minimal_lr = minimal_lr
+
+  def __call__(self, step):
+    step = int(step)
+    if self.lr_decay_type == 'exponential':
+      assert self.steps_per_epoch is not None
+      decay_steps = self.steps_per_epoch * self.decay_epochs
+      # tf.keras ExponentialDecay(staircase=True): initial * factor ^ floor(step / decay_steps).  Keras divides in float32,
+      # this host in double: where decay_steps is not exactly representable the two can sit one stair apart for the one
+      # step at a boundary (not pinned: TensorFlow is not available to the tests)
+      lr = self.initial_lr * self.decay_factor ** math.floor(step / decay_steps)
+    elif self.lr_decay_type == 'cosine':
+      assert self.total_steps is not None
+      lr = 0.5 * self.initial_lr * (1 + math.cos(math.pi * float(step) / self.total_steps))
+    elif self.lr_decay_type == 'linear':
+      assert self.total_steps is not None
+      lr = (1.0 - float(step) / self.total_steps) * self.initial_lr
+    else:
+      lr = self.initial_lr
+    if self.minimal_lr:
+      lr = max(lr, self.minimal_lr)
+    if self.warmup_epochs:
+      warmup_steps = int(self.warmup_epochs * self.steps_per_epoch)
+      if step < warmup_steps:
+        lr = self.initial_lr * float(step) / float(warmup_steps)
+    return float(lr)
+
+  def get_config(self):
+    return {k: getattr(self, k) for k in ('initial_lr', 'steps_per_epoch', 'lr_decay_type', 'decay_factor',
+                                          'decay_epochs', 'total_steps', 'warmup_epochs', 'minimal_lr')}
+
+
+class TrainableModel(effnetv2_model.EffNetV2Model):
+  """EffNetV2Model plus the reference's train_step / test_step (main_tf2.py:62-117).
+
+  learning_rate: a float or a callable of the iteration count (WarmupLearningRateSchedule).  use_graph: capture the step
+  at its second call for a batch shape and replay it afterwards; False = every launch eager (the tests compare both).
+  check_device_labels: also range-check labels that arrive as device tensors (one synchronisation per step).
+  ``momentum`` is build_tf2_optimizer's (0.9), used by 'rmsprop' and 'momentum'."""
+
+  def __init__(self, model_name='efficientnetv2-s', model_config=None, name=None, weight_decay=0.0, optimizer='rmsprop',
+               learning_rate=0.016, label_smoothing=0.0, ema_decay=None, momentum=0.9, use_graph=True, check_device_labels=False,
+               **kwargs):
+    super().__init__(model_name=model_name, model_config=model_config, include_top=True, name=name or model_name, **kwargs)
+    optimizer = str(optimizer).lower()
+    if optimizer not in OPTIMIZERS:
+      raise ValueError('Unknown optimizer: %s (build_tf2_optimizer has %s)' % (optimizer, ', '.join(OPTIMIZERS)))
+    if self._mconfig.conv_dropout:
+      raise ValueError('conv_dropout=%r is not built (None in every named model)' % (self._mconfig.conv_dropout,))
+    if not self.spec.num_classes:
+      raise ValueError('a classifier needs num_classes > 0')
+    if not 0.0 <= float(self._mconfig.dropout_rate or 0.0) < 1.0:
+      raise ValueError('dropout_rate %r outside [0, 1)' % (self._mconfig.dropout_rate,))
+    self.weight_decay = float(weight_decay)
+    self.optimizer = optimizer
+    self.momentum = 0.0 if optimizer == 'sgd' else float(momentum)
+    self.learning_rate = learning_rate
+    self.label_smoothing = float(label_smoothing)
+    self.ema_decay = None if not ema_decay else float(ema_decay)
+    self.use_graph = bool(use_graph)
+    self.check_device_labels = bool(check_device_labels)
+    self.iterations = 0
+    self._graph = None
+    self._pending_state = None
+
+  # ---- plumbing ------------------------------------------------------------------------------------------------------
+  def _ensure_engine(self, batch, height, width):
+    eng = super()._ensure_engine(batch, height, width)
+    eng.head_dropout = float(self._mconfig.dropout_rate or 0.0)
+    if self.optimizer in ('rmsprop', 'adam'):
+      eng.arena.use_second_slot('rms' if self.optimizer == 'rmsprop' else 'adam_v')
+    if self._pending_state is not None:
+      state, self._pending_state = self._pending_state, None
+      self._apply_state(eng, state)
+    return eng
+
+  def _lr(self):
+    lr = self.learning_rate
+    return float(lr(self.iterations)) if callable(lr) else float(lr)
+
+  def _prepare(self, data):
+    """(images, labels) or the reference's ({'image': ...}, {'label': ...}) -> (executor, device images, device labels)."""
+    images, labels = data
+    if isinstance(images, dict):
+      images, labels = images['image'], labels['label']
+    if isinstance(images, np.ndarray):
+      images = torch.from_numpy(images)
+    if images.dim() != 4 or images.shape[-1] != 3:
+      raise ValueError('images must be [batch, height, width, 3], got %s' % (tuple(images.shape),))
+    labels = torch.as_tensor(labels)
+    if labels.dim() != 1 or labels.is_floating_point() or labels.numel() != images.shape[0]:
+      raise ValueError('labels must be sparse integer class ids [batch] (soft labels: mixup / cutmix are not built)')
+    if labels.device.type == 'cpu' or self.check_device_labels:
+      # (labels already on the device are the caller's promise unless check_device_labels: the check waits for the device)
+      if int(labels.min()) < 0 or int(labels.max()) >= self.spec.num_classes:
+        raise ValueError('labels outside [0, %d)' % self.spec.num_classes)
+    eng = self._ensure_engine(int(images.shape[0]), int(images.shape[1]), int(images.shape[2]))
+    images = images.to(device=eng.device, dtype=eng.tdtype).contiguous()
+    return eng, images, labels.to(device=eng.device, dtype=torch.int32).contiguous()
+
+  def _metrics(self, eng, lr=None):
+    s = eng.cls_sums.detach().cpu().numpy()
+    out = {'loss': float(s[0]) + float(s[3]), 'reg_l2_loss': float(s[3]), 'acc_top1': float(s[1]) / eng.batch,
+           'acc_top5': float(s[2]) / eng.batch}
+    if lr is not None:
+      out['gradient_norm'] = float(eng.gnorm.item())
+      out['learning_rate'] = lr
+    return out
+
+  # ---- the step ------------------------------------------------------------------------------------------------------
+  def _step_body(self, eng, images, labels):
+    eng.forward(images, training=True)
+    eng.softmax_loss(labels, self.label_smoothing)
+    eng.backward()
+    eng.update_local(self.weight_decay)
+    eng.update_apply(self.optimizer, self.momentum, self.ema_decay is not None)
+
+  def _graph_step(self, eng, images, labels):
+    g = self._graph
+    if g is None or g['engine'] is not eng:
+      g = self._graph = {'engine': eng, 'steps': 0, 'graph': None, 'images': torch.empty_like(images),
+                         'labels': torch.empty_like(labels)}
+    if images.data_ptr() != g['images'].data_ptr():
+      g['images'].copy_(images, non_blocking=True)
+    if labels.data_ptr() != g['labels'].data_ptr():
+      g['labels'].copy_(labels, non_blocking=True)
+    if g['steps'] == 0:
+      # first step eager: allocates every buffer (the masks among them) and runs the one-time kernel attribute setup
+      self._step_body(eng, g['images'], g['labels'])
+    else:
+      if g['graph'] is None:
+        torch.cuda.synchronize()
+        # the capture pass runs the host bookkeeping once WITHOUT executing anything: the counters stay where they were
+        counters = (eng.arena.version, eng.arena.step_count)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+          self._step_body(eng, g['images'], g['labels'])
+        eng.arena.version, eng.arena.step_count = counters
+        g['graph'] = graph
+      g['graph'].replay()
+      eng.arena.version += 1
+      eng.arena.step_count += 1
+    g['steps'] += 1
+
+  def input_buffers(self):
+    """(images, labels) static device buffers of the captured step (None before the first graph step)."""
+    g = self._graph
+    return (g['images'], g['labels']) if g else None
+
+  def train_step(self, data, sync_loss=True):
+    """data = (images [B,H,W,3], labels int [B]) -> {'loss', 'reg_l2_loss', 'acc_top1', 'acc_top5', 'gradient_norm',
+    'learning_rate'} of this step's batch (main_tf2.py:89-103; sync_loss=False skips the read-back).
+    Labels outside [0, num_classes) raise before anything is launched when they arrive on the host.  Labels that are
+    already DEVICE tensors are not looked at (that would synchronise every step) unless the model was built with
+    check_device_labels=True: an out-of-range device label is then the caller's error, and the kernel -- which reads
+    nothing out of bounds for it -- returns a finite loss for a row without a hot class, with no signal."""
+    eng, images, labels = self._prepare(data)
+    lr = self._lr()
+    eng.set_update_hyper(lr, self.ema_decay, self.optimizer)
+    if eng.drop_masks or eng.dropout_mask is not None:
+      eng.refresh_drop_masks()      # (an engine's first step draws its masks where it creates them)
+    if self.use_graph:
+      self._graph_step(eng, images, labels)
+    else:
+      self._step_body(eng, images, labels)
+    self.iterations += 1
+    if not sync_loss:
+      return {'learning_rate': lr}
+    return self._metrics(eng, lr)
+
+  def test_step(self, data):
+    """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117)."""
+    eng, images, labels = self._prepare(data)
+    eng.forward(images, training=False)
+    eng.softmax_loss(labels, self.label_smoothing)
+    # the compiled loss's regularisation term; the gradient arena of the last train_step stays as it is
+    eng.l2_loss_eval(self.weight_decay)
+    return self._metrics(eng)
+
+  # ---- state ---------------------------------------------------------------------------------------------------------
+  def get_optimizer_state(self):
+    """Optimizer slots ('velocity' = the momentum slot, 'rms' = RMSprop's mean square or 'adam_v'), EMA shadows, the
+    iteration count (it drives the learning-rate schedule) and the state of the generator behind the dropout and
+    stochastic-depth draws, so that a resumed run continues the uninterrupted one bit for bit."""
+    if self.engine is None:
+      raise RuntimeError('the network has not been built yet (call it once)')
+    state = self.engine.arena.get_optimizer_state()
+    state['iterations'] = self.iterations
+    state['rng_state'] = self.engine._rng.get_state().cpu().numpy().copy()
+    return state
+
+  def set_optimizer_state(self, state):
+    if self.engine is None:
+      self._pending_state = dict(state)      # applied when the first executor is built
+      self.iterations = int(state['iterations'])
+      return
+    self._apply_state(self.engine, state)
+
+  def _apply_state(self, eng, state):
+    eng.arena.set_optimizer_state(state)
+    self.iterations = int(state['iterations'])
+    if 'rng_state' in state:
+      eng._rng.set_state(torch.as_tensor(state['rng_state'], dtype=torch.uint8))

@@ -222,23 +222,38 @@ class ParamArena(object):
       self._slice(self.ema, None, name).copy_(t)
 
   def get_optimizer_state(self):
-    """Host copy of the optimizer slots: momentum (Adam: first moment), EMA shadows, iteration count; Adam's second moment
-    when that optimizer has run."""
+    """Host copy of the optimizer slots: momentum (Adam: first moment), EMA shadows, iteration count; the second slot when
+    an optimizer that has one has run -- under 'adam_v' (Adam's second moment) or 'rms' (RMSprop's mean square)."""
     state = {'velocity': self.velocity.cpu().numpy().copy(), 'ema': self.ema.cpu().numpy().copy(),
              'iterations': self.step_count}
     if getattr(self, 'adam_v', None) is not None:
-      state['adam_v'] = self.adam_v.cpu().numpy().copy()
+      state[self.second_slot_key] = self.adam_v.cpu().numpy().copy()
     return state
 
   def set_optimizer_state(self, state):
     self.velocity.copy_(torch.as_tensor(state['velocity']))
     self.ema.copy_(torch.as_tensor(state['ema']))
-    if 'adam_v' in state:
-      self.second_moment().copy_(torch.as_tensor(state['adam_v']))
+    for key in ('adam_v', 'rms'):
+      if key in state:
+        self.use_second_slot(key)
+        self.second_moment().copy_(torch.as_tensor(state[key]))
     self.step_count = int(state['iterations'])
 
+  second_slot_key = 'adam_v'
+
+  def use_second_slot(self, key):
+    """Names the optimizer that owns the second slot arena: 'adam_v' (Adam's v, the default) or 'rms' (RMSprop's mean
+    square, effnetv2_train.TrainableModel) -- the key it has in get_optimizer_state.  One optimizer per arena: once
+    steps have been applied with the slot allocated, another owner is refused (Adam's v is not RMSprop's ms)."""
+    assert key in ('adam_v', 'rms'), key
+    if key != self.second_slot_key and getattr(self, 'adam_v', None) is not None and self.step_count > 0:
+      raise ValueError('the second optimizer slot of this arena holds %r after %d steps; it cannot become %r'
+                       % (self.second_slot_key, self.step_count, key))
+    self.second_slot_key = key
+
   def second_moment(self):
-    """Adam's v slot, allocated on first use (the SGD configurations never pay for it)."""
+    """The second slot arena (attribute `adam_v`: the name plans and state files know it by), allocated on first use (the
+    SGD configurations never pay for it): Adam's v, or RMSprop's ms when use_second_slot('rms') said so."""
     if getattr(self, 'adam_v', None) is None:
       self.adam_v = torch.zeros_like(self.velocity)
     return self.adam_v

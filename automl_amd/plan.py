@@ -42,6 +42,7 @@ State files (edet_net_save_state / edet_net_load_state, read_state / write_state
                count x f32 }
 """
 import bisect
+import contextlib
 import ctypes
 import os
 import re
@@ -648,26 +649,36 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
   The state the plan starts from is the network's state after one un-recorded warm-up pass of each program.
   """
   b, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
-  eng = net._ensure_engine(b, h, w)
-  assert eng.sync_bn is None and eng._overlap_reduce is None, 'plans record the default step structure'
-  images = net._to_device_images(images, eng)
-  dl = None
-  if labels is not None:
-    dl = net._labels_to_device(labels, eng)
-    assert 'mean_num_positives' in dl, "the recorded step computes the normalizer on the device: labels['mean_num_positives']"
+  # A plan carries whole allocator blocks.  A buffer that the caching allocator serves from a cached block of an earlier,
+  # larger tensor drags that block's slack into the file (up to 1 MiB per large buffer; a block beyond max_init_bytes loses
+  # its initial contents instead), so the file would follow whatever the process did before.  A network that gets its
+  # executor here gets it -- with the buffers of the warm-up passes and the device copies of the inputs -- from an allocator
+  # pool of its own: the same network recorded twice has the same blocks.  (The pool lives as long as the executor.)
+  fresh = net.engine is None
+  pool = torch.cuda.MemPool() if fresh else None
+  with (torch.cuda.use_mem_pool(pool) if fresh else contextlib.nullcontext()):
+    eng = net._ensure_engine(b, h, w)
+    assert eng.sync_bn is None and eng._overlap_reduce is None, 'plans record the default step structure'
+    images = net._to_device_images(images, eng)
+    dl = None
+    if labels is not None:
+      dl = net._labels_to_device(labels, eng)
+      assert 'mean_num_positives' in dl, "the recorded step computes the normalizer on the device: labels['mean_num_positives']"
 
-  det = None
-  if detect_raw_hw is not None:
-    det = _Detect(net, eng, images, detect_raw_hw)
-    if raw_images is not None:
-      det.raw.copy_(torch.as_tensor(raw_images).to(det.raw.device))
-  # warm-up: every buffer of both programs exists afterwards
-  eng.forward(images, training=False)
-  if det is not None:
-    det.run()
-  if dl is not None:
-    train_pass(eng, images, dl, learning_rate, ema_decay)
-  torch.cuda.synchronize()
+    det = None
+    if detect_raw_hw is not None:
+      det = _Detect(net, eng, images, detect_raw_hw)
+      if raw_images is not None:
+        det.raw.copy_(torch.as_tensor(raw_images).to(det.raw.device))
+    # warm-up: every buffer of both programs exists afterwards
+    eng.forward(images, training=False)
+    if det is not None:
+      det.run()
+    if dl is not None:
+      train_pass(eng, images, dl, learning_rate, ema_decay)
+    torch.cuda.synchronize()
+  if fresh:
+    eng._plan_pool = pool
   rec = Recorder()
   persistent = [eng.params_flat, eng.velocity, eng.ema, eng.state_flat, eng.seg_flags, eng.seg_offsets, eng.seg_factor,
                 eng.hyper]

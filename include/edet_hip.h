@@ -414,6 +414,26 @@ int edet_box_loss(const void* box_out, int ld, const float* box_targets,
                   float grad_scale, const float* norm_scale_dev, void* dbox, float* dbias, float* sums,
                   void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
+/* ---- EfficientNetV2 classifier loss and head dropout (efficientnetv2/main_tf2.py:89-117,199-207) ----
+ * edet_softmax_xent: tf.keras.losses.CategoricalCrossentropy(label_smoothing, from_logits=True) with the default mean over
+ * the batch (main_tf2.py:201-202), its gradient, and the counts behind TopKCategoricalAccuracy(k=1) / (k=5) (:203-206), in
+ * one pass.  logits [batch][ld] in `dtype` (num_classes valid columns), labels int32 [batch] in [0, num_classes) -- sparse
+ * labels only; the CALLER checks the range (a label outside it is an argument error, the kernel merely reads nothing out of
+ * bounds for one).  Per row in fp32: m = max x, lse = m + log sum exp(x - m), y_c = (1 - s)[c == label] + s / num_classes,
+ * loss = lse - sum_c y_c x_c.  dlogits [batch][ld] = (softmax - y) * grad_scale / batch, padding columns written as zeros;
+ * sums[0] += mean loss, sums[1] / sums[2] += rows whose label is in the top 1 / top 5 (ties: the number of logits strictly
+ * greater than the label's is < k).  Rows are added in a fixed order through `workspace` ([ceil(batch / 4)][3] floats;
+ * without one a single workgroup walks the rows): no atomics, the same bits on every run.
+ * Stated from the Keras definition; TensorFlow is not installed where this library is tested, so the fp32 restatement in
+ * tests/test_effnetv2_train.py (itself pinned against torch.nn.functional.cross_entropy) is what the tests compare with. */
+int edet_softmax_xent(const void* logits, int ld, const int32_t* labels, int batch, int num_classes,
+                      float label_smoothing, float grad_scale, void* dlogits, float* sums, void* workspace,
+                      size_t workspace_bytes, int dtype, void* stream);
+/* dst[i] = (dtype) (src[i] * mask[i]): the head dropout (effnetv2_model.py:464-467,483-484: after global pooling, before the
+ * dense layer) folded into the cast of the pooled sums; mask = fp32 {0, 1 / (1 - rate)} drawn by the caller, NULL = edet_cast.
+ * dst may be src (fp32): the same mask on d(pooled) in the backward pass. */
+int edet_dropout_cast(const float* src, const float* mask, void* dst, int64_t count, int dtype, void* stream);
+
 /* ---- optimizer -----------------------------------------------------------------
  * train_lib.py:486-491 (L2), :675-682 (per-tensor clip_by_norm then
  * clip_by_global_norm), Keras SGD momentum, TFA MovingAverage (:176-199).
@@ -449,6 +469,15 @@ int edet_opt_sgd_ema(float* params, float* grads, float* velocity, float* ema,
 int edet_opt_adam_ema(float* params, const float* grads, float* m, float* v, float* ema,
                       const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
                       const float* hyper_dev, float beta1, float beta2, float epsilon, void* stream);
+/* tf.keras.optimizers.RMSprop(lr, rho, momentum, epsilon) as efficientnetv2/main_tf2.py:49-52 builds it (0.9, 0.9, 0.001;
+ * the V2 default, hparams.py:249), TensorFlow's ApplyRMSProp form with momentum: ms += (1 - rho)(g^2 - ms);
+ * mom = momentum * mom + lr * g / sqrt(ms + epsilon); w -= mom.  ms, mom = the two slot arenas (both start at zero, Keras
+ * add_slot); hyper_dev[0] = learning rate, hyper_dev[1] = EMA decay; clip factors, frozen segments and the optional EMA shadow
+ * as for edet_opt_adam_ema (ema == NULL: the reference's TF2 trainer has none).  Stated from TensorFlow's documented
+ * kernel, not run against it: the numpy restatement in tests/test_effnetv2_train.py is what pins it. */
+int edet_opt_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
+                         const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
+                         const float* hyper_dev, float rho, float momentum, float epsilon, void* stream);
 
 /* ---- step plumbing (round 6): the few operations of a step that are not layers, so that EVERY launch of a step goes
  * through this ABI and a step can be recorded and replayed without the Python interpreter (include/edet_net.h).

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""EfficientNetV2 classifier training on one MI355X, for LABNOTES.md (NOT the bench.py line).  One phase per process
+(scripts/bench_v2_train.sh chains them under time limits), one JSON line each:
+  opt    edet_opt_rmsprop_ema against edet_opt_adam_ema on the model's arena (same bytes moved): HIP events around
+         `--launches` launches each, alternating, `--reps` repetitions -> medians, spreads (max - min), implied GB/s;
+  step   ms per TrainableModel.train_step (RMSprop, default dropout and stochastic depth, hipGraph replay);
+  fwdbwd ms per forward(training) + backward of EffNetV2Model with dropout_rate=0, launched eagerly: what the step had
+         before the loss, the dropout and the update existed."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from automl_amd import _lib, effnetv2_configs, effnetv2_model, effnetv2_train, engine as engine_lib  # noqa: E402
+from automl_amd._lib import call, ptr  # noqa: E402
+
+
+def bench_opt(args):
+  spec = effnetv2_model.V2Spec(effnetv2_configs.model_config(args.model))
+  a = engine_lib.ParamArena(spec, 'cuda:0', effnetv2_model.init_params(spec, 0))
+  n = a.n_train_elems
+  a.grads_flat.copy_(torch.randn(n, device='cuda:0') * 1e-2)
+  slot2 = a.second_moment()
+  hyper = torch.tensor([1e-6, 0.9999], dtype=torch.float32, device='cuda:0')
+  st = torch.cuda.current_stream().cuda_stream
+  common = (ptr(a.ema), ptr(a.seg_offsets), ptr(a.seg_factor), ptr(a.seg_flags), a.nseg, ptr(hyper))
+
+  def rms():
+    call('edet_opt_rmsprop_ema', ptr(a.params_flat), ptr(a.grads_flat), ptr(slot2), ptr(a.velocity), *common, 0.9, 0.9, 1e-3, st)
+
+  def adam():
+    call('edet_opt_adam_ema', ptr(a.params_flat), ptr(a.grads_flat), ptr(a.velocity), ptr(slot2), *common, 0.9, 0.999, 1e-7, st)
+  times = {'rmsprop': [], 'adam': []}
+  for fn in (rms, adam):
+    for _ in range(5):
+      fn()
+  torch.cuda.synchronize()
+  for _ in range(args.reps):
+    for name, fn in (('rmsprop', rms), ('adam', adam)):
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(args.launches):
+        fn()
+      e1.record()
+      torch.cuda.synchronize()
+      times[name].append(e0.elapsed_time(e1) / args.launches)
+  nbytes = 9 * 4 * n      # reads g, w, two slots, ema; writes w, two slots, ema
+  out = {'phase': 'opt', 'model': args.model, 'arena_elems': n, 'segments': a.nseg, 'bytes_per_launch': nbytes,
+         'launches': args.launches, 'reps': args.reps}
+  for name, t in times.items():
+    med = float(np.median(t))
+    out[name] = {'median_ms': round(med, 5), 'spread_ms': round(max(t) - min(t), 5), 'min_ms': round(min(t), 5),
+                 'GBps': round(nbytes / (med * 1e-3) / 1e9, 1)}
+  allow = max(out['rmsprop']['spread_ms'], out['adam']['spread_ms'])
+  out['rmsprop_within_adam_plus_spread'] = out['rmsprop']['median_ms'] <= out['adam']['median_ms'] + allow
+  print(json.dumps(out))
+
+
+def _data(args):
+  rng = np.random.default_rng(2)
+  images = torch.from_numpy(rng.standard_normal((args.batch, args.size, args.size, 3)).astype(np.float32))
+  return images.to('cuda:0', torch.bfloat16).contiguous(), torch.from_numpy(rng.integers(0, 1000, args.batch)).to('cuda:0', torch.int32)
+
+
+def bench_step(args):
+  net = effnetv2_train.TrainableModel(args.model, dtype='bf16', learning_rate=1e-4, weight_decay=1e-5, label_smoothing=0.1,
+                                      use_graph=True)
+  images, labels = _data(args)
+  first = net.train_step((images, labels))
+  for _ in range(max(args.warmup, 2)):
+    net.train_step((images, labels), sync_loss=False)
+  images, labels = net.input_buffers()
+  torch.cuda.synchronize()
+  t0 = time.perf_counter()
+  for _ in range(args.steps):
+    net.train_step((images, labels), sync_loss=False)
+  torch.cuda.synchronize()
+  dt = (time.perf_counter() - t0) / args.steps
+  last = net.train_step((images, labels))
+  print(json.dumps({'phase': 'step', 'workload': '%s %dx%d batch %d bf16 train_step (rmsprop, dropout %g, stochastic depth), '
+                    'hipGraph replay' % (args.model, args.size, args.size, args.batch, net.cfg_model.dropout_rate),
+                    'ms_per_step': round(dt * 1e3, 3), 'images_per_sec': round(args.batch / dt, 1),
+                    'first_loss': first['loss'], 'last_loss': last['loss'], 'steps': args.steps}))
+
+
+def bench_fwdbwd(args):
+  net = effnetv2_model.EffNetV2Model(args.model, 'dropout_rate=0', dtype='bf16')
+  images, _ = _data(args)
+  eng = net._ensure_engine(args.batch, args.size, args.size)
+  dlog = torch.randn(args.batch, net.spec.num_classes, device='cuda:0') * 1e-3
+
+  def one():
+    eng.forward(images, training=True)
+    eng.backward(dlog)
+  for _ in range(max(args.warmup, 2)):
+    one()
+  torch.cuda.synchronize()
+  t0 = time.perf_counter()
+  for _ in range(args.steps):
+    one()
+  torch.cuda.synchronize()
+  dt = (time.perf_counter() - t0) / args.steps
+  print(json.dumps({'phase': 'fwdbwd', 'workload': '%s %dx%d batch %d bf16 forward(training) + backward, dropout_rate=0, eager '
+                    'launches' % (args.model, args.size, args.size, args.batch), 'ms_per_pass': round(dt * 1e3, 3),
+                    'steps': args.steps}))
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('phase', choices=['opt', 'step', 'fwdbwd'])
+  ap.add_argument('--model', default='efficientnetv2-s')
+  ap.add_argument('--batch', type=int, default=128)
+  ap.add_argument('--size', type=int, default=224)
+  ap.add_argument('--steps', type=int, default=20)
+  ap.add_argument('--warmup', type=int, default=3)
+  ap.add_argument('--launches', type=int, default=20)
+  ap.add_argument('--reps', type=int, default=11)
+  args = ap.parse_args()
+  if not torch.cuda.is_available():
+    raise SystemExit('bench_v2_train.py needs an MI355X: there is no CPU path and no CPU timing')
+  _lib.load()
+  {'opt': bench_opt, 'step': bench_step, 'fwdbwd': bench_fwdbwd}[args.phase](args)
+
+
+if __name__ == '__main__':
+  main()
