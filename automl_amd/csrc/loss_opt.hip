@@ -357,22 +357,59 @@ __global__ __launch_bounds__(THREADS) void k_scale(float* grads, const int64_t* 
   for (int64_t i = b + threadIdx.x; i < e; i += THREADS) grads[i] *= f;
 }
 
-// Keras SGD: v = m*v - lr*g ; w += v.  TFA MovingAverage: ema -= (1-decay)*(ema - w)
-__device__ __forceinline__ void sgd1(float g, float& v, float& w, float& em, float lr, float momentum,
-                                     float decay, bool has_ema) {
-  v = momentum * v - lr * g;
-  w += v;
-  if (has_ema) em -= (1.f - decay) * (em - w);
-}
+// ---- the parameter update: one walk over a segment's slice (update_walk), whatever the optimizer.  A rule holds its scalars, says how
+// many slot arrays it keeps (SLOTS) and updates one element; the TFA MovingAverage shadow (ema -= (1-decay)*(ema - w)) rides
+// on every rule.  hyper[0] = the step's learning rate (Adam: bias-corrected by the host), hyper[1] = the EMA decay.
+// Keras SGD: v = m*v - lr*g ; w += v
+struct SgdRule {
+  static constexpr int SLOTS = 1;
+  float momentum;
+  __device__ __forceinline__ void operator()(float g, float& v, float&, float& w, float& em, float lr, float decay,
+                                             bool has_ema) const {
+    v = momentum * v - lr * g;
+    w += v;
+    if (has_ema) em -= (1.f - decay) * (em - w);
+  }
+};
 
-__global__ __launch_bounds__(THREADS) void k_sgd_ema(float* params, float* grads, float* vel, float* ema,
-                                                    const int64_t* seg_off, const float* seg_factor,
-                                                    const int32_t* seg_flags, const float* hyper, float momentum) {
+// tf.keras.optimizers.Adam (ResourceApplyAdam): m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); w -= alpha m / (sqrt(v) + eps)
+// with alpha = lr sqrt(1 - b2^t) / (1 - b1^t) formed by the host for this step (hyper[0])
+struct AdamRule {
+  static constexpr int SLOTS = 2;
+  float b1, b2, eps;
+  __device__ __forceinline__ void operator()(float g, float& m, float& u, float& w, float& em, float alpha, float decay,
+                                             bool has_ema) const {
+    m += (g - m) * (1.f - b1);
+    u += (g * g - u) * (1.f - b2);
+    w -= (m * alpha) / (sqrtf(u) + eps);
+    if (has_ema) em -= (1.f - decay) * (em - w);
+  }
+};
+
+// TensorFlow's ApplyRMSProp with momentum (what tf.keras.optimizers.RMSprop runs): ms += (1 - rho)(g^2 - ms);
+// mom = momentum mom + lr g / sqrt(ms + eps); w -= mom
+struct RmspropRule {
+  static constexpr int SLOTS = 2;
+  float rho, momentum, eps;
+  __device__ __forceinline__ void operator()(float g, float& ms, float& mom, float& w, float& em, float lr, float decay,
+                                             bool has_ema) const {
+    ms += (g * g - ms) * (1.f - rho);
+    mom = momentum * mom + (lr * g) / sqrtf(ms + eps);
+    w -= mom;
+    if (has_ema) em -= (1.f - decay) * (em - w);
+  }
+};
+
+template <typename Rule>
+__device__ __forceinline__ void update_walk(Rule rule, float* params, const float* grads, float* slot_a, float* slot_b,
+                                            float* ema, const int64_t* seg_off, const float* seg_factor,
+                                            const int32_t* seg_flags, const float* hyper) {
+  constexpr bool two = Rule::SLOTS == 2;      // slot_b is read and written by the two-slot rules only
   const int s = blockIdx.x;
   int64_t b, e;
   if (!slice_range(seg_off, s, blockIdx.y, b, e)) return;
-  // frozen variables are not in the optimizer's variable list (tf2/train_lib.py:478-491,683): value, momentum slot and
-  // EMA shadow stay exactly as they are
+  // frozen variables are not in the optimizer's variable list (tf2/train_lib.py:478-491,683): value, slots and EMA shadow
+  // stay exactly as they are
   if (seg_flags && (seg_flags[s] & EDET_SEG_FROZEN)) return;
   const float f = seg_factor ? seg_factor[s] : 1.f;
   const float lr = hyper[0], decay = hyper[1];
@@ -380,29 +417,56 @@ __global__ __launch_bounds__(THREADS) void k_sgd_ema(float* params, float* grads
   if ((b & 3) == 0) {
     const int64_t nv = (e - b) >> 2;
     const float4* g4 = reinterpret_cast<const float4*>(grads + b);
-    float4* v4 = reinterpret_cast<float4*>(vel + b);
+    float4* p4 = reinterpret_cast<float4*>(slot_a + b);
+    float4* q4 = reinterpret_cast<float4*>(two ? slot_b + b : nullptr);
     float4* w4 = reinterpret_cast<float4*>(params + b);
     float4* e4 = has_ema ? reinterpret_cast<float4*>(ema + b) : nullptr;
     for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
       const float4 g = g4[i];
-      float4 v = v4[i], w = w4[i], em = has_ema ? e4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-      sgd1(g.x * f, v.x, w.x, em.x, lr, momentum, decay, has_ema);
-      sgd1(g.y * f, v.y, w.y, em.y, lr, momentum, decay, has_ema);
-      sgd1(g.z * f, v.z, w.z, em.z, lr, momentum, decay, has_ema);
-      sgd1(g.w * f, v.w, w.w, em.w, lr, momentum, decay, has_ema);
-      v4[i] = v;
+      float4 p = p4[i], q = make_float4(0.f, 0.f, 0.f, 0.f), w = w4[i], em = has_ema ? e4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (two) q = q4[i];
+      rule(g.x * f, p.x, q.x, w.x, em.x, lr, decay, has_ema);
+      rule(g.y * f, p.y, q.y, w.y, em.y, lr, decay, has_ema);
+      rule(g.z * f, p.z, q.z, w.z, em.z, lr, decay, has_ema);
+      rule(g.w * f, p.w, q.w, w.w, em.w, lr, decay, has_ema);
+      p4[i] = p;
+      if constexpr (two) q4[i] = q;
       w4[i] = w;
       if (has_ema) e4[i] = em;
     }
     b += nv << 2;
   }
   for (int64_t i = b + threadIdx.x; i < e; i += THREADS) {
-    float v = vel[i], w = params[i], em = has_ema ? ema[i] : 0.f;
-    sgd1(grads[i] * f, v, w, em, lr, momentum, decay, has_ema);
-    vel[i] = v;
+    float p = slot_a[i], q = 0.f, w = params[i], em = has_ema ? ema[i] : 0.f;
+    if constexpr (two) q = slot_b[i];
+    rule(grads[i] * f, p, q, w, em, lr, decay, has_ema);
+    slot_a[i] = p;
+    if constexpr (two) slot_b[i] = q;
     params[i] = w;
     if (has_ema) ema[i] = em;
   }
+}
+
+// The kernels keep their names and parameter lists: the committed rocprofv3 statistics (profiles/) and the coverage test
+// that reads them know the update by kernel symbol.  The second launch bound (8 waves per SIMD, so at most 64 VGPRs) is
+// for the two-slot rules: without it the 4-wide Adam body takes 73 VGPRs and drops to 6 waves.
+__global__ __launch_bounds__(THREADS, 8) void k_sgd_ema(float* params, float* grads, float* vel, float* ema,
+                                                    const int64_t* seg_off, const float* seg_factor,
+                                                    const int32_t* seg_flags, const float* hyper, float momentum) {
+  update_walk(SgdRule{momentum}, params, grads, vel, nullptr, ema, seg_off, seg_factor, seg_flags, hyper);
+}
+
+__global__ __launch_bounds__(THREADS, 8) void k_adam_ema(float* params, const float* grads, float* m1, float* m2, float* ema,
+                                                     const int64_t* seg_off, const float* seg_factor,
+                                                     const int32_t* seg_flags, const float* hyper, float b1, float b2, float eps) {
+  update_walk(AdamRule{b1, b2, eps}, params, grads, m1, m2, ema, seg_off, seg_factor, seg_flags, hyper);
+}
+
+__global__ __launch_bounds__(THREADS, 8) void k_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
+                                                        const int64_t* seg_off, const float* seg_factor,
+                                                        const int32_t* seg_flags, const float* hyper, float rho, float momentum,
+                                                        float eps) {
+  update_walk(RmspropRule{rho, momentum, eps}, params, grads, ms, mom, ema, seg_off, seg_factor, seg_flags, hyper);
 }
 
 }  // namespace
@@ -518,37 +582,15 @@ extern "C" int edet_opt_scale(float* grads, const int64_t* seg_offsets, const fl
   return 0;
 }
 
-namespace {
-// tf.keras.optimizers.Adam (ResourceApplyAdam): m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); w -= alpha m / (sqrt(v) + eps)
-// with alpha = lr sqrt(1 - b2^t) / (1 - b1^t) formed by the host for this step (hyper[0]); TFA MovingAverage on top
-__device__ __forceinline__ void adam1(float g, float& m, float& u, float& w, float& em, float alpha, float b1, float b2,
-                                      float eps, float decay, bool has_ema) {
-  m += (g - m) * (1.f - b1);
-  u += (g * g - u) * (1.f - b2);
-  w -= (m * alpha) / (sqrtf(u) + eps);
-  if (has_ema) em -= (1.f - decay) * (em - w);
+extern "C" int edet_opt_sgd_ema(float* params, float* grads, float* velocity, float* ema,
+                                const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
+                                const float* hyper_dev, float momentum, void* stream) {
+  EDET_CHECK(params && grads && velocity && seg_offsets && hyper_dev && nseg > 0, "edet_opt_sgd_ema: bad arguments");
+  edet_launch(k_sgd_ema, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, grads, velocity, ema, seg_offsets,
+              seg_factor, seg_flags, hyper_dev, momentum);
+  EDET_LAUNCH_CHECK("edet_opt_sgd_ema");
+  return 0;
 }
-
-__global__ __launch_bounds__(THREADS) void k_adam_ema(float* params, const float* grads, float* m1, float* m2, float* ema,
-                                                     const int64_t* seg_off, const float* seg_factor,
-                                                     const int32_t* seg_flags, const float* hyper, float b1, float b2, float eps) {
-  const int s = blockIdx.x;
-  int64_t b, e;
-  if (!slice_range(seg_off, s, blockIdx.y, b, e)) return;
-  if (seg_flags && (seg_flags[s] & EDET_SEG_FROZEN)) return;      // not in the optimizer's variable list
-  const float f = seg_factor ? seg_factor[s] : 1.f;
-  const float alpha = hyper[0], decay = hyper[1];
-  const bool has_ema = ema != nullptr;
-  for (int64_t i = b + threadIdx.x; i < e; i += THREADS) {
-    float m = m1[i], u = m2[i], w = params[i], em = has_ema ? ema[i] : 0.f;
-    adam1(grads[i] * f, m, u, w, em, alpha, b1, b2, eps, decay, has_ema);
-    m1[i] = m;
-    m2[i] = u;
-    params[i] = w;
-    if (has_ema) ema[i] = em;
-  }
-}
-}  // namespace
 
 extern "C" int edet_opt_adam_ema(float* params, const float* grads, float* m, float* v, float* ema,
                                  const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
@@ -560,12 +602,13 @@ extern "C" int edet_opt_adam_ema(float* params, const float* grads, float* m, fl
   return 0;
 }
 
-extern "C" int edet_opt_sgd_ema(float* params, float* grads, float* velocity, float* ema,
-                                const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
-                                const float* hyper_dev, float momentum, void* stream) {
-  EDET_CHECK(params && grads && velocity && seg_offsets && hyper_dev && nseg > 0, "edet_opt_sgd_ema: bad arguments");
-  edet_launch(k_sgd_ema, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, grads, velocity, ema, seg_offsets, seg_factor, seg_flags, hyper_dev, momentum);
-  EDET_LAUNCH_CHECK("edet_opt_sgd_ema");
+extern "C" int edet_opt_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
+                                    const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
+                                    const float* hyper_dev, float rho, float momentum, float epsilon, void* stream) {
+  EDET_CHECK(params && grads && ms && mom && seg_offsets && hyper_dev && nseg > 0, "edet_opt_rmsprop_ema: bad arguments");
+  edet_launch(k_rmsprop_ema, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, grads, ms, mom, ema, seg_offsets,
+              seg_factor, seg_flags, hyper_dev, rho, momentum, epsilon);
+  EDET_LAUNCH_CHECK("edet_opt_rmsprop_ema");
   return 0;
 }
 
@@ -773,58 +816,6 @@ __global__ __launch_bounds__(THREADS) void k_dropout_cast(const float* src, cons
   for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += stride)
     dst[i] = from_f<T>(mask ? src[i] * mask[i] : src[i]);
 }
-
-// TensorFlow's ApplyRMSProp with momentum (what tf.keras.optimizers.RMSprop runs): ms += (1 - rho)(g^2 - ms);
-// mom = momentum mom + lr g / sqrt(ms + eps); w -= mom; TFA MovingAverage on top as for the other optimizers
-__device__ __forceinline__ void rms1(float g, float& ms, float& mom, float& w, float& em, float lr, float rho, float momentum,
-                                     float eps, float decay, bool has_ema) {
-  ms += (g * g - ms) * (1.f - rho);
-  mom = momentum * mom + (lr * g) / sqrtf(ms + eps);
-  w -= mom;
-  if (has_ema) em -= (1.f - decay) * (em - w);
-}
-
-__global__ __launch_bounds__(THREADS) void k_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
-                                                        const int64_t* seg_off, const float* seg_factor,
-                                                        const int32_t* seg_flags, const float* hyper, float rho, float momentum,
-                                                        float eps) {
-  const int s = blockIdx.x;
-  int64_t b, e;
-  if (!slice_range(seg_off, s, blockIdx.y, b, e)) return;
-  if (seg_flags && (seg_flags[s] & EDET_SEG_FROZEN)) return;      // not in the optimizer's variable list
-  const float f = seg_factor ? seg_factor[s] : 1.f;
-  const float lr = hyper[0], decay = hyper[1];
-  const bool has_ema = ema != nullptr;
-  if ((b & 3) == 0) {
-    const int64_t nv = (e - b) >> 2;
-    const float4* g4 = reinterpret_cast<const float4*>(grads + b);
-    float4* s4 = reinterpret_cast<float4*>(ms + b);
-    float4* m4 = reinterpret_cast<float4*>(mom + b);
-    float4* w4 = reinterpret_cast<float4*>(params + b);
-    float4* e4 = has_ema ? reinterpret_cast<float4*>(ema + b) : nullptr;
-    for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
-      const float4 g = g4[i];
-      float4 q = s4[i], v = m4[i], w = w4[i], em = has_ema ? e4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-      rms1(g.x * f, q.x, v.x, w.x, em.x, lr, rho, momentum, eps, decay, has_ema);
-      rms1(g.y * f, q.y, v.y, w.y, em.y, lr, rho, momentum, eps, decay, has_ema);
-      rms1(g.z * f, q.z, v.z, w.z, em.z, lr, rho, momentum, eps, decay, has_ema);
-      rms1(g.w * f, q.w, v.w, w.w, em.w, lr, rho, momentum, eps, decay, has_ema);
-      s4[i] = q;
-      m4[i] = v;
-      w4[i] = w;
-      if (has_ema) e4[i] = em;
-    }
-    b += nv << 2;
-  }
-  for (int64_t i = b + threadIdx.x; i < e; i += THREADS) {
-    float q = ms[i], v = mom[i], w = params[i], em = has_ema ? ema[i] : 0.f;
-    rms1(grads[i] * f, q, v, w, em, lr, rho, momentum, eps, decay, has_ema);
-    ms[i] = q;
-    mom[i] = v;
-    params[i] = w;
-    if (has_ema) ema[i] = em;
-  }
-}
 }  // namespace
 
 extern "C" int edet_softmax_xent(const void* logits, int ld, const int32_t* labels, int batch, int num_classes,
@@ -859,15 +850,5 @@ extern "C" int edet_dropout_cast(const float* src, const float* mask, void* dst,
   else if (dtype == EDET_F32) edet_launch(k_dropout_cast<float>, dim3((unsigned)grid), dim3(THREADS), 0, to_stream(stream), src, mask, (float*)dst, count);
   else EDET_CHECK(false, "edet_dropout_cast: bad dtype %d", dtype);
   EDET_LAUNCH_CHECK("edet_dropout_cast");
-  return 0;
-}
-
-extern "C" int edet_opt_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
-                                    const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
-                                    const float* hyper_dev, float rho, float momentum, float epsilon, void* stream) {
-  EDET_CHECK(params && grads && ms && mom && seg_offsets && hyper_dev && nseg > 0, "edet_opt_rmsprop_ema: bad arguments");
-  edet_launch(k_rmsprop_ema, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, grads, ms, mom, ema, seg_offsets,
-              seg_factor, seg_flags, hyper_dev, rho, momentum, epsilon);
-  EDET_LAUNCH_CHECK("edet_opt_rmsprop_ema");
   return 0;
 }

@@ -10,7 +10,8 @@ Scope: the forward pass in both BatchNo
 pass of the whole graph (``backward(d_outputs)``: Fused-MBConv dense convolutions, MBConv, SE, stochastic depth,
 head, dense layer).  The classifier's training step -- softmax cross-entropy with label smoothing, head dropout, the
 RMSprop / momentum / Adam update (``efficientnetv2/main_tf2.py``) -- is ``effnetv2_train.TrainableModel`` on the
-V2Engine methods at the end of this file (``softmax_loss``, ``update_local`` / ``update_apply``, ``head_dropout``).
+V2Engine methods at the end of this file (``softmax_loss``, ``head_dropout``) and the engine's update step
+(``Engine.optimizer_local`` / ``optimizer_apply`` with the trainer's ``engine.Update`` description).
 ``EffNetV2Model.__call__(training=True)`` itself still refuses dropout (pass ``model_config='dropout_rate=0'``): it has
 no labels to train with, and only the trainer owns the draws.  ``conv_dropout`` is not built anywhere.
 """
@@ -285,10 +286,7 @@ class V2Engine(engine_lib.Engine):
     r.grad_written = True
     super().backward()
 
-  # ---- classifier training (efficientnetv2/main_tf2.py:36-117): loss, dropout draws, update ----------------------------
-  RMSPROP_RHO, RMSPROP_MOMENTUM, RMSPROP_EPSILON = 0.9, 0.9, 0.001      # build_tf2_optimizer, main_tf2.py:36-52
-  ADAM_BETA1 = 0.9                                                      # tf.keras.optimizers.Adam(learning_rate) defaults
-
+  # ---- classifier training (efficientnetv2/main_tf2.py:62-117): loss, dropout draws; the update is Engine's ------------
   def _draw_dropout_mask(self):
     """tf.keras.layers.Dropout(rate): keep with probability 1 - rate, kept values scaled by 1 / (1 - rate); one draw per
     (image, feature).  From the engine's generator, like the stochastic-depth masks."""
@@ -316,27 +314,9 @@ class V2Engine(engine_lib.Engine):
          ptr(dl.data), ptr(self.cls_sums), *self._ws(), self.dtype, self.stream)
     self._dlogits_ready = self.training
 
-  def set_update_hyper(self, lr, ema_decay, optimizer):
-    """hyper[0] = the step's learning rate (Adam: bias-corrected for t = iterations + 1, as Engine.set_hyper), hyper[1] =
-    EMA decay; outside the captured step."""
-    if optimizer == 'adam':
-      t = self.arena.step_count + 1
-      lr = lr * math.sqrt(1.0 - self.ADAM_BETA2 ** t) / (1.0 - self.ADAM_BETA1 ** t)
-    self.hyper[:2].copy_(torch.tensor([lr, ema_decay or 0.0], dtype=torch.float32), non_blocking=True)
-
-  def update_local(self, weight_decay):
-    """TrainableModel._reg_l2_loss (main_tf2.py:80-87: the detection trainer's regular expression, so the arena's L2
-    flags) added to the gradient and to cls_sums[3]; no clipping (gclip = 0, hparams.py:261) -- clip 0 yields the
-    gradient norm and factors of one.  The update values come from the trainer: the model config has no training keys."""
-    st = self.stream
-    call('edet_opt_l2_norms', ptr(self.grads_flat), ptr(self.params_flat), ptr(self.seg_offsets), ptr(self.seg_flags),
-         self.nseg, float(weight_decay), ptr(self.seg_sqnorm), st)
-    call('edet_opt_clip_factors', ptr(self.seg_sqnorm), self.nseg, 0.0, ptr(self.seg_factor), ptr(self.gnorm),
-         ptr(self.cls_sums[3:]), st)
-
   def l2_loss_eval(self, weight_decay):
     """The same L2 term for an evaluation pass (test_step, main_tf2.py:105-117), added to cls_sums[3] WITHOUT touching the
-    gradient arena, the clip factors or the gradient norm (update_local adds weight_decay * w to the gradients): per-segment
+    gradient arena, the clip factors or the gradient norm (optimizer_local adds weight_decay * w to the gradients): per-segment
     sums of squares by torch.segment_reduce, weighted by the arena's L2 flags.  Not on the training path."""
     a = self.arena
     if getattr(a, '_l2_weights', None) is None:
@@ -344,25 +324,6 @@ class V2Engine(engine_lib.Engine):
       a._l2_weights = (a.seg_flags == _lib.SEG_L2).to(torch.float32)
     sq = torch.segment_reduce(self.params_flat * self.params_flat, 'sum', lengths=a._seg_lengths, unsafe=True)
     self.cls_sums[3:4].add_((0.5 * float(weight_decay)) * (sq * a._l2_weights).sum().reshape(1))
-
-  def update_apply(self, optimizer, momentum, use_ema):
-    """build_tf2_optimizer (main_tf2.py:36-59): 'rmsprop' (rho 0.9, momentum 0.9, epsilon 0.001), 'momentum' / 'sgd'
-    (Keras SGD, `momentum` = 0 for 'sgd'), 'adam' (Keras defaults); lr / EMA decay from self.hyper."""
-    a = self.arena
-    common = (ptr(self.ema) if use_ema else None, ptr(self.seg_offsets), None, ptr(self.seg_flags), self.nseg, ptr(self.hyper))
-    if optimizer == 'rmsprop':
-      call('edet_opt_rmsprop_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(a.second_moment()), ptr(self.velocity),
-           *common, self.RMSPROP_RHO, float(momentum), self.RMSPROP_EPSILON, self.stream)
-    elif optimizer == 'adam':
-      call('edet_opt_adam_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(self.velocity), ptr(a.second_moment()),
-           *common, self.ADAM_BETA1, self.ADAM_BETA2, self.ADAM_EPSILON, self.stream)
-    elif optimizer in ('momentum', 'sgd'):
-      call('edet_opt_sgd_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(self.velocity), *common, float(momentum),
-           self.stream)
-    else:
-      raise ValueError('unknown optimizer %r' % (optimizer,))
-    a.version += 1
-    a.step_count += 1
 
   def _fused_mbconv(self, xin, b, scope):
     """FusedMBConvBlock.call (effnetv2_model.py:373-406)."""

@@ -7,9 +7,9 @@ from_logits=True)`` with the ``acc_top1`` / ``acc_top5`` metrics (:199-207), and
 (``efficientnetv2/utils.py:78-131``).
 
 One step = forward(training) with stochastic depth and head dropout -> ``edet_softmax_xent`` (loss, d logits and the
-metric counts in one pass) -> ``V2Engine.backward`` -> ``edet_opt_l2_norms`` / ``edet_opt_clip_factors`` (the L2 term of
-``_reg_l2_loss`` and the gradient norm; the reference clips nothing, gclip = 0) -> ``edet_opt_rmsprop_ema`` (or the SGD /
-Adam kernel).  The BatchNorm moving statistics move in the forward pass.  With ``use_graph`` the step is captured once
+metric counts in one pass) -> ``V2Engine.backward`` -> ``Engine.optimizer_local`` (the L2 term of ``_reg_l2_loss`` and the
+gradient norm; the reference clips nothing, gclip = 0) -> ``Engine.optimizer_apply`` with this trainer's ``engine.Update``
+(``edet_opt_rmsprop_ema``, or the SGD / Adam entry point).  The BatchNorm moving statistics move in the forward pass.  With ``use_graph`` the step is captured once
 into a hipGraph and replayed; the learning rate travels through a device vector and the dropout / stochastic-depth masks
 are redrawn outside the graph.
 
@@ -24,8 +24,19 @@ import numpy as np
 import torch
 
 from automl_amd import effnetv2_model
+from automl_amd import engine as engine_lib
 
 OPTIMIZERS = ('rmsprop', 'momentum', 'sgd', 'adam')
+
+
+def build_update(optimizer, momentum):
+  """build_tf2_optimizer (main_tf2.py:36-59) as the engine's update description: 'rmsprop' (rho 0.9, momentum, epsilon
+  0.001), 'momentum' / 'sgd' (Keras SGD; the trainer passes momentum 0 for 'sgd'), 'adam' (tf.keras.optimizers.Adam(learning_rate) defaults)."""
+  if optimizer == 'rmsprop':
+    return engine_lib.Update('rmsprop', momentum, epsilon=0.001, rho=0.9)
+  if optimizer == 'adam':
+    return engine_lib.Update('adam', 0.9, engine_lib.Engine.ADAM_BETA2, engine_lib.Engine.ADAM_EPSILON)
+  return engine_lib.Update('sgd', momentum)
 
 
 class WarmupLearningRateSchedule(object):
@@ -98,6 +109,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.weight_decay = float(weight_decay)
     self.optimizer = optimizer
     self.momentum = 0.0 if optimizer == 'sgd' else float(momentum)
+    self.update = build_update(optimizer, self.momentum)
     self.learning_rate = learning_rate
     self.label_smoothing = float(label_smoothing)
     self.ema_decay = None if not ema_decay else float(ema_decay)
@@ -111,6 +123,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   def _ensure_engine(self, batch, height, width):
     eng = super()._ensure_engine(batch, height, width)
     eng.head_dropout = float(self._mconfig.dropout_rate or 0.0)
+    eng.update = self.update
     if self.optimizer in ('rmsprop', 'adam'):
       eng.arena.use_second_slot('rms' if self.optimizer == 'rmsprop' else 'adam_v')
     if self._pending_state is not None:
@@ -156,8 +169,8 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     eng.forward(images, training=True)
     eng.softmax_loss(labels, self.label_smoothing)
     eng.backward()
-    eng.update_local(self.weight_decay)
-    eng.update_apply(self.optimizer, self.momentum, self.ema_decay is not None)
+    eng.optimizer_local(False, weight_decay=self.weight_decay, clip=0.0, l2_sum=eng.cls_sums[3:])
+    eng.optimizer_apply(self.ema_decay is not None, False)
 
   def _graph_step(self, eng, images, labels):
     g = self._graph
@@ -174,16 +187,9 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     else:
       if g['graph'] is None:
         torch.cuda.synchronize()
-        # the capture pass runs the host bookkeeping once WITHOUT executing anything: the counters stay where they were
-        counters = (eng.arena.version, eng.arena.step_count)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-          self._step_body(eng, g['images'], g['labels'])
-        eng.arena.version, eng.arena.step_count = counters
-        g['graph'] = graph
+        g['graph'] = engine_lib.capture_graph(eng.arena, lambda: self._step_body(eng, g['images'], g['labels']))
       g['graph'].replay()
-      eng.arena.version += 1
-      eng.arena.step_count += 1
+      eng.arena.count_step()
     g['steps'] += 1
 
   def input_buffers(self):
@@ -200,7 +206,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     nothing out of bounds for it -- returns a finite loss for a row without a hot class, with no signal."""
     eng, images, labels = self._prepare(data)
     lr = self._lr()
-    eng.set_update_hyper(lr, self.ema_decay, self.optimizer)
+    eng.set_hyper(lr, self.ema_decay)
     if eng.drop_masks or eng.dropout_mask is not None:
       eng.refresh_drop_masks()      # (an engine's first step draws its masks where it creates them)
     if self.use_graph:

@@ -13,6 +13,7 @@ Design:
 Reference structure followed: efficientdet/tf2/efficientdet_keras.py:787-915 (EfficientDetNet),
 efficientdet/backbone/efficientnet_model.py:360-416,710-779, efficientdet/tf2/train_lib.py:493-684.
 """
+import collections
 import contextlib
 import ctypes
 import re
@@ -258,6 +259,31 @@ class ParamArena(object):
       self.adam_v = torch.zeros_like(self.velocity)
     return self.adam_v
 
+  def count_step(self):
+    """One optimizer step has been applied to the variables, by an eager update or by a replayed graph."""
+    self.version += 1
+    self.step_count += 1
+
+
+def capture_graph(arena, body, pool=None):
+  """body() captured into a new hipGraph.  thread_local: other threads of the process (the RCCL watchdog) may touch the
+  HIP runtime meanwhile.  The capture pass runs the body's host bookkeeping once WITHOUT executing anything, so the
+  arena's counters are put back where they were (also when the capture raises); ParamArena.count_step accounts for every
+  replay."""
+  counters = (arena.version, arena.step_count)
+  graph = torch.cuda.CUDAGraph()
+  try:
+    with torch.cuda.graph(graph, pool=pool, capture_error_mode='thread_local'):
+      body()
+  finally:
+    arena.version, arena.step_count = counters
+  return graph
+
+
+# What an engine's update step runs: kind = 'sgd' (Keras SGD; momentum), 'adam' (momentum = beta_1, beta2, epsilon) or
+# 'rmsprop' (rho, momentum, epsilon).  Scalars a kind does not use stay None.
+Update = collections.namedtuple('Update', 'kind momentum beta2 epsilon rho', defaults=(None, None, None))
+
 
 class Branch(object):
   """What an independent chain of launches needs of its own: a HIP stream, the BatchNorm partial-sum rows and the
@@ -345,12 +371,20 @@ class Engine(object):
     self.sync_bn = None
     self.bn_bessel = True        # Keras fused BatchNorm: Bessel-corrected batch variance into moving_variance
     self.drop_masks = {}      # block scope -> (mask [n,c] fp32 = floor(p + u_n) / p, survival probability p)
-    # optimizer = 'adam' (train_lib.py:183-186): Keras defaults for what the reference does not set
-    self.adam = str(getattr(config, 'optimizer', 'sgd')).lower() == 'adam'
-    if self.adam:
+    # optimizer = 'adam' (train_lib.py:183-186: beta_1 = momentum, Keras defaults for what the reference does not set),
+    # anything else Keras SGD; a trainer with other optimizers (effnetv2_train) assigns its own description
+    momentum = float(getattr(config, 'momentum', 0.0))
+    if str(getattr(config, 'optimizer', 'sgd')).lower() == 'adam':
+      self.update = Update('adam', momentum, self.ADAM_BETA2, self.ADAM_EPSILON)
       self.arena.second_moment()
+    else:
+      self.update = Update('sgd', momentum)
     self._rng = torch.Generator(device=self.device)
     self._rng.manual_seed(1000003 * seed + 17)
+
+  @property
+  def adam(self):
+    return self.update.kind == 'adam'
 
   @property
   def esize(self):
@@ -1454,14 +1488,9 @@ class Engine(object):
     self._join_side()                 # (first bucket: the side chain's share of the tower gradients)
     seg = self._seg_host
     s0, s1 = seg.index(lo), seg.index(hi)
-    c = self.config
     no = self._bucket_no
     sq = self.buf('ovl:sq%d' % no, (2 * (s1 - s0) * _lib.OPT_SPLIT,), torch.float32)
-    st = self.stream
-    call('edet_opt_l2_norms', ptr(self.grads_flat), ptr(self.params_flat), self.seg_offsets.data_ptr() + 8 * s0,
-         self.seg_flags.data_ptr() + 4 * s0, s1 - s0, float(c.weight_decay), ptr(sq), st)
-    call('edet_opt_clip_factors', ptr(sq), s1 - s0, 0.0, self.seg_factor.data_ptr() + 4 * s0,
-         self._bucket_gn.data_ptr() + 4 * no, ptr(self.loss_sums[2:]), st)
+    self.optimizer_local(False, clip=0.0, first=s0, end=s1, sqnorm=sq, gnorm=self._bucket_gn[no:])
     main = torch.cuda.current_stream(self.device)
     ready = torch.cuda.Event()
     ready.record(main)
@@ -1484,11 +1513,11 @@ class Engine(object):
     """Per-step scalars -> device (hyper[0] = learning rate, hyper[1] = EMA decay).  Stream-ordered H2D
     copy from pageable memory (staged synchronously by the runtime, so the host values may change at once);
     kept OUTSIDE the captured step."""
-    if self.adam:
+    if self.update.kind == 'adam':
       # tf.keras Adam's bias-corrected rate of THIS step (t = iterations + 1), ResourceApplyAdam's alpha
       t = self.arena.step_count + 1
-      b1 = float(self.config.momentum)
-      lr = lr * math.sqrt(1.0 - self.ADAM_BETA2 ** t) / (1.0 - b1 ** t)
+      b1, b2 = self.update.momentum, self.update.beta2
+      lr = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
     self.hyper[:2].copy_(torch.tensor([lr, ema_decay or 0.0], dtype=torch.float32), non_blocking=True)
 
   def set_normalizer(self, mean_num_positives):
@@ -1498,36 +1527,49 @@ class Engine(object):
       m = m.float().contiguous()
     call('edet_loss_normalizer', ptr(m), m.numel(), self.hyper.data_ptr() + 8, self.stream)
 
-  def optimizer_local(self, scale_for_reduce):
+  def optimizer_local(self, scale_for_reduce, weight_decay=None, clip=None, l2_sum=None, first=0, end=None, sqnorm=None,
+                      gnorm=None):
     """L2 (train_lib.py:486-491) + per-tensor and global-norm clip factors of the LOCAL gradient (:675-682);
-    scale_for_reduce applies the factors in place (the data-parallel path all-reduces the clipped gradient)."""
+    scale_for_reduce applies the factors in place (the data-parallel path all-reduces the clipped gradient).
+    weight_decay / clip default to the detection config's; l2_sum is where the L2 loss is added (loss_sums[2:]).
+    first / end: the segment range (every segment by default); sqnorm: scratch for the squared norms (seg_sqnorm); gnorm:
+    where the norm of the range goes (self.gnorm) -- _reduce_bucket passes its own for the range it has finished."""
     c = self.config
     st = self.stream
+    if weight_decay is None:
+      weight_decay = c.weight_decay
+    if clip is None:
+      clip = abs(c.clip_gradients_norm) if c.clip_gradients_norm else 0.0
+    s0, s1 = first, self.nseg if end is None else end
+    sq = self.seg_sqnorm if sqnorm is None else sqnorm
+    gn = self.gnorm if gnorm is None else gnorm
+    offs, factor = self.seg_offsets.data_ptr() + 8 * s0, self.seg_factor.data_ptr() + 4 * s0
     # (frozen variables -- ParamArena.set_frozen -- are handled by the kernels through their segment flag)
-    call('edet_opt_l2_norms', ptr(self.grads_flat), ptr(self.params_flat), ptr(self.seg_offsets),
-         ptr(self.seg_flags), self.nseg, float(c.weight_decay), ptr(self.seg_sqnorm), st)
-    clip = abs(c.clip_gradients_norm) if c.clip_gradients_norm else 0.0
-    call('edet_opt_clip_factors', ptr(self.seg_sqnorm), self.nseg, float(clip), ptr(self.seg_factor),
-         ptr(self.gnorm), ptr(self.loss_sums[2:]), st)
+    call('edet_opt_l2_norms', ptr(self.grads_flat), ptr(self.params_flat), offs, self.seg_flags.data_ptr() + 4 * s0,
+         s1 - s0, float(weight_decay), ptr(sq), st)
+    call('edet_opt_clip_factors', ptr(sq), s1 - s0, float(clip), factor, ptr(gn),
+         ptr(self.loss_sums[2:] if l2_sum is None else l2_sum), st)
     if scale_for_reduce:
-      call('edet_opt_scale', ptr(self.grads_flat), ptr(self.seg_offsets), ptr(self.seg_factor), self.nseg, st)
+      call('edet_opt_scale', ptr(self.grads_flat), offs, factor, s1 - s0, st)
 
   def optimizer_apply(self, use_ema, already_scaled):
-    """SGD momentum (or Adam) + EMA (train_lib.py:176-199) with lr / decay from self.hyper (set_hyper)."""
-    if self.adam:
-      call('edet_opt_adam_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(self.velocity), ptr(self.arena.second_moment()),
-           ptr(self.ema) if use_ema else None, ptr(self.seg_offsets), None if already_scaled else ptr(self.seg_factor),
-           ptr(self.seg_flags), self.nseg, ptr(self.hyper), float(self.config.momentum), self.ADAM_BETA2, self.ADAM_EPSILON,
-           self.stream)
-      self.arena.version += 1
-      self.arena.step_count += 1
-      return
-    call('edet_opt_sgd_ema', ptr(self.params_flat), ptr(self.grads_flat), ptr(self.velocity),
-         ptr(self.ema) if use_ema else None, ptr(self.seg_offsets),
-         None if already_scaled else ptr(self.seg_factor), ptr(self.seg_flags), self.nseg, ptr(self.hyper),
-         float(self.config.momentum), self.stream)
-    self.arena.version += 1
-    self.arena.step_count += 1
+    """The update the engine's description names (train_lib.py:176-199; build_tf2_optimizer, main_tf2.py:36-59) + EMA,
+    with lr / decay from self.hyper (set_hyper)."""
+    u = self.update
+    tail = (ptr(self.ema) if use_ema else None, ptr(self.seg_offsets), None if already_scaled else ptr(self.seg_factor),
+            ptr(self.seg_flags), self.nseg, ptr(self.hyper))
+    head = (ptr(self.params_flat), ptr(self.grads_flat))
+    if u.kind == 'sgd':
+      call('edet_opt_sgd_ema', *head, ptr(self.velocity), *tail, float(u.momentum), self.stream)
+    elif u.kind == 'adam':
+      call('edet_opt_adam_ema', *head, ptr(self.velocity), ptr(self.arena.second_moment()), *tail, float(u.momentum),
+           u.beta2, u.epsilon, self.stream)
+    elif u.kind == 'rmsprop':
+      call('edet_opt_rmsprop_ema', *head, ptr(self.arena.second_moment()), ptr(self.velocity), *tail, u.rho,
+           float(u.momentum), u.epsilon, self.stream)
+    else:
+      raise ValueError('unknown optimizer %r' % (u.kind,))
+    self.arena.count_step()
 
   def optimizer_step(self, lr, ema_decay=None, all_reduce=None):
     """L2 + clip (local, before the reduce) + [all-reduce SUM] + SGD momentum + EMA."""

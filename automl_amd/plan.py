@@ -44,6 +44,7 @@ State files (edet_net_save_state / edet_net_load_state, read_state / write_state
 import bisect
 import contextlib
 import ctypes
+import gc
 import os
 import re
 import struct
@@ -214,6 +215,9 @@ class Recorder(object):
     other live block of at most max_bytes (tables, scalars, inputs).  The blocks of the tensors in `without` (inputs the
     host writes before it runs anything) get no initial contents whatever their size.  Call AFTER a warm-up pass (all
     buffers exist) and BEFORE the recorded passes."""
+    # an executor that is garbage but not yet collected (it sits in reference cycles) still owns live blocks; collected
+    # while the copies below run, its private pool is released and a listed block is gone: collect first
+    gc.collect()
     torch.cuda.synchronize()
     blocks = self.live_blocks()
     starts = [a for a, _ in blocks]
@@ -697,8 +701,8 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
   rec.variables = [(name, shape, tr, off, n) for name, (off, n, shape, tr) in eng.arena.offsets.items()]
   rec.props.update({'optimizer': 1 if eng.adam else 0, 'iterations': int(eng.arena.step_count)})
   if eng.adam:
-    for key, v in (('adam_beta1_bits', float(eng.config.momentum)), ('adam_beta2_bits', eng.ADAM_BETA2),
-                   ('adam_epsilon_bits', eng.ADAM_EPSILON)):
+    for key, v in (('adam_beta1_bits', eng.update.momentum), ('adam_beta2_bits', eng.update.beta2),
+                   ('adam_epsilon_bits', eng.update.epsilon)):
       rec.props[key] = struct.unpack('<Q', struct.pack('<d', v))[0]
   expected = {}
   # every program re-makes the compute copies of the variables (and, in inference, the BatchNorm vectors): a replayed step

@@ -12,6 +12,7 @@ import os
 import torch
 
 from automl_amd import efficientdet_net
+from automl_amd import engine as engine_lib
 
 
 def update_learning_rate_schedule_parameters(params):
@@ -290,47 +291,35 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     else:
       if g['graphs'] is None:
         torch.cuda.synchronize()
-        # the capture pass runs optimizer_apply's host bookkeeping once WITHOUT executing anything: keep the counters
-        # where they were, the replay below accounts for the step
-        counters = (eng.arena.version, eng.arena.step_count)
         ga = gb = None
         if overlap:
           # forward, backward with the bucketed collectives on their own stream (a parallel branch of the graph), update
-          ga = torch.cuda.CUDAGraph()
-          with torch.cuda.graph(ga, capture_error_mode='thread_local'):
-            body_a()
+          ga = engine_lib.capture_graph(eng.arena, body_a)
           g['overlap'] = True
         elif reduce_fn is not None and self.one_graph_dp:
           # The collective captured INSIDE the step's graph (RCCL 2.26 supports stream capture): no host hop between the
           # two halves.  Opt-in (EDET_DP_ONE_GRAPH=1): exercised on the device at world size 1 only -- no multi-GPU node
           # was available to any round -- so the default stays the two-graph structure below; if the capture itself
           # raises, the step falls back to it.
+          def one_graph():
+            body_a()
+            reduce_fn(eng.grads_flat)
+            body_b()
           try:
-            ga = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga, capture_error_mode='thread_local'):
-              body_a()
-              reduce_fn(eng.grads_flat)
-              body_b()
+            ga = engine_lib.capture_graph(eng.arena, one_graph)
           except Exception as e:      # noqa: BLE001 -- any capture failure: the robust structure
             import warnings
             warnings.warn('one-graph data-parallel capture failed (%s); using two graphs around an eager all-reduce' % (e,))
             ga = None
             torch.cuda.synchronize()
-          eng.arena.version, eng.arena.step_count = counters
         if ga is None:
-          ga = torch.cuda.CUDAGraph()
-          # thread_local: other threads of the process (the RCCL watchdog) may touch the HIP runtime meanwhile
-          with torch.cuda.graph(ga, capture_error_mode='thread_local'):
-            body_a()
+          ga = engine_lib.capture_graph(eng.arena, body_a)
           if reduce_fn is not None and not overlap:
-            gb = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode='thread_local'):
-              body_b()
+            gb = engine_lib.capture_graph(eng.arena, body_b, pool=ga.pool())
           g['one_graph'] = False
         else:
           g['one_graph'] = True
         g['graphs'] = (ga, gb)
-        eng.arena.version, eng.arena.step_count = counters
       ga, gb = g['graphs']
       eng.refresh_drop_masks()      # stochastic-depth draws live in static buffers the graph reads
       ga.replay()
@@ -345,8 +334,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
           e1.record()
           timer.append((e0, e1))
         gb.replay()
-      eng.arena.version += 1        # what optimizer_apply does on the host when it is not replayed
-      eng.arena.step_count += 1
+      eng.arena.count_step()        # what optimizer_apply does on the host when it is not replayed
     g['steps'] += 1
 
   def _ensure_engine(self, batch, height, width):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """EfficientNetV2 classifier training on one MI355X, for LABNOTES.md (NOT the bench.py line).  One phase per process
 (scripts/bench_v2_train.sh chains them under time limits), one JSON line each:
-  opt    edet_opt_rmsprop_ema against edet_opt_adam_ema on the model's arena (same bytes moved): HIP events around
-         `--launches` launches each, alternating, `--reps` repetitions -> medians, spreads (max - min), implied GB/s;
+  opt    edet_opt_sgd_ema, edet_opt_rmsprop_ema and edet_opt_adam_ema on the model's arena (the last two move the same
+         bytes): HIP events around `--launches` launches each, alternating, `--reps` repetitions -> medians, spreads
+         (max - min), implied GB/s;
   step   ms per TrainableModel.train_step (RMSprop, default dropout and stochastic depth, hipGraph replay);
   fwdbwd ms per forward(training) + backward of EffNetV2Model with dropout_rate=0, launched eagerly: what the step had
          before the loss, the dropout and the update existed."""
@@ -31,18 +32,22 @@ def bench_opt(args):
   st = torch.cuda.current_stream().cuda_stream
   common = (ptr(a.ema), ptr(a.seg_offsets), ptr(a.seg_factor), ptr(a.seg_flags), a.nseg, ptr(hyper))
 
+  def sgd():
+    call('edet_opt_sgd_ema', ptr(a.params_flat), ptr(a.grads_flat), ptr(a.velocity), *common, 0.9, st)
+
   def rms():
     call('edet_opt_rmsprop_ema', ptr(a.params_flat), ptr(a.grads_flat), ptr(slot2), ptr(a.velocity), *common, 0.9, 0.9, 1e-3, st)
 
   def adam():
     call('edet_opt_adam_ema', ptr(a.params_flat), ptr(a.grads_flat), ptr(a.velocity), ptr(slot2), *common, 0.9, 0.999, 1e-7, st)
-  times = {'rmsprop': [], 'adam': []}
-  for fn in (rms, adam):
+  rules = (('sgd', sgd), ('rmsprop', rms), ('adam', adam))
+  times = {name: [] for name, _ in rules}
+  for _, fn in rules:
     for _ in range(5):
       fn()
   torch.cuda.synchronize()
   for _ in range(args.reps):
-    for name, fn in (('rmsprop', rms), ('adam', adam)):
+    for name, fn in rules:
       e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
       e0.record()
       for _ in range(args.launches):
@@ -50,13 +55,14 @@ def bench_opt(args):
       e1.record()
       torch.cuda.synchronize()
       times[name].append(e0.elapsed_time(e1) / args.launches)
-  nbytes = 9 * 4 * n      # reads g, w, two slots, ema; writes w, two slots, ema
-  out = {'phase': 'opt', 'model': args.model, 'arena_elems': n, 'segments': a.nseg, 'bytes_per_launch': nbytes,
-         'launches': args.launches, 'reps': args.reps}
+  out = {'phase': 'opt', 'model': args.model, 'arena_elems': n, 'segments': a.nseg, 'launches': args.launches,
+         'reps': args.reps}
   for name, t in times.items():
     med = float(np.median(t))
+    # reads g, w, the slots, ema; writes w, the slots, ema: 9 arrays with two slots, 7 with SGD's one
+    nbytes = (7 if name == 'sgd' else 9) * 4 * n
     out[name] = {'median_ms': round(med, 5), 'spread_ms': round(max(t) - min(t), 5), 'min_ms': round(min(t), 5),
-                 'GBps': round(nbytes / (med * 1e-3) / 1e9, 1)}
+                 'bytes_per_launch': nbytes, 'GBps': round(nbytes / (med * 1e-3) / 1e9, 1)}
   allow = max(out['rmsprop']['spread_ms'], out['adam']['spread_ms'])
   out['rmsprop_within_adam_plus_spread'] = out['rmsprop']['median_ms'] <= out['adam']['median_ms'] + allow
   print(json.dumps(out))
