@@ -10,8 +10,8 @@ Scope: the forward pass in both BatchNo
 pass of the whole graph (``backward(d_outputs)``: Fused-MBConv dense convolutions, MBConv, SE, stochastic depth,
 head, dense layer).  The classifier's training step -- softmax cross-entropy with label smoothing, head dropout, the
 RMSprop / momentum / Adam update (``efficientnetv2/main_tf2.py``) -- is ``effnetv2_train.TrainableModel`` on the
-V2Engine methods at the end of this file (``softmax_loss``, ``head_dropout``) and the engine's update step
-(``Engine.optimizer_local`` / ``optimizer_apply`` with the trainer's ``engine.Update`` description).
+V2Engine methods at the end of this file (``softmax_loss``, ``head_dropout``) and the layer engine's update step
+(``LayerEngine.optimizer_local`` / ``optimizer_apply`` with the trainer's ``Update`` description).
 ``EffNetV2Model.__call__(training=True)`` itself still refuses dropout (pass ``model_config='dropout_rate=0'``): it has
 no labels to train with, and only the trainer owns the draws.  ``conv_dropout`` is not built anywhere.
 """
@@ -24,9 +24,8 @@ import torch
 
 from automl_amd import _lib
 from automl_amd import effnetv2_configs
-from automl_amd import engine as engine_lib
+from automl_amd import layer_engine
 from automl_amd import netspec as netspec_lib
-from automl_amd import utils
 from automl_amd._lib import ACT_NONE, ACT_SWISH, call, ptr
 from automl_amd.netspec import ParamSpec
 
@@ -45,6 +44,7 @@ class V2Spec(object):
       raise ValueError('only channels_last (NHWC) is built')
     self.bn_momentum = float(mconfig.bn_momentum)
     self.bn_epsilon = float(mconfig.bn_epsilon)
+    self.act_code = ACT_SWISH      # (act_fn silu / swish, checked above)
     self.name = mconfig.model_name
     self.stem_filters, self.blocks = effnetv2_configs.expand_blocks(mconfig)
     # stochastic depth (effnetv2_model.py:624-629): survival_prob 0.8 -> per block 1 - 0.2 * idx / n
@@ -138,48 +138,29 @@ def init_params(spec, seed=0):
   return collections.OrderedDict((p.name, init_value(p, rng)) for p in spec.params)
 
 
-class V2Engine(engine_lib.Engine):
-  """Launch plan of one EffNetV2Model on one MI355X (buffers, BatchNorm plumbing and the layer
-  primitives come from engine.Engine)."""
+class V2Engine(layer_engine.LayerEngine):
+  """Launch plan of one EffNetV2Model on one MI355X (buffers, BatchNorm plumbing, the layer primitives and the update
+  step come from LayerEngine): the graph, the classifier head with its dropout, and the softmax loss."""
 
-  def __init__(self, spec, batch_size, image_size, dtype='bf16', device='cuda:0', seed=0, params=None, arena=None):
+  def __init__(self, spec, batch_size, image_size, update, dtype='bf16', device='cuda:0', seed=0, params=None, arena=None):
     if arena is None and (params is None or any(p.name not in params for p in spec.params)):
       params = {**init_params(spec, seed), **(params or {})}      # a partial set keeps the other initial values
-    super().__init__(spec.mconfig, batch_size, image_size, dtype=dtype, device=device, seed=seed,
-                     params=params, spec=spec, arena=arena)
+    super().__init__(spec, batch_size, image_size, dtype=dtype, device=device, seed=seed, params=params, arena=arena,
+                     update=update)
     # head dropout (effnetv2_model.py:464-467,483-484): set by effnetv2_train.TrainableModel only -- 0 = the plain cast
     self.head_dropout = 0.0
     self.dropout_mask = None      # fp32 [B, feature_size] in {0, 1 / (1 - rate)}, redrawn by refresh_drop_masks
     self.cls_sums = self.zbuf('cls_sums', (4,))      # mean loss, top-1 rows, top-5 rows, L2 loss (zeroed every pass)
 
   def forward(self, images, training=False, update_moving=True):
-    """images: device tensor [B,H,W,3] in the engine dtype.  Fills self.endpoints / self.outputs."""
+    """images: device tensor [B,H,W,3] in the engine dtype.  Fills self.endpoints / self.outputs.  A training pass reads
+    the stochastic-depth and dropout masks as they are: they are drawn where they are created and redrawn by
+    refresh_drop_masks, which the trainer calls in front of every step (eager or replayed) and nothing here does."""
     spec = self.spec
-    assert tuple(images.shape) == (self.batch, self.image_size[0], self.image_size[1], 3), images.shape
-    assert images.dtype == self.tdtype and images.is_contiguous()
     self._begin(training, update_moving)
-    self.images = images
-    n, h, w = self.batch, self.image_size[0], self.image_size[1]
+    n = self.batch
     name = spec.name
-    oh, _, _ = utils.same_padding(h, 3, 2)
-    ow, _, _ = utils.same_padding(w, 3, 2)
-    y0 = engine_lib.Raw(self, 'stem', n, oh, ow, spec.stem_filters)
-    bn0 = self.get_bn(name + '/stem/tpu_batch_normalization', spec.stem_filters)
-    call('edet_stem_fwd', ptr(images), n, h, w, ptr(self.param(name + '/stem/conv2d/kernel')), ptr(y0.data),
-         spec.stem_filters, y0.ld, ptr(self.partials) if training else None, ctypes.byref(self._nparts),
-         self.dtype, self.stream, nbytes=(n * h * w * 3 + y0.rows * y0.c) * self.esize)
-    self._bn_forward(bn0, y0.rows, self._nparts.value)
-    x = engine_lib.View(y0, bn0, ACT_SWISH)
-    if training:
-      v0, wstem = x, name + '/stem/conv2d/kernel'
-
-      def stem_bwd():
-        g = self._gview(v0)
-        # behind the partial sums that earlier layers left for the deferred reductions (Engine._ws / _ws_mark)
-        call('edet_stem_bwd_weight', ptr(images), n, h, w, ctypes.byref(g), ptr(self.grad(wstem)), *self._ws(), self.dtype,
-             self.stream, nbytes=(n * h * w * 3 + y0.rows * y0.c) * self.esize)
-        self._ws_mark()
-      self.tape.append(stem_bwd)
+    x = self.stem(name, images, self.act)
     if training or spec.blocks[0].has_residual or spec.blocks[0].conv_type == 1:
       # the dense convolutions (and a first block that adds its input back) read a STORED tensor: the stem
       # output is materialised in activated form (one extra pass over a stride-2, 24..32-channel map)
@@ -208,7 +189,7 @@ class V2Engine(engine_lib.Engine):
     self._dlogits_ready = False
     self._dropout_on = False
     if spec.num_classes:
-      pv = engine_lib.Raw(self, 'head:pooled', n, 1, 1, r.c, needs_grad=False)
+      pv = layer_engine.Raw(self, 'head:pooled', n, 1, 1, r.c, needs_grad=False)
       self._dropout_on = bool(training and self.head_dropout)
       if self._dropout_on:
         if self.dropout_mask is None:
@@ -222,9 +203,9 @@ class V2Engine(engine_lib.Engine):
       inv = self.buf('head:inv_hw', (2, r.c), torch.float32)
       inv[0].fill_(self.pooled_inv_hw)
       inv[1].zero_()
-      view = engine_lib.View(pv)
+      view = layer_engine.View(pv)
       wt, ldk, _, _ = self._pw_copies(name + '/head/dense/kernel', r.c, spec.num_classes)
-      out = engine_lib.Raw(self, 'head:logits', n, 1, 1, spec.num_classes, needs_grad=False)
+      out = layer_engine.Raw(self, 'head:logits', n, 1, 1, spec.num_classes, needs_grad=False)
       tv = view.tview()
       tv.scale, tv.shift = inv[0].data_ptr(), inv[1].data_ptr()      # mean = sum / (H*W) folded into the load
       call('edet_pw_fwd', ctypes.byref(tv), ptr(wt), ldk, ptr(self.param(name + '/head/dense/bias')),
@@ -251,7 +232,7 @@ class V2Engine(engine_lib.Engine):
     if spec.num_classes:
       pv, tv, inv = self._fc
       ncls = spec.num_classes
-      dl = engine_lib.Raw(self, 'head:dlogits', n, 1, 1, ncls, needs_grad=False)
+      dl = layer_engine.Raw(self, 'head:dlogits', n, 1, 1, ncls, needs_grad=False)
       if d_out is not None:
         dl.data.zero_()
         dl.data.reshape(n, -1)[:, :ncls] = d_out.to(self.tdtype)
@@ -286,7 +267,7 @@ class V2Engine(engine_lib.Engine):
     r.grad_written = True
     super().backward()
 
-  # ---- classifier training (efficientnetv2/main_tf2.py:62-117): loss, dropout draws; the update is Engine's ------------
+  # ---- classifier training (efficientnetv2/main_tf2.py:62-117): loss, dropout draws; the update is LayerEngine's -------
   def _draw_dropout_mask(self):
     """tf.keras.layers.Dropout(rate): keep with probability 1 - rate, kept values scaled by 1 / (1 - rate); one draw per
     (image, feature).  From the engine's generator, like the stochastic-depth masks."""
@@ -309,7 +290,7 @@ class V2Engine(engine_lib.Engine):
     assert out is not None, 'softmax_loss needs a model with a classifier head (include_top)'
     assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == self.batch
     ncls = self.spec.num_classes
-    dl = engine_lib.Raw(self, 'head:dlogits', out.n, 1, 1, ncls, needs_grad=False)
+    dl = layer_engine.Raw(self, 'head:dlogits', out.n, 1, 1, ncls, needs_grad=False)
     call('edet_softmax_xent', ptr(out.data), out.ld, ptr(labels), out.n, ncls, float(label_smoothing), float(grad_scale),
          ptr(dl.data), ptr(self.cls_sums), *self._ws(), self.dtype, self.stream)
     self._dlogits_ready = self.training
@@ -347,6 +328,7 @@ class V2Engine(engine_lib.Engine):
 
 class EffNetV2Model(object):
   """EfficientNetV2 / EfficientNet (V2 code base) forward model, same call surface as the reference."""
+  update = layer_engine.Update('sgd', 0.0)      # this model applies no update; effnetv2_train.TrainableModel names its own
 
   def __init__(self, model_name='efficientnetv2-s', model_config=None, include_top=True, name=None,
                dtype='bf16', device='cuda:0', seed=0, params=None):
@@ -366,7 +348,7 @@ class EffNetV2Model(object):
     e = self.engine
     if e is None or e.batch != batch or e.image_size != (height, width):
       # a new shape gets new buffers; the variables stay in the arena the previous executor used
-      self.engine = V2Engine(self.spec, batch, (height, width), dtype=self._dtype, device=self._device,
+      self.engine = V2Engine(self.spec, batch, (height, width), self.update, dtype=self._dtype, device=self._device,
                              seed=self._seed, params=self._init_params, arena=None if e is None else e.arena)
     return self.engine
 

@@ -7,8 +7,8 @@ from_logits=True)`` with the ``acc_top1`` / ``acc_top5`` metrics (:199-207), and
 (``efficientnetv2/utils.py:78-131``).
 
 One step = forward(training) with stochastic depth and head dropout -> ``edet_softmax_xent`` (loss, d logits and the
-metric counts in one pass) -> ``V2Engine.backward`` -> ``Engine.optimizer_local`` (the L2 term of ``_reg_l2_loss`` and the
-gradient norm; the reference clips nothing, gclip = 0) -> ``Engine.optimizer_apply`` with this trainer's ``engine.Update``
+metric counts in one pass) -> ``V2Engine.backward`` -> ``LayerEngine.optimizer_local`` (the L2 term of ``_reg_l2_loss`` and the
+gradient norm; the reference clips nothing, gclip = 0) -> ``LayerEngine.optimizer_apply`` with this trainer's ``Update``
 (``edet_opt_rmsprop_ema``, or the SGD / Adam entry point).  The BatchNorm moving statistics move in the forward pass.  With ``use_graph`` the step is captured once
 into a hipGraph and replayed; the learning rate travels through a device vector and the dropout / stochastic-depth masks
 are redrawn outside the graph.
@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from automl_amd import effnetv2_model
-from automl_amd import engine as engine_lib
+from automl_amd.layer_engine import LayerEngine, Update, capture_graph
 
 OPTIMIZERS = ('rmsprop', 'momentum', 'sgd', 'adam')
 
@@ -33,10 +33,10 @@ def build_update(optimizer, momentum):
   """build_tf2_optimizer (main_tf2.py:36-59) as the engine's update description: 'rmsprop' (rho 0.9, momentum, epsilon
   0.001), 'momentum' / 'sgd' (Keras SGD; the trainer passes momentum 0 for 'sgd'), 'adam' (tf.keras.optimizers.Adam(learning_rate) defaults)."""
   if optimizer == 'rmsprop':
-    return engine_lib.Update('rmsprop', momentum, epsilon=0.001, rho=0.9)
+    return Update('rmsprop', momentum, epsilon=0.001, rho=0.9)
   if optimizer == 'adam':
-    return engine_lib.Update('adam', 0.9, engine_lib.Engine.ADAM_BETA2, engine_lib.Engine.ADAM_EPSILON)
-  return engine_lib.Update('sgd', momentum)
+    return Update('adam', 0.9, LayerEngine.ADAM_BETA2, LayerEngine.ADAM_EPSILON)
+  return Update('sgd', momentum)
 
 
 class WarmupLearningRateSchedule(object):
@@ -109,7 +109,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.weight_decay = float(weight_decay)
     self.optimizer = optimizer
     self.momentum = 0.0 if optimizer == 'sgd' else float(momentum)
-    self.update = build_update(optimizer, self.momentum)
+    self.update = build_update(optimizer, self.momentum)      # what every executor of this model is built with
     self.learning_rate = learning_rate
     self.label_smoothing = float(label_smoothing)
     self.ema_decay = None if not ema_decay else float(ema_decay)
@@ -123,7 +123,6 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   def _ensure_engine(self, batch, height, width):
     eng = super()._ensure_engine(batch, height, width)
     eng.head_dropout = float(self._mconfig.dropout_rate or 0.0)
-    eng.update = self.update
     if self.optimizer in ('rmsprop', 'adam'):
       eng.arena.use_second_slot('rms' if self.optimizer == 'rmsprop' else 'adam_v')
     if self._pending_state is not None:
@@ -187,7 +186,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     else:
       if g['graph'] is None:
         torch.cuda.synchronize()
-        g['graph'] = engine_lib.capture_graph(eng.arena, lambda: self._step_body(eng, g['images'], g['labels']))
+        g['graph'] = capture_graph(eng.arena, lambda: self._step_body(eng, g['images'], g['labels']))
       g['graph'].replay()
       eng.arena.count_step()
     g['steps'] += 1

@@ -38,6 +38,7 @@ class NetSpec(object):
     if c.act_type not in codes:
       raise ValueError('Unsupported act_type {}'.format(c.act_type))
     self.act_code = codes[c.act_type]
+    self.bn_momentum, self.bn_epsilon = BN_MOMENTUM, BN_EPSILON
     if not c.separable_conv or c.conv_bn_act_pattern:
       raise ValueError('only the default separable_conv / conv-bn ordering of the d0..d7x configs is built')
     self.stem_filters, self.blocks = eb.backbone_blocks(
