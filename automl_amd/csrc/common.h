@@ -76,6 +76,20 @@ template <typename T> __device__ __forceinline__ T from_f(float v);
 template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) { return f2bf(v); }
 
+// ---------------------------------------------------------------- 8 bf16 in 16 bytes <-> 8 floats
+__device__ __forceinline__ void unpack8(const uint4 raw, float x[8]) {
+  x[0] = __uint_as_float(raw.x << 16); x[1] = __uint_as_float(raw.x & 0xffff0000u);
+  x[2] = __uint_as_float(raw.y << 16); x[3] = __uint_as_float(raw.y & 0xffff0000u);
+  x[4] = __uint_as_float(raw.z << 16); x[5] = __uint_as_float(raw.z & 0xffff0000u);
+  x[6] = __uint_as_float(raw.w << 16); x[7] = __uint_as_float(raw.w & 0xffff0000u);
+}
+__device__ __forceinline__ uint4 pack8(const float x[8]) {
+  uint4 o;
+  o.x = pack2bf(x[0], x[1]); o.y = pack2bf(x[2], x[3]);
+  o.z = pack2bf(x[4], x[5]); o.w = pack2bf(x[6], x[7]);
+  return o;
+}
+
 // ---------------------------------------------------------------- 8-element vector I/O
 // p must be 16-byte aligned for bf16 (8 elems) and fp32 (2 x float4).
 template <typename T> __device__ __forceinline__ void load8(const T* p, float v[8]);
@@ -86,11 +100,7 @@ template <> __device__ __forceinline__ void load8<float>(const float* p, float v
   v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* p, float v[8]) {
-  uint4 a = *reinterpret_cast<const uint4*>(p);
-  v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xffff0000u);
-  v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xffff0000u);
-  v[4] = __uint_as_float(a.z << 16); v[5] = __uint_as_float(a.z & 0xffff0000u);
-  v[6] = __uint_as_float(a.w << 16); v[7] = __uint_as_float(a.w & 0xffff0000u);
+  unpack8(*reinterpret_cast<const uint4*>(p), v);
 }
 template <typename T> __device__ __forceinline__ void store8(T* p, const float v[8]);
 template <> __device__ __forceinline__ void store8<float>(float* p, const float v[8]) {
@@ -98,10 +108,7 @@ template <> __device__ __forceinline__ void store8<float>(float* p, const float 
   *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
 }
 template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const float v[8]) {
-  uint4 a;
-  a.x = pack2bf(v[0], v[1]); a.y = pack2bf(v[2], v[3]);
-  a.z = pack2bf(v[4], v[5]); a.w = pack2bf(v[6], v[7]);
-  *reinterpret_cast<uint4*>(p) = a;
+  *reinterpret_cast<uint4*>(p) = pack8(v);
 }
 __device__ __forceinline__ void loadf8(const float* p, float v[8]) { load8<float>(p, v); }
 
@@ -234,7 +241,10 @@ __device__ __forceinline__ void grad_load(const edet_gview_t& g, const GradCoef&
 // a fixed tree, so the same bits on every run; afterwards every lane of a class holds the class total.  All 64 lanes
 // must be active at the call.  Used by the fp32 / generic kernels instead of LDS atomics; the waves of a workgroup then
 // add their totals into LDS one wave after the other (wave order), and workgroups hand partial rows to
-// edet_reduce_partials -- no floating-point atomics anywhere on the way.
+// edet_reduce_partials -- no floating-point atomics anywhere on the way.  The same holds for the SE gate gradient: a data-
+// gradient kernel given epi.dgate stores the gradient of the gated value as it is, and its dispatch forms the sums afterwards
+// from the stored gradient (k_gate_sums in pw_gemm.hip: one writer per element, a fixed order).  No kernel adds to dgate with
+// a global atomic (tests/test_abi.py scans the sources for it).
 template <int NV>
 __device__ __forceinline__ void wave_group_sum(float (&v)[NV], int group) {
   for (int off = group; off < 64; off <<= 1) {
@@ -242,13 +252,6 @@ __device__ __forceinline__ void wave_group_sum(float (&v)[NV], int group) {
     for (int e = 0; e < NV; ++e) v[e] += __shfl_xor(v[e], off, 64);
   }
 }
-
-// Internal bit of edet_bwd_epi_t::flags (set by the bf16 dispatch of edet_pw_bwd / edet_pw_bwd_data, never by callers): the
-// SE gate-gradient sums of this data-gradient launch are formed AFTERWARDS from the stored gradient by k_gate_sums (one
-// writer per element, a fixed order) -- the kernel stores d as it is and adds nothing to dgate itself.  r06: the wide
-// two-kernel paths (pw_big.hip, pw_stream.hip) added their sums with floating-point atomics, the last ones of the bf16
-// training step (efficientdet-d7x: 1344 -> 224 / 960 -> 160 at 96 x 96).
-#define EDET_EPI_GATE_SUMS_LATER 0x40000000
 
 // TF 'SAME' geometry
 __host__ __device__ inline int same_out(int in, int s) { return (in + s - 1) / s; }
@@ -264,6 +267,13 @@ int edet_reduce_partials(const float* ws, int P, int64_t n, float* dst, hipStrea
 int edet_reduce_partials_set(const float* ws, int P, int64_t n, float* dst, hipStream_t st);
 // two destinations: dst_a[i] += column i for i < n_a (dst_a may be NULL), dst_b[i - n_a] += column i for n_a <= i < n
 int edet_reduce_partials2(const float* ws, int P, int64_t n, float* dst_a, int64_t n_a, float* dst_b, hipStream_t st);
+
+// Lets kernel `kern` be launched with `bytes` of dynamic LDS: above 64 KiB a kernel has to opt in.  The runtime is asked once
+// per kernel (again only if a later launch needs more); false = it refused.  (error.cpp)
+bool edet_lds_optin(const void* kern, size_t bytes);
+template <typename... KArgs> inline bool edet_lds_optin(void (*kern)(KArgs...), size_t bytes) {
+  return edet_lds_optin(reinterpret_cast<const void*>(kern), bytes);
+}
 
 // workgroups of kernel `fn` (block size `threads`, `lds` bytes of dynamic LDS) the device holds at once; 0 = unknown
 int edet_resident_wgs(const void* fn, int threads, size_t lds);

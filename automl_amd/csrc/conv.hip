@@ -10,12 +10,7 @@
 // group run back to back on one XCD).
 // fp32 (validation mode) and shapes outside the envelope: a direct kernel, one thread per output pixel x 4
 // output channels, weights read through L1 -- correct, not fast.
-#include "common.h"
-
-int cvh_try_conv_fwd(const edet_tview_t* in, const void* wt, int ldw, int k, int s, void* out, int cout, int ldo,
-                     float* stat_partials, int* nparts_out, hipStream_t st);
-int pwb_try_conv_fwd(const edet_tview_t* in, const void* wt, int ldw, int k, int s, const float* bias, void* out,
-                     int cout, int ldo, float* stat_partials, int* nparts_out, hipStream_t st);
+#include "pw_impl.h"
 
 namespace {
 
@@ -184,11 +179,6 @@ __global__ __launch_bounds__(DTHREADS) void k_conv_wgrad_direct(const ConvBwdArg
 }
 
 }  // namespace
-
-int pwb_try_conv_dgrad(const edet_gview_t* dy, const void* w_t, int ldw, int k, int s, const edet_tview_t* in,
-                       const edet_bwd_epi_t* epi, int* nparts_out, hipStream_t st);
-int pwb_try_conv_wgrad(const edet_tview_t* in, const edet_gview_t* dy, int k, int s, float* dweight, void* workspace,
-                       size_t workspace_bytes, hipStream_t st);
 
 static int conv_bwd_common(ConvBwdArgs& a, const edet_tview_t* in, const edet_gview_t* dy, int k, int stride,
                            const char* who) {

@@ -20,7 +20,7 @@
 // uses MBConv only).  Weights [cout][9 cin], reduction index (ky 3 + kx) cin + c contiguous (edet_conv_fwd's layout).
 #include <stdlib.h>
 
-#include "common.h"
+#include "pw_impl.h"
 
 namespace cvh {
 
@@ -43,18 +43,6 @@ struct Args {
   float* stat_partials;
 };
 
-__device__ __forceinline__ void unpack8(const uint4 raw, float x[8]) {
-  x[0] = __uint_as_float(raw.x << 16); x[1] = __uint_as_float(raw.x & 0xffff0000u);
-  x[2] = __uint_as_float(raw.y << 16); x[3] = __uint_as_float(raw.y & 0xffff0000u);
-  x[4] = __uint_as_float(raw.z << 16); x[5] = __uint_as_float(raw.z & 0xffff0000u);
-  x[6] = __uint_as_float(raw.w << 16); x[7] = __uint_as_float(raw.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float x[8]) {
-  uint4 o;
-  o.x = pack2bf(x[0], x[1]); o.y = pack2bf(x[2], x[3]);
-  o.z = pack2bf(x[4], x[5]); o.w = pack2bf(x[6], x[7]);
-  return o;
-}
 
 // CIN: input channels (multiple of 8).  WIDE: 128-column tiles (2 x 2 waves of 64 x 64), else 32-column tiles (4 x 1
 // waves of 32 x 32).  S: stride (1, 2).
@@ -318,16 +306,14 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv3_halo(const Args a) {
 
 template <int CIN, bool WIDE, int S> int launch(const Args& a, hipStream_t st) {
   using G = Geo<CIN, WIDE, S>;
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_halo<CIN, WIDE, S>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, G::SMEM_BYTES) == hipSuccess;
-  if (!ok) return 0;
+  if (!edet_lds_optin(&k_conv3_halo<CIN, WIDE, S>, G::SMEM_BYTES)) return 0;
   edet_launch(k_conv3_halo<CIN, WIDE, S>, dim3(a.ngrp), dim3(THREADS), G::SMEM_BYTES, st, a);
   return 1;
 }
 
 }  // namespace cvh
 
-// return 1 = handled, 0 = shape outside the envelope (the caller goes on to the implicit GEMM), < 0 = error.
+// Outside the envelope the caller goes on to the implicit GEMM.
 // Envelope: 3 x 3, stride 1 (stride 2 up to 32 input channels), the Fused-MBConv widths of the EfficientNetV2 family (effnetv2_configs.py: 16 / 24 / 32 / 48 /
 // 64 / 80 / 96 input channels), at most 512 output channels, no SE gate on the input view.
 int cvh_try_conv_fwd(const edet_tview_t* in, const void* wt, int ldw, int k, int s, void* out, int cout, int ldo,

@@ -1,4 +1,4 @@
-// Thread-local error message of the C ABI (edet_last_error) and the debug launch log.
+// Thread-local error message of the C ABI (edet_last_error), the debug launch log and the per-kernel caches (LDS opt-in, occupancy).
 #include <cxxabi.h>
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -9,6 +9,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 
 #include "../../include/edet_hip.h"
 
@@ -70,6 +71,20 @@ extern "C" int edet_debug_launch_names(char* buf, size_t capacity, size_t* neede
     buf[n] = 0;
   }
   return 0;
+}
+
+// ---- opt-in to more than 64 KiB of dynamic LDS: kernel -> (largest byte count asked for, the runtime's answer) ----------
+static std::mutex g_lds_mu;
+static std::map<const void*, std::pair<size_t, bool>> g_lds;
+
+bool edet_lds_optin(const void* kern, size_t bytes) {
+  if (bytes <= 64 * 1024) return true;
+  std::lock_guard<std::mutex> lock(g_lds_mu);
+  auto it = g_lds.find(kern);
+  if (it != g_lds.end() && it->second.first >= bytes) return it->second.second;
+  const bool ok = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+  g_lds[kern] = std::make_pair(bytes, ok);
+  return ok;
 }
 
 // ---- resident workgroups of a kernel on the current device (occupancy x compute units), cached -------------------------

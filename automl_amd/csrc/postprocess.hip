@@ -755,9 +755,7 @@ extern "C" int edet_pre_nms(const void* const* cls_levels, const void* const* bo
   hipStream_t st = to_stream(stream);
 #define PRE_CASE(T, VB)                                                                                      \
   do {                                                                                                         \
-    if (lds > 48 * 1024)                                                                                       \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_pre_nms<T, VB>),                                     \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                               \
+    (void)edet_lds_optin(k_pre_nms<T, VB>, lds);                                                               \
     edet_launch(k_pre_nms<T, VB>, grid, dim3(64), lds, st, a, table, table + ngroups);                                        \
   } while (0)
   if (dtype == EDET_BF16) {

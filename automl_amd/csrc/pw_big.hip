@@ -10,7 +10,9 @@
 //
 //   k_big_gemm<BWD=false>  out[m][j]  = sum_k view(in)[m][k] * Wt[j][k] + bias[j]      (+ BN stat partials)
 //   k_big_gemm<BWD=true>   d in[m][k] = sum_n dy[m][n] * W[k][n], chained through act'(z), the optional
-//                          accumulate, the BN-backward sums and the SE dgate sums in the epilogue
+//                          accumulate and the BN-backward sums in the epilogue; with epi.dgate != NULL the gradient
+//                          of the gated value is stored as it is (the SE gate-gradient sums belong to the dispatch:
+//                          k_gate_sums, pw_gemm.hip)
 //   k_big_wgrad            dW[k][n]   = sum_m view(in)[m][k] * dy[m][n]  (split over m, partials -> workspace)
 //
 // Tile 128 x 128 per 256-thread workgroup (2 x 2 waves, 64 x 64 per wave = 2 x 2 v_mfma_f32_32x32x16_bf16),
@@ -25,7 +27,7 @@
 // gradients (TF Conv2DBackpropInput / Conv2DBackpropFilter under tf.GradientTape, train_lib.py:623-669).
 #include <stdlib.h>
 
-#include "common.h"
+#include "pw_impl.h"
 
 namespace pwb {
 
@@ -41,18 +43,6 @@ constexpr int LDC_BF = BJ * 2 + 16;          // bf16 C tile row stride (272)
 constexpr int LDC_F32 = BJ * 4 + 16;         // fp32 C tile row stride (528)
 static_assert(BM * LDC_F32 <= SMEM_BYTES, "fp32 C tile must fit in the staging buffers");
 
-__device__ __forceinline__ void unpack8(const uint4 raw, float x[8]) {
-  x[0] = __uint_as_float(raw.x << 16); x[1] = __uint_as_float(raw.x & 0xffff0000u);
-  x[2] = __uint_as_float(raw.y << 16); x[3] = __uint_as_float(raw.y & 0xffff0000u);
-  x[4] = __uint_as_float(raw.z << 16); x[5] = __uint_as_float(raw.z & 0xffff0000u);
-  x[6] = __uint_as_float(raw.w << 16); x[7] = __uint_as_float(raw.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float x[8]) {
-  uint4 o;
-  o.x = pack2bf(x[0], x[1]); o.y = pack2bf(x[2], x[3]);
-  o.z = pack2bf(x[4], x[5]); o.w = pack2bf(x[6], x[7]);
-  return o;
-}
 
 // the first `nvalid` (1..7) bf16 elements of a 16-byte chunk, the others zeroed (a reduction length that is not a multiple
 // of 8: the chunk that straddles it carries padding columns, which may hold anything)
@@ -127,7 +117,6 @@ __global__ __launch_bounds__(THREADS, 2) void k_big_gemm(const GemmArgs a) {
   const int j0 = jt * BJ;
   const bool want_stats = a.stat_partials != nullptr;
   const bool want_gate = BWD && a.epi.dgate != nullptr;       // SE-gated input: the gradient of the gated value is stored as it is
-  const bool gate_sums = want_gate && !(a.epi.flags & EDET_EPI_GATE_SUMS_LATER);      // ... and its sums are formed here (atomics)
   const bool swish = !OACT && a.tv.act == EDET_ACT_SWISH, affine = a.tv.scale != nullptr;
   constexpr bool other = OACT;
   const bool gated = !BWD && a.tv.gate != nullptr;
@@ -293,11 +282,11 @@ __global__ __launch_bounds__(THREADS, 2) void k_big_gemm(const GemmArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[x][y][e] = 0.f;
 
-    // BWD: the saved conv input of this tile's epilogue (act', SE gate sums, BatchNorm-backward sums).  Requested
+    // BWD: the saved conv input of this tile's epilogue (act', BatchNorm-backward sums).  Requested
     // during the LAST reduction step -- the staging registers of the streamed operand are free by then -- so that it
     // is in flight under the last MFMAs, the C-tile round trip through LDS and its barrier instead of after them.
     uint4 xr[BWD ? BM / 16 : 1];
-    const bool need_x = BWD && (swish || other || want_gate || want_stats);
+    const bool need_x = BWD && (want_stats || (!want_gate && (swish || other)));
 
     __syncthreads();                     // the previous row tile's epilogue is done with the LDS
     if (!prefetched) issue(0);
@@ -437,23 +426,10 @@ __global__ __launch_bounds__(THREADS, 2) void k_big_gemm(const GemmArgs a) {
       if (!CONV && mt + 1 < mt_end) { setup(mt + 1); issue(0); prefetched = true; } else prefetched = false;   // next tile's first stage
       const bf16_t* X = reinterpret_cast<const bf16_t*>(a.tv.data);
       bf16_t* GO = reinterpret_cast<bf16_t*>(a.epi.gout);
-      float sc[8], sh[8], s1[8], s2[8], gp[8];
+      float sc[8], sh[8], s1[8], s2[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { sc[e] = 1.f; sh[e] = 0.f; s1[e] = s2[e] = gp[e] = 0.f; }
+      for (int e = 0; e < 8; ++e) { sc[e] = 1.f; sh[e] = 0.f; s1[e] = s2[e] = 0.f; }
       if (ecol_ok && affine) { loadf8(a.tv.scale + ej, sc); loadf8(a.tv.shift + ej, sh); }
-      // dgate sums: a tile inside one image (the common case) is reduced through LDS to one atomic per
-      // channel; a tile that straddles images flushes per thread whenever the image changes
-      const int timg0 = m0 / a.hw, timg1 = (min(m0 + BM, a.M) - 1) / a.hw;
-      const bool single_img = timg0 == timg1;
-      int gp_img = -1;
-      auto flush_gate = [&]() {
-        if (gp_img >= 0) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) atomicAdd(&a.epi.dgate[(size_t)gp_img * a.J + ej + e], gp[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gp[e] = 0.f;
-      };
       // the 16 threads of one row group walk the rows er, er+16, ... (xr: requested in the last reduction step)
 #pragma unroll
       for (int i = 0; i < BM / 16; ++i) {
@@ -467,17 +443,6 @@ __global__ __launch_bounds__(THREADS, 2) void k_big_gemm(const GemmArgs a) {
           unpack8(xr[i], x);
           const size_t off = (size_t)m * a.tv.ld + ej;
           if (want_gate) {
-            if (gate_sums) {
-              if (!single_img) {
-                const int img = m / a.hw;
-                if (img != gp_img) { flush_gate(); gp_img = img; }
-              }
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const float z = fmaf(x[e], sc[e], sh[e]);
-                gp[e] = fmaf(d[e], other ? act_other_(a.tv.act, z) : (swish ? swishf_(z) : z), gp[e]);
-              }
-            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) g[e] = d[e];
           } else if (swish) {
@@ -501,23 +466,6 @@ __global__ __launch_bounds__(THREADS, 2) void k_big_gemm(const GemmArgs a) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) { s1[e] += g[e]; s2[e] = fmaf(g[e], x[e], s2[e]); }
           }
-        }
-      }
-      if (gate_sums) {
-        if (single_img) {
-          __syncthreads();
-          float* red = reinterpret_cast<float*>(smem);          // [16][BJ]
-#pragma unroll
-          for (int e = 0; e < 8; ++e) red[er * BJ + ec * 8 + e] = gp[e];
-          __syncthreads();
-          if (tid < BJ && j0 + tid < a.J) {
-            float t = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) t += red[i * BJ + tid];
-            atomicAdd(&a.epi.dgate[(size_t)timg0 * a.J + j0 + tid], t);
-          }
-        } else if (ecol_ok) {
-          flush_gate();
         }
       }
       if (want_stats) {
@@ -911,106 +859,110 @@ __global__ __launch_bounds__(THREADS, 2) void k_big_wgrad_bal(const WgArgs a) {
     }
 }
 
-inline bool big_lds_ok(const void* kern) {
-  return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES) == hipSuccess;
+// what the pointwise and the dense-convolution launches share: operands, tile / group numbers (the statistic partial rows)
+inline void fill_gemm(GemmArgs& a, const edet_tview_t* in, const edet_gview_t* dy, const void* Bm, int ldb, int M, int R, int J,
+                      int hw) {
+  memset(&a, 0, sizeof(a));
+  a.tv = *in;
+  if (dy) a.gv = *dy;
+  a.Bm = reinterpret_cast<const bf16_t*>(Bm); a.ldb = ldb;
+  a.M = M; a.R = R; a.J = J; a.hw = hw;
+  a.ntm = (M + BM - 1) / BM; a.ntj = (J + BJ - 1) / BJ;
+  a.tpw = (a.ntm + EDET_MAX_PARTS - 1) / EDET_MAX_PARTS;      // consecutive row tiles per workgroup: as few as the partial-row limit allows
+  a.ngrp = (a.ntm + a.tpw - 1) / a.tpw;
+}
+inline int gemm_grid(const GemmArgs& a) { return (a.ngrp + 7) / 8 * 8 * a.ntj; }
+
+// CONV geometry of a k x k convolution, stride s, TF 'SAME' (GemmArgs and WgArgs): the row space has row_w columns and row_hw
+// pixels per image, the gathered image is gh x gw with gc channels, the padding that of the convolution's input (in_h x in_w)
+template <typename A>
+inline void fill_conv(A& a, int k, int s, int gc, int gh, int gw, int row_w, int row_hw, int in_h, int in_w) {
+  a.ck = k; a.cs = s; a.cin = gc; a.ih = gh; a.iw = gw; a.cow = row_w; a.cohw = row_hw;
+  a.pad_t = same_pad_before(in_h, k, s); a.pad_l = same_pad_before(in_w, k, s);
+}
+
+// The instantiations of one kernel family a host function may launch, kern[GBN][OACT] (GBN: BatchNorm backward on dy, OACT:
+// relu / relu6 / hswish view; NULL = not in this function's envelope).  All of them are opted in to the staging buffers' LDS
+// (in the order [0][0], [0][1], [1][0], [1][1]) before the one the call needs is launched: 0 = the runtime refused one.
+template <typename A>
+inline int launch_variant(void (*const (&kern)[2][2])(const A), bool gbn, bool oact, int grid, const A& a, hipStream_t st) {
+  for (int g = 0; g < 2; ++g)
+    for (int o = 0; o < 2; ++o)
+      if (kern[g][o] && !edet_lds_optin(kern[g][o], SMEM_BYTES)) return 0;
+  edet_launch(kern[gbn][oact], dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  return 1;
+}
+
+// row splits of a weight gradient: `S` wanted, at least 4 steps of 64 rows each, bounded by the workspace; false = no room
+inline bool fill_wgrad_splits(WgArgs& a, int S, size_t workspace_bytes) {
+  const int max_by_rows = (a.M + 4 * BK - 1) / (4 * BK);
+  if (S > max_by_rows) S = max_by_rows;
+  const int64_t max_by_ws = (int64_t)(workspace_bytes / sizeof(float)) / ((int64_t)a.K * a.N);
+  if (S > max_by_ws) S = (int)max_by_ws;
+  if (S < 1) return false;
+  a.rows_per_split = ((a.M + S - 1) / S + BK - 1) / BK * BK;
+  a.S = (a.M + a.rows_per_split - 1) / a.rows_per_split;
+  return true;
 }
 
 }  // namespace pwb
 
-// consecutive row tiles per workgroup: as few as the partial-row limit allows
-static int big_tpw(int ntm) { return (ntm + EDET_MAX_PARTS - 1) / EDET_MAX_PARTS; }
-
-// the LDS-DMA forward kernel (pw_glds.hip); same return convention
-int pwg_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
-                int ldo, float* stat_partials, int* nparts_out, int tpw, hipStream_t st);
-// Which wide forward layers go to the LDS-DMA kernel: the SE-gated views (the MBConv project layers: 5-19 % faster there,
-// r06al); it ties or loses a few per cent on the others.  EDET_PW_GLDS = 0: never; 2: every shape of its envelope (read
-// per call: lab switch and the bit-equality test).  The two kernels give the same bits, so the rule is free to change.
+// Which wide forward layers go to the LDS-DMA kernel (pw_glds.hip): the SE-gated views (the MBConv project layers: 5-19 %
+// faster there, r06al); it ties or loses a few per cent on the others.  EDET_PW_GLDS = 0: never; 2: every shape of its envelope
+// (read per call: lab switch and the bit-equality test).  The two kernels give the same bits, so the rule is free to change.
 static bool glds_wanted(const edet_tview_t* in) {
   const int mode = edet_env_int("EDET_PW_GLDS", 1);
   return mode == 2 || (mode == 1 && in->gate != nullptr);
 }
 
-// return 1 = handled, 0 = shape outside the envelope (caller falls back), < 0 = error
 int pwb_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
                 int ldo, float* stat_partials, int* nparts_out, hipStream_t st) {
   using namespace pwb;
   const int K = in->c, N = cout;
   if (K % 8 != 0 || in->ld % 8 != 0 || ldw % 8 != 0 || ldo % 8 != 0 || ldo < (N + 7) / 8 * 8) return 0;
   GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tv = *in;
-  a.Bm = reinterpret_cast<const bf16_t*>(wt); a.ldb = ldw;
-  a.M = in->n * in->h * in->w; a.R = K; a.J = N; a.hw = in->h * in->w;
+  fill_gemm(a, in, nullptr, wt, ldw, in->n * in->h * in->w, K, N, in->h * in->w);
   a.bias = bias; a.out = reinterpret_cast<bf16_t*>(out); a.ldo = ldo; a.stat_partials = stat_partials;
-  a.ntm = (a.M + BM - 1) / BM; a.ntj = (N + BJ - 1) / BJ;
-  a.tpw = big_tpw(a.ntm);
   if (glds_wanted(in)) {
     const int rc = pwg_try_fwd(in, wt, ldw, bias, out, cout, ldo, stat_partials, nparts_out, a.tpw, st);
     if (rc != 0) return rc;
   }
-  a.ngrp = (a.ntm + a.tpw - 1) / a.tpw;
   if (nparts_out) *nparts_out = a.ngrp;
-  static const bool ok = big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<false, false>)) &&
-                         big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<false, false, false, true>));
-  if (!ok) return 0;
-  const int grid = (a.ngrp + 7) / 8 * 8 * a.ntj;
-  if (in->act > EDET_ACT_SWISH) edet_launch(k_big_gemm<false, false, false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  else edet_launch(k_big_gemm<false, false>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  static void (*const kern[2][2])(const GemmArgs) = {{k_big_gemm<false, false>, k_big_gemm<false, false, false, true>}, {nullptr, nullptr}};
+  if (!launch_variant(kern, false, in->act > EDET_ACT_SWISH, gemm_grid(a), a, st)) return 0;
   EDET_LAUNCH_CHECK("edet_pw_fwd(big)");
   return 1;
 }
 
-// forward with fp32 output [rows][ldo] (ldo in floats, >= cout rounded up to 8); no statistics
 int pwb_fwd_f32out(const edet_tview_t* in, const void* wt, int ldw, const float* bias, float* out, int cout, int ldo,
                    hipStream_t st) {
   using namespace pwb;
   const int K = in->c, N = cout;
   if (K % 8 != 0 || in->ld % 8 != 0 || ldw % 8 != 0 || ldo % 4 != 0 || ldo < (N + 7) / 8 * 8) return 0;
   GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tv = *in;
-  a.Bm = reinterpret_cast<const bf16_t*>(wt); a.ldb = ldw;
-  a.M = in->n * in->h * in->w; a.R = K; a.J = N; a.hw = in->h * in->w;
+  fill_gemm(a, in, nullptr, wt, ldw, in->n * in->h * in->w, K, N, in->h * in->w);
   a.bias = bias; a.out = reinterpret_cast<bf16_t*>(out); a.ldo = ldo;
-  a.ntm = (a.M + BM - 1) / BM; a.ntj = (N + BJ - 1) / BJ;
-  a.tpw = big_tpw(a.ntm);
-  a.ngrp = (a.ntm + a.tpw - 1) / a.tpw;
-  static const bool ok = big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<false, false, false, false, true>)) &&
-                         big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<false, false, false, true, true>));
-  if (!ok) return 0;
-  const int grid = (a.ngrp + 7) / 8 * 8 * a.ntj;
-  if (in->act > EDET_ACT_SWISH) edet_launch(k_big_gemm<false, false, false, true, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  else edet_launch(k_big_gemm<false, false, false, false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  static void (*const kern[2][2])(const GemmArgs) = {{k_big_gemm<false, false, false, false, true>, k_big_gemm<false, false, false, true, true>},
+                                                     {nullptr, nullptr}};
+  if (!launch_variant(kern, false, in->act > EDET_ACT_SWISH, gemm_grid(a), a, st)) return 0;
   EDET_LAUNCH_CHECK("edet_pw_fwd_f32out");
   return 1;
 }
 
-// dense k x k convolution (stride s, TF 'SAME') as an implicit GEMM: wt [cout][k*k*cin], reduction index
-// (ky*k + kx)*cin + c contiguous.  return 1 = handled, 0 = shape outside the envelope, < 0 = error
 int pwb_try_conv_fwd(const edet_tview_t* in, const void* wt, int ldw, int k, int s, const float* bias, void* out,
                      int cout, int ldo, float* stat_partials, int* nparts_out, hipStream_t st) {
   if (in->act > EDET_ACT_SWISH) return 0;     // relu / relu6 / hswish: the direct dense-convolution kernels (conv.hip)
   using namespace pwb;
   const int cin = in->c, N = cout;
   if (cin % 8 != 0 || in->ld % 8 != 0 || ldw % 8 != 0 || ldo % 8 != 0 || ldo < (N + 7) / 8 * 8) return 0;
-  GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tv = *in;
-  a.Bm = reinterpret_cast<const bf16_t*>(wt); a.ldb = ldw;
   const int oh = same_out(in->h, s), ow = same_out(in->w, s);
-  a.M = in->n * oh * ow; a.R = k * k * cin; a.J = N; a.hw = oh * ow;
-  a.ck = k; a.cs = s; a.cin = cin; a.ih = in->h; a.iw = in->w; a.cow = ow; a.cohw = oh * ow;
-  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
+  GemmArgs a;
+  fill_gemm(a, in, nullptr, wt, ldw, in->n * oh * ow, k * k * cin, N, oh * ow);
+  fill_conv(a, k, s, cin, in->h, in->w, ow, oh * ow, in->h, in->w);
   a.bias = bias; a.out = reinterpret_cast<bf16_t*>(out); a.ldo = ldo; a.stat_partials = stat_partials;
-  a.ntm = (a.M + BM - 1) / BM; a.ntj = (N + BJ - 1) / BJ;
-  a.tpw = big_tpw(a.ntm);
-  a.ngrp = (a.ntm + a.tpw - 1) / a.tpw;
   if (nparts_out) *nparts_out = a.ngrp;
-  static const bool ok = big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<false, false, true>));
-  if (!ok) return 0;
-  const int grid = (a.ngrp + 7) / 8 * 8 * a.ntj;
-  edet_launch(k_big_gemm<false, false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  static void (*const kern[2][2])(const GemmArgs) = {{k_big_gemm<false, false, true>, nullptr}, {nullptr, nullptr}};
+  if (!launch_variant(kern, false, false, gemm_grid(a), a, st)) return 0;
   EDET_LAUNCH_CHECK("edet_conv_fwd(big)");
   return 1;
 }
@@ -1025,26 +977,12 @@ int pwb_try_dgrad(const edet_gview_t* dy, const void* w, int ldw, const edet_tvi
   // kernels cannot take (efficientdet-d3 and up: 160 .. 384 filters); the straddling chunk is masked
   if (R % 8 != 0 && (dy->a || KO < 160 || dy->ld < (R + 7) / 8 * 8 || ldw < (R + 7) / 8 * 8)) return 0;
   GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tv = *in; a.gv = *dy;
-  a.Bm = reinterpret_cast<const bf16_t*>(w); a.ldb = ldw;
-  a.M = in->n * in->h * in->w; a.R = R; a.J = KO; a.hw = in->h * in->w;
+  fill_gemm(a, in, dy, w, ldw, in->n * in->h * in->w, R, KO, in->h * in->w);
   a.epi = *epi; a.stat_partials = epi->stat_partials;
-  a.ntm = (a.M + BM - 1) / BM; a.ntj = (KO + BJ - 1) / BJ;
-  a.tpw = big_tpw(a.ntm);
-  a.ngrp = (a.ntm + a.tpw - 1) / a.tpw;
   if (nparts_out) *nparts_out = a.ngrp;
-  static const bool ok1 = big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<true, false>)) &&
-                          big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<true, false, false, true>));
-  static const bool ok2 = big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<true, true>)) &&
-                          big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<true, true, false, true>));
-  if (!ok1 || !ok2) return 0;
-  const int grid = (a.ngrp + 7) / 8 * 8 * a.ntj;
-  if (in->act > EDET_ACT_SWISH) {
-    if (dy->a) edet_launch(k_big_gemm<true, true, false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-    else edet_launch(k_big_gemm<true, false, false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  } else if (dy->a) edet_launch(k_big_gemm<true, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  else edet_launch(k_big_gemm<true, false>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  static void (*const kern[2][2])(const GemmArgs) = {{k_big_gemm<true, false>, k_big_gemm<true, false, false, true>},
+                                                     {k_big_gemm<true, true>, k_big_gemm<true, true, false, true>}};
+  if (!launch_variant(kern, dy->a != nullptr, in->act > EDET_ACT_SWISH, gemm_grid(a), a, st)) return 0;
   EDET_LAUNCH_CHECK("edet_pw_bwd_data(big)");
   return 1;
 }
@@ -1074,35 +1012,20 @@ int pwb_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, float* dweight
   // rounded DOWN: two workgroups of this kernel are resident per compute unit (512 at a time), and a grid of 513 or
   // 1026 (288 x 48: 3 tiles x 171 splits; 1152 x 320: 27 x 38) runs a last round for one or two stragglers
   // (r03e: efficientdet-d7x 384x384x288->48 went from 0.93 to 1.19 ms per call when the target dropped to 512)
-  int S = wg_target / ntile;
-  if (S < 1) S = 1;
-  const int max_by_rows = (a.M + 4 * BK - 1) / (4 * BK);
-  if (S > max_by_rows) S = max_by_rows;
-  const int64_t max_by_ws = (int64_t)(workspace_bytes / sizeof(float)) / kn;
-  if (S > max_by_ws) S = (int)max_by_ws;
-  if (S < 1) return 0;
-  a.rows_per_split = ((a.M + S - 1) / S + BK - 1) / BK * BK;
-  a.S = (a.M + a.rows_per_split - 1) / a.rows_per_split;
+  const int S = wg_target / ntile;
+  if (!fill_wgrad_splits(a, S < 1 ? 1 : S, workspace_bytes)) return 0;
   // the balanced-staging kernel (r02a, 17 mid-size layers of D0 at batch 128: 6.03 ms against 6.53 ms for the
   // two-waves-per-operand staging of k_big_wgrad, which remains for the dense-convolution variant)
-  static const bool ok1 = big_lds_ok(reinterpret_cast<const void*>(&k_big_wgrad_bal<false>)) &&
-                          big_lds_ok(reinterpret_cast<const void*>(&k_big_wgrad_bal<false, true>));
-  static const bool ok2 = big_lds_ok(reinterpret_cast<const void*>(&k_big_wgrad_bal<true>)) &&
-                          big_lds_ok(reinterpret_cast<const void*>(&k_big_wgrad_bal<true, true>));
-  if (!ok1 || !ok2) return 0;
-  const int grid = (a.S + 7) / 8 * 8 * ntile;
-  if (in->act > EDET_ACT_SWISH) {
-    if (dy->a) edet_launch(k_big_wgrad_bal<true, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-    else edet_launch(k_big_wgrad_bal<false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  } else if (dy->a) edet_launch(k_big_wgrad_bal<true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  else edet_launch(k_big_wgrad_bal<false>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  static void (*const kern[2][2])(const WgArgs) = {{k_big_wgrad_bal<false>, k_big_wgrad_bal<false, true>},
+                                                   {k_big_wgrad_bal<true>, k_big_wgrad_bal<true, true>}};
+  if (!launch_variant(kern, dy->a != nullptr, in->act > EDET_ACT_SWISH, (a.S + 7) / 8 * 8 * ntile, a, st)) return 0;
   EDET_LAUNCH_CHECK("edet_pw_bwd_weight(big)");
   if (edet_reduce_partials(a.ws, a.S, kn, dweight, st) != 0) return -2;
   return 1;
 }
 
 // ---- dense k x k convolution backward as implicit GEMMs (conv.hip dispatches here for bf16) -------------------
-// data gradient: w_t [cin][ldw] with the reduction index (ky*k + kx)*cout + co contiguous; rows = input pixels
+// data gradient: rows = input pixels
 int pwb_try_conv_dgrad(const edet_gview_t* dy, const void* w_t, int ldw, int k, int s, const edet_tview_t* in,
                        const edet_bwd_epi_t* epi, int* nparts_out, hipStream_t st) {
   if (in->act > EDET_ACT_SWISH) return 0;     // relu / relu6 / hswish: the direct dense-convolution kernels (conv.hip)
@@ -1110,30 +1033,18 @@ int pwb_try_conv_dgrad(const edet_gview_t* dy, const void* w_t, int ldw, int k, 
   const int cout = dy->c, cin = in->c;
   if (cout % 8 != 0 || cin % 8 != 0 || in->ld % 8 != 0 || dy->ld % 8 != 0 || ldw % 8 != 0) return 0;
   GemmArgs a;
-  memset(&a, 0, sizeof(a));
-  a.tv = *in; a.gv = *dy;
-  a.Bm = reinterpret_cast<const bf16_t*>(w_t); a.ldb = ldw;
-  a.M = in->n * in->h * in->w; a.R = k * k * cout; a.J = cin; a.hw = in->h * in->w;
-  a.ck = k; a.cs = s; a.cin = cout;                 // channels of the STREAMED operand (dy)
-  a.ih = dy->h; a.iw = dy->w;                       // gathered image = dy
-  a.cow = in->w; a.cohw = in->h * in->w;            // row space = input pixels
-  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
+  fill_gemm(a, in, dy, w_t, ldw, in->n * in->h * in->w, k * k * cout, cin, in->h * in->w);
+  // the STREAMED operand and gathered image is dy (cout channels); row space = input pixels
+  fill_conv(a, k, s, cout, dy->h, dy->w, in->w, in->h * in->w, in->h, in->w);
   a.epi = *epi; a.stat_partials = epi->stat_partials;
-  a.ntm = (a.M + BM - 1) / BM; a.ntj = (cin + BJ - 1) / BJ;
-  a.tpw = big_tpw(a.ntm);
-  a.ngrp = (a.ntm + a.tpw - 1) / a.tpw;
   if (nparts_out) *nparts_out = a.ngrp;
-  static const bool ok1 = big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<true, false, true>));
-  static const bool ok2 = big_lds_ok(reinterpret_cast<const void*>(&k_big_gemm<true, true, true>));
-  if (!ok1 || !ok2) return 0;
-  const int grid = (a.ngrp + 7) / 8 * 8 * a.ntj;
-  if (dy->a) edet_launch(k_big_gemm<true, true, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  else edet_launch(k_big_gemm<true, false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  static void (*const kern[2][2])(const GemmArgs) = {{k_big_gemm<true, false, true>, nullptr}, {k_big_gemm<true, true, true>, nullptr}};
+  if (!launch_variant(kern, dy->a != nullptr, false, gemm_grid(a), a, st)) return 0;
   EDET_LAUNCH_CHECK("edet_conv_bwd_data(big)");
   return 1;
 }
 
-// weight gradient: dweight fp32 HWIO [k][k][cin][cout] += gathered(in)^T dy
+// weight gradient: rows = output pixels (dy rows)
 int pwb_try_conv_wgrad(const edet_tview_t* in, const edet_gview_t* dy, int k, int s, float* dweight, void* workspace,
                        size_t workspace_bytes, hipStream_t st) {
   if (in->act > EDET_ACT_SWISH) return 0;     // relu / relu6 / hswish: the direct dense-convolution kernels (conv.hip)
@@ -1144,26 +1055,13 @@ int pwb_try_conv_wgrad(const edet_tview_t* in, const edet_gview_t* dy, int k, in
   memset(&a, 0, sizeof(a));
   a.tv = *in; a.gv = *dy; a.ws = reinterpret_cast<float*>(workspace);
   a.M = dy->n * dy->h * dy->w; a.K = K; a.N = N; a.hw = dy->h * dy->w;
-  a.ck = k; a.cs = s; a.cin = cin; a.ih = in->h; a.iw = in->w; a.cow = dy->w; a.cohw = dy->h * dy->w;
-  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
+  fill_conv(a, k, s, cin, in->h, in->w, dy->w, dy->h * dy->w, in->h, in->w);
   a.ntk = (K + 127) / 128; a.ntn = (N + 127) / 128;
   const int ntile = a.ntk * a.ntn;
-  const int64_t kn = (int64_t)K * N;
-  int S = (2048 + ntile - 1) / ntile;
-  const int max_by_rows = (a.M + 4 * BK - 1) / (4 * BK);
-  if (S > max_by_rows) S = max_by_rows;
-  const int64_t max_by_ws = (int64_t)(workspace_bytes / sizeof(float)) / kn;
-  if (S > max_by_ws) S = (int)max_by_ws;
-  if (S < 1) return 0;
-  a.rows_per_split = ((a.M + S - 1) / S + BK - 1) / BK * BK;
-  a.S = (a.M + a.rows_per_split - 1) / a.rows_per_split;
-  static const bool ok1 = big_lds_ok(reinterpret_cast<const void*>(&k_big_wgrad<false, true>));
-  static const bool ok2 = big_lds_ok(reinterpret_cast<const void*>(&k_big_wgrad<true, true>));
-  if (!ok1 || !ok2) return 0;
-  const int grid = (a.S + 7) / 8 * 8 * ntile;
-  if (dy->a) edet_launch(k_big_wgrad<true, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
-  else edet_launch(k_big_wgrad<false, true>, dim3(grid), dim3(THREADS), SMEM_BYTES, st, a);
+  if (!fill_wgrad_splits(a, (2048 + ntile - 1) / ntile, workspace_bytes)) return 0;
+  static void (*const kern[2][2])(const WgArgs) = {{k_big_wgrad<false, true>, nullptr}, {k_big_wgrad<true, true>, nullptr}};
+  if (!launch_variant(kern, dy->a != nullptr, false, (a.S + 7) / 8 * 8 * ntile, a, st)) return 0;
   EDET_LAUNCH_CHECK("edet_conv_bwd_weight(big)");
-  if (edet_reduce_partials(a.ws, a.S, kn, dweight, st) != 0) return -2;
+  if (edet_reduce_partials(a.ws, a.S, (int64_t)K * N, dweight, st) != 0) return -2;
   return 1;
 }

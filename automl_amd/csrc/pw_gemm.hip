@@ -16,7 +16,7 @@
 // efficientdet/tf2/efficientdet_keras.py:195-207,286-290,459-464,546-556.
 #include <stdlib.h>
 
-#include "common.h"
+#include "pw_impl.h"
 
 namespace {
 
@@ -608,14 +608,7 @@ void launch_wgrad_nj(const WgradArgs& a, int grid, hipStream_t st) {
   constexpr int TJ = NJ * 16;
   const size_t lds = sizeof(T) == 2 ? (size_t)(64 + TJ) * (BMR + 8) * 2
                                      : (size_t)BMR * ((64 + 4) + (TJ + 4)) * 4;
-  if (lds > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad<T, NJ>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-  }
+  (void)edet_lds_optin(&k_wgrad<T, NJ>, lds);
   edet_launch(k_wgrad<T, NJ>, dim3(grid), dim3(THREADS), lds, st, a);
 }
 
@@ -654,14 +647,6 @@ int launch_wgrad(WgradArgs& a, void* workspace, size_t workspace_bytes, hipStrea
 }
 
 }  // namespace
-
-// workgroup-tiled bf16 kernels for the wide layers (pw_big.hip); same return convention
-int pwb_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
-                int ldo, float* stat_partials, int* nparts_out, hipStream_t st);
-int pwb_try_dgrad(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in,
-                  const edet_bwd_epi_t* epi, int* nparts_out, hipStream_t st);
-int pwb_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, float* dweight, void* workspace,
-                  size_t workspace_bytes, hipStream_t st);
 
 // Which bf16 implementation serves a (rows, cin, cout) pointwise layer.  The streaming kernels own the
 // HBM-bound layers (few channels, many rows); the tiled kernels own the layers whose weight matrix is large
@@ -706,13 +691,6 @@ static int pw_route(int op, int64_t rows, int cin, int cout, TryBig try_big, Try
   return rc;
 }
 
-// streaming bf16 kernels (pw_stream.hip); return 1 = handled, 0 = shape outside their envelope
-int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
-                int ldo, float* stat_partials, int* nparts_out, hipStream_t st);
-
-int pws_try_dgrad(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in,
-                  const edet_bwd_epi_t* epi, int* nparts_out, hipStream_t st);
-
 extern "C" int edet_pw_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias,
                            void* out, int cout, int ldo, float* stat_partials, int* nparts_out,
                            int dtype, void* stream) {
@@ -738,9 +716,6 @@ extern "C" int edet_pw_fwd(const edet_tview_t* in, const void* wt, int ldw, cons
   if (dtype == EDET_F32) return launch_gemm<float, false>(a, nparts_out, to_stream(stream));
   EDET_CHECK(false, "edet_pw_fwd: bad dtype %d", dtype);
 }
-
-int pwb_fwd_f32out(const edet_tview_t* in, const void* wt, int ldw, const float* bias, float* out, int cout, int ldo,
-                   hipStream_t st);
 
 extern "C" int edet_pw_fwd_f32out(const edet_tview_t* in, const void* wt, int ldw, const float* bias, float* out,
                                   int cout, int ldo, void* stream) {
@@ -770,15 +745,13 @@ extern "C" int edet_pw_bwd_data(const edet_gview_t* dy, const void* w, int ldw,
   a.M = in->n * in->h * in->w; a.R = dy->c; a.J = in->c; a.hw = in->h * in->w;
   a.epi = *epi; a.stat_partials = epi->stat_partials;
   if (dtype == EDET_BF16) {
-    // SE-gated input: the tuned kernels store the gradient of the gated value and leave the gate-gradient sums to
-    // k_gate_sums below (one writer per element; r06: their own sums were floating-point atomics, the last of the bf16
-    // training step) -- the generic kernel (launch_gemm) does the same on its own
-    edet_bwd_epi_t e2 = *epi;
-    if (epi->dgate) e2.flags |= EDET_EPI_GATE_SUMS_LATER;
+    // SE-gated input (epi->dgate): the tuned kernels store the gradient of the gated value as it is, and the gate-gradient
+    // sums are formed from it by k_gate_sums below (one writer per element, a fixed order) -- the generic kernel
+    // (launch_gemm) does the same on its own
     const int rc = pw_route(
         PW_OP_DGRAD, a.M, in->c, dy->c,
-        [&] { return pwb_try_dgrad(dy, w, ldw, in, &e2, nparts_out, to_stream(stream)); },
-        [&] { return pws_try_dgrad(dy, w, ldw, in, &e2, nparts_out, to_stream(stream)); });
+        [&] { return pwb_try_dgrad(dy, w, ldw, in, epi, nparts_out, to_stream(stream)); },
+        [&] { return pws_try_dgrad(dy, w, ldw, in, epi, nparts_out, to_stream(stream)); });
     if (rc > 0 && epi->dgate) {
       edet_launch(k_gate_sums<bf16_t>, dim3(a.tv.n * cdiv(a.J, 64)), dim3(THREADS), 0, to_stream(stream), a);
       EDET_LAUNCH_CHECK("edet_pw_bwd_data (gate sums)");
@@ -789,9 +762,6 @@ extern "C" int edet_pw_bwd_data(const edet_gview_t* dy, const void* w, int ldw,
   if (dtype == EDET_F32) return launch_gemm<float, true>(a, nparts_out, to_stream(stream));
   EDET_CHECK(false, "edet_pw_bwd_data: bad dtype %d", dtype);
 }
-
-int pws_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, float* dweight, void* workspace,
-                  size_t workspace_bytes, hipStream_t st);
 
 extern "C" int edet_pw_bwd_weight(const edet_tview_t* in, const edet_gview_t* dy, float* dweight,
                                   void* workspace, size_t workspace_bytes, int dtype, void* stream) {
@@ -813,15 +783,6 @@ extern "C" int edet_pw_bwd_weight(const edet_tview_t* in, const edet_gview_t* dy
   if (dtype == EDET_F32) return launch_wgrad<float>(a, workspace, workspace_bytes, to_stream(stream));
   EDET_CHECK(false, "edet_pw_bwd_weight: bad dtype %d", dtype);
 }
-
-// streaming fused data + weight gradient (pw_stream.hip); return 1 = handled, 0 = shape outside its envelope
-int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in,
-                      const edet_bwd_epi_t* epi, int* nparts_out, float* dweight, void* workspace,
-                      size_t workspace_bytes, hipStream_t st);
-
-// one-pass tiled data + weight gradient (pw_tile_bwd.hip); same return convention
-int pwt_try_bwd(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in, const edet_bwd_epi_t* epi,
-                int* nparts_out, float* dweight, void* workspace, size_t workspace_bytes, hipStream_t st);
 
 extern "C" int edet_pw_bwd(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in,
                            const edet_bwd_epi_t* epi, int* nparts_out, float* dweight, void* workspace,

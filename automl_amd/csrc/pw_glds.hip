@@ -31,7 +31,7 @@
 // (project) with the preceding BatchNorm / activation / SE multiply (:183-195, :378-392).
 #include <stdlib.h>
 
-#include "common.h"
+#include "pw_impl.h"
 
 namespace pwg {
 
@@ -74,18 +74,6 @@ struct Args {
   float* stat_partials;
 };
 
-__device__ __forceinline__ void unpack8(const uint4 raw, float x[8]) {
-  x[0] = __uint_as_float(raw.x << 16); x[1] = __uint_as_float(raw.x & 0xffff0000u);
-  x[2] = __uint_as_float(raw.y << 16); x[3] = __uint_as_float(raw.y & 0xffff0000u);
-  x[4] = __uint_as_float(raw.z << 16); x[5] = __uint_as_float(raw.z & 0xffff0000u);
-  x[6] = __uint_as_float(raw.w << 16); x[7] = __uint_as_float(raw.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float x[8]) {
-  uint4 o;
-  o.x = pack2bf(x[0], x[1]); o.y = pack2bf(x[2], x[3]);
-  o.z = pack2bf(x[4], x[5]); o.w = pack2bf(x[6], x[7]);
-  return o;
-}
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
@@ -342,9 +330,7 @@ __global__ __launch_bounds__(THREADS, BK == 64 ? 1 : 2) void k_wide_fwd(const Ar
 }
 
 template <int BK, bool COEF, bool SWISH> int launch(const Args& a, int grid, hipStream_t st) {
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wide_fwd<BK, COEF, SWISH>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, Geo<BK>::SMEM_BYTES) == hipSuccess;
-  if (!ok) return 0;
+  if (!edet_lds_optin(&k_wide_fwd<BK, COEF, SWISH>, Geo<BK>::SMEM_BYTES)) return 0;
   edet_launch(k_wide_fwd<BK, COEF, SWISH>, dim3(grid), dim3(THREADS), Geo<BK>::SMEM_BYTES, st, a);
   return 1;
 }
@@ -357,7 +343,7 @@ template <int BK> int launch_bk(const Args& a, int grid, bool coef, bool sw, hip
 
 }  // namespace pwg
 
-// return 1 = handled, 0 = shape outside the envelope (the caller goes on to k_big_gemm), < 0 = error.
+// Outside the envelope the caller goes on to k_big_gemm.
 // Envelope: swish / linear views; with an SE gate at least 43 pixels per image (a row tile touches at most four images);
 // reduction length a multiple of 8 and at least 2 x 64 (shorter reductions have nothing to prefetch).
 int pwg_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,

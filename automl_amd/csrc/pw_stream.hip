@@ -23,7 +23,7 @@
 // and the pointwise half of SeparableConv2D (:195-207, :459-464, :546-556).
 #include <stdlib.h>
 
-#include "common.h"
+#include "pw_impl.h"
 
 namespace pws {
 
@@ -84,20 +84,6 @@ struct FwdArgs {
   int nvec_out;       // valid 16-byte chunks per output row = ceil(N / 8)
 };
 
-__device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) { return pack2bf(lo, hi); }
-
-__device__ __forceinline__ void unpack8(const uint4 raw, float x[8]) {
-  x[0] = __uint_as_float(raw.x << 16); x[1] = __uint_as_float(raw.x & 0xffff0000u);
-  x[2] = __uint_as_float(raw.y << 16); x[3] = __uint_as_float(raw.y & 0xffff0000u);
-  x[4] = __uint_as_float(raw.z << 16); x[5] = __uint_as_float(raw.z & 0xffff0000u);
-  x[6] = __uint_as_float(raw.w << 16); x[7] = __uint_as_float(raw.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float x[8]) {
-  uint4 o;
-  o.x = pack_bf2(x[0], x[1]); o.y = pack_bf2(x[2], x[3]);
-  o.z = pack_bf2(x[4], x[5]); o.w = pack_bf2(x[6], x[7]);
-  return o;
-}
 
 // activated value of 8 raw bf16 elements -> 8 bf16 packed
 // OACT: the view's activation is relu / relu6 / hswish (utils.activation_fn, utils.py:36-53; `act` carries the code) --
@@ -312,8 +298,8 @@ __global__ __launch_bounds__(THREADS, NS <= 8 ? 3 : 2) void k_pw_fwd(const FwdAr
               const int ch = c0 + nt * 32 + 8 * g + 4 * h;
               const float4 b4 = *reinterpret_cast<const float4*>(biasL + n0 + ch);
               uint2 pk;
-              pk.x = pack_bf2(acc[4 * g + 0] + b4.x, acc[4 * g + 1] + b4.y);
-              pk.y = pack_bf2(acc[4 * g + 2] + b4.z, acc[4 * g + 3] + b4.w);
+              pk.x = pack2bf(acc[4 * g + 0] + b4.x, acc[4 * g + 1] + b4.y);
+              pk.y = pack2bf(acc[4 * g + 2] + b4.z, acc[4 * g + 3] + b4.w);
               *reinterpret_cast<uint2*>(Ct + j * a.SC + (nt * 32 + 8 * g + 4 * h) * 2) = pk;
             }
           }
@@ -396,7 +382,8 @@ inline size_t plan_lds(int Npad, int a_rows, int SA, int SW, size_t cap, int* NW
 // dy = a*dz + b*y + c, two tensors per row) and an fp32 C tile; the epilogue works on 64-channel chunks with
 // a fixed 8-channel column per lane (col = lane & 7, 8 rows per pass), reads the saved conv input x, applies
 // act'(z), optionally accumulates into the existing gradient, stores 16 B per lane and keeps the BatchNorm
-// backward sums (sum g, sum g*xhat) / the SE dgate sums (sum D*act(z)) in registers across the sub-tiles.
+// backward sums (sum g, sum g*xhat) in registers across the sub-tiles.  With epi.dgate != NULL the gradient of the gated
+// value is stored as it is; the SE gate-gradient sums belong to the dispatch (k_gate_sums, pw_gemm.hip).
 struct BwdArgs {
   edet_gview_t gv;    // dy (contraction length R = gv.c)
   edet_tview_t tv;    // conv input view: raw x, scale, shift, gate, act; KO = tv.c output columns
@@ -420,7 +407,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_pw_dgrad(const BwdArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int j = lane & 31, h = lane >> 5;
   unsigned char* Wl = smem;                                             // [KOpad][SW]
-  float* red = reinterpret_cast<float*>(Wl + (size_t)a.KOpad * a.SW);   // [2][KOpad] stats, then [KOpad] gate
+  float* red = reinterpret_cast<float*>(Wl + (size_t)a.KOpad * a.SW);   // [2][KOpad] stats
   const int a_rows = TR * a.G;
   const int a_alloc = a.pst * a.cr.rp;
   const size_t wave_bytes = (size_t)a_alloc * a.SA + (size_t)TR * a.SC + (size_t)3 * a.KOpad * 4;
@@ -428,15 +415,14 @@ __global__ __launch_bounds__(THREADS, 2) void k_pw_dgrad(const BwdArgs a) {
   unsigned char* At = wbase;                                            // [a_alloc][SA] bf16 dy
   unsigned char* Ct = wbase + (size_t)a_alloc * a.SA;                   // [32][SC] fp32
   float* wst = reinterpret_cast<float*>(Ct + TR * a.SC);                // [2][KOpad] stat sums of this wave
-  float* wgt = wst + 2 * a.KOpad;                                       // [KOpad] dgate sums of the current image
+  // (a third [KOpad] row per wave follows wst: reserved by the host's LDS formula, unused)
   const bool want_stats = a.epi.stat_partials != nullptr;
   const bool want_gate = a.epi.dgate != nullptr;      // SE-gated input: the gradient of the gated value is stored as it is
-  const bool gate_sums = want_gate && !(a.epi.flags & EDET_EPI_GATE_SUMS_LATER);   // ... and its sums are formed here (atomics)
   const bool swish = !OACT && a.tv.act == EDET_ACT_SWISH, affine = a.tv.scale != nullptr;
   constexpr bool other = OACT;
 
   for (int i = tid; i < 2 * a.KOpad; i += THREADS) red[i] = 0.f;
-  for (int i = lane; i < 3 * a.KOpad; i += 64) wst[i] = 0.f;
+  for (int i = lane; i < 2 * a.KOpad; i += 64) wst[i] = 0.f;
   for (int i = lane; i < a_alloc * a.SA / 16; i += 64) reinterpret_cast<uint4*>(At)[i] = make_uint4(0, 0, 0, 0);
   {  // weights -> LDS (zero-filled beyond KO and beyond R)
     const int slots = a.SW / 16;
@@ -482,7 +468,6 @@ __global__ __launch_bounds__(THREADS, 2) void k_pw_dgrad(const BwdArgs a) {
 
   // epilogue mapping: 64-channel chunk, 8 lanes per row
   const int ecol = lane & 7, erow = lane >> 3;
-  int gate_img = -1;                       // image whose dgate sums are in wgt
   if (st0 < st1) issue(st0);
   for (int st = st0; st < st1; ++st) {
     const int row0 = st * a_rows;
@@ -514,34 +499,16 @@ __global__ __launch_bounds__(THREADS, 2) void k_pw_dgrad(const BwdArgs a) {
     if (st + 1 < st1) issue(st + 1);
     __builtin_amdgcn_wave_barrier();
 
-    // dgate bookkeeping: sums in wgt belong to one image; a super-tile that straddles two images goes
-    // straight to global atomics
-    bool gate_direct = false;
-    if (gate_sums) {
-      const int img0 = row0 / a.hw, img1 = (row0 + rows_in_st - 1) / a.hw;
-      gate_direct = img0 != img1;
-      if (gate_img >= 0 && (gate_direct || img0 != gate_img)) {
-        for (int c = lane; c < a.KO; c += 64) {
-          const float v = wgt[c];
-          if (v != 0.f) atomicAdd(&a.epi.dgate[(size_t)gate_img * a.KO + c], v);
-          wgt[c] = 0.f;
-        }
-        gate_img = -1;
-      }
-      if (!gate_direct) gate_img = img0;
-      __builtin_amdgcn_wave_barrier();
-    }
-
     for (int c0 = 0; c0 < a.KOpad; c0 += ECC) {
       const int ccols = min(ECC, a.KOpad - c0);                // 32 or 64
       const int ch0 = c0 + ecol * 8;                           // this lane's 8 output channels
       const bool col_ok = ch0 < a.KO && ecol * 8 < ccols;
-      // s1: sum g (stats) or sum D*act(z) (gate); s2: sum g*x, turned into sum g*xhat when it is flushed
+      // s1: sum g; s2: sum g*x, turned into sum g*xhat when it is flushed
       float sc[8], sh[8], s1[8], s2[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) { sc[e] = 1.f; sh[e] = 0.f; s1[e] = s2[e] = 0.f; }
       if (col_ok && affine) { loadf8(a.tv.scale + ch0, sc); loadf8(a.tv.shift + ch0, sh); }
-      const bool need_x = swish || other || want_gate || want_stats;
+      const bool need_x = want_stats || (!want_gate && (swish || other));
       for (int sub = 0; sub * TR < rows_in_st; ++sub) {
         const int trow0 = row0 + sub * TR;
         const int rows_valid = min(TR, rows_in_st - sub * TR);
@@ -573,26 +540,9 @@ __global__ __launch_bounds__(THREADS, 2) void k_pw_dgrad(const BwdArgs a) {
             float x[8], g[8];
             unpack8(xr[p], x);
             const size_t off = (size_t)(trow0 + r) * a.tv.ld + ch0;
-            if (want_gate && !gate_sums) {
+            if (want_gate) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) g[e] = d[e];
-            } else if (want_gate) {
-              float gsum[8];
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                const float z = fmaf(x[e], sc[e], sh[e]);
-                gsum[e] = d[e] * (other ? act_other_(a.tv.act, z) : (swish ? swishf_(z) : z));
-                g[e] = d[e];
-              }
-              if (gate_direct) {
-                const int img = (trow0 + r) / a.hw;
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                  if (ch0 + e < a.KO) atomicAdd(&a.epi.dgate[(size_t)img * a.KO + ch0 + e], gsum[e]);
-              } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) s1[e] += gsum[e];
-              }
             } else if (swish) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) g[e] = d[e] * swish_gradf_(fmaf(x[e], sc[e], sh[e]));
@@ -624,34 +574,21 @@ __global__ __launch_bounds__(THREADS, 2) void k_pw_dgrad(const BwdArgs a) {
         __builtin_amdgcn_wave_barrier();
       }
       // chunk sums -> wave LDS accumulators (8 lanes share a column: LDS atomics)
-      if (col_ok) {
-        if (want_stats) {
-          float mu[8], rs[8];
-          loadf8(a.epi.mean + ch0, mu);
-          loadf8(a.epi.rstd + ch0, rs);
+      if (col_ok && want_stats) {
+        float mu[8], rs[8];
+        loadf8(a.epi.mean + ch0, mu);
+        loadf8(a.epi.rstd + ch0, rs);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            if (ch0 + e < a.KO) {
-              atomicAdd(&wst[ch0 + e], s1[e]);
-              atomicAdd(&wst[a.KOpad + ch0 + e], rs[e] * (s2[e] - mu[e] * s1[e]));   // sum g*(x-mean)*rstd
-            }
+        for (int e = 0; e < 8; ++e) {
+          if (ch0 + e < a.KO) {
+            atomicAdd(&wst[ch0 + e], s1[e]);
+            atomicAdd(&wst[a.KOpad + ch0 + e], rs[e] * (s2[e] - mu[e] * s1[e]));   // sum g*(x-mean)*rstd
           }
-        }
-        if (gate_sums && !gate_direct) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (ch0 + e < a.KO) atomicAdd(&wgt[ch0 + e], s1[e]);
         }
       }
     }
   }
   __builtin_amdgcn_wave_barrier();
-  if (gate_sums && gate_img >= 0) {
-    for (int c = lane; c < a.KO; c += 64) {
-      const float v = wgt[c];
-      if (v != 0.f) atomicAdd(&a.epi.dgate[(size_t)gate_img * a.KO + c], v);
-    }
-  }
   if (want_stats) {
     for (int c = lane; c < a.KO; c += 64) {
       atomicAdd(&red[c], wst[c]);
@@ -905,7 +842,7 @@ __global__ __launch_bounds__(THREADS, 2) void k_pw_wgrad(const WgArgs a) {
 //     backward coefficients stay in registers), dy = a*dz + b*y + c goes to the LDS tile Dt as bf16, x is parked raw
 //     in the LDS tile Xt;
 //   * D'[k][row] = W[k][:] . dy[row][:] on 32x32x16 MFMAs, through the fp32 C tile into the 8-channel-per-lane
-//     epilogue of k_pw_dgrad (act'(z), accumulate, BatchNorm-backward sums, SE dgate sums), which takes x from Xt
+//     epilogue of k_pw_dgrad (act'(z), accumulate, BatchNorm-backward sums), which takes x from Xt
 //     and leaves the ACTIVATED operand act(bn(x)) * gate there as bf16;
 //   * dW[k][n] += sum_rows xa[row][k] * dy[row][n] on 16x16x32 MFMAs whose contraction runs over the tile's 32
 //     rows: fragments are gathered column-wise (8 consecutive rows of one channel per lane) from Xt and Dt; the dW
@@ -948,10 +885,10 @@ struct FusedArgs {
 // 30 % -- the waits degrade to vmcnt(0)); the host picks the instantiation that fits the step with the fewest rows
 // to spare.  The round-2 kernel had two pairs, (8, 1) and (12, 2): 8 passes of 32 rows each for a 16-channel gradient
 // whose 32-row tile needs one -- the reason the project layers measured slower in it.
-// NCH: 64-channel epilogue chunks (KOpad <= 64 NCH); the per-channel sums (BatchNorm backward, SE gate gradient)
-// are carried in registers across all tiles of the wave and reach LDS once per kernel (or once per image).
+// NCH: 64-channel epilogue chunks (KOpad <= 64 NCH); the per-channel sums of the BatchNorm backward are carried in
+// registers across all tiles of the wave and reach LDS once per kernel.
 // BETA: the instantiation can accumulate into gout (epi.beta; the old gradient rides along with x)
-// STRADDLE: a 32-row tile may lie in two images (hw % 32 != 0) while an SE gate / gate gradient is involved
+// STRADDLE: a 32-row tile may lie in two images (hw % 32 != 0) while an SE gate is involved
 template <int NSR, int NSX, bool GBN, int FT_S, int FT_L, bool NOY = false, int NCH = 1, bool BETA = true, bool STRADDLE = true>
 __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) {
   static_assert(!NOY || GBN, "NOY is a form of the BatchNorm backward on load");
@@ -975,11 +912,9 @@ __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) 
   unsigned char* Ot = Xt + (size_t)srows * a.SX;                        // [srows][SX] bf16 old gout (beta only)
   unsigned char* Ct = Ot + (has_beta ? (size_t)srows * a.SX : 0);       // [32][SC] fp32
   float* wst = reinterpret_cast<float*>(Ct + TR * a.SC);                // [2][KOpad] sums (g, g*x) of this wave
-  float* wgt = wst + 2 * a.KOpad;                                       // [KOpad] dgate sums of one image
-  float* gateL = wgt + a.KOpad;                                         // [KOpad] SE gate of the current image
+  float* gateL = wst + 3 * a.KOpad;                                     // [KOpad] SE gate of the current image (the row before it: reserved, unused)
   // NOY: the host guarantees a plain input view and no sums (compile-time false: the code is not generated)
   const bool want_stats = !NOY && a.epi.stat_partials != nullptr;
-  const bool want_gate = !NOY && a.epi.dgate != nullptr;
   const bool swish = !NOY && a.tv.act == EDET_ACT_SWISH, affine = !NOY && a.tv.scale != nullptr;
   const bool gated = !NOY && a.tv.gate != nullptr;
 
@@ -990,7 +925,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) 
     coefS[i] = (affine && i < a.KO) ? a.tv.scale[i] : 1.f;
     coefH[i] = (affine && i < a.KO) ? a.tv.shift[i] : 0.f;
   }
-  for (int i = lane; i < 3 * a.KOpad; i += 64) wst[i] = 0.f;
+  for (int i = lane; i < 2 * a.KOpad; i += 64) wst[i] = 0.f;
   for (int i = lane; i < a.KOpad; i += 64) gateL[i] = 1.f;
   for (int i = lane; i < (int)(((size_t)srows * a.SA + (size_t)srows * a.SX) / 16); i += 64)
     reinterpret_cast<uint4*>(Dt)[i] = make_uint4(0, 0, 0, 0);
@@ -1122,7 +1057,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) 
     loadf8(a.gv.a + colR * 8, ga); loadf8(a.gv.b + colR * 8, gb); loadf8(a.gv.cc + colR * 8, gc);
   }
   // this lane's running column sums over all its tiles (its 8 channels of every epilogue chunk never change):
-  // ra = sum g (BatchNorm backward) or sum d*act (SE gate gradient, per image), rb = sum g*x; NOY: xacc = sum x
+  // ra = sum g, rb = sum g*x (BatchNorm backward); NOY: xacc = sum x
   float ra[NCH][8], rb[NCH][8];
 #pragma unroll
   for (int ci = 0; ci < NCH; ++ci)
@@ -1147,27 +1082,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) 
     return nv <= 1 ? 0 : (nv <= 2 ? 1 : (nv <= 4 ? 2 : 3));
   };
   const int fi = lane & 15, fq = lane >> 4;        // 16x16x32 fragment coordinates
-  int gate_img = -1;                               // image whose dgate sums are in ra
   int gateL_img = -1;                              // image whose SE gate is in gateL
-  // SE gate gradient sums of image `gate_img`: registers -> wgt (the row-lanes of a column: LDS atomics) -> global
-  auto flush_gate = [&]() {
-#pragma unroll
-    for (int ci = 0; ci < NCH; ++ci) {
-      const int ch0 = ci * ECC + (lane & ((1 << chunk_lsh(ci)) - 1)) * 8;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if (ch0 < a.KO) atomicAdd(&wgt[ch0 + e], ra[ci][e]);
-        ra[ci][e] = 0.f;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int c = lane; c < a.KO; c += 64) {
-      const float v = wgt[c];
-      if (v != 0.f) atomicAdd(&a.epi.dgate[(size_t)gate_img * a.KO + c], v);
-      wgt[c] = 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-  };
   if (t0 < t1) issue(t0);
   for (int t = t0; t < t1; ++t) {
     const int rowS = t * srows;
@@ -1238,17 +1153,6 @@ __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) 
         gateL_img = img0;
         __builtin_amdgcn_wave_barrier();
       }
-      // dgate bookkeeping: the sums in ra belong to one image; a tile that straddles two images goes straight to
-      // global atomics
-      bool gate_direct = false;
-      if (want_gate) {
-        gate_direct = !one_img;
-        if (gate_img >= 0 && (gate_direct || img0 != gate_img)) {
-          flush_gate();
-          gate_img = -1;
-        }
-        if (!gate_direct) gate_img = img0;
-      }
 
       // ---- data gradient, 64 input channels at a time, and the activated operand for the weight gradient
       const unsigned char* arow = Dg + (size_t)j * a.SA + h * 16;
@@ -1299,39 +1203,18 @@ __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) 
             }
             // z (pre-activation), its activation av and the chained gradient gg
             if (swish) {
-              if (want_gate) {       // the gate gradient's consumer applies act' itself: gg = d
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                  const float z = fmaf(x[e], sc[e], sh[e]);
-                  av[e] = z * sigmoidf_(z);
-                  gg[e] = d[e];
-                }
-              } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                  const float z = fmaf(x[e], sc[e], sh[e]);
-                  const float sg = sigmoidf_(z);
-                  av[e] = z * sg;
-                  gg[e] = d[e] * (sg * (1.0f + z * (1.0f - sg)));
-                }
+              for (int e = 0; e < 8; ++e) {
+                const float z = fmaf(x[e], sc[e], sh[e]);
+                const float sg = sigmoidf_(z);
+                av[e] = z * sg;
+                gg[e] = d[e] * (sg * (1.0f + z * (1.0f - sg)));
               }
             } else {
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 av[e] = fmaf(x[e], sc[e], sh[e]);
                 gg[e] = d[e];
-              }
-            }
-            if (want_gate) {
-              if (STRADDLE && gate_direct) {
-                if (r < rows_valid) {
-                  const int img = (row0 + r) / a.hw;
-#pragma unroll
-                  for (int e = 0; e < 8; ++e) atomicAdd(&a.epi.dgate[(size_t)img * a.KO + ch0 + e], d[e] * av[e]);
-                }
-              } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ra[ci][e] = fmaf(d[e], av[e], ra[ci][e]);
               }
             }
             if (gated) {
@@ -1404,7 +1287,6 @@ __global__ __launch_bounds__(THREADS, 1) void k_pw_bwd_fused(const FusedArgs a) 
     }
   }
   __builtin_amdgcn_wave_barrier();
-  if (want_gate && gate_img >= 0) flush_gate();
   if (NOY) {     // the lanes' column sums -> wst[0 .. KO) (the row-lanes of a column: LDS atomics, once per kernel)
     const int ch0 = (lane & ((1 << chunk_lsh(0)) - 1)) * 8;
     if (ch0 < a.KO) {
@@ -1517,17 +1399,8 @@ __global__ __launch_bounds__(256) void k_noy_apply(const float* __restrict__ psu
   dweight[i] += ga[n] * psum[i] + gb[n] * t + gc[n] * psum[(size_t)KO * R + (size_t)KO * KO + k];
 }
 
-template <typename KernelT>
-inline bool allow_big_lds(KernelT kern, size_t lds) {
-  if (lds <= 64 * 1024) return true;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             160 * 1024) == hipSuccess;
-}
-
 }  // namespace pws
 
-// Returns 1 when the streaming kernel handled the call, 0 when the shape is outside its envelope
-// (the caller then falls back to the tiled kernel in pw_gemm.hip), negative on error.
 int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
                 int ldo, float* stat_partials, int* nparts_out, hipStream_t st) {
   using namespace pws;
@@ -1606,7 +1479,7 @@ int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bi
   if (nparts_out) *nparts_out = grid;
 #define PWS_FWD(NS_, OACT_, EXACT_)                                                      \
   do {                                                                                  \
-    if (!allow_big_lds(&k_pw_fwd<NS_, EXACT_, OACT_>, lds)) return 0;                   \
+    if (!edet_lds_optin(&k_pw_fwd<NS_, EXACT_, OACT_>, lds)) return 0;                   \
     edet_launch(k_pw_fwd<NS_, EXACT_, OACT_>, dim3(grid), dim3(THREADS), lds, st, a);   \
   } while (0)
   switch (NS) {
@@ -1665,7 +1538,7 @@ int pws_try_dgrad(const edet_gview_t* dy, const void* w, int ldw, const edet_tvi
   if (nparts_out) *nparts_out = grid;
 #define PWS_DGRAD(NS_, GBN_, OACT_)                                                    \
   do {                                                                                 \
-    if (!allow_big_lds(&k_pw_dgrad<NS_, GBN_, OACT_>, lds)) return 0;                  \
+    if (!edet_lds_optin(&k_pw_dgrad<NS_, GBN_, OACT_>, lds)) return 0;                  \
     edet_launch(k_pw_dgrad<NS_, GBN_, OACT_>, dim3(grid), dim3(THREADS), lds, st, a);  \
   } while (0)
   if (in->act > EDET_ACT_SWISH) { if (gbn) PWS_DGRAD(8, true, true); else PWS_DGRAD(8, false, true); }
@@ -1719,8 +1592,8 @@ int pws_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, float* dweight
   return 1;
 }
 
-// Both gradients of one pointwise layer in one pass: 1 = handled, 0 = outside the envelope (the caller runs the two
-// separate kernels), < 0 = error.  dweight [KO][R] fp32 is accumulated into (edet_reduce_partials).
+// Both gradients of one pointwise layer in one pass (outside the envelope the caller runs the two separate kernels).
+// dweight [KO][R] fp32 is accumulated into (edet_reduce_partials).
 int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in,
                       const edet_bwd_epi_t* epi, int* nparts_out, float* dweight, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
@@ -1728,9 +1601,9 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
   using namespace pws;
   const int R = dy->c, KO = in->c;
   if (!workspace || KO % 8 != 0 || dy->ld % 8 != 0 || in->ld % 8 != 0 || R > 160 || KO > 160) return 0;
-  if (epi->stat_partials && epi->dgate) return 0;     // one set of running sums per lane: BatchNorm backward OR gate
-  if (in->gate && epi->dgate) return 0;               // r06: this kernel's gate-gradient sums are atomics -- the tiled one-pass kernel
-                                                      // (ordered slots) or the two-kernel path + k_gate_sums take SE-gated inputs
+  if (epi->stat_partials && epi->dgate) return 0;
+  if (in->gate && epi->dgate) return 0;               // this kernel forms no SE gate-gradient sums (r06: its own were global atomics): the
+                                                      // tiled one-pass kernel (ordered slots) or the two-kernel path + k_gate_sums do
   FusedArgs a;
   memset(&a, 0, sizeof(a));
   a.gv = *dy; a.tv = *in; a.W = reinterpret_cast<const bf16_t*>(w); a.ldw = ldw; a.epi = *epi;
@@ -1757,8 +1630,8 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
     // 640x640 batch 128: 160x160x96->24 0.436 against 0.582 ms here, 80x80x144->40 0.226 / 0.274, 160x160x144->24 0.803 /
     // 0.796 (a tie, and the tiled kernel has no atomics); 320x320x32->16 stays here (0.787 against 0.841 ms).
     // EDET_PWT=0 (the tiled kernel off) restores the round-3 envelope.
-    // ... and every SE-gated projection: this kernel adds its gate-gradient sums into dgate with global atomics, the
-    // tiled kernel in a fixed order (320x320x32->16: 0.84 against 0.79 ms here -- the price of a reproducible step)
+    // ... and every SE-gated projection: the tiled kernel forms the gate-gradient sums in a fixed order, this one could only
+    // with global atomics (r06, since removed; 320x320x32->16: 0.84 against 0.79 ms here -- the price of a reproducible step)
     if ((KO > 32 || in->gate) && edet_env_int("EDET_PWT", 1) != 0) return 0;
     if (in->gate && a.hw % TR != 0) return 0;   // ... and take every 32-row tile to lie in one image where a gate is involved
     if (tmax <= 4 && KO <= 64) ft = 44;
@@ -1841,7 +1714,7 @@ int pws_try_bwd_fused(const edet_gview_t* dy, const void* w, int ldw, const edet
   if (nparts_out) *nparts_out = grid;
 #define PWS_FUSED(NSR_, NSX_, GBN_, FS_, FL_, NOY_, NCH_, BETA_)                                                       \
   do {                                                                                                                 \
-    if (!allow_big_lds(&k_pw_bwd_fused<NSR_, NSX_, GBN_, FS_, FL_, NOY_, NCH_, BETA_, BETA_>, lds)) return 0;                 \
+    if (!edet_lds_optin(&k_pw_bwd_fused<NSR_, NSX_, GBN_, FS_, FL_, NOY_, NCH_, BETA_, BETA_>, lds)) return 0;                 \
     edet_launch(k_pw_bwd_fused<NSR_, NSX_, GBN_, FS_, FL_, NOY_, NCH_, BETA_, BETA_>, dim3(grid), dim3(THREADS), lds, st, a); \
   } while (0)
 #define PWS_FUSED_GB(NSR_, NSX_, FS_, FL_, NCH_, BETA_)                    \

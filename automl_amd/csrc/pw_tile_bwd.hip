@@ -29,7 +29,7 @@
 // 459-464,546-556 under the GradientTape of efficientdet/tf2/train_lib.py:623-669.
 #include <stdlib.h>
 
-#include "common.h"
+#include "pw_impl.h"
 
 namespace pwt {
 
@@ -57,18 +57,6 @@ struct Args {
   int nsl;              // KT-channel slices of K
 };
 
-__device__ __forceinline__ void unpack8(const uint4 raw, float x[8]) {
-  x[0] = __uint_as_float(raw.x << 16); x[1] = __uint_as_float(raw.x & 0xffff0000u);
-  x[2] = __uint_as_float(raw.y << 16); x[3] = __uint_as_float(raw.y & 0xffff0000u);
-  x[4] = __uint_as_float(raw.z << 16); x[5] = __uint_as_float(raw.z & 0xffff0000u);
-  x[6] = __uint_as_float(raw.w << 16); x[7] = __uint_as_float(raw.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float x[8]) {
-  uint4 o;
-  o.x = pack2bf(x[0], x[1]); o.y = pack2bf(x[2], x[3]);
-  o.z = pack2bf(x[4], x[5]); o.w = pack2bf(x[6], x[7]);
-  return o;
-}
 // the first `nvalid` (<= 8) bf16 elements of a chunk, the others zeroed (padding columns may hold anything)
 __device__ __forceinline__ uint4 keep_first(uint4 v, int nvalid) {
   uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -544,9 +532,7 @@ template <int KT, int NT, bool GBN, int XM, bool OACT, int NSL = 1, int PF = 1>
 int launch(Args& a, int* nparts_out, size_t workspace_bytes, hipStream_t st) {
   auto kern = k_pw_bwd_tile<KT, NT, GBN, XM, OACT, NSL, PF>;
   constexpr size_t lds = lds_bytes(KT, NT, NSL, GBN || XM != 0);
-  static const bool lds_ok = lds <= 64 * 1024 ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-  if (!lds_ok) return 0;
+  if (!edet_lds_optin(kern, lds)) return 0;
   static const int resident = edet_resident_wgs(reinterpret_cast<const void*>(kern), THREADS, lds);
   a.nsl = (a.K + KT - 1) / KT;
   // Row splits: the rounds of resident workgroups below, at least 4 steps each, bounded by the statistic partial rows and
@@ -586,7 +572,7 @@ int launch(Args& a, int* nparts_out, size_t workspace_bytes, hipStream_t st) {
 
 }  // namespace pwt
 
-// return 1 = handled, 0 = shape outside the envelope (the caller runs the two-kernel path), < 0 = error
+// Outside the envelope the caller runs the two-kernel path.
 int pwt_try_bwd(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in, const edet_bwd_epi_t* epi,
                 int* nparts_out, float* dweight, void* workspace, size_t workspace_bytes, hipStream_t st) {
   using namespace pwt;

@@ -424,8 +424,9 @@ class LayerEngine(object):
   ZCHUNK = 4 * 1024 * 1024      # floats per zero-arena chunk (16 MiB)
 
   def zbuf(self, key, shape):
-    """fp32 buffer that is zeroed at the start of every step (atomic accumulation targets: SE pooled sums and gate
-    gradients, fusion-weight gradients, loss sums).  Carved out of a few large chunks so that the ~60 buffers of a
+    """fp32 buffer that is zeroed at the start of every step: the kernels ADD into it, in a fixed order and without
+    atomics (SE pooled sums; gate gradients, which k_gate_sums / k_gate_finish add into; fusion-weight gradients, loss
+    sums).  Carved out of a few large chunks so that the ~60 buffers of a
     step cost one fill launch per chunk instead of one each."""
     t = self._bufs.get(key)
     if t is None:
@@ -894,7 +895,7 @@ class LayerEngine(object):
       self._cast_version = self.arena.version
     for bn in self.bns.values():
       bn.bwd_ready = False
-    for t in self._zero_list:      # atomic accumulation targets (SE pooled sums, ...) start every pass at zero
+    for t in self._zero_list:      # buffers the kernels add into (SE pooled sums, gate gradients, ...) start every pass at zero
       call('edet_zero', ptr(t), t.numel() * 4, self.stream)
     if training:
       call('edet_zero', ptr(self.grads_flat), self.grads_flat.numel() * 4, self.stream)

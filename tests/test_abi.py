@@ -75,6 +75,25 @@ def test_environment_variables_are_documented():
   assert not missing, missing
 
 
+def test_no_kernel_adds_to_dgate_atomically():
+  """DESIGN.md section 4 and include/edet_hip.h say the training path has no floating-point atomics.  The SE gate gradient
+  was the last place that had them: a data-gradient kernel given epi.dgate stores the gradient of the gated value as it is,
+  and its dispatch forms the sums afterwards (k_gate_sums, k_gate_finish).  No HIP source may add to epi.dgate with
+  atomicAdd, and the dispatch flag that once switched such code off is gone with it."""
+  csrc = os.path.join(ROOT, 'automl_amd', 'csrc')
+  hips = sorted(n for n in os.listdir(csrc) if n.endswith('.hip'))
+  assert len(hips) >= 17, hips
+  for name in hips:
+    text = open(os.path.join(csrc, name)).read()
+    assert not re.search(r'atomicAdd\s*\([^;]*dgate', text), name      # e.g. atomicAdd(&a.epi.dgate[...], v)
+  flag = 'EDET_EPI_GATE_SUMS' + '_LATER'
+  for top in ('automl_amd', 'include', 'tests'):
+    for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+      for name in files:
+        if name.endswith(('.hip', '.h', '.cpp', '.inc', '.py', '.c')):
+          assert flag not in open(os.path.join(dirpath, name)).read(), os.path.join(dirpath, name)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
   monkeypatch.setattr(_lib, '_lib', None)
   monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libedet_hip.so')
