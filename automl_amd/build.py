@@ -25,7 +25,8 @@ def _stale(target, deps):
 
 def build_library(force=False, verbose=False):
   """Compiles every HIP source for gfx950 and links libedet_hip.so; returns its path."""
-  hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pw_impl.h'), os.path.join(_HERE, '..', 'include', 'edet_hip.h'),
+  hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pw_impl.h'), os.path.join(CSRC, 'dw_impl.h'),
+          os.path.join(_HERE, '..', 'include', 'edet_hip.h'),
           os.path.join(_HERE, '..', 'include', 'edet_net.h'), os.path.join(CSRC, 'plan_stubs.inc')]
   objdir = os.path.join(CSRC, 'build')
   os.makedirs(objdir, exist_ok=True)

@@ -1,44 +1,52 @@
 // Depthwise k x k convolution (k in {3,5}, stride in {1,2}, TF 'SAME') for the bf16 path: row-marching
 // kernels with an LDS row exchange.
 //
-// A depthwise conv moves ~4 bytes per output element and does k*k FMAs on it: pure HBM streaming.  Each
-// thread owns one output column and CPT consecutive channels and marches DOWN the image: per input row it
-// loads the k horizontally adjacent pixels it needs (the neighbouring threads read the same cache lines, so
-// every byte comes from HBM once and k times from L1), applies the producer's BatchNorm + swish on load and
-// accumulates into a rotating set of ceil(k/stride) output-row accumulators held in registers; a finished
-// output row is written once.  The k*k weights of the thread's channels stay in registers (fp32) for the whole
-// kernel; CPT = 4 (k = 3) or 2 (k = 5) keeps the kernel near 100 VGPRs = 4-5 waves per SIMD, which is what
-// hides the HBM latency here (there is no barrier anywhere in the main loop).
+// A depthwise conv moves ~4 bytes per output element and does k*k FMAs on it.  Each thread owns one column of the
+// marched space and CPT consecutive channels and marches DOWN the image.  Per row it loads and transforms only ITS OWN
+// pixel (plus one halo pixel for the first few threads of the workgroup): the producer's BatchNorm + activation on
+// load, or the BatchNorm backward of dy.  It parks the fp32 result in a two-row LDS ring and, after ONE workgroup
+// barrier per row, reads the K horizontal neighbours back from LDS (conflict-free: consecutive lanes = consecutive
+// channels).  Global loads run a few rows ahead of the barrier in a register FIFO, so the HBM latency is covered by
+// the march.  (The first kernels had no barrier: every thread loaded its K neighbours from L1 and transformed each of
+// them itself.  PMC counters showed them 50-76 % VALU-bound, not HBM-bound: K*(act) + K*K VALU operations per
+// element where the exchange needs act + K*K, and K L1 loads where it needs one.)  The taps accumulate into a rotating
+// set of ceil(k/stride) row accumulators held in registers; a finished row is written once.  The k*k weights of the
+// thread's channels stay in registers (fp32) for the whole kernel.  CPT is 4 or 2, chosen by the host per kernel size
+// and map (the thresholds and their measurements stand at the host functions below).
 //
-// The same marching structure gives the weight gradient (accumulate in[r][x+kx] * dy[oy][x] into k*k
-// register sums per thread, reduced per workgroup into a workspace slab, summed by a second kernel) and
-// the data gradient (march over dy rows, scatter into the in-flight input-row accumulators, then chain
-// through act'(z), the optional accumulate and the BatchNorm backward sums in the row epilogue).  Round 6: both
-// gradients of a layer come from ONE march (k_bwd_one, any stride; edet_dw_bwd), the separate kernels stay behind the
-// separate entry points.
+// The kernels:
+//   k_fwd_v2     forward (edet_dw_fwd): march over the input rows, ceil(k/stride) output rows in flight.
+//   k_bwd_one    data gradient AND weight gradient of a layer from one march over the dy rows, any stride
+//                (edet_dw_bwd).
+//   k_wgrad_lx   weight gradient alone (edet_dw_bwd_weight): in[r][x+kx] * dy[oy][x] into k*k register sums per
+//                thread, reduced per workgroup into a workspace slab that a second kernel sums.
+//   k_dgrad_lx   data gradient alone (edet_dw_bwd_data): march over the dy rows, scatter into the in-flight input-row
+//                accumulators, then act'(z), the optional accumulate and the BatchNorm backward sums in the row epilogue.
+// k_fwd_v2 and k_bwd_one work on 2-vectors of adjacent channels through raw buffer accesses (dw_impl.h, shared with
+// the fused MBConv head in mbconv_fused.hip); the two _lx kernels keep the older Raw<CPT> / float[CPT] helpers below.
 //
 // Reference call sites: efficientdet/backbone/efficientnet_model.py:320-327 (MBConv DepthwiseConv2D),
 // efficientdet/tf2/efficientdet_keras.py:195-207,459-464,546-556 (depthwise half of SeparableConv2D).
 #include <stdlib.h>
 
-#include "common.h"
+#include "dw_impl.h"
 
 namespace dwm {
 
+using namespace dwi;
+
 constexpr int THREADS = 256;
 
+// ---- CPT bf16 channels as they lie in memory (k_wgrad_lx, k_dgrad_lx)
 template <int CPT> struct Raw;
-template <> struct Raw<8> { uint4 v; };
 template <> struct Raw<4> { uint2 v; };
 template <> struct Raw<2> { uint32_t v; };
 
 template <int CPT> __device__ __forceinline__ Raw<CPT> raw_zero();
-template <> __device__ __forceinline__ Raw<8> raw_zero<8>() { Raw<8> r; r.v = make_uint4(0, 0, 0, 0); return r; }
 template <> __device__ __forceinline__ Raw<4> raw_zero<4>() { Raw<4> r; r.v = make_uint2(0, 0); return r; }
 template <> __device__ __forceinline__ Raw<2> raw_zero<2>() { Raw<2> r; r.v = 0; return r; }
 
 template <int CPT> __device__ __forceinline__ Raw<CPT> raw_load(const bf16_t* p);
-template <> __device__ __forceinline__ Raw<8> raw_load<8>(const bf16_t* p) { Raw<8> r; r.v = *reinterpret_cast<const uint4*>(p); return r; }
 template <> __device__ __forceinline__ Raw<4> raw_load<4>(const bf16_t* p) { Raw<4> r; r.v = *reinterpret_cast<const uint2*>(p); return r; }
 template <> __device__ __forceinline__ Raw<2> raw_load<2>(const bf16_t* p) { Raw<2> r; r.v = *reinterpret_cast<const uint32_t*>(p); return r; }
 
@@ -47,20 +55,12 @@ __device__ __forceinline__ void up2(uint32_t u, float& lo, float& hi) {
   hi = __uint_as_float(u & 0xffff0000u);
 }
 template <int CPT> __device__ __forceinline__ void raw_unpack(const Raw<CPT>& r, float x[CPT]);
-template <> __device__ __forceinline__ void raw_unpack<8>(const Raw<8>& r, float x[8]) {
-  up2(r.v.x, x[0], x[1]); up2(r.v.y, x[2], x[3]); up2(r.v.z, x[4], x[5]); up2(r.v.w, x[6], x[7]);
-}
 template <> __device__ __forceinline__ void raw_unpack<4>(const Raw<4>& r, float x[4]) {
   up2(r.v.x, x[0], x[1]); up2(r.v.y, x[2], x[3]);
 }
 template <> __device__ __forceinline__ void raw_unpack<2>(const Raw<2>& r, float x[2]) { up2(r.v, x[0], x[1]); }
 
 template <int CPT> __device__ __forceinline__ void store_bf(bf16_t* p, const float x[CPT]);
-template <> __device__ __forceinline__ void store_bf<8>(bf16_t* p, const float x[8]) {
-  uint4 o;
-  o.x = pack2bf(x[0], x[1]); o.y = pack2bf(x[2], x[3]); o.z = pack2bf(x[4], x[5]); o.w = pack2bf(x[6], x[7]);
-  *reinterpret_cast<uint4*>(p) = o;
-}
 template <> __device__ __forceinline__ void store_bf<4>(bf16_t* p, const float x[4]) {
   uint2 o;
   o.x = pack2bf(x[0], x[1]); o.y = pack2bf(x[2], x[3]);
@@ -75,8 +75,22 @@ template <int CPT> __device__ __forceinline__ void loadf(const float* p, float x
   for (int e = 0; e < CPT; ++e) x[e] = p[e];
 }
 
-// static slot of a (possibly negative) relative output row
-__host__ __device__ constexpr int slot_of(int rel, int n) { return ((rel % n) + n) % n; }
+template <int CPT> __device__ __forceinline__ void lds_put(float* p, const float x[CPT]);
+template <> __device__ __forceinline__ void lds_put<4>(float* p, const float x[4]) {
+  *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
+}
+template <> __device__ __forceinline__ void lds_put<2>(float* p, const float x[2]) {
+  *reinterpret_cast<float2*>(p) = make_float2(x[0], x[1]);
+}
+template <int CPT> __device__ __forceinline__ void lds_get(const float* p, float x[CPT]);
+template <> __device__ __forceinline__ void lds_get<4>(const float* p, float x[4]) {
+  const float4 v = *reinterpret_cast<const float4*>(p);
+  x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+}
+template <> __device__ __forceinline__ void lds_get<2>(const float* p, float x[2]) {
+  const float2 v = *reinterpret_cast<const float2*>(p);
+  x[0] = v.x; x[1] = v.y;
+}
 
 struct Args {
   edet_tview_t in;      // fwd / wgrad: activated input view; dgrad: the conv input view (chain target)
@@ -177,60 +191,24 @@ __device__ __forceinline__ void block_channel_sums(const Args& a, const Lane& l,
   }
 }
 
-// =====================================================================================================
-// LDS row-exchange variants (the default).  PMC counters of the kernels above showed them 50-76 % VALU-bound,
-// not HBM-bound: every thread re-applied the producer's BatchNorm + swish (or the BatchNorm backward) to
-// each of the K horizontally adjacent pixels it loaded, i.e. K times per element.  Here a thread loads and
-// transforms only ITS OWN pixel of a row (plus one halo pixel for the first K - S threads), parks the
-// fp32 result in a two-row LDS ring, and after one workgroup barrier per row reads the K neighbours back
-// from LDS (conflict-free: consecutive lanes = consecutive channels).  Global loads stay two rows ahead of
-// the barrier, so the HBM latency is still covered by the march; VALU work per element drops from
-// K*(act) + K*K to act + K*K and the L1 traffic from K to 1 load per element.
-template <int CPT> __device__ __forceinline__ void lds_put(float* p, const float x[CPT]);
-template <> __device__ __forceinline__ void lds_put<4>(float* p, const float x[4]) {
-  *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-}
-template <> __device__ __forceinline__ void lds_put<2>(float* p, const float x[2]) {
-  *reinterpret_cast<float2*>(p) = make_float2(x[0], x[1]);
-}
-template <> __device__ __forceinline__ void lds_put<8>(float* p, const float x[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(x[4], x[5], x[6], x[7]);
-}
-template <int CPT> __device__ __forceinline__ void lds_get(const float* p, float x[CPT]);
-template <> __device__ __forceinline__ void lds_get<8>(const float* p, float x[8]) {
-  const float4 u = *reinterpret_cast<const float4*>(p);
-  const float4 v = *reinterpret_cast<const float4*>(p + 4);
-  x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = v.x; x[5] = v.y; x[6] = v.z; x[7] = v.w;
-}
-template <> __device__ __forceinline__ void lds_get<4>(const float* p, float x[4]) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-}
-template <> __device__ __forceinline__ void lds_get<2>(const float* p, float x[2]) {
-  const float2 v = *reinterpret_cast<const float2*>(p);
-  x[0] = v.x; x[1] = v.y;
-}
-
 // floats of LDS in front of the row ring (block_channel_sums scratch)
 __host__ __device__ inline int red_floats(int nch, int cpt) { return THREADS * cpt + THREADS; }
 
-// PF = rows of global loads in flight per thread ahead of the row being consumed (register FIFO).  With two
-// rows the march was latency-bound: a row step (~0.3 us of work) had to wait for a load issued only two
-// steps earlier (HBM latency under load ~2 us).
-// r02j lab: deeper forward FIFOs (8-9 rows at stride 1, 6 at stride 2) are slower (4.79 -> 5.24 ms over the 15 layer
-// shapes: they cost the fourth wave per SIMD), and so are stride-2 gradient kernels with 3-6 rows in flight at two
-// waves per SIMD (11.05 -> 11.29 ms).
+// Rows of global loads in flight per thread ahead of the row being consumed (register FIFO) in the two _lx kernels.  With
+// two rows the march was latency-bound: a row step (~0.3 us of work) had to wait for a load issued only two steps earlier
+// (HBM latency under load ~2 us).
+// r02j lab: stride-2 gradient kernels with 3-6 rows in flight at two waves per SIMD are slower (11.05 -> 11.29 ms over the
+// 15 layer shapes).
 template <int S, int CPT> struct PfDepth {
-  static constexpr int fwd = CPT == 8 ? 3 : (S == 1 ? 6 : 4);
   static constexpr int bwd = CPT == 4 ? (S == 1 ? 4 : 2) : (S == 1 ? 6 : 3);   // register budget of the 3-wave kernels
   static constexpr int dgrad = CPT == 4 ? (S == 1 ? 3 : 1) : (S == 1 ? 6 : 3);
 };
 
-__host__ __device__ constexpr int gcd_(int x, int y) { return y == 0 ? x : gcd_(y, x % y); }
-
-// weight gradient with the activated input row exchanged through LDS (see k_fwd_v2); dy is the thread's own
-// column, so its BatchNorm backward was already applied once per element.
+// =====================================================================================================
+// The separate gradients (edet_dw_bwd_weight, edet_dw_bwd_data; edet_dw_bwd runs k_bwd_one below).
+//
+// weight gradient with the activated input row exchanged through LDS (the march of k_fwd_v2); dy is the thread's own
+// column, so its BatchNorm backward is applied once per element.
 template <int K, int S, int CPT, bool GBN, bool OACT>
 __global__ __launch_bounds__(THREADS) void k_wgrad_lx(const Args a) {
   constexpr int PF = PfDepth<S, CPT>::bwd;          // input rows in flight
@@ -628,10 +606,11 @@ __global__ __launch_bounds__(THREADS, 3) void k_dgrad_lx(const Args a) {
 
 // =====================================================================================================
 // One-pass backward for ANY stride (round 6): data gradient AND weight gradient from a single read of (dz, y, x).
-// Round 5 ran the stride-2 layers as k_dgrad_lx + k_wgrad_lx -- two marches over the same three tensors (320x320x96:
-// 7.6 GB fetched by each) -- and the stride-1 fused kernel above spent two thirds of its VALU slots outside the
-// multiply-adds (r06 ISA count of k_bwd_fused<5, 2>: 172 VALU instructions per row step for 50 packed FMAs: 64-bit
-// address arithmetic per load, 38 register moves feeding badly paired v_pk_fma_f32, cndmask chains).  This kernel:
+// Before it a layer's backward was k_dgrad_lx + k_wgrad_lx (and at stride 1 an earlier fused kernel): two marches over
+// the same three tensors (320x320x96: 7.6 GB fetched by each), and kernels that spent two thirds of their VALU slots
+// outside the multiply-adds (r06 ISA count of that fused kernel at k = 5, two channels: 172 VALU instructions per row
+// step for 50 packed FMAs: 64-bit address arithmetic per load, 38 register moves feeding badly paired v_pk_fma_f32,
+// cndmask chains).  This kernel:
 //   * thread = dy column q x CPT channels, marches over the dy rows oy (as k_dgrad_lx): the transformed dy row goes
 //     through the LDS ring, the D = ceil(K / S) column neighbours dy[oy][q - d] come back after one barrier;
 //   * the thread's OWN S input columns ix = q S + u - pad_l are kept as a K-row register window of act(z) (weight
@@ -645,72 +624,11 @@ __global__ __launch_bounds__(THREADS, 3) void k_dgrad_lx(const Args a) {
 // Window slots are rows modulo K (a row leaves in the step before the row K later enters); the row loop is unrolled
 // over lcm(K, NF) steps so that slots and the load FIFO are static register indices.  x pixels outside the tile enter
 // the window as zeros: every (x pixel, dy pixel) pair is counted by exactly one tile.
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-template <int NV> struct RawV { uint32_t u[NV]; };
-// Raw buffer access: address = descriptor base (4 SGPRs, uniform: the image) + soff (SGPR, uniform: the row) + voff (one
-// VGPR, the thread's column / channel offset, constant over a tile) -- no VALU address arithmetic per load.  (Plain
-// pointers did not get there: the compiler widened the hoisted 32-bit offsets to 64-bit VGPR pairs and added the row
-// pointer on the VALU, two to four instructions per load.)  num_records = 2^31 - 1: the range check is not used,
-// rows and columns are clamped by the caller.
-typedef __amdgpu_buffer_rsrc_t brsrc_t;
-__device__ __forceinline__ brsrc_t make_rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-template <int NV> __device__ __forceinline__ RawV<NV> ldg(brsrc_t r, uint32_t voff, uint32_t soff);
-template <> __device__ __forceinline__ RawV<1> ldg<1>(brsrc_t r, uint32_t voff, uint32_t soff) {
-  RawV<1> v; v.u[0] = __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0); return v;
-}
-template <> __device__ __forceinline__ RawV<2> ldg<2>(brsrc_t r, uint32_t voff, uint32_t soff) {
-  const auto t = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
-  RawV<2> v; v.u[0] = t[0]; v.u[1] = t[1]; return v;
-}
-template <int NV> __device__ __forceinline__ void unpackv(const RawV<NV>& r, f2 (&x)[NV]) {
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    x[i].x = __uint_as_float(r.u[i] << 16);
-    x[i].y = __uint_as_float(r.u[i] & 0xffff0000u);
-  }
-}
-template <int NV> __device__ __forceinline__ void stg(brsrc_t r, uint32_t voff, uint32_t soff, const f2 (&x)[NV]);
-template <> __device__ __forceinline__ void stg<1>(brsrc_t r, uint32_t voff, uint32_t soff, const f2 (&x)[1]) {
-  __builtin_amdgcn_raw_buffer_store_b32(pack2bf(x[0].x, x[0].y), r, voff, soff, 0);
-}
-template <> __device__ __forceinline__ void stg<2>(brsrc_t r, uint32_t voff, uint32_t soff, const f2 (&x)[2]) {
-  typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-  u2 o; o[0] = pack2bf(x[0].x, x[0].y); o[1] = pack2bf(x[1].x, x[1].y);
-  __builtin_amdgcn_raw_buffer_store_b64(o, r, voff, soff, 0);
-}
-template <int NV> __device__ __forceinline__ void lds_putv(float* p, const f2 (&x)[NV]);
-template <> __device__ __forceinline__ void lds_putv<1>(float* p, const f2 (&x)[1]) { *reinterpret_cast<f2*>(p) = x[0]; }
-template <> __device__ __forceinline__ void lds_putv<2>(float* p, const f2 (&x)[2]) {
-  *reinterpret_cast<float4*>(p) = make_float4(x[0].x, x[0].y, x[1].x, x[1].y);
-}
-template <int NV> __device__ __forceinline__ void lds_getv(const float* p, f2 (&x)[NV]);
-template <> __device__ __forceinline__ void lds_getv<1>(const float* p, f2 (&x)[1]) { x[0] = *reinterpret_cast<const f2*>(p); }
-template <> __device__ __forceinline__ void lds_getv<2>(const float* p, f2 (&x)[2]) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  x[0].x = v.x; x[0].y = v.y; x[1].x = v.z; x[1].y = v.w;
-}
-template <int NV> __device__ __forceinline__ void loadv(const float* p, f2 (&x)[NV]) {
-#pragma unroll
-  for (int i = 0; i < NV; ++i) x[i] = *reinterpret_cast<const f2*>(p + 2 * i);
-}
 
 // load FIFO depth (register sets) of k_bwd_one.  r06 lab: twice the depth changes nothing (7.97 -> 7.87 ms over the 15
 // layer shapes) -- these kernels are bound by instruction issue at two waves per SIMD, not by bytes in flight.
 template <int K, int S, int CPT> struct OneDepth {
   static constexpr int nf = K == 3 ? ((CPT == 4 || S == 2) ? 3 : 6) : 5;
-};
-
-// floor(a / b), b > 0
-__host__ __device__ constexpr int fdiv_(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-__host__ __device__ constexpr int cdiv_(int a, int b) { return -fdiv_(-a, b); }
-// a uniform "lo <= v < lo + span" as one unsigned compare
-struct URange {
-  int lo; uint32_t span;
-  __device__ __forceinline__ void set(int l, int h) { lo = l; span = h > l ? (uint32_t)(h - l) : 0u; }
-  __device__ __forceinline__ bool has(int v) const { return (uint32_t)(v - lo) < span; }
 };
 
 // ACTM: activation of the input view -- 0 none (a stored tensor), 1 swish, 2 relu / relu6 / hswish / mish / srelu
@@ -832,7 +750,6 @@ __global__ __launch_bounds__(THREADS, (CPT * K >= 10 || S == 2) ? 2 : 3) void k_
 #pragma unroll
       for (int tt = 0; tt < U; ++tt) {
         const int oy = ob + tt;
-        constexpr int dummy_ = 0; (void)dummy_;
         const int fc = tt % NF, fn = (tt + PF) % NF;
         load_step(oy + PF, fz[fn], fy[GBN ? fn : 0], fhz[fn], fhy[GBN ? fn : 0], fx[fn]);
         // ---- S new input rows enter the window
@@ -980,8 +897,8 @@ __global__ __launch_bounds__(THREADS, (CPT * K >= 10 || S == 2) ? 2 : 3) void k_
 }
 
 // =====================================================================================================
-// Forward, round 6: the round-2..5 kernel (k_fwd_lx) rewritten with the instruction economy of k_bwd_one (the r05 counters show the forward
-// kernels 29-37 % issue-stalled at four waves per SIMD): raw buffer loads (uniform row offset + a per-thread byte
+// Forward (round 6): the earlier forward kernel rewritten with the instruction economy of k_bwd_one (the r05 counters showed it
+// 29-37 % issue-stalled at four waves per SIMD): raw buffer loads (uniform row offset + a per-thread byte
 // offset that is constant over a tile), 2-vectors of adjacent channels, the uniform row conditions as ranges of the
 // step index, all K neighbour reads of a step in front of its multiply-adds.  Same march: thread = output column x
 // CPT channels over the input rows t = r + pad_t of its tile, ceil(K / S) output rows in flight.
@@ -1086,7 +1003,6 @@ __global__ __launch_bounds__(THREADS, (K == 3 && CPT == 2) ? 6 : 4) void k_fwd_v
 #pragma unroll
       for (int tt = 0; tt < U; ++tt) {
         const int t = tb + tt;
-        constexpr int dummy_ = 0; (void)dummy_;
         load_row(t + PF, fm[(tt + PF) % NF], fh[(tt + PF) % NF]);
         const bool row_ok = row_rng.has(t);          // uniform
         float* buf = ring + (t & 1) * WIN * width;
@@ -1171,31 +1087,37 @@ inline void xcd_map(Args& a) {
   if (a.xcd) a.P -= a.P % 8;
 }
 
-// space_w / space_h: extent of the marched tile space (output pixels; for dgrad the q / oy step space)
-template <int CPT>
-inline void plan(Args& a, int C, int n, int space_w, int space_h, int max_p, int k, int slack_h = 0, int p_small = 2048) {
-  const int nvec = (C + CPT - 1) / CPT;
+// what every launch starts from: the input view and the 'SAME' geometry of a k x k convolution with stride s over it
+inline void fill_args(Args& a, const edet_tview_t* in, int k, int s) {
+  memset(&a, 0, sizeof(a));
+  a.in = *in;
+  a.oh = same_out(in->h, s); a.ow = same_out(in->w, s);
+  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
+}
+
+// partial rows of k*k*c floats that the weight-gradient workspace holds, at most EDET_MAX_PARTS; 0 = no room
+inline int ws_max_p(size_t workspace_bytes, int64_t kkc) {
+  const int64_t rows = (int64_t)(workspace_bytes / sizeof(float)) / kkc;
+  return (int)(rows < EDET_MAX_PARTS ? rows : EDET_MAX_PARTS);
+}
+
+// the step space of the kernels that march over dy (k_dgrad_lx, k_bwd_one): columns q and rows oy whose taps reach the map
+inline int q_extent(int size, int pad, int s) { return (size + pad + s - 1) / s; }
+
+// Tiles, channel groups and tile slots of a launch with `cpt` channels per thread.
+// space_w / space_h: extent of the marched tile space (output pixels; for the marches over dy the q / oy step space)
+inline void plan(Args& a, int cpt, int space_w, int space_h, int max_p, int k, int slack_h = 0, int p_small = 2048) {
+  const int nvec = (a.in.c + cpt - 1) / cpt;
   // <= 128 contiguous bytes per pixel and workgroup.  (r02t lab: 64- or 32-byte channel groups for the two-channel
   // kernels -- wider column tiles, half the column halo -- are slower: backward 11.04 -> 11.40 / 12.01 ms, forward
   // 4.77 -> 4.87 / 5.01 ms over the 15 layer shapes.)
-  a.nch = pick_nch(nvec, 128 / (CPT * 2));
+  a.nch = pick_nch(nvec, 128 / (cpt * 2));
   a.ngroups = (nvec + a.nch - 1) / a.nch;
   a.TX = THREADS / a.nch;
-  {
-    // Balanced row tiles: at most 80 rows on the 160 / 320-row maps, 40 below (fixed 32-row tiles left a short last
-    // tile that still pays the K - 1 halo rows and the pipeline fill; taller tiles than this leave the 80-row maps
-    // with too few tiles to fill the chip).  r02i / r02j lab, 15 depthwise layer shapes of D0 640x640 batch 128:
-    // backward 12.08 -> 11.49 (40) -> 10.81 ms (80), forward 5.08 -> 4.71 -> 4.59 ms.
-    // slack_h: rows of the marched space beyond the map (the padding rows of k_bwd_one's shifted row space) that must
-    // not cost an extra tile
-    const int cap = space_h >= 160 ? 80 : 40;
-    const int nt = max(1, (space_h - slack_h + cap - 1) / cap);
-    a.TY = (space_h + nt - 1) / nt;
-  }
-  if (a.TY > space_h) a.TY = space_h;
+  a.TY = dw_row_tile(space_h, slack_h);
   a.tiles_x = (space_w + a.TX - 1) / a.TX;
   a.tiles_y = (space_h + a.TY - 1) / a.TY;
-  a.ntiles = n * a.tiles_x * a.tiles_y;
+  a.ntiles = a.in.n * a.tiles_x * a.tiles_y;
   // Persistent workgroups x channel groups.  r03d lab (targets of 4096 / 2048 / 8192 workgroups, the 15 depthwise layer
   // shapes of D0 640x640 batch 128): the 3x3 layers on the 160 / 320-row maps want many short-lived
   // workgroups (8192: 320x320x32 fused backward 1.00 -> 0.86 ms, forward 0.61 -> 0.52 ms), every other layer fewer,
@@ -1211,85 +1133,112 @@ inline void plan(Args& a, int C, int n, int space_w, int space_h, int max_p, int
   xcd_map(a);
 }
 
+// Dynamic LDS of a planned launch: the scratch of block_channel_sums, then the two-row ring.  Its window is, for the
+// marches over the input rows (k_fwd_v2, k_wgrad_lx), the TX * S input columns of the tile and the K - S halo columns;
+// for the marches over dy (k_dgrad_lx, k_bwd_one), the TX dy columns and the ceil(K / S) - 1 halo columns.
+inline size_t ring_bytes(const Args& a, int win, int cpt) { return (size_t)2 * win * a.nch * cpt * sizeof(float); }
+inline size_t lds_in_march(const Args& a, int k, int s, int cpt) {
+  return (size_t)red_floats(a.nch, cpt) * sizeof(float) + ring_bytes(a, a.TX * s + k - s, cpt);
+}
+inline size_t lds_dy_march(const Args& a, int k, int s, int cpt) {
+  return (size_t)red_floats(a.nch, cpt) * sizeof(float) + ring_bytes(a, a.TX + (k + s - 1) / s - 1, cpt);
+}
+
+// One (K, S, CPT) variant of a kernel family with its instantiations over the family's remaining template switches:
+// kern[0][ACTM] for k_fwd_v2, kern[GBN][OACT] for k_wgrad_lx / k_dgrad_lx, kern[GBN][ACTM] for k_bwd_one
+// (GBN: BatchNorm backward on dy; OACT: relu / relu6 / hswish view; ACTM: 0 no activation, 1 swish, 2 the OACT family).
+// The four tables below name every instantiation of this file, each once.
+typedef void (*kern_t)(const Args);
+struct Variant { int k, s, cpt; kern_t kern[2][3]; };
+template <int K, int S, int CPT> Variant fwd_variant() {
+  return {K, S, CPT, {{k_fwd_v2<K, S, CPT, 0>, k_fwd_v2<K, S, CPT, 1>, k_fwd_v2<K, S, CPT, 2>}, {nullptr, nullptr, nullptr}}};
+}
+template <int K, int S, int CPT> Variant wgrad_variant() {
+  return {K, S, CPT, {{k_wgrad_lx<K, S, CPT, false, false>, k_wgrad_lx<K, S, CPT, false, true>, nullptr},
+                      {k_wgrad_lx<K, S, CPT, true, false>, k_wgrad_lx<K, S, CPT, true, true>, nullptr}}};
+}
+template <int K, int S, int CPT> Variant dgrad_variant() {
+  return {K, S, CPT, {{k_dgrad_lx<K, S, CPT, false, false>, k_dgrad_lx<K, S, CPT, false, true>, nullptr},
+                      {k_dgrad_lx<K, S, CPT, true, false>, k_dgrad_lx<K, S, CPT, true, true>, nullptr}}};
+}
+template <int K, int S, int CPT> Variant one_variant() {
+  return {K, S, CPT, {{k_bwd_one<K, S, CPT, false, 0>, k_bwd_one<K, S, CPT, false, 1>, k_bwd_one<K, S, CPT, false, 2>},
+                      {k_bwd_one<K, S, CPT, true, 0>, k_bwd_one<K, S, CPT, true, 1>, k_bwd_one<K, S, CPT, true, 2>}}};
+}
+static const Variant fwd_variants[] = {fwd_variant<3, 1, 2>(), fwd_variant<3, 2, 2>(), fwd_variant<3, 1, 4>(),
+                                       fwd_variant<3, 2, 4>(), fwd_variant<5, 1, 2>(), fwd_variant<5, 2, 2>()};
+static const Variant wgrad_variants[] = {wgrad_variant<3, 1, 4>(), wgrad_variant<3, 2, 2>(), wgrad_variant<3, 2, 4>(),
+                                         wgrad_variant<5, 1, 2>(), wgrad_variant<5, 2, 2>()};
+static const Variant dgrad_variants[] = {dgrad_variant<3, 1, 4>(), dgrad_variant<3, 2, 2>(), dgrad_variant<3, 2, 4>(),
+                                         dgrad_variant<5, 1, 2>(), dgrad_variant<5, 2, 2>()};
+static const Variant one_variants[] = {one_variant<3, 1, 4>(), one_variant<3, 1, 2>(), one_variant<3, 2, 2>(),
+                                       one_variant<5, 1, 2>(), one_variant<5, 2, 2>()};
+
+// the variant of a table for (k, s, cpt); NULL: the family has no kernel for it
+template <int N> inline const Variant* find_variant(const Variant (&tab)[N], int k, int s, int cpt) {
+  for (const Variant& v : tab)
+    if (v.k == k && v.s == s && v.cpt == cpt) return &v;
+  return nullptr;
+}
+
+inline void launch(kern_t kern, const Args& a, size_t lds, hipStream_t st) {
+  edet_launch(kern, dim3(a.P * a.ngroups), dim3(THREADS), lds, st, a);
+}
+
+// ACTM of a view's activation code
+inline int actm_of(int act) { return act == EDET_ACT_NONE ? 0 : (act == EDET_ACT_SWISH ? 1 : 2); }
+
+// Channels per thread, (k, s, map) -> CPT.  5x5: always two (with the 25 weights per channel in registers that keeps the
+// kernels near 100 VGPRs).  3x3, by the map and not by the batch (the parity runs launch what the batch-128 step launches):
+// forward: four channels per thread on the large maps, two (six rows of loads in flight, more waves) from 40 x 40 OUTPUT
+// pixels down -- r04 lab, D0 640x640 batch 128: 40x40x64 0.0340 (4) / 0.0278 ms (2), 40x40x480 0.162 / 0.140, 80x80x240
+// stride 2 0.166 / 0.142, 20x20x1152 0.097 / 0.089, but 80x80x64 0.057 / 0.068 and 320x320x32 0.43 / 0.56.
+inline int fwd_cpt(int k, int out_pixels) { return (k == 3 && out_pixels > 40 * 40) ? 4 : 2; }
+// separate gradient kernels, stride 1: four.  Stride 2: 4 on the large maps, 2 (deeper load FIFO, more waves) up to
+// 80 x 80 input pixels -- r04 lab, D0 640x640 batch 128, data + weight gradient: 320x320x96 2.55 (4) / 2.77 ms (2),
+// 80x80x240 0.529 (4) / 0.460 ms (2).
+inline int lx_cpt(int k, int s, int in_pixels) { return (k == 3 && (s == 1 || in_pixels > 80 * 80)) ? 4 : 2; }
+// one-pass backward, stride 1: 4 channels per thread (8-byte loads, 2 waves/SIMD) wins on the large maps, 2 channels per
+// thread (3-4 waves/SIMD) on the small ones (r02: 320x320x32 1.08 vs 1.55 ms, 40x40x64 1.25 vs 1.05 ms; r04, 64 channels:
+// 80x80 0.147 (2) -> 0.137 ms (4), 40x40 0.0485 -> 0.0480 with the threshold at 80x80, 0.057 with 4 channels there too).
+// Stride 2: two.
+inline int one_cpt(int k, int s, int64_t in_pixels) { return (k == 3 && s == 1 && in_pixels >= 80 * 80) ? 4 : 2; }
+
 }  // namespace dwm
 
-// return 1 = handled, 0 = not applicable (caller falls back), < 0 = error
+// The four entry points (declared in dw_impl.h): 1 = handled, 0 = not applicable (nothing launched), < 0 = error.
 int dwm_try_fwd(const edet_tview_t* in, const float* weight, int k, int s, void* out, int ldo,
                 float* stat_partials, int* nparts_out, hipStream_t st) {
   using namespace dwm;
   if (in->gate || in->c % 8 != 0) return 0;
   Args a;
-  memset(&a, 0, sizeof(a));
-  a.in = *in; a.w = weight; a.out = reinterpret_cast<bf16_t*>(out); a.ldo = ldo; a.stat_partials = stat_partials;
-  a.oh = same_out(in->h, s); a.ow = same_out(in->w, s);
-  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
+  fill_args(a, in, k, s);
+  a.w = weight; a.out = reinterpret_cast<bf16_t*>(out); a.ldo = ldo; a.stat_partials = stat_partials;
   // the kernel's 32-bit offsets inside one image
   if ((int64_t)in->h * in->w * in->ld * 2 >= 0x7fffffffLL || (int64_t)a.oh * a.ow * ldo * 2 >= 0x7fffffffLL) return 0;
-  // 3x3: four channels per thread on the large maps, two (six rows of loads in flight, more waves) from 40 x 40 OUTPUT
-  // pixels down -- r04 lab, D0 640x640 batch 128: 40x40x64 0.0340 (4) / 0.0278 ms (2), 40x40x480 0.162 / 0.140, 80x80x240
-  // stride 2 0.166 / 0.142, 20x20x1152 0.097 / 0.089, but 80x80x64 0.057 / 0.068 and 320x320x32 0.43 / 0.56.  By the map,
-  // not the batch.
-  const bool c2 = a.oh * a.ow <= 40 * 40;
-  const int actm = in->act == EDET_ACT_NONE ? 0 : (in->act == EDET_ACT_SWISH ? 1 : 2);
-#define DWM_FWD2(K_, S_, CPT_)                                                            \
-  do {                                                                                    \
-    plan<CPT_>(a, in->c, in->n, a.ow, a.oh, EDET_MAX_PARTS, K_, 0, 4096);                 \
-    const size_t lds0 = (size_t)red_floats(a.nch, CPT_) * sizeof(float);                  \
-    const size_t ring = (size_t)2 * (a.TX * S_ + K_ - S_) * a.nch * CPT_ * sizeof(float); \
-    const dim3 grid(a.P * a.ngroups), block(THREADS);                                     \
-    if (actm == 0) edet_launch(k_fwd_v2<K_, S_, CPT_, 0>, grid, block, lds0 + ring, st, a);      \
-    else if (actm == 1) edet_launch(k_fwd_v2<K_, S_, CPT_, 1>, grid, block, lds0 + ring, st, a); \
-    else edet_launch(k_fwd_v2<K_, S_, CPT_, 2>, grid, block, lds0 + ring, st, a);                \
-  } while (0)
-  if (k == 3 && s == 1 && c2) DWM_FWD2(3, 1, 2);
-  else if (k == 3 && s == 2 && c2) DWM_FWD2(3, 2, 2);
-  else if (k == 3 && s == 1) DWM_FWD2(3, 1, 4);
-  else if (k == 3 && s == 2) DWM_FWD2(3, 2, 4);
-  else if (k == 5 && s == 1) DWM_FWD2(5, 1, 2);
-  else if (k == 5 && s == 2) DWM_FWD2(5, 2, 2);
-  else return 0;
-#undef DWM_FWD2
+  const Variant* v = find_variant(fwd_variants, k, s, fwd_cpt(k, a.oh * a.ow));
+  if (!v) return 0;
+  plan(a, v->cpt, a.ow, a.oh, EDET_MAX_PARTS, k, 0, 4096);
+  launch(v->kern[0][actm_of(in->act)], a, lds_in_march(a, k, s, v->cpt), st);
   if (nparts_out) *nparts_out = a.P;
   EDET_LAUNCH_CHECK("edet_dw_fwd(march)");
   return 1;
 }
-
-// channels per thread of the 3x3 stride-2 gradient kernels: 4 on the large maps, 2 (deeper load FIFO, more waves) up to
-// 80 x 80 input pixels -- r04 lab, D0 640x640 batch 128, data + weight gradient: 320x320x96 2.55 (4) / 2.77 ms (2),
-// 80x80x240 0.529 (4) / 0.460 ms (2).  By the map, not the batch (the parity runs launch what the batch-128 step launches).
-static int s2_cpt(int hw) { return hw > 80 * 80 ? 4 : 2; }
 
 int dwm_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, int k, int s, float* dweight, void* workspace,
                   size_t workspace_bytes, hipStream_t st) {
   using namespace dwm;
   if (in->gate || in->c % 8 != 0 || !workspace) return 0;
   Args a;
-  memset(&a, 0, sizeof(a));
-  const bool oact = in->act > EDET_ACT_SWISH;      // relu / relu6 / hswish: the OACT instantiations
-  a.in = *in; a.gy = *dy; a.ws = reinterpret_cast<float*>(workspace);
-  a.oh = same_out(in->h, s); a.ow = same_out(in->w, s);
-  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
+  fill_args(a, in, k, s);
+  a.gy = *dy; a.ws = reinterpret_cast<float*>(workspace);
   const int64_t kkc = (int64_t)k * k * in->c;
-  int max_p = (int)((int64_t)(workspace_bytes / sizeof(float)) / kkc);
+  const int max_p = ws_max_p(workspace_bytes, kkc);
   if (max_p < 1) return 0;
-  if (max_p > 1024) max_p = 1024;
-  const bool gbn = dy->a != nullptr;
-#define DWM_WG(K_, S_, CPT_)                                                              \
-  do {                                                                                    \
-    plan<CPT_>(a, in->c, in->n, a.ow, a.oh, max_p, K_);                                   \
-    const size_t lds = (size_t)red_floats(a.nch, CPT_) * sizeof(float);                   \
-    const size_t ring = (size_t)2 * (a.TX * S_ + K_ - S_) * a.nch * CPT_ * sizeof(float); \
-    const dim3 grid(a.P * a.ngroups), block(THREADS);                                     \
-    if (gbn) { if (oact) edet_launch(k_wgrad_lx<K_, S_, CPT_, true, true>, grid, block, lds + ring, st, a); else edet_launch(k_wgrad_lx<K_, S_, CPT_, true, false>, grid, block, lds + ring, st, a); }          \
-    else { if (oact) edet_launch(k_wgrad_lx<K_, S_, CPT_, false, true>, grid, block, lds + ring, st, a); else edet_launch(k_wgrad_lx<K_, S_, CPT_, false, false>, grid, block, lds + ring, st, a); }             \
-  } while (0)
-  if (k == 3 && s == 1) DWM_WG(3, 1, 4);
-  else if (k == 3 && s == 2 && s2_cpt(in->h * in->w) == 2) DWM_WG(3, 2, 2);
-  else if (k == 3 && s == 2) DWM_WG(3, 2, 4);
-  else if (k == 5 && s == 1) DWM_WG(5, 1, 2);
-  else if (k == 5 && s == 2) DWM_WG(5, 2, 2);
-  else return 0;
-#undef DWM_WG
+  const Variant* v = find_variant(wgrad_variants, k, s, lx_cpt(k, s, in->h * in->w));
+  if (!v) return 0;
+  plan(a, v->cpt, a.ow, a.oh, max_p, k);
+  launch(v->kern[dy->a != nullptr][in->act > EDET_ACT_SWISH], a, lds_in_march(a, k, s, v->cpt), st);
   EDET_LAUNCH_CHECK("edet_dw_bwd_weight(march)");
   if (edet_reduce_partials(a.ws, a.P, kkc, dweight, st) != 0) return -2;
   return 1;
@@ -1300,84 +1249,36 @@ int dwm_try_dgrad(const edet_gview_t* dy, const float* weight, int k, int s, con
   using namespace dwm;
   if (in->gate || epi->dgate || in->c % 8 != 0) return 0;
   Args a;
-  memset(&a, 0, sizeof(a));
-  const bool oact = in->act > EDET_ACT_SWISH;      // relu / relu6 / hswish: the OACT instantiations
-  a.in = *in; a.gy = *dy; a.w = weight; a.epi = *epi;
-  a.oh = same_out(in->h, s); a.ow = same_out(in->w, s);
-  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
-  const int QW = (in->w + a.pad_l + s - 1) / s, QH = (in->h + a.pad_t + s - 1) / s;
-  const bool gbn = dy->a != nullptr;
-#define DWM_DG(K_, S_, CPT_)                                                              \
-  do {                                                                                    \
-    plan<CPT_>(a, in->c, in->n, QW, QH, EDET_MAX_PARTS, K_);                              \
-    const size_t lds = (size_t)red_floats(a.nch, CPT_) * sizeof(float);                   \
-    const size_t ring = (size_t)2 * (a.TX + (K_ + S_ - 1) / S_ - 1) * a.nch * CPT_ * sizeof(float); \
-    const dim3 grid(a.P * a.ngroups), block(THREADS);                                     \
-    if (gbn) { if (oact) edet_launch(k_dgrad_lx<K_, S_, CPT_, true, true>, grid, block, lds + ring, st, a); else edet_launch(k_dgrad_lx<K_, S_, CPT_, true, false>, grid, block, lds + ring, st, a); }          \
-    else { if (oact) edet_launch(k_dgrad_lx<K_, S_, CPT_, false, true>, grid, block, lds + ring, st, a); else edet_launch(k_dgrad_lx<K_, S_, CPT_, false, false>, grid, block, lds + ring, st, a); }             \
-  } while (0)
-  if (k == 3 && s == 1) DWM_DG(3, 1, 4);
-  else if (k == 3 && s == 2 && s2_cpt(in->h * in->w) == 2) DWM_DG(3, 2, 2);
-  else if (k == 3 && s == 2) DWM_DG(3, 2, 4);
-  else if (k == 5 && s == 1) DWM_DG(5, 1, 2);
-  else if (k == 5 && s == 2) DWM_DG(5, 2, 2);
-  else return 0;
-#undef DWM_DG
+  fill_args(a, in, k, s);
+  a.gy = *dy; a.w = weight; a.epi = *epi;
+  const Variant* v = find_variant(dgrad_variants, k, s, lx_cpt(k, s, in->h * in->w));
+  if (!v) return 0;
+  plan(a, v->cpt, q_extent(in->w, a.pad_l, s), q_extent(in->h, a.pad_t, s), EDET_MAX_PARTS, k);
+  launch(v->kern[dy->a != nullptr][in->act > EDET_ACT_SWISH], a, lds_dy_march(a, k, s, v->cpt), st);
   if (nparts_out) *nparts_out = a.P;
   EDET_LAUNCH_CHECK("edet_dw_bwd_data(march)");
   return 1;
 }
 
-// data + weight gradient in one pass (k_bwd_one, any stride): 1 = handled, 0 = not applicable (the caller runs the two
-// separate kernels)
 int dwm_try_bwd_fused(const edet_gview_t* dy, const float* weight, int k, int s, const edet_tview_t* in,
                       const edet_bwd_epi_t* epi, int* nparts_out, float* dweight, void* workspace,
                       size_t workspace_bytes, hipStream_t st) {
   using namespace dwm;
-  // k = 3, stride 1: 4 channels per thread (8-byte loads, 2 waves/SIMD) wins on the large maps, 2 channels per thread
-  // (3-4 waves/SIMD) on the small ones (r02: 320x320x32 1.08 vs 1.55 ms, 40x40x64 1.25 vs 1.05 ms; r04, 64 channels:
-  // 80x80 0.147 (2) -> 0.137 ms (4), 40x40 0.0485 -> 0.0480 with the threshold at 80x80, 0.057 with 4 channels there too)
-  const bool k3c4 = (int64_t)in->h * in->w >= 80 * 80;
-  if ((s != 1 && s != 2) || (k != 3 && k != 5) || in->gate || epi->dgate || in->c % 8 != 0 || !workspace) return 0;
+  if (in->gate || epi->dgate || in->c % 8 != 0 || !workspace) return 0;
   if ((int64_t)in->h * in->w * in->ld * 2 >= 0x7fffffffLL) return 0;      // the kernel's 32-bit offsets inside one image
+  const Variant* v = find_variant(one_variants, k, s, one_cpt(k, s, (int64_t)in->h * in->w));
+  if (!v) return 0;
   Args a;
-  memset(&a, 0, sizeof(a));
-  a.in = *in; a.gy = *dy; a.w = weight; a.epi = *epi; a.ws = reinterpret_cast<float*>(workspace);
-  a.oh = same_out(in->h, s); a.ow = same_out(in->w, s);
-  a.pad_t = same_pad_before(in->h, k, s); a.pad_l = same_pad_before(in->w, k, s);
+  fill_args(a, in, k, s);
+  a.gy = *dy; a.w = weight; a.epi = *epi; a.ws = reinterpret_cast<float*>(workspace);
   const int64_t kkc = (int64_t)k * k * in->c;
-  int max_p = (int)((int64_t)(workspace_bytes / sizeof(float)) / kkc);
+  const int max_p = ws_max_p(workspace_bytes, kkc);
   if (max_p < 1) return 0;
-  if (max_p > EDET_MAX_PARTS) max_p = EDET_MAX_PARTS;
-  const bool gbn = dy->a != nullptr;
-  {
-    const int QW = (in->w + a.pad_l + s - 1) / s, QH = (in->h + a.pad_t + s - 1) / s;
-    const int actm = in->act == EDET_ACT_NONE ? 0 : (in->act == EDET_ACT_SWISH ? 1 : 2);
-#define DWM_ONE(K_, S_, CPT_)                                                             \
-  do {                                                                                    \
-    plan<CPT_>(a, in->c, in->n, QW, QH, max_p, K_, QH - a.oh);                            \
-    const size_t lds = (size_t)red_floats(a.nch, CPT_) * sizeof(float);                   \
-    const size_t ring = (size_t)2 * (a.TX + (K_ + S_ - 1) / S_ - 1) * a.nch * CPT_ * sizeof(float); \
-    const dim3 grid(a.P * a.ngroups), block(THREADS);                                     \
-    if (gbn) {                                                                            \
-      if (actm == 0) edet_launch(k_bwd_one<K_, S_, CPT_, true, 0>, grid, block, lds + ring, st, a);      \
-      else if (actm == 1) edet_launch(k_bwd_one<K_, S_, CPT_, true, 1>, grid, block, lds + ring, st, a); \
-      else edet_launch(k_bwd_one<K_, S_, CPT_, true, 2>, grid, block, lds + ring, st, a);                \
-    } else {                                                                              \
-      if (actm == 0) edet_launch(k_bwd_one<K_, S_, CPT_, false, 0>, grid, block, lds + ring, st, a);      \
-      else if (actm == 1) edet_launch(k_bwd_one<K_, S_, CPT_, false, 1>, grid, block, lds + ring, st, a); \
-      else edet_launch(k_bwd_one<K_, S_, CPT_, false, 2>, grid, block, lds + ring, st, a);                \
-    }                                                                                     \
-  } while (0)
-    if (k == 3 && s == 1 && k3c4) DWM_ONE(3, 1, 4);
-    else if (k == 3 && s == 1) DWM_ONE(3, 1, 2);
-    else if (k == 3 && s == 2) DWM_ONE(3, 2, 2);
-    else if (k == 5 && s == 1) DWM_ONE(5, 1, 2);
-    else DWM_ONE(5, 2, 2);
-#undef DWM_ONE
-    if (nparts_out) *nparts_out = a.P;
-    EDET_LAUNCH_CHECK("edet_dw_bwd(one pass)");
-    if (edet_reduce_partials(a.ws, a.P, kkc, dweight, st) != 0) return -2;
-  }
+  const int QH = q_extent(in->h, a.pad_t, s);
+  plan(a, v->cpt, q_extent(in->w, a.pad_l, s), QH, max_p, k, QH - a.oh);
+  launch(v->kern[dy->a != nullptr][actm_of(in->act)], a, lds_dy_march(a, k, s, v->cpt), st);
+  if (nparts_out) *nparts_out = a.P;
+  EDET_LAUNCH_CHECK("edet_dw_bwd(one pass)");
+  if (edet_reduce_partials(a.ws, a.P, kkc, dweight, st) != 0) return -2;
   return 1;
 }

@@ -8,7 +8,7 @@
 //
 // Reference call sites: efficientdet/backbone/efficientnet_model.py:320-327 (MBConv depthwise),
 // efficientdet/tf2/efficientdet_keras.py:195-207,459-464,546-556 (depthwise half of SeparableConv2D).
-#include "common.h"
+#include "dw_impl.h"
 
 namespace {
 
@@ -499,18 +499,6 @@ int run(int which, int k, int s, DwArgs& a, int dtype, void* stream, int* nparts
 
 }  // namespace
 
-// bf16 row-marching kernels (dw_march.hip): 1 = handled, 0 = not applicable
-int dwm_try_fwd(const edet_tview_t* in, const float* weight, int k, int s, void* out, int ldo,
-                float* stat_partials, int* nparts_out, hipStream_t st);
-int dwm_try_wgrad(const edet_tview_t* in, const edet_gview_t* dy, int k, int s, float* dweight, void* workspace,
-                  size_t workspace_bytes, hipStream_t st);
-int dwm_try_dgrad(const edet_gview_t* dy, const float* weight, int k, int s, const edet_tview_t* in,
-                  const edet_bwd_epi_t* epi, int* nparts_out, hipStream_t st);
-
-int dwm_try_bwd_fused(const edet_gview_t* dy, const float* weight, int k, int s, const edet_tview_t* in,
-                      const edet_bwd_epi_t* epi, int* nparts_out, float* dweight, void* workspace,
-                      size_t workspace_bytes, hipStream_t st);
-
 extern "C" int edet_dw_fwd(const edet_tview_t* in, const float* weight, int k, int stride,
                            void* out, int ldo, float* stat_partials, int* nparts_out,
                            int dtype, void* stream) {
@@ -558,8 +546,8 @@ extern "C" int edet_dw_bwd_weight(const edet_tview_t* in, const edet_gview_t* dy
   return run(DW_BWD_WEIGHT, k, stride, a, dtype, stream, nullptr, workspace, workspace_bytes);
 }
 
-// Data gradient and weight gradient of one depthwise layer.  Stride 1, bf16: one fused kernel (dw_march.hip,
-// k_bwd_fused) that reads (dz, y, x) once; everything else: the two separate entry points, in this order.
+// Data gradient and weight gradient of one depthwise layer.  bf16, any stride: one kernel (dw_march.hip, k_bwd_one) that
+// reads (dz, y, x) once; everything else: the two separate entry points, in this order.
 extern "C" int edet_dw_bwd(const edet_gview_t* dy, const float* weight, int k, int stride,
                            const edet_tview_t* in, const edet_bwd_epi_t* epi, int* nparts_out,
                            float* dweight, void* workspace, size_t workspace_bytes, int dtype, void* stream) {

@@ -24,14 +24,14 @@
 // inference needs no such pass and never stores the expanded tensor at all.
 #include <stdlib.h>
 
-#include "common.h"
+#include "dw_impl.h"
 
 namespace mbf {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
+using namespace dwi;      // f2, make_rsrc, URange, slot_of, fdiv_, gcd_: the march's helpers
+
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t brsrc_t;
 
 constexpr int THREADS = 256; // k_exp_stats
 constexpr int GC = 48;      // expanded channels per wave: three 16-row MFMA blocks
@@ -41,18 +41,6 @@ constexpr int GC = 48;      // expanded channels per wave: three 16-row MFMA blo
 // FIFO then becomes a wait for (nearly) ALL of them, the stores of the expanded row included (r06 lab: s_waitcnt vmcnt(1)
 // in front of every store and MFMA; the training kernel took the inference kernel's time PLUS the time of its stores).
 constexpr uint32_t OOB = 0x80000000u;
-
-__device__ __forceinline__ brsrc_t make_rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-__host__ __device__ constexpr int gcd_(int x, int y) { return y == 0 ? x : gcd_(y, x % y); }
-__host__ __device__ constexpr int fdiv_(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-__host__ __device__ constexpr int slot_of(int rel, int n) { return ((rel % n) + n) % n; }
-struct URange {
-  int lo; uint32_t span;
-  __device__ __forceinline__ void set(int l, int h) { lo = l; span = h > l ? (uint32_t)(h - l) : 0u; }
-  __device__ __forceinline__ bool has(int v) const { return (uint32_t)(v - lo) < span; }
-};
 
 struct Args {
   edet_tview_t in;            // block input [n][H][W][cin]: affine view (the producer's BatchNorm) or a stored tensor
@@ -505,6 +493,34 @@ inline void pick_slots(Args& a, const void* fn, int threads, size_t lds) {
   a.P = 8 * ((t8 + rounds - 1) / rounds);
 }
 
+// One (K, S, workgroup shape) variant of k_exp_dw_fwd: what the host needs of its geometry and its four instantiations,
+// kern[ACTM - 1][STORE_E].  The table names every instantiation of the kernel once.  (The six-wave shape Sh3 -- a whole
+// pixel of 144 channels per workgroup -- lost against three Sh1 workgroups per window and the launch rule below does not
+// choose it; its instantiations stay under the spill check of tests/test_abi.py.)
+typedef void (*kern_t)(const Args);
+struct Head {
+  int k, s, ngr;              // ngr: channel groups per workgroup (Shape::NGR)
+  int nt, txv;                // threads per workgroup, output columns per window
+  size_t lds_ring, lds_stage; // ring + coefficient tables; the staged raw row (STORE_E only)
+  kern_t kern[2][2];
+};
+template <int K, int S, typename SH> Head head() {
+  return {K, S, SH::NGR, SH::NT, Geo<K, S, SH>::TXV,
+          (size_t)(2 * SH::WINC * SH::GCP + SH::TABF) * sizeof(float), (size_t)2 * SH::WINC * SH::ESTG,
+          {{k_exp_dw_fwd<K, S, 1, false, SH>, k_exp_dw_fwd<K, S, 1, true, SH>},
+           {k_exp_dw_fwd<K, S, 2, false, SH>, k_exp_dw_fwd<K, S, 2, true, SH>}}};
+}
+typedef Shape<1, 4> Sh1;
+typedef Shape<2, 2> Sh2;
+typedef Shape<3, 2> Sh3;
+static const Head heads[] = {head<3, 1, Sh1>(), head<3, 1, Sh2>(), head<3, 1, Sh3>(), head<3, 2, Sh1>(), head<3, 2, Sh2>(),
+                             head<3, 2, Sh3>(), head<5, 2, Sh1>(), head<5, 2, Sh2>(), head<5, 2, Sh3>()};
+inline const Head* find_head(int k, int s, int ngr) {
+  for (const Head& h : heads)
+    if (h.k == k && h.s == s && h.ngr == ngr) return &h;
+  return nullptr;
+}
+
 inline bool supported(const edet_tview_t* in, int cexp, int k, int s, int dtype) {
   if (dtype != EDET_BF16 || !in) return false;
   if (in->gate || in->act != EDET_ACT_NONE) return false;
@@ -582,48 +598,18 @@ extern "C" int edet_mbconv_expand_dw_fwd(const edet_tview_t* in, const void* wt,
   // fewest recomputed halo columns, no barrier across more than four waves (160x160x24->144, six-wave whole-pixel shape
   // against three workgroups per window: training 0.78 / 0.56 vs 0.64 / 0.54 ms for k3s1 / k5s2, inference 0.60 / 0.50 vs
   // 0.46 / 0.31).
-  const bool whole = se && a.ngroups == 2;
-  const int ngr = (whole && a.ngroups > 1) ? a.ngroups : 1;
+  const int ngr = (se && a.ngroups == 2) ? 2 : 1;
+  const Head* hd = find_head(k, stride, ngr);
+  EDET_CHECK(hd, "edet_mbconv_expand_dw_fwd: no kernel for k %d, stride %d", k, stride);
   a.ngb = a.ngroups / ngr;
-  const int winc = ngr == 1 ? 64 : 32;      // Shape<1,4>, Shape<2,2>, Shape<3,2>
-  const int txv = (winc - k) / stride + 1;
-  {
-    const int cap = a.oh >= 160 ? 80 : 40;
-    const int nt = (a.oh + cap - 1) / cap;
-    a.TY = (a.oh + nt - 1) / nt;
-  }
-  a.tiles_x = (a.ow + txv - 1) / txv;
+  a.TY = dw_row_tile(a.oh);
+  a.tiles_x = (a.ow + hd->txv - 1) / hd->txv;
   a.tiles_y = (a.oh + a.TY - 1) / a.TY;
   a.ntiles = in->n * a.tiles_x * a.tiles_y;
-  hipStream_t st = to_stream(stream);
-  const bool sw = act == EDET_ACT_SWISH;
-#define MBF_GO2(K_, S_, SH_)                                                                    \
-  do {                                                                                          \
-    const size_t lds = (size_t)(2 * SH_::WINC * SH_::GCP + SH_::TABF) * sizeof(float) +         \
-                       (se ? (size_t)2 * SH_::WINC * SH_::ESTG : 0);                            \
-    pick_slots(a, reinterpret_cast<const void*>(sw ? (se ? k_exp_dw_fwd<K_, S_, 1, true, SH_> : k_exp_dw_fwd<K_, S_, 1, false, SH_>) \
-                                                      : (se ? k_exp_dw_fwd<K_, S_, 2, true, SH_> : k_exp_dw_fwd<K_, S_, 2, false, SH_>)), \
-               SH_::NT, lds);                                                                   \
-    const dim3 grid(a.P * a.ngb), block(SH_::NT);                                               \
-    if (sw) { if (se) edet_launch(k_exp_dw_fwd<K_, S_, 1, true, SH_>, grid, block, lds, st, a); \
-              else edet_launch(k_exp_dw_fwd<K_, S_, 1, false, SH_>, grid, block, lds, st, a); } \
-    else { if (se) edet_launch(k_exp_dw_fwd<K_, S_, 2, true, SH_>, grid, block, lds, st, a);    \
-           else edet_launch(k_exp_dw_fwd<K_, S_, 2, false, SH_>, grid, block, lds, st, a); }    \
-  } while (0)
-  typedef Shape<1, 4> Sh1;
-  typedef Shape<2, 2> Sh2;
-  typedef Shape<3, 2> Sh3;
-#define MBF_GO(K_, S_)                                  \
-  do {                                                  \
-    if (ngr == 1) MBF_GO2(K_, S_, Sh1);                 \
-    else if (ngr == 2) MBF_GO2(K_, S_, Sh2);            \
-    else MBF_GO2(K_, S_, Sh3);                          \
-  } while (0)
-  if (k == 3 && stride == 1) MBF_GO(3, 1);
-  else if (k == 3 && stride == 2) MBF_GO(3, 2);
-  else MBF_GO(5, 2);
-#undef MBF_GO
-#undef MBF_GO2
+  kern_t kern = hd->kern[act == EDET_ACT_SWISH ? 0 : 1][se];
+  const size_t lds = hd->lds_ring + (se ? hd->lds_stage : 0);
+  pick_slots(a, reinterpret_cast<const void*>(kern), hd->nt, lds);
+  edet_launch(kern, dim3(a.P * a.ngb), dim3(hd->nt), lds, to_stream(stream), a);
   EDET_LAUNCH_CHECK("edet_mbconv_expand_dw_fwd");
   if (nparts_out) *nparts_out = a.P;
   return 0;

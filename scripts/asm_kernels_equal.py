@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""Compares two `hipcc --cuda-device-only -S` outputs of one source kernel by kernel.
+
+usage: asm_kernels_equal.py PARENT.s CHANGE.s
+
+The compiler emits the kernels of a file in the order in which the host code first names their instantiations, so a
+change that only reorders the host code's launch tables moves whole kernels in the assembly.  This script cuts both
+files into one block per kernel (its .text, kernel descriptor and resource comment sections) plus the metadata entry of
+each kernel and the rest of the file, drops the lines of the per-compilation `__hip_cuid_<hash>` symbol and the function
+ordinal from local labels and the comments that quote them (`.LBB<ordinal>_<block>`, `.Lfunc_end<ordinal>`; the comment
+column moves with the label's length), and compares the blocks by kernel name.  Prints the names that differ or exist on one side only; exit status 0 = every kernel and
+the rest of the file are identical.
+"""
+import re
+import sys
+
+SECTION = re.compile(r'^\t\.section\t\.text\.([^,]+),')
+ORDINAL = re.compile(r'(?<![A-Za-z0-9])(L?BB|Lfunc_begin|Lfunc_end)\d+')
+
+
+def cut(path):
+  lines = [re.sub(' +;', ' ;', ORDINAL.sub(r'\1', l)) for l in open(path) if '__hip_cuid_' not in l]
+  meta_at = next(i for i, l in enumerate(lines) if l.startswith('\t.amdgpu_metadata'))
+  blocks, name, cur = {}, 'HEAD', []
+  for l in lines[:meta_at]:
+    m = SECTION.match(l)
+    if m and m.group(1) != name:
+      blocks[name] = cur
+      name, cur = m.group(1), []
+    cur.append(l)
+  # what follows the last kernel (register maximums of the file, ident, stack note) is not part of that kernel
+  stop = next((i for i, l in enumerate(cur) if l.startswith('\t.section\t.AMDGPU.gpr_maximums')), len(cur))
+  blocks[name], blocks['TAIL'] = cur[:stop], cur[stop:]
+  entry, rest = None, []
+  for l in lines[meta_at:]:
+    if l.startswith('  - .'):
+      entry = []
+      rest.append(entry)
+    elif not l.startswith('    ') and not l.startswith('  - '):
+      entry = None
+    if entry is not None:
+      entry.append(l)
+    else:
+      blocks.setdefault('META', []).append(l)
+  for e in rest:
+    key = next(l.split()[-1] for l in e if l.strip().startswith('.name:'))
+    blocks['meta:' + key] = e
+  return blocks
+
+
+def main():
+  a, b = cut(sys.argv[1]), cut(sys.argv[2])
+  bad = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+  kernels = [k for k in a if not k.startswith('meta:') and k not in ('HEAD', 'TAIL', 'META')]
+  same_order = [k for k in a] == [k for k in b]
+  print('%d kernels in %s, %d blocks differ%s' % (len(kernels), sys.argv[1], len(bad), '' if same_order else ' (emission order differs)'))
+  for k in bad[:10]:
+    print('  differs:', k, '(parent only)' if k not in b else '(change only)' if k not in a else '')
+  return 1 if bad else 0
+
+
+if __name__ == '__main__':
+  sys.exit(main())

@@ -94,6 +94,16 @@ def test_no_kernel_adds_to_dgate_atomically():
           assert flag not in open(os.path.join(dirpath, name)).read(), os.path.join(dirpath, name)
 
 
+def test_march_helpers_are_defined_once():
+  """The raw-buffer descriptor and the unsigned range compare of the depthwise march (dw_march.hip, mbconv_fused.hip) are
+  defined in one file under csrc/ (dw_impl.h), not once per kernel file."""
+  csrc = os.path.join(ROOT, 'automl_amd', 'csrc')
+  names = sorted(n for n in os.listdir(csrc) if n.endswith(('.hip', '.h', '.cpp', '.inc')))
+  for pattern in (r'\bmake_rsrc\s*\(\s*const void\s*\*', r'\bstruct\s+URange\b'):
+    defined_in = [n for n in names if re.search(pattern, open(os.path.join(csrc, n)).read())]
+    assert defined_in == ['dw_impl.h'], (pattern, defined_in)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
   monkeypatch.setattr(_lib, '_lib', None)
   monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libedet_hip.so')
