@@ -127,6 +127,10 @@ SIGNATURES = {
     'edet_softmax_xent': [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                           ctypes.c_size_t, c_int, c_void_p],
     'edet_dropout_cast': [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
+    'edet_softmax_xent_soft': [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                               ctypes.c_size_t, c_int, c_void_p],
+    'edet_mix_images': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    'edet_mix_labels': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     'edet_zero': [c_void_p, ctypes.c_size_t, c_void_p],
     'edet_compact_rows': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p],
     'edet_cast_to_f32': [c_void_p, c_void_p, c_int64, c_int, c_void_p],

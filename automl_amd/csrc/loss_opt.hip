@@ -808,6 +808,106 @@ __global__ __launch_bounds__(THREADS) void k_softmax_xent(const T* __restrict__ 
   }
 }
 
+// 8 fp32 soft labels of columns [c0, c0 + 8) of a row, columns >= nc as zeros.  vec: the rows are 16-byte aligned and
+// padded to a multiple of 8 columns (two 16-byte loads); otherwise column by column, reading nothing behind column nc.
+__device__ __forceinline__ void load8_soft(const float* __restrict__ y, int c0, int nc, bool vec, float v[8]) {
+  if (vec && c0 < nc) {
+    loadf8(y + c0, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = c0 + e < nc ? v[e] : 0.f;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = c0 + e < nc ? y[c0 + e] : 0.f;
+  }
+}
+
+// The same loss against dense fp32 labels y [batch][label_ld] (one-hot, mixup / cutmix mixtures, anything a caller made):
+// Keras smooths whatever it is given, y'_c = (1 - s) y_c + s / nc, and nothing here assumes that a row sums to 1:
+// loss = lse * sum y' - sum y'_c x_c, d x_c = (softmax_c * sum y' - y'_c) * grad_scale / B.  The sums are taken of x - m, so
+// that the loss is sum y' * log(sum exp(x - m)) - sum y'_c (x_c - m) without the cancellation of two numbers of the size of
+// the logits.  TopKCategoricalAccuracy takes the row's class as argmax_c y_c (the first index on ties, found in the pass
+// that finds m) and then counts as the sparse kernel does.  Same structure, same ordered sums.
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_softmax_xent_soft(const T* __restrict__ logits, int ld, const float* __restrict__ soft,
+                                                              int label_ld, int vec, int batch, int nc, float ls, float gscale,
+                                                              float inv_b, T* __restrict__ dlogits, float* sums, float* part) {
+  __shared__ float sh[XENT_ROWS][3];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float uni = ls / (float)nc, hot = 1.f - ls;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int row = blockIdx.x * XENT_ROWS + wv; row < batch; row += gridDim.x * XENT_ROWS) {
+    const T* x = logits + (size_t)row * ld;
+    const float* y = soft + (size_t)row * label_ld;
+    float m = -INFINITY, ybest = -INFINITY;
+    int cls = nc;
+    for (int c0 = lane * 8; c0 < nc; c0 += 64 * 8) {
+      float v[8], yv[8];
+      load8<T>(x + c0, v);
+      load8_soft(y, c0, nc, vec, yv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (c0 + e < nc) {
+          m = fmaxf(m, v[e]);
+          if (yv[e] > ybest) { ybest = yv[e]; cls = c0 + e; }      // (a lane walks its columns in rising order)
+        }
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      m = fmaxf(m, __shfl_xor(m, off, 64));
+      const float oy = __shfl_xor(ybest, off, 64);
+      const int oc = __shfl_xor(cls, off, 64);
+      if (oy > ybest || (oy == ybest && oc < cls)) { ybest = oy; cls = oc; }
+    }
+    const bool cls_ok = cls < nc;
+    const float xl = cls_ok ? to_f<T>(x[cls]) : 0.f;
+    float r[5] = {0.f, 0.f, 0.f, 0.f, 0.f};      // sum exp(x - m), sum (x - m), logits > the class's, sum y, sum y (x - m)
+    for (int c0 = lane * 8; c0 < nc; c0 += 64 * 8) {
+      float v[8], yv[8];
+      load8<T>(x + c0, v);
+      load8_soft(y, c0, nc, vec, yv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (c0 + e < nc) {
+          const float d = v[e] - m;
+          r[0] += __expf(d);
+          r[1] += d;
+          r[2] += v[e] > xl ? 1.f : 0.f;
+          r[3] += yv[e];
+          r[4] += yv[e] * d;
+        }
+      }
+    }
+    wave_group_sum(r, 1);
+    const float inv_se = 1.f / r[0];
+    const float ysum = hot * r[3] + ls;          // sum_c y'_c
+    acc[0] += (ysum * __logf(r[0]) - hot * r[4] - uni * r[1]) * inv_b;
+    acc[1] += (cls_ok && r[2] < 1.f) ? 1.f : 0.f;
+    acc[2] += (cls_ok && r[2] < 5.f) ? 1.f : 0.f;
+    T* dx = dlogits + (size_t)row * ld;
+    const float pscale = inv_se * ysum;
+    for (int c0 = lane * 8; c0 < ld; c0 += 64 * 8) {
+      float v[8], yv[8], g[8];
+      load8<T>(x + c0, v);
+      load8_soft(y, c0, nc, vec, yv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        g[e] = c0 + e < nc ? (__expf(v[e] - m) * pscale - (hot * yv[e] + uni)) * gscale : 0.f;      // padding columns: zeros
+      store8<T>(dx + c0, g);
+    }
+  }
+  if (lane == 0) {
+    sh[wv][0] = acc[0]; sh[wv][1] = acc[1]; sh[wv][2] = acc[2];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    float t = 0.f;
+    for (int w = 0; w < XENT_ROWS; ++w) t += sh[w][threadIdx.x];
+    if (part) part[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
+    else sums[threadIdx.x] += t;          // (no partial buffer: the kernel runs as ONE workgroup)
+  }
+}
+
 // out = cast(src * mask): the head dropout (effnetv2_model.py:464-467,483-484) folded into the cast of the pooled sums;
 // mask == NULL is edet_cast.  In place (dst == src, fp32) for the backward pass.
 template <typename T>
@@ -838,6 +938,30 @@ extern "C" int edet_softmax_xent(const void* logits, int ld, const int32_t* labe
   else EDET_CHECK(false, "edet_softmax_xent: bad dtype %d", dtype);
   if (part && edet_reduce_partials2(part, g, 3, nullptr, 0, sums, to_stream(stream)) != 0) return -2;
   EDET_LAUNCH_CHECK("edet_softmax_xent");
+  return 0;
+}
+
+extern "C" int edet_softmax_xent_soft(const void* logits, int ld, const float* soft_labels, int label_ld, int batch, int num_classes,
+                                      float label_smoothing, float grad_scale, void* dlogits, float* sums, void* workspace,
+                                      size_t workspace_bytes, int dtype, void* stream) {
+  EDET_CHECK(logits && soft_labels && dlogits && sums, "edet_softmax_xent_soft: null pointer");
+  EDET_CHECK(batch > 0 && num_classes >= 1, "edet_softmax_xent_soft: batch %d, num_classes %d", batch, num_classes);
+  EDET_CHECK(ld % 8 == 0 && ld >= num_classes, "edet_softmax_xent_soft: bad ld %d (num_classes %d)", ld, num_classes);
+  EDET_CHECK(label_ld >= num_classes, "edet_softmax_xent_soft: bad label_ld %d (num_classes %d)", label_ld, num_classes);
+  EDET_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "edet_softmax_xent_soft: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  int g = (batch + XENT_ROWS - 1) / XENT_ROWS;
+  if (g > 1024) g = 1024;
+  float* part = (g > 1 && workspace && workspace_bytes >= (size_t)g * 3 * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
+  if (!part) g = 1;
+  const float inv_b = 1.f / (float)batch;
+  const int vec = label_ld % 8 == 0 && reinterpret_cast<uintptr_t>(soft_labels) % 16 == 0;
+  if (dtype == EDET_BF16)
+    edet_launch(k_softmax_xent_soft<bf16_t>, dim3(g), dim3(THREADS), 0, to_stream(stream), (const bf16_t*)logits, ld, soft_labels, label_ld, vec, batch, num_classes, label_smoothing, grad_scale * inv_b, inv_b, (bf16_t*)dlogits, sums, part);
+  else if (dtype == EDET_F32)
+    edet_launch(k_softmax_xent_soft<float>, dim3(g), dim3(THREADS), 0, to_stream(stream), (const float*)logits, ld, soft_labels, label_ld, vec, batch, num_classes, label_smoothing, grad_scale * inv_b, inv_b, (float*)dlogits, sums, part);
+  else EDET_CHECK(false, "edet_softmax_xent_soft: bad dtype %d", dtype);
+  if (part && edet_reduce_partials2(part, g, 3, nullptr, 0, sums, to_stream(stream)) != 0) return -2;
+  EDET_LAUNCH_CHECK("edet_softmax_xent_soft");
   return 0;
 }
 

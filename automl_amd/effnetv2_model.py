@@ -10,7 +10,8 @@ Scope: the forward pass in both BatchNo
 pass of the whole graph (``backward(d_outputs)``: Fused-MBConv dense convolutions, MBConv, SE, stochastic depth,
 head, dense layer).  The classifier's training step -- softmax cross-entropy with label smoothing, head dropout, the
 RMSprop / momentum / Adam update (``efficientnetv2/main_tf2.py``) -- is ``effnetv2_train.TrainableModel`` on the
-V2Engine methods at the end of this file (``softmax_loss``, ``head_dropout``) and the layer engine's update step
+V2Engine methods at the end of this file (``softmax_loss`` for sparse or soft labels, ``head_dropout``, ``mix_batch`` for
+mixup / cutmix) and the layer engine's update step
 (``LayerEngine.optimizer_local`` / ``optimizer_apply`` with the trainer's ``Update`` description).
 ``EffNetV2Model.__call__(training=True)`` itself still refuses dropout (pass ``model_config='dropout_rate=0'``): it has
 no labels to train with, and only the trainer owns the draws.  ``conv_dropout`` is not built anywhere.
@@ -283,17 +284,61 @@ class V2Engine(layer_engine.LayerEngine):
       self._draw_dropout_mask()
 
   def softmax_loss(self, labels, label_smoothing=0.0, grad_scale=1.0):
-    """CategoricalCrossentropy(label_smoothing, from_logits=True) of the logits of the last forward pass against sparse
-    int32 device labels [B] (main_tf2.py:199-207): adds the mean loss and the top-1 / top-5 row counts to cls_sums[0:3]
-    and, after a training forward pass, leaves d(logits) for backward().  The caller has checked the label range."""
+    """CategoricalCrossentropy(label_smoothing, from_logits=True) of the logits of the last forward pass (main_tf2.py:199-207)
+    against device labels: sparse int32 [B] (edet_softmax_xent; the caller has checked the range) or dense fp32 [B, >= C]
+    with C valid columns (edet_softmax_xent_soft: one-hot or mixed rows, what the reference's input pipeline hands its
+    loss).  Adds the mean loss and the top-1 / top-5 row counts to cls_sums[0:3] and, after a training forward pass, leaves
+    d(logits) for backward()."""
     out = self.logits
     assert out is not None, 'softmax_loss needs a model with a classifier head (include_top)'
-    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == self.batch
     ncls = self.spec.num_classes
     dl = layer_engine.Raw(self, 'head:dlogits', out.n, 1, 1, ncls, needs_grad=False)
-    call('edet_softmax_xent', ptr(out.data), out.ld, ptr(labels), out.n, ncls, float(label_smoothing), float(grad_scale),
-         ptr(dl.data), ptr(self.cls_sums), *self._ws(), self.dtype, self.stream)
+    if labels.dtype == torch.int32:
+      assert labels.is_contiguous() and labels.numel() == self.batch
+      call('edet_softmax_xent', ptr(out.data), out.ld, ptr(labels), out.n, ncls, float(label_smoothing), float(grad_scale),
+           ptr(dl.data), ptr(self.cls_sums), *self._ws(), self.dtype, self.stream)
+    else:
+      assert labels.dtype == torch.float32 and labels.is_contiguous() and labels.dim() == 2, 'labels: int32 [B] or fp32 [B, C]'
+      assert labels.shape[0] == self.batch and labels.shape[1] >= ncls, (tuple(labels.shape), ncls)
+      call('edet_softmax_xent_soft', ptr(out.data), out.ld, ptr(labels), int(labels.shape[1]), out.n, ncls,
+           float(label_smoothing), float(grad_scale), ptr(dl.data), ptr(self.cls_sums), *self._ws(), self.dtype, self.stream)
     self._dlogits_ready = self.training
+
+  # ---- mixup / cutmix (efficientnetv2/datasets.py:191-301) on the device -------------------------------------------------
+  mix_weights = mix_boxes = soft_labels = None      # static buffers of mix_batch, created by set_mix_draws
+  n_mixup = 0
+
+  def set_mix_draws(self, weights, boxes, n_mixup):
+    """This step's draws, made on the host by the trainer (effnetv2_train.draw_mix), into the static buffers that
+    mix_batch's kernels read: weights fp32 [B] (mixup rows), boxes int32 [B, 4] = y1, x1, y2, x2 (cutmix rows); rows
+    [0, n_mixup) are the mixup part.  Like refresh_drop_masks this runs OUTSIDE any captured graph, in front of every step;
+    the copies are asynchronous from pinned memory and the step that follows them on the stream sees them."""
+    b = self.batch
+    if self.mix_weights is None:
+      self.mix_weights = self.buf('mix:weights', (b,), torch.float32)
+      self.mix_boxes = self.buf('mix:boxes', (b, 4), torch.int32)
+      ld = (self.spec.num_classes + 7) // 8 * 8
+      self.soft_labels = self.buf('mix:soft_labels', (b, ld), torch.float32)
+    assert 0 <= int(n_mixup) <= b
+    self.n_mixup = int(n_mixup)
+    w = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float32).reshape(b)).pin_memory()
+    x = torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.int32).reshape(b, 4)).pin_memory()
+    self.mix_weights.copy_(w, non_blocking=True)
+    self.mix_boxes.copy_(x, non_blocking=True)
+
+  def mix_batch(self, images, labels):
+    """Mixes images [B, H, W, 3] (engine dtype, dense) IN PLACE and the sparse int32 labels [B] into the static soft-label
+    buffer with the draws of set_mix_draws: edet_mix_images + edet_mix_labels, the first launches of a mixed step.
+    -> soft labels fp32 [B, ld] for softmax_loss."""
+    assert self.mix_weights is not None, 'mix_batch needs set_mix_draws first'
+    b, (h, w) = self.batch, self.image_size
+    assert images.is_contiguous() and images.dtype == self.tdtype and tuple(images.shape) == (b, h, w, 3), tuple(images.shape)
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == b
+    call('edet_mix_images', ptr(images), b, h, w, 3, self.n_mixup, ptr(self.mix_weights), ptr(self.mix_boxes), self.dtype,
+         self.stream, nbytes=2 * images.numel() * self.esize)
+    call('edet_mix_labels', ptr(labels), b, self.spec.num_classes, h, w, self.n_mixup, ptr(self.mix_weights),
+         ptr(self.mix_boxes), ptr(self.soft_labels), int(self.soft_labels.shape[1]), self.stream)
+    return self.soft_labels
 
   def l2_loss_eval(self, weight_decay):
     """The same L2 term for an evaluation pass (test_step, main_tf2.py:105-117), added to cls_sums[3] WITHOUT touching the

@@ -6,16 +6,24 @@ hparams.py:249; 'momentum', 'sgd', 'adam'), the compiled loss ``CategoricalCross
 from_logits=True)`` with the ``acc_top1`` / ``acc_top5`` metrics (:199-207), and ``WarmupLearningRateSchedule``
 (``efficientnetv2/utils.py:78-131``).
 
-One step = forward(training) with stochastic depth and head dropout -> ``edet_softmax_xent`` (loss, d logits and the
-metric counts in one pass) -> ``V2Engine.backward`` -> ``LayerEngine.optimizer_local`` (the L2 term of ``_reg_l2_loss`` and the
+One step = [``V2Engine.mix_batch``: mixup / cutmix of the images in place and of the labels into soft labels, when an
+alpha is non-zero] -> forward(training) with stochastic depth and head dropout -> ``edet_softmax_xent`` /
+``edet_softmax_xent_soft`` (loss, d logits and the metric counts in one pass) -> ``V2Engine.backward`` -> ``LayerEngine.optimizer_local`` (the L2 term of ``_reg_l2_loss`` and the
 gradient norm; the reference clips nothing, gclip = 0) -> ``LayerEngine.optimizer_apply`` with this trainer's ``Update``
 (``edet_opt_rmsprop_ema``, or the SGD / Adam entry point).  The BatchNorm moving statistics move in the forward pass.  With ``use_graph`` the step is captured once
 into a hipGraph and replayed; the learning rate travels through a device vector and the dropout / stochastic-depth masks
-are redrawn outside the graph.
+are redrawn outside the graph, and so are the mixup weights and cutmix boxes.
 
-Single GPU.  Not built, and raising or absent rather than ignored: data-parallel classifier training, mixup / cutmix
-and soft labels (both 0 in hparams.py:282-283), ``conv_dropout``, progressive resizing, the TF1 trainer's
-EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
+Labels are the reference's dense float labels [B, C] (``datasets.py:321-323``: one-hot, or mixed by the caller's own
+pipeline; used as they are) or sparse integer class ids [B].  Mixup / cutmix (``datasets.py:191-301``; ``mixup_alpha`` /
+``cutmix_alpha`` of the constructor, ``set_mix_alphas`` between steps, ``mix_alphas(model_name)`` for a named model's
+recipe) run on the device and take integer labels: rows [0, n_mixup) of the batch are mixed by mixup and the rest by
+cutmix, each part with itself in reverse order as ``mixing`` does (``mix_split``); the draws come from a host generator
+seeded by the model's seed whose state travels with the optimizer state.  Mixing float labels on the device is not built
+(a ``ValueError``).
+
+Single GPU.  Not built, and raising or absent rather than ignored: data-parallel classifier training, ``conv_dropout``,
+RandAugment / AutoAugment, progressive resizing, the TF1 trainer's EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
 reference's TF2 trainer, keeps none).
 """
 import math
@@ -85,17 +93,93 @@ class WarmupLearningRateSchedule(object):
                                           'decay_epochs', 'total_steps', 'warmup_epochs', 'minimal_lr')}
 
 
+# ---- mixup / cutmix draws (efficientnetv2/datasets.py:191-301): pure host functions ------------------------------------
+def mix_alphas(model_name):
+  """(data.mixup_alpha, data.cutmix_alpha) of a named model's training recipe (effnetv2_configs; hparams.py:282-283 = 0, 0
+  where the model names none).  The reference ramps them per progressive-training stage (main_tf2.py:262-275):
+  TrainableModel.set_mix_alphas."""
+  from automl_amd import effnetv2_configs
+  data = effnetv2_configs.get_model_config(model_name).as_dict().get('data') or {}
+  return float(data.get('mixup_alpha') or 0.0), float(data.get('cutmix_alpha') or 0.0)
+
+
+def mix_split(batch, mixup_alpha, cutmix_alpha):
+  """Rows [0, n_mixup) are mixed by mixup, rows [n_mixup, batch) by cutmix (datasets.py:287-300: both -> batch // 2, mixup
+  only -> batch, cutmix only -> 0); None = no mixing."""
+  if mixup_alpha and cutmix_alpha:
+    return batch // 2
+  if mixup_alpha:
+    return batch
+  if cutmix_alpha:
+    return 0
+  return None
+
+
+def cutmix_box(r_y, r_x, area, h, w):
+  """cutmix_mask (datasets.py:191-211) for its three draws -> (y1, x1, y2, x2), half-open: ratio = float32(sqrt(1 - area)),
+  r_w = int(ratio * w), r_h = int(ratio * h) (float32 products, truncated), the box of that size centred on (r_y, r_x),
+  clipped to the image."""
+  ratio = np.float32(np.sqrt(1.0 - float(area)))
+  r_w = int(ratio * np.float32(w))
+  r_h = int(ratio * np.float32(h))
+  clip = lambda v, hi: int(min(max(v, 0), hi))
+  return (clip(r_y - r_h // 2, h), clip(r_x - r_w // 2, w), clip(r_y + r_h // 2, h), clip(r_x + r_w // 2, w))
+
+
+def mix_rng(seed):
+  """The generator behind the mixup / cutmix draws of a model built with `seed`."""
+  return np.random.Generator(np.random.PCG64([int(seed), 0x6d6978]))
+
+
+def draw_beta(rng, alpha, n):
+  """n draws of Beta(alpha, alpha), float64."""
+  return rng.beta(alpha, alpha, size=n)
+
+
+def draw_mix(rng, batch, h, w, mixup_alpha, cutmix_alpha):
+  """One step's draws -> (weights float32 [batch], boxes int32 [batch, 4]).  Mixup rows (datasets.py:261-262):
+  w_i = max(beta, 1 - beta), beta ~ Beta(alpha, alpha); their boxes are empty.  Cutmix rows (:191-203): r_x ~ U{0..w-1},
+  r_y ~ U{0..h-1}, area ~ Beta(alpha, alpha) -> cutmix_box; their weights are 1."""
+  n = mix_split(batch, mixup_alpha, cutmix_alpha)
+  weights = np.ones(batch, np.float32)
+  boxes = np.zeros((batch, 4), np.int32)
+  if n:
+    beta = draw_beta(rng, mixup_alpha, n)
+    weights[:n] = np.maximum(beta, 1.0 - beta).astype(np.float32)
+  for i in range(n, batch):
+    r_x = int(rng.integers(0, w))
+    r_y = int(rng.integers(0, h))
+    boxes[i] = cutmix_box(r_y, r_x, float(draw_beta(rng, cutmix_alpha, 1)[0]), h, w)
+  return weights, boxes
+
+
+def _pack_rng_state(rng):
+  """PCG64 state -> uint64 [6] (state and increment as two words each, the buffered 32-bit half)."""
+  st = rng.bit_generator.state
+  m = (1 << 64) - 1
+  s, inc = int(st['state']['state']), int(st['state']['inc'])
+  return np.array([s & m, s >> 64, inc & m, inc >> 64, int(st['has_uint32']), int(st['uinteger'])], dtype=np.uint64)
+
+
+def _unpack_rng_state(rng, words):
+  v = [int(x) for x in np.asarray(words, dtype=np.uint64)]
+  rng.bit_generator.state = {'bit_generator': 'PCG64', 'state': {'state': v[0] | (v[1] << 64), 'inc': v[2] | (v[3] << 64)},
+                             'has_uint32': v[4], 'uinteger': v[5]}
+
+
 class TrainableModel(effnetv2_model.EffNetV2Model):
   """EffNetV2Model plus the reference's train_step / test_step (main_tf2.py:62-117).
 
   learning_rate: a float or a callable of the iteration count (WarmupLearningRateSchedule).  use_graph: capture the step
   at its second call for a batch shape and replay it afterwards; False = every launch eager (the tests compare both).
   check_device_labels: also range-check labels that arrive as device tensors (one synchronisation per step).
-  ``momentum`` is build_tf2_optimizer's (0.9), used by 'rmsprop' and 'momentum'."""
+  ``momentum`` is build_tf2_optimizer's (0.9), used by 'rmsprop' and 'momentum'.
+  mixup_alpha / cutmix_alpha: the Beta parameters of datasets.py:244-301 (0 = off, the default: the step is then exactly
+  the unmixed one); a named model's own pair is mix_alphas(model_name)."""
 
   def __init__(self, model_name='efficientnetv2-s', model_config=None, name=None, weight_decay=0.0, optimizer='rmsprop',
                learning_rate=0.016, label_smoothing=0.0, ema_decay=None, momentum=0.9, use_graph=True, check_device_labels=False,
-               **kwargs):
+               mixup_alpha=0.0, cutmix_alpha=0.0, **kwargs):
     super().__init__(model_name=model_name, model_config=model_config, include_top=True, name=name or model_name, **kwargs)
     optimizer = str(optimizer).lower()
     if optimizer not in OPTIMIZERS:
@@ -118,6 +202,24 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.iterations = 0
     self._graph = None
     self._pending_state = None
+    self.mixup_alpha = self.cutmix_alpha = 0.0
+    self._mix_rng = mix_rng(self._seed)
+    self.set_mix_alphas(mixup_alpha, cutmix_alpha)
+
+  def set_mix_alphas(self, mixup_alpha, cutmix_alpha):
+    """New mixup / cutmix Beta parameters from the next step on (the reference ramps them per progressive-training stage,
+    main_tf2.py:262-275); 0 = off.  The captured step is dropped when the split of the batch changes (mixing switched on or
+    off, or one of the two parts appearing or disappearing): the next step runs eager and the one after it is captured again."""
+    mixup_alpha, cutmix_alpha = float(mixup_alpha or 0.0), float(cutmix_alpha or 0.0)
+    if mixup_alpha < 0 or cutmix_alpha < 0:
+      raise ValueError('mixup_alpha %r / cutmix_alpha %r must be >= 0' % (mixup_alpha, cutmix_alpha))
+    if mix_split(2, mixup_alpha, cutmix_alpha) != mix_split(2, self.mixup_alpha, self.cutmix_alpha):
+      self._graph = None
+    self.mixup_alpha, self.cutmix_alpha = mixup_alpha, cutmix_alpha
+
+  @property
+  def mixing(self):
+    return bool(self.mixup_alpha or self.cutmix_alpha)
 
   # ---- plumbing ------------------------------------------------------------------------------------------------------
   def _ensure_engine(self, batch, height, width):
@@ -134,8 +236,10 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     lr = self.learning_rate
     return float(lr(self.iterations)) if callable(lr) else float(lr)
 
-  def _prepare(self, data):
-    """(images, labels) or the reference's ({'image': ...}, {'label': ...}) -> (executor, device images, device labels)."""
+  def _prepare(self, data, mixing=False):
+    """(images, labels) or the reference's ({'image': ...}, {'label': ...}) -> (executor, device images, device labels).
+    Labels: integer class ids [batch] -> int32, or float [batch, num_classes] (one-hot or already mixed rows, used as they
+    are) -> float32.  mixing: the step will mix this batch on the device -- integer labels only."""
     images, labels = data
     if isinstance(images, dict):
       images, labels = images['image'], labels['label']
@@ -144,15 +248,26 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     if images.dim() != 4 or images.shape[-1] != 3:
       raise ValueError('images must be [batch, height, width, 3], got %s' % (tuple(images.shape),))
     labels = torch.as_tensor(labels)
-    if labels.dim() != 1 or labels.is_floating_point() or labels.numel() != images.shape[0]:
-      raise ValueError('labels must be sparse integer class ids [batch] (soft labels: mixup / cutmix are not built)')
-    if labels.device.type == 'cpu' or self.check_device_labels:
-      # (labels already on the device are the caller's promise unless check_device_labels: the check waits for the device)
-      if int(labels.min()) < 0 or int(labels.max()) >= self.spec.num_classes:
-        raise ValueError('labels outside [0, %d)' % self.spec.num_classes)
+    soft = labels.is_floating_point()
+    if soft:
+      if labels.dim() != 2 or tuple(labels.shape) != (images.shape[0], self.spec.num_classes):
+        raise ValueError('float labels must be [batch, num_classes] = [%d, %d], got %s' % (
+            images.shape[0], self.spec.num_classes, tuple(labels.shape)))
+      if mixing:
+        raise ValueError('mixup / cutmix on the device take sparse integer labels [batch]; float labels are used as they '
+                         'are: mix them in the input pipeline and set both alphas to 0')
+    else:
+      if labels.dim() != 1 or labels.numel() != images.shape[0]:
+        raise ValueError('labels must be integer class ids [batch] or float [batch, num_classes], got %s' % (tuple(labels.shape),))
+      if labels.device.type == 'cpu' or self.check_device_labels:
+        # (labels already on the device are the caller's promise unless check_device_labels: the check waits for the device)
+        if int(labels.min()) < 0 or int(labels.max()) >= self.spec.num_classes:
+          raise ValueError('labels outside [0, %d)' % self.spec.num_classes)
     eng = self._ensure_engine(int(images.shape[0]), int(images.shape[1]), int(images.shape[2]))
-    images = images.to(device=eng.device, dtype=eng.tdtype).contiguous()
-    return eng, images, labels.to(device=eng.device, dtype=torch.int32).contiguous()
+    dev_images = images.to(device=eng.device, dtype=eng.tdtype).contiguous()
+    if mixing and not self.use_graph and dev_images.data_ptr() == images.data_ptr():
+      dev_images = dev_images.clone()      # the eager step mixes in place: never in the caller's own tensor
+    return eng, dev_images, labels.to(device=eng.device, dtype=torch.float32 if soft else torch.int32).contiguous()
 
   def _metrics(self, eng, lr=None):
     s = eng.cls_sums.detach().cpu().numpy()
@@ -165,6 +280,8 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   # ---- the step ------------------------------------------------------------------------------------------------------
   def _step_body(self, eng, images, labels):
+    if self.mixing:
+      labels = eng.mix_batch(images, labels)      # the first launches of the step; images in place
     eng.forward(images, training=True)
     eng.softmax_loss(labels, self.label_smoothing)
     eng.backward()
@@ -173,9 +290,10 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   def _graph_step(self, eng, images, labels):
     g = self._graph
-    if g is None or g['engine'] is not eng:
+    if g is None or g['engine'] is not eng or g['labels'].dtype != labels.dtype or g['labels'].shape != labels.shape:
       g = self._graph = {'engine': eng, 'steps': 0, 'graph': None, 'images': torch.empty_like(images),
                          'labels': torch.empty_like(labels)}
+    # (refilled every step: the in-place mixing of a step never sees an already mixed buffer)
     if images.data_ptr() != g['images'].data_ptr():
       g['images'].copy_(images, non_blocking=True)
     if labels.data_ptr() != g['labels'].data_ptr():
@@ -192,22 +310,30 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     g['steps'] += 1
 
   def input_buffers(self):
-    """(images, labels) static device buffers of the captured step (None before the first graph step)."""
+    """(images, labels) static device buffers of the captured step (None before the first graph step).  A caller that
+    fills them directly (and passes them to train_step) skips the copy; with mixup / cutmix on, the step then mixes the
+    caller's own image buffer in place, so it has to be refilled before every step."""
     g = self._graph
     return (g['images'], g['labels']) if g else None
 
   def train_step(self, data, sync_loss=True):
-    """data = (images [B,H,W,3], labels int [B]) -> {'loss', 'reg_l2_loss', 'acc_top1', 'acc_top5', 'gradient_norm',
-    'learning_rate'} of this step's batch (main_tf2.py:89-103; sync_loss=False skips the read-back).
+    """data = (images [B,H,W,3], labels int [B] or float [B,C]) -> {'loss', 'reg_l2_loss', 'acc_top1', 'acc_top5',
+    'gradient_norm', 'learning_rate'} of this step's batch (main_tf2.py:89-103; sync_loss=False skips the read-back).
+    With a non-zero mixup_alpha / cutmix_alpha the batch is mixed on the device first (integer labels only), and the loss
+    and the metrics are those of the mixed batch, as in the reference, whose trainer only ever sees the mixed one.
     Labels outside [0, num_classes) raise before anything is launched when they arrive on the host.  Labels that are
     already DEVICE tensors are not looked at (that would synchronise every step) unless the model was built with
     check_device_labels=True: an out-of-range device label is then the caller's error, and the kernel -- which reads
     nothing out of bounds for it -- returns a finite loss for a row without a hot class, with no signal."""
-    eng, images, labels = self._prepare(data)
+    eng, images, labels = self._prepare(data, mixing=self.mixing)
     lr = self._lr()
     eng.set_hyper(lr, self.ema_decay)
     if eng.drop_masks or eng.dropout_mask is not None:
       eng.refresh_drop_masks()      # (an engine's first step draws its masks where it creates them)
+    if self.mixing:
+      h, w = eng.image_size
+      weights, boxes = draw_mix(self._mix_rng, eng.batch, h, w, self.mixup_alpha, self.cutmix_alpha)
+      eng.set_mix_draws(weights, boxes, mix_split(eng.batch, self.mixup_alpha, self.cutmix_alpha))
     if self.use_graph:
       self._graph_step(eng, images, labels)
     else:
@@ -218,7 +344,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     return self._metrics(eng, lr)
 
   def test_step(self, data):
-    """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117)."""
+    """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117).  Never mixes; both label kinds."""
     eng, images, labels = self._prepare(data)
     eng.forward(images, training=False)
     eng.softmax_loss(labels, self.label_smoothing)
@@ -229,13 +355,15 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   # ---- state ---------------------------------------------------------------------------------------------------------
   def get_optimizer_state(self):
     """Optimizer slots ('velocity' = the momentum slot, 'rms' = RMSprop's mean square or 'adam_v'), EMA shadows, the
-    iteration count (it drives the learning-rate schedule) and the state of the generator behind the dropout and
-    stochastic-depth draws, so that a resumed run continues the uninterrupted one bit for bit."""
+    iteration count (it drives the learning-rate schedule) and the states of the two generators -- 'rng_state' behind the
+    dropout and stochastic-depth draws, 'mix_rng_state' behind the mixup / cutmix draws -- so that a resumed run continues
+    the uninterrupted one bit for bit."""
     if self.engine is None:
       raise RuntimeError('the network has not been built yet (call it once)')
     state = self.engine.arena.get_optimizer_state()
     state['iterations'] = self.iterations
     state['rng_state'] = self.engine._rng.get_state().cpu().numpy().copy()
+    state['mix_rng_state'] = _pack_rng_state(self._mix_rng)
     return state
 
   def set_optimizer_state(self, state):
@@ -250,3 +378,5 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.iterations = int(state['iterations'])
     if 'rng_state' in state:
       eng._rng.set_state(torch.as_tensor(state['rng_state'], dtype=torch.uint8))
+    if 'mix_rng_state' in state:
+      _unpack_rng_state(self._mix_rng, state['mix_rng_state'])

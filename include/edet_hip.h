@@ -435,6 +435,37 @@ int edet_softmax_xent(const void* logits, int ld, const int32_t* labels, int bat
  * dst may be src (fp32): the same mask on d(pooled) in the backward pass. */
 int edet_dropout_cast(const float* src, const float* mask, void* dst, int64_t count, int dtype, void* stream);
 
+/* ---- soft labels, mixup and cutmix (efficientnetv2/datasets.py:191-301, :321-323) ----
+ * edet_softmax_xent_soft: edet_softmax_xent against dense fp32 labels soft_labels [batch][label_ld] (num_classes valid
+ * columns, label_ld >= num_classes; 16-byte loads when label_ld is a multiple of 8 and the pointer is 16-byte aligned) --
+ * what the reference's input pipeline hands its loss: one-hot rows or mixtures of them.  Keras smooths whatever y it is
+ * given, y'_c = (1 - s) y_c + s / num_classes, and a row need not sum to 1: loss = lse * sum_c y'_c - sum_c y'_c x_c,
+ * dlogits = (softmax_c * sum_c y'_c - y'_c) * grad_scale / batch, padding columns written as zeros.  The metrics are
+ * TopKCategoricalAccuracy's: the row's class is argmax_c y_c (the first index on ties), counted as edet_softmax_xent counts
+ * it.  Same sums, workspace, order and run-to-run identity as edet_softmax_xent; no atomics. */
+int edet_softmax_xent_soft(const void* logits, int ld, const float* soft_labels, int label_ld, int batch, int num_classes,
+                           float label_smoothing, float grad_scale, void* dlogits, float* sums, void* workspace,
+                           size_t workspace_bytes, int dtype, void* stream);
+/* edet_mix_images: mixup and cutmix of images [batch][height][width][channels] (dense, `dtype`) IN PLACE.  Rows
+ * [0, n_mixup) are mixed by mixup, rows [n_mixup, batch) by cutmix, each part with itself in reverse (datasets.py:238,267
+ * within the halves of :287-294): the partner of mixup row i is n_mixup - 1 - i, of cutmix row i n_mixup + batch - 1 - i.
+ * mixup: out_i = x_i w_i + x_partner (1 - w_i) in fp32, rounded once to `dtype`; cutmix: out_i = x_partner inside row i's
+ * OWN box, x_i outside it.  weights: device fp32 [batch] (read for the mixup rows); boxes: device int32 [batch][4] =
+ * y1, x1, y2, x2, half-open, clamped to the image by the kernel (read for the cutmix rows) -- device memory, so that a
+ * replayed graph sees new draws.  One thread owns the same chunk of a row and of its partner and reads both before it writes
+ * either; a row that is its own partner is written once (mixup) or left alone (cutmix).  16-byte chunks when
+ * height * width * channels elements are a whole number of them, element by element otherwise.  The cutmix part reads and
+ * writes only the image rows that one of the pair's two boxes touches.  Nothing is summed: the same bits on every run. */
+int edet_mix_images(void* images, int batch, int height, int width, int channels, int n_mixup, const float* weights,
+                    const int32_t* boxes, int dtype, void* stream);
+/* edet_mix_labels: the labels of the same mixing.  labels int32 [batch] -> soft_labels fp32 [batch][label_ld], columns
+ * [num_classes, label_ld) written as zeros.  mixup rows: w_i onehot(l_i) + (1 - w_i) onehot(l_partner); cutmix rows:
+ * (1 - A) onehot(l_i) + A onehot(l_partner), A = (sum of the clamped box areas of the cutmix rows) / ((batch - n_mixup) *
+ * height * width): ONE scalar for the whole part, the mean mask area of datasets.py:236 (an integer sum, exact in any
+ * order).  A label outside [0, num_classes) adds nothing to its rows (the caller checks the range). */
+int edet_mix_labels(const int32_t* labels, int batch, int num_classes, int height, int width, int n_mixup,
+                    const float* weights, const int32_t* boxes, float* soft_labels, int label_ld, void* stream);
+
 /* ---- optimizer -----------------------------------------------------------------
  * train_lib.py:486-491 (L2), :675-682 (per-tensor clip_by_norm then
  * clip_by_global_norm), Keras SGD momentum, TFA MovingAverage (:176-199).

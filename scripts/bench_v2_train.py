@@ -4,7 +4,11 @@
   opt    edet_opt_sgd_ema, edet_opt_rmsprop_ema and edet_opt_adam_ema on the model's arena (the last two move the same
          bytes): HIP events around `--launches` launches each, alternating, `--reps` repetitions -> medians, spreads
          (max - min), implied GB/s;
-  step   ms per TrainableModel.train_step (RMSprop, default dropout and stochastic depth, hipGraph replay);
+  step   ms per TrainableModel.train_step (RMSprop, default dropout and stochastic depth, hipGraph replay); with
+         `--mix ALPHA` mixup and cutmix are on at that alpha (half the batch each) and the static image buffer is refilled
+         from the caller's batch every step, as a mixing step needs;
+  mix    the mix pass alone (edet_mix_images + edet_mix_labels on the step's buffers): HIP events around `--launches`
+         passes, `--reps` repetitions -> median, spread, bytes moved and implied GB/s;
   fwdbwd ms per forward(training) + backward of EffNetV2Model with dropout_rate=0, launched eagerly: what the step had
          before the loss, the dropout and the update existed."""
 import argparse
@@ -76,12 +80,13 @@ def _data(args):
 
 def bench_step(args):
   net = effnetv2_train.TrainableModel(args.model, dtype='bf16', learning_rate=1e-4, weight_decay=1e-5, label_smoothing=0.1,
-                                      use_graph=True)
+                                      use_graph=True, mixup_alpha=args.mix, cutmix_alpha=args.mix)
   images, labels = _data(args)
   first = net.train_step((images, labels))
   for _ in range(max(args.warmup, 2)):
     net.train_step((images, labels), sync_loss=False)
-  images, labels = net.input_buffers()
+  if not args.mix:      # (a mixing step mixes the static buffer in place: it is refilled from `images` every step)
+    images, labels = net.input_buffers()
   torch.cuda.synchronize()
   t0 = time.perf_counter()
   for _ in range(args.steps):
@@ -90,9 +95,47 @@ def bench_step(args):
   dt = (time.perf_counter() - t0) / args.steps
   last = net.train_step((images, labels))
   print(json.dumps({'phase': 'step', 'workload': '%s %dx%d batch %d bf16 train_step (rmsprop, dropout %g, stochastic depth), '
-                    'hipGraph replay' % (args.model, args.size, args.size, args.batch, net.cfg_model.dropout_rate),
+                    'hipGraph replay%s' % (args.model, args.size, args.size, args.batch, net.cfg_model.dropout_rate,
+                                          ', mixup + cutmix alpha %g' % args.mix if args.mix else ''),
                     'ms_per_step': round(dt * 1e3, 3), 'images_per_sec': round(args.batch / dt, 1),
                     'first_loss': first['loss'], 'last_loss': last['loss'], 'steps': args.steps}))
+
+
+def bench_mix(args):
+  alpha = args.mix or 0.4
+  net = effnetv2_train.TrainableModel(args.model, dtype='bf16', use_graph=False, mixup_alpha=alpha, cutmix_alpha=alpha)
+  images, labels = _data(args)
+  eng = net._ensure_engine(args.batch, args.size, args.size)
+  n_mixup = effnetv2_train.mix_split(args.batch, alpha, alpha)
+  weights, boxes = effnetv2_train.draw_mix(net._mix_rng, args.batch, args.size, args.size, alpha, alpha)
+  eng.set_mix_draws(weights, boxes, n_mixup)
+  for _ in range(3):
+    eng.mix_batch(images, labels)
+  torch.cuda.synchronize()
+  times = []
+  for _ in range(args.reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.launches):
+      eng.mix_batch(images, labels)
+    e1.record()
+    torch.cuda.synchronize()
+    times.append(e0.elapsed_time(e1) / args.launches)
+  # mixup rows: read and written once; cutmix: the image rows of each pair's two boxes, read and written in both images
+  row = args.size * 3 * 2
+  moved = 2 * n_mixup * args.size * row
+  m = args.batch - n_mixup
+  for k in range(m // 2):
+    i, p = n_mixup + k, args.batch - 1 - k
+    spans = [(b[0], b[2]) for b in (boxes[i], boxes[p]) if b[2] > b[0] and b[3] > b[1]]
+    if spans:
+      moved += 2 * 2 * (max(s[1] for s in spans) - min(s[0] for s in spans)) * row
+  moved += args.batch * eng.soft_labels.shape[1] * 4
+  med = float(np.median(times))
+  print(json.dumps({'phase': 'mix', 'workload': '%s %dx%d batch %d bf16 mix pass (mixup rows %d, cutmix rows %d, alpha %g)' % (
+      args.model, args.size, args.size, args.batch, n_mixup, m, alpha), 'median_ms': round(med, 5),
+      'spread_ms': round(max(times) - min(times), 5), 'min_ms': round(min(times), 5), 'bytes_per_pass': int(moved),
+      'GBps': round(moved / (med * 1e-3) / 1e9, 1), 'launches': args.launches, 'reps': args.reps}))
 
 
 def bench_fwdbwd(args):
@@ -119,7 +162,7 @@ def bench_fwdbwd(args):
 
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument('phase', choices=['opt', 'step', 'fwdbwd'])
+  ap.add_argument('phase', choices=['opt', 'step', 'mix', 'fwdbwd'])
   ap.add_argument('--model', default='efficientnetv2-s')
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--size', type=int, default=224)
@@ -127,11 +170,12 @@ def main():
   ap.add_argument('--warmup', type=int, default=3)
   ap.add_argument('--launches', type=int, default=20)
   ap.add_argument('--reps', type=int, default=11)
+  ap.add_argument('--mix', type=float, default=0.0, help='mixup_alpha = cutmix_alpha of the step / mix phases (0 = off)')
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('bench_v2_train.py needs an MI355X: there is no CPU path and no CPU timing')
   _lib.load()
-  {'opt': bench_opt, 'step': bench_step, 'fwdbwd': bench_fwdbwd}[args.phase](args)
+  {'opt': bench_opt, 'step': bench_step, 'mix': bench_mix, 'fwdbwd': bench_fwdbwd}[args.phase](args)
 
 
 if __name__ == '__main__':
