@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libedet_hip.so')
 
 EDET_F32, EDET_BF16 = 0, 1
+EDET_U8 = 2      # edet_randaug_apply's out_dtype only
 ACT_NONE, ACT_SWISH, ACT_RELU, ACT_RELU6, ACT_HSWISH, ACT_MISH, ACT_SRELU = 0, 1, 2, 3, 4, 5, 6
 ACT_CODES = {'swish': ACT_SWISH, 'silu': ACT_SWISH, 'swish_native': ACT_SWISH, 'relu': ACT_RELU, 'relu6': ACT_RELU6,
              'hswish': ACT_HSWISH, 'mish': ACT_MISH, 'srelu': ACT_SRELU}
@@ -131,6 +132,8 @@ SIGNATURES = {
                                ctypes.c_size_t, c_int, c_void_p],
     'edet_mix_images': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     'edet_mix_labels': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    'edet_randaug_stats': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    'edet_randaug_apply': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     'edet_zero': [c_void_p, ctypes.c_size_t, c_void_p],
     'edet_compact_rows': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p],
     'edet_cast_to_f32': [c_void_p, c_void_p, c_int64, c_int, c_void_p],

@@ -11,7 +11,7 @@ pass of the whole graph (``backward(d_outputs)``: Fused-MBConv dense convolution
 head, dense layer).  The classifier's training step -- softmax cross-entropy with label smoothing, head dropout, the
 RMSprop / momentum / Adam update (``efficientnetv2/main_tf2.py``) -- is ``effnetv2_train.TrainableModel`` on the
 V2Engine methods at the end of this file (``softmax_loss`` for sparse or soft labels, ``head_dropout``, ``mix_batch`` for
-mixup / cutmix) and the layer engine's update step
+mixup / cutmix, ``randaug_batch`` for RandAugment on uint8 images) and the layer engine's update step
 (``LayerEngine.optimizer_local`` / ``optimizer_apply`` with the trainer's ``Update`` description).
 ``EffNetV2Model.__call__(training=True)`` itself still refuses dropout (pass ``model_config='dropout_rate=0'``): it has
 no labels to train with, and only the trainer owns the draws.  ``conv_dropout`` is not built anywhere.
@@ -339,6 +339,40 @@ class V2Engine(layer_engine.LayerEngine):
     call('edet_mix_labels', ptr(labels), b, self.spec.num_classes, h, w, self.n_mixup, ptr(self.mix_weights),
          ptr(self.mix_boxes), ptr(self.soft_labels), int(self.soft_labels.shape[1]), self.stream)
     return self.soft_labels
+
+  # ---- RandAugment (efficientnetv2/autoaugment.py:663-702) on the device -----------------------------------------------
+  ra_ops = ra_iargs = ra_fargs = ra_luts = None      # static buffers of randaug_batch, created by set_randaug_draws
+
+  def set_randaug_draws(self, ops, iargs, fargs):
+    """This step's RandAugment arguments, made on the host by the trainer (autoaugment.randaug_draws / randaug_args), into
+    the static buffers that randaug_batch's kernels read: ops int32 [L, B], iargs int32 [L, B, 4], fargs fp32 [L, B, 8].
+    Like set_mix_draws this runs OUTSIDE any captured graph, in front of every step, by asynchronous copies from pinned
+    memory.  The number of layers is fixed at the first call (it is part of the launch sequence)."""
+    b = self.batch
+    ops = np.ascontiguousarray(ops, dtype=np.int32)
+    layers = int(ops.shape[0])
+    if self.ra_ops is None:
+      self.ra_ops = self.buf('randaug:ops', (layers, b), torch.int32)
+      self.ra_iargs = self.buf('randaug:iargs', (layers, b, 4), torch.int32)
+      self.ra_fargs = self.buf('randaug:fargs', (layers, b, 8), torch.float32)
+      self.ra_luts = self.buf('randaug:luts', (b, 3, 256), torch.uint8)
+    assert tuple(ops.shape) == tuple(self.ra_ops.shape), (ops.shape, tuple(self.ra_ops.shape))
+    for dst, src, dt in ((self.ra_ops, ops, np.int32), (self.ra_iargs, iargs, np.int32), (self.ra_fargs, fargs, np.float32)):
+      dst.copy_(torch.from_numpy(np.ascontiguousarray(src, dtype=dt).reshape(tuple(dst.shape))).pin_memory(), non_blocking=True)
+
+  def randaug_batch(self, images_u8, augment=True):
+    """uint8 images [B, H, W, 3] -> the static network-input buffer (engine dtype), normalised (x - 128) / 128 by the last
+    layer's launch: per layer edet_randaug_stats + edet_randaug_apply with the arguments of set_randaug_draws, ping-pong
+    through two uint8 buffers.  augment=False (test_step), or no layers: the normalising copy alone."""
+    from automl_amd import autoaugment
+    b, (h, w) = self.batch, self.image_size
+    assert images_u8.dtype == torch.uint8 and images_u8.is_contiguous() and tuple(images_u8.shape) == (b, h, w, 3), (
+        images_u8.dtype, tuple(images_u8.shape))
+    out = self.buf('randaug:images', (b, h, w, 3), self.tdtype)
+    if not augment or self.ra_ops is None or self.ra_ops.shape[0] == 0:
+      return autoaugment.apply_layers(images_u8, out, None, None, None, None, None, self.stream)
+    scratch = [self.buf('randaug:scratch%d' % k, (b, h, w, 3), torch.uint8) for k in range(min(int(self.ra_ops.shape[0]) - 1, 2))]
+    return autoaugment.apply_layers(images_u8, out, self.ra_ops, self.ra_iargs, self.ra_fargs, self.ra_luts, scratch, self.stream)
 
   def l2_loss_eval(self, weight_decay):
     """The same L2 term for an evaluation pass (test_step, main_tf2.py:105-117), added to cls_sums[3] WITHOUT touching the

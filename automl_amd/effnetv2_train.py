@@ -6,13 +6,21 @@ hparams.py:249; 'momentum', 'sgd', 'adam'), the compiled loss ``CategoricalCross
 from_logits=True)`` with the ``acc_top1`` / ``acc_top5`` metrics (:199-207), and ``WarmupLearningRateSchedule``
 (``efficientnetv2/utils.py:78-131``).
 
-One step = [``V2Engine.mix_batch``: mixup / cutmix of the images in place and of the labels into soft labels, when an
+One step = [``V2Engine.randaug_batch``: RandAugment of the uint8 batch and its normalisation into the static image
+buffer, with ``augname='randaug'``] -> [``V2Engine.mix_batch``: mixup / cutmix of the images in place and of the labels into soft labels, when an
 alpha is non-zero] -> forward(training) with stochastic depth and head dropout -> ``edet_softmax_xent`` /
 ``edet_softmax_xent_soft`` (loss, d logits and the metric counts in one pass) -> ``V2Engine.backward`` -> ``LayerEngine.optimizer_local`` (the L2 term of ``_reg_l2_loss`` and the
 gradient norm; the reference clips nothing, gclip = 0) -> ``LayerEngine.optimizer_apply`` with this trainer's ``Update``
 (``edet_opt_rmsprop_ema``, or the SGD / Adam entry point).  The BatchNorm moving statistics move in the forward pass.  With ``use_graph`` the step is captured once
 into a hipGraph and replayed; the learning rate travels through a device vector and the dropout / stochastic-depth masks
-are redrawn outside the graph, and so are the mixup weights and cutmix boxes.
+are redrawn outside the graph, and so are the mixup weights and cutmix boxes and the RandAugment arguments.
+
+RandAugment (``augname='randaug'``, ``ra_num_layers``, ``ra_magnitude``; ``randaug_params(model_name)`` for a named model's
+recipe, ``set_randaug`` between steps; ``automl_amd/autoaugment.py``) runs on the device in front of the mixing, per image as
+in the reference (``preprocessing.py:107-153``): ``train_step`` then takes the **uint8** images [B, H, W, 3] that the reference
+hands ``distort_image`` after crop, resize, flip and the clip / cast of ``preprocessing.py:49-50``, and normalises them
+(x - 128) / 128 itself; ``test_step`` only normalises.  The draws come from a third host generator seeded by the model's
+seed, whose state travels with the optimizer state under 'randaug_rng_state' (present only when ``augname`` is set).
 
 Labels are the reference's dense float labels [B, C] (``datasets.py:321-323``: one-hot, or mixed by the caller's own
 pipeline; used as they are) or sparse integer class ids [B].  Mixup / cutmix (``datasets.py:191-301``; ``mixup_alpha`` /
@@ -23,7 +31,8 @@ seeded by the model's seed whose state travels with the optimizer state.  Mixing
 (a ``ValueError``).
 
 Single GPU.  Not built, and raising or absent rather than ignored: data-parallel classifier training, ``conv_dropout``,
-RandAugment / AutoAugment, progressive resizing, the TF1 trainer's EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
+AutoAugment v0 and ``ra_aa``, the legacy ``effnetv1_*`` preprocessing, the random crop / resize / flip in front of
+RandAugment, progressive resizing, the TF1 trainer's EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
 reference's TF2 trainer, keeps none).
 """
 import math
@@ -31,6 +40,7 @@ import math
 import numpy as np
 import torch
 
+from automl_amd import autoaugment
 from automl_amd import effnetv2_model
 from automl_amd.layer_engine import LayerEngine, Update, capture_graph
 
@@ -101,6 +111,15 @@ def mix_alphas(model_name):
   from automl_amd import effnetv2_configs
   data = effnetv2_configs.get_model_config(model_name).as_dict().get('data') or {}
   return float(data.get('mixup_alpha') or 0.0), float(data.get('cutmix_alpha') or 0.0)
+
+
+def randaug_params(model_name):
+  """(data.augname, data.ra_num_layers, data.ram) of a named model's training recipe (effnetv2_configs; the layer count
+  defaults to preprocessing.py:115's 2, the magnitude to :116's 15); augname None where the model names none."""
+  from automl_amd import effnetv2_configs
+  data = effnetv2_configs.get_model_config(model_name).as_dict().get('data') or {}
+  ram = data.get('ram')
+  return data.get('augname') or None, int(data.get('ra_num_layers') or 2), 15 if ram is None else ram
 
 
 def mix_split(batch, mixup_alpha, cutmix_alpha):
@@ -175,11 +194,14 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   check_device_labels: also range-check labels that arrive as device tensors (one synchronisation per step).
   ``momentum`` is build_tf2_optimizer's (0.9), used by 'rmsprop' and 'momentum'.
   mixup_alpha / cutmix_alpha: the Beta parameters of datasets.py:244-301 (0 = off, the default: the step is then exactly
-  the unmixed one); a named model's own pair is mix_alphas(model_name)."""
+  the unmixed one); a named model's own pair is mix_alphas(model_name).
+  augname: None (the default: nothing changes) or 'randaug' -- RandAugment of ra_num_layers layers at ra_magnitude on the
+  device (the reference's defaults, preprocessing.py:115-116; a named model's own are randaug_params(model_name));
+  train_step then takes uint8 images.  The other names of the reference raise."""
 
   def __init__(self, model_name='efficientnetv2-s', model_config=None, name=None, weight_decay=0.0, optimizer='rmsprop',
                learning_rate=0.016, label_smoothing=0.0, ema_decay=None, momentum=0.9, use_graph=True, check_device_labels=False,
-               mixup_alpha=0.0, cutmix_alpha=0.0, **kwargs):
+               mixup_alpha=0.0, cutmix_alpha=0.0, augname=None, ra_num_layers=2, ra_magnitude=15, **kwargs):
     super().__init__(model_name=model_name, model_config=model_config, include_top=True, name=name or model_name, **kwargs)
     optimizer = str(optimizer).lower()
     if optimizer not in OPTIMIZERS:
@@ -205,6 +227,25 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.mixup_alpha = self.cutmix_alpha = 0.0
     self._mix_rng = mix_rng(self._seed)
     self.set_mix_alphas(mixup_alpha, cutmix_alpha)
+    self.augname = None if augname is None else autoaugment.check_aug_name(augname)
+    self.ra_num_layers = int(ra_num_layers)
+    if self.ra_num_layers < 0:
+      raise ValueError('ra_num_layers %r must be >= 0' % (ra_num_layers,))
+    self.ra_magnitude = autoaugment.check_magnitude(ra_magnitude)
+    self._ra_rng = autoaugment.randaug_rng(self._seed)
+    self._ra_forced = None
+
+  def set_randaug(self, magnitude):
+    """A new RandAugment magnitude from the next step on (the reference ramps it per progressive-training stage,
+    main_tf2.py:262-275); a float in [0, 20].  Only the argument buffers change: the captured step is kept."""
+    if self.augname is None:
+      raise ValueError('set_randaug on a model built without augname')
+    self.ra_magnitude = autoaugment.check_magnitude(magnitude)
+
+  def force_randaug_draws(self, draws):
+    """Use these draws (autoaugment.randaug_draws' four arrays [ra_num_layers, batch]) for every following step instead of
+    drawing; None = draw again.  For tests and debugging."""
+    self._ra_forced = draws
 
   def set_mix_alphas(self, mixup_alpha, cutmix_alpha):
     """New mixup / cutmix Beta parameters from the next step on (the reference ramps them per progressive-training stage,
@@ -236,10 +277,11 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     lr = self.learning_rate
     return float(lr(self.iterations)) if callable(lr) else float(lr)
 
-  def _prepare(self, data, mixing=False):
+  def _prepare(self, data, mixing=False, augment=False):
     """(images, labels) or the reference's ({'image': ...}, {'label': ...}) -> (executor, device images, device labels).
     Labels: integer class ids [batch] -> int32, or float [batch, num_classes] (one-hot or already mixed rows, used as they
-    are) -> float32.  mixing: the step will mix this batch on the device -- integer labels only."""
+    are) -> float32.  mixing: the step will mix this batch on the device -- integer labels only.  augment: the step will
+    RandAugment this batch -- uint8 images only; with augname set uint8 images stay uint8 (the engine normalises them)."""
     images, labels = data
     if isinstance(images, dict):
       images, labels = images['image'], labels['label']
@@ -247,6 +289,9 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       images = torch.from_numpy(images)
     if images.dim() != 4 or images.shape[-1] != 3:
       raise ValueError('images must be [batch, height, width, 3], got %s' % (tuple(images.shape),))
+    if augment and images.dtype != torch.uint8:
+      raise ValueError('augname=%r: train_step takes uint8 images [batch, height, width, 3] (what the reference hands '
+                       'distort_image, preprocessing.py:49-50,107-111), got %s' % (self.augname, images.dtype))
     labels = torch.as_tensor(labels)
     soft = labels.is_floating_point()
     if soft:
@@ -264,7 +309,10 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
         if int(labels.min()) < 0 or int(labels.max()) >= self.spec.num_classes:
           raise ValueError('labels outside [0, %d)' % self.spec.num_classes)
     eng = self._ensure_engine(int(images.shape[0]), int(images.shape[1]), int(images.shape[2]))
-    dev_images = images.to(device=eng.device, dtype=eng.tdtype).contiguous()
+    if self.augname is not None and images.dtype == torch.uint8:
+      dev_images = images.to(device=eng.device).contiguous()
+    else:
+      dev_images = images.to(device=eng.device, dtype=eng.tdtype).contiguous()
     if mixing and not self.use_graph and dev_images.data_ptr() == images.data_ptr():
       dev_images = dev_images.clone()      # the eager step mixes in place: never in the caller's own tensor
     return eng, dev_images, labels.to(device=eng.device, dtype=torch.float32 if soft else torch.int32).contiguous()
@@ -280,6 +328,8 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   # ---- the step ------------------------------------------------------------------------------------------------------
   def _step_body(self, eng, images, labels):
+    if self.augname is not None:
+      images = eng.randaug_batch(images)      # uint8 -> the engine's own normalised buffer (mixed in place below)
     if self.mixing:
       labels = eng.mix_batch(images, labels)      # the first launches of the step; images in place
     eng.forward(images, training=True)
@@ -325,7 +375,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     already DEVICE tensors are not looked at (that would synchronise every step) unless the model was built with
     check_device_labels=True: an out-of-range device label is then the caller's error, and the kernel -- which reads
     nothing out of bounds for it -- returns a finite loss for a row without a hot class, with no signal."""
-    eng, images, labels = self._prepare(data, mixing=self.mixing)
+    eng, images, labels = self._prepare(data, mixing=self.mixing, augment=self.augname is not None)
     lr = self._lr()
     eng.set_hyper(lr, self.ema_decay)
     if eng.drop_masks or eng.dropout_mask is not None:
@@ -334,6 +384,12 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       h, w = eng.image_size
       weights, boxes = draw_mix(self._mix_rng, eng.batch, h, w, self.mixup_alpha, self.cutmix_alpha)
       eng.set_mix_draws(weights, boxes, mix_split(eng.batch, self.mixup_alpha, self.cutmix_alpha))
+    if self.augname is not None:
+      h, w = eng.image_size
+      draws = self._ra_forced
+      if draws is None:
+        draws = autoaugment.randaug_draws(self._ra_rng, eng.batch, self.ra_num_layers)
+      eng.set_randaug_draws(*autoaugment.randaug_args(draws, self.ra_magnitude, h, w))
     if self.use_graph:
       self._graph_step(eng, images, labels)
     else:
@@ -344,8 +400,11 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     return self._metrics(eng, lr)
 
   def test_step(self, data):
-    """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117).  Never mixes; both label kinds."""
+    """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117).  Never mixes and never augments; both
+    label kinds; with augname set, uint8 images are normalised (x - 128) / 128 on the way in."""
     eng, images, labels = self._prepare(data)
+    if images.dtype == torch.uint8:
+      images = eng.randaug_batch(images, augment=False)
     eng.forward(images, training=False)
     eng.softmax_loss(labels, self.label_smoothing)
     # the compiled loss's regularisation term; the gradient arena of the last train_step stays as it is
@@ -356,14 +415,16 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   def get_optimizer_state(self):
     """Optimizer slots ('velocity' = the momentum slot, 'rms' = RMSprop's mean square or 'adam_v'), EMA shadows, the
     iteration count (it drives the learning-rate schedule) and the states of the two generators -- 'rng_state' behind the
-    dropout and stochastic-depth draws, 'mix_rng_state' behind the mixup / cutmix draws -- so that a resumed run continues
-    the uninterrupted one bit for bit."""
+    dropout and stochastic-depth draws, 'mix_rng_state' behind the mixup / cutmix draws and, only when augname is set,
+    'randaug_rng_state' behind the RandAugment draws -- so that a resumed run continues the uninterrupted one bit for bit."""
     if self.engine is None:
       raise RuntimeError('the network has not been built yet (call it once)')
     state = self.engine.arena.get_optimizer_state()
     state['iterations'] = self.iterations
     state['rng_state'] = self.engine._rng.get_state().cpu().numpy().copy()
     state['mix_rng_state'] = _pack_rng_state(self._mix_rng)
+    if self.augname is not None:
+      state['randaug_rng_state'] = _pack_rng_state(self._ra_rng)
     return state
 
   def set_optimizer_state(self, state):
@@ -380,3 +441,5 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       eng._rng.set_state(torch.as_tensor(state['rng_state'], dtype=torch.uint8))
     if 'mix_rng_state' in state:
       _unpack_rng_state(self._mix_rng, state['mix_rng_state'])
+    if self.augname is not None and 'randaug_rng_state' in state:
+      _unpack_rng_state(self._ra_rng, state['randaug_rng_state'])

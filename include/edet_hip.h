@@ -466,6 +466,28 @@ int edet_mix_images(void* images, int batch, int height, int width, int channels
 int edet_mix_labels(const int32_t* labels, int batch, int num_classes, int height, int width, int n_mixup,
                     const float* weights, const int32_t* boxes, float* soft_labels, int label_ld, void* stream);
 
+/* ---- RandAugment (efficientnetv2/autoaugment.py:79-441, :663-702) on uint8 images [batch][height][width][3] ----
+ * One layer applies one operation per image; the choice and its arguments are device memory, so that the launch sequence
+ * does not depend on the draws and a replayed graph sees new ones.  Operation ids (available_ops, :683-686):
+ * 0 AutoContrast, 1 Equalize, 2 Invert, 3 Rotate, 4 Posterize, 5 Solarize, 6 Color, 7 Contrast, 8 Brightness, 9 Sharpness,
+ * 10 ShearX, 11 ShearY, 12 TranslateX, 13 TranslateY, 14 Cutout, 15 SolarizeAdd; 16 (and anything outside [0, 16]) = copy.
+ * ops int32 [batch]; iargs int32 [batch][4]: Posterize {shift = 8 - bits}, Solarize {threshold}, SolarizeAdd {addition,
+ * threshold}, Cutout {y1, x1, y2, x2 half-open}; fargs fp32 [batch][8]: {a0, a1, a2, b0, b1, b2, factor, unused} -- the
+ * geometric operations read source pixel (round(a0 x + a1 y + a2), round(b0 x + b1 y + b2)), halves away from zero, 128
+ * outside the image; Color / Contrast / Brightness / Sharpness blend with `factor`.  Every index is clamped in the kernel.
+ * The arithmetic (single fp32 operations in a stated order, truncating conversions) is restated in tests/randaug_ref.py and
+ * compared bit for bit.
+ * edet_randaug_stats: for the images whose operation is AutoContrast or Equalize, per-channel histograms (integer LDS
+ * atomics) -> luts uint8 [batch][3][256]; the other images' tables are left alone.  Run it in front of edet_randaug_apply
+ * of the same layer on the same src.
+ * edet_randaug_apply: dst = layer(src), src != dst.  out_dtype EDET_U8: dst uint8, same layout; EDET_F32 / EDET_BF16: the
+ * normalised network input (v - 128) / 128 (preprocessing.py:153; exact in both).  ops == NULL: every image is copied
+ * (with out_dtype F32 / BF16: the normalising copy of a batch without augmentation); iargs / fargs / luts may then be NULL. */
+#define EDET_U8 2
+int edet_randaug_stats(const uint8_t* src, int batch, int height, int width, const int32_t* ops, uint8_t* luts, void* stream);
+int edet_randaug_apply(const uint8_t* src, void* dst, int batch, int height, int width, const int32_t* ops,
+                       const int32_t* iargs, const float* fargs, const uint8_t* luts, int out_dtype, void* stream);
+
 /* ---- optimizer -----------------------------------------------------------------
  * train_lib.py:486-491 (L2), :675-682 (per-tensor clip_by_norm then
  * clip_by_global_norm), Keras SGD momentum, TFA MovingAverage (:176-199).

@@ -6,9 +6,13 @@
          (max - min), implied GB/s;
   step   ms per TrainableModel.train_step (RMSprop, default dropout and stochastic depth, hipGraph replay); with
          `--mix ALPHA` mixup and cutmix are on at that alpha (half the batch each) and the static image buffer is refilled
-         from the caller's batch every step, as a mixing step needs;
+         from the caller's batch every step, as a mixing step needs; with `--randaug` RandAugment is on at the model's own
+         magnitude (uint8 images, refilled every step);
   mix    the mix pass alone (edet_mix_images + edet_mix_labels on the step's buffers): HIP events around `--launches`
          passes, `--reps` repetitions -> median, spread, bytes moved and implied GB/s;
+  randaug the RandAugment pass alone (V2Engine.randaug_batch: the layers' edet_randaug_stats + edet_randaug_apply, the last
+         one storing the normalised bf16 input) with the drawn mix of operations, then the whole batch one operation for each
+         of the 16: HIP events around `--launches` passes, `--reps` repetitions -> median, spread, bytes moved, implied GB/s;
   fwdbwd ms per forward(training) + backward of EffNetV2Model with dropout_rate=0, launched eagerly: what the step had
          before the loss, the dropout and the update existed."""
 import argparse
@@ -22,7 +26,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from automl_amd import _lib, effnetv2_configs, effnetv2_model, effnetv2_train, engine as engine_lib  # noqa: E402
+from automl_amd import _lib, autoaugment, effnetv2_configs, effnetv2_model, effnetv2_train, engine as engine_lib  # noqa: E402
 from automl_amd._lib import call, ptr  # noqa: E402
 
 
@@ -78,14 +82,24 @@ def _data(args):
   return images.to('cuda:0', torch.bfloat16).contiguous(), torch.from_numpy(rng.integers(0, 1000, args.batch)).to('cuda:0', torch.int32)
 
 
+def _data_u8(args):
+  rng = np.random.default_rng(2)
+  images = torch.from_numpy(rng.integers(0, 256, (args.batch, args.size, args.size, 3)).astype(np.uint8))
+  return images.to('cuda:0').contiguous(), torch.from_numpy(rng.integers(0, 1000, args.batch)).to('cuda:0', torch.int32)
+
+
 def bench_step(args):
+  extra = {}
+  if args.randaug:
+    name, layers, ram = effnetv2_train.randaug_params(args.model)
+    extra = dict(augname=name, ra_num_layers=layers, ra_magnitude=ram)
   net = effnetv2_train.TrainableModel(args.model, dtype='bf16', learning_rate=1e-4, weight_decay=1e-5, label_smoothing=0.1,
-                                      use_graph=True, mixup_alpha=args.mix, cutmix_alpha=args.mix)
-  images, labels = _data(args)
+                                      use_graph=True, mixup_alpha=args.mix, cutmix_alpha=args.mix, **extra)
+  images, labels = _data_u8(args) if args.randaug else _data(args)
   first = net.train_step((images, labels))
   for _ in range(max(args.warmup, 2)):
     net.train_step((images, labels), sync_loss=False)
-  if not args.mix:      # (a mixing step mixes the static buffer in place: it is refilled from `images` every step)
+  if not args.mix and not args.randaug:      # (a mixing step mixes the static buffer in place: it is refilled from `images` every step)
     images, labels = net.input_buffers()
   torch.cuda.synchronize()
   t0 = time.perf_counter()
@@ -96,7 +110,9 @@ def bench_step(args):
   last = net.train_step((images, labels))
   print(json.dumps({'phase': 'step', 'workload': '%s %dx%d batch %d bf16 train_step (rmsprop, dropout %g, stochastic depth), '
                     'hipGraph replay%s' % (args.model, args.size, args.size, args.batch, net.cfg_model.dropout_rate,
-                                          ', mixup + cutmix alpha %g' % args.mix if args.mix else ''),
+                                          (', mixup + cutmix alpha %g' % args.mix if args.mix else '') +
+                                          (', RandAugment %d layers M=%g' % (extra['ra_num_layers'], extra['ra_magnitude'])
+                                           if args.randaug else '')),
                     'ms_per_step': round(dt * 1e3, 3), 'images_per_sec': round(args.batch / dt, 1),
                     'first_loss': first['loss'], 'last_loss': last['loss'], 'steps': args.steps}))
 
@@ -138,6 +154,47 @@ def bench_mix(args):
       'GBps': round(moved / (med * 1e-3) / 1e9, 1), 'launches': args.launches, 'reps': args.reps}))
 
 
+def bench_randaug(args):
+  name, layers, ram = effnetv2_train.randaug_params(args.model)
+  net = effnetv2_train.TrainableModel(args.model, dtype='bf16', use_graph=False, augname=name, ra_num_layers=layers, ra_magnitude=ram)
+  images, _ = _data_u8(args)
+  eng = net._ensure_engine(args.batch, args.size, args.size)
+  n = images.numel()
+  # per layer: the apply launch reads and writes the batch (uint8; the last layer writes bf16), the statistics launch reads
+  # the images whose operation is AutoContrast or Equalize once more
+  def moved(ops):
+    stats = int(np.isin(ops, (0, 1)).sum()) * (n // args.batch)
+    return stats + n * (2 * (layers - 1) + 1 + 2)
+
+  def measure(draws):
+    ops, iargs, fargs = autoaugment.randaug_args(draws, ram, args.size, args.size)
+    eng.set_randaug_draws(ops, iargs, fargs)
+    for _ in range(3):
+      eng.randaug_batch(images)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(args.reps):
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(args.launches):
+        eng.randaug_batch(images)
+      e1.record()
+      torch.cuda.synchronize()
+      times.append(e0.elapsed_time(e1) / args.launches)
+    med, b = float(np.median(times)), moved(ops)
+    return {'median_ms': round(med, 5), 'spread_ms': round(max(times) - min(times), 5), 'min_ms': round(min(times), 5),
+            'bytes_per_pass': int(b), 'GBps': round(b / (med * 1e-3) / 1e9, 1)}
+  out = {'phase': 'randaug', 'workload': '%s %dx%d batch %d, %d RandAugment layers at M=%g + normalisation to bf16' % (
+      args.model, args.size, args.size, args.batch, layers, ram), 'launches': args.launches, 'reps': args.reps}
+  out['drawn'] = measure(autoaugment.randaug_draws(net._ra_rng, args.batch, layers))
+  shape = (layers, args.batch)
+  rng = np.random.default_rng(3)
+  for k, op_name in enumerate(autoaugment.AVAILABLE_OPS):
+    sign = np.where(rng.random(shape) >= 0.5, 1.0, -1.0).astype(np.float32)
+    out[op_name] = measure((np.full(shape, k, np.int32), sign, rng.random(shape), rng.random(shape)))
+  print(json.dumps(out))
+
+
 def bench_fwdbwd(args):
   net = effnetv2_model.EffNetV2Model(args.model, 'dropout_rate=0', dtype='bf16')
   images, _ = _data(args)
@@ -162,7 +219,7 @@ def bench_fwdbwd(args):
 
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument('phase', choices=['opt', 'step', 'mix', 'fwdbwd'])
+  ap.add_argument('phase', choices=['opt', 'step', 'mix', 'randaug', 'fwdbwd'])
   ap.add_argument('--model', default='efficientnetv2-s')
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--size', type=int, default=224)
@@ -171,11 +228,12 @@ def main():
   ap.add_argument('--launches', type=int, default=20)
   ap.add_argument('--reps', type=int, default=11)
   ap.add_argument('--mix', type=float, default=0.0, help='mixup_alpha = cutmix_alpha of the step / mix phases (0 = off)')
+  ap.add_argument('--randaug', action='store_true', help='step phase: RandAugment on, at the named model\'s layers and magnitude')
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('bench_v2_train.py needs an MI355X: there is no CPU path and no CPU timing')
   _lib.load()
-  {'opt': bench_opt, 'step': bench_step, 'mix': bench_mix, 'fwdbwd': bench_fwdbwd}[args.phase](args)
+  {'opt': bench_opt, 'step': bench_step, 'mix': bench_mix, 'randaug': bench_randaug, 'fwdbwd': bench_fwdbwd}[args.phase](args)
 
 
 if __name__ == '__main__':
