@@ -374,6 +374,32 @@ class V2Engine(layer_engine.LayerEngine):
     scratch = [self.buf('randaug:scratch%d' % k, (b, h, w, 3), torch.uint8) for k in range(min(int(self.ra_ops.shape[0]) - 1, 2))]
     return autoaugment.apply_layers(images_u8, out, self.ra_ops, self.ra_iargs, self.ra_fargs, self.ra_luts, scratch, self.stream)
 
+  # ---- crop, resize and flip (efficientnetv2/preprocessing.py:22-70) on the device --------------------------------------
+  crop_rows = None      # static int32 [B, 8] buffer of crop_batch (edet_crop_image_t rows), created by set_crop_rows
+
+  def set_crop_rows(self, rows):
+    """This step's crops and flip bits, made on the host by the trainer (v2_preprocessing.train_rows / eval_rows), into the
+    static buffer that crop_batch's kernel reads: int32 [B, 8] in edet_crop_image_t's field order.  Like set_mix_draws this
+    runs OUTSIDE any captured graph, in front of every step, by an asynchronous copy from pinned memory."""
+    b = self.batch
+    if self.crop_rows is None:
+      self.crop_rows = self.buf('crop:rows', (b, 8), torch.int32)
+    r = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32).reshape(b, 8)).pin_memory()
+    self.crop_rows.copy_(r, non_blocking=True)
+
+  def crop_batch(self, raw_u8, to_u8):
+    """Decoded uint8 images on a common canvas [B, Hc, Wc, 3] -> this executor's image size with the rows of set_crop_rows:
+    edet_crop_resize, the first launch of a step.  to_u8: into a static uint8 buffer (clipped and truncated,
+    preprocessing.py:49-50) that randaug_batch reads next; else into the static network-input buffer in the engine's dtype,
+    normalised (v - 128) / 128."""
+    from automl_amd import v2_preprocessing
+    assert self.crop_rows is not None, 'crop_batch needs set_crop_rows first'
+    b, (h, w) = self.batch, self.image_size
+    assert raw_u8.dtype == torch.uint8 and raw_u8.is_contiguous() and raw_u8.dim() == 4 and raw_u8.shape[0] == b and \
+        raw_u8.shape[3] == 3, (raw_u8.dtype, tuple(raw_u8.shape))
+    out = self.buf('crop:u8', (b, h, w, 3), torch.uint8) if to_u8 else self.buf('crop:images', (b, h, w, 3), self.tdtype)
+    return v2_preprocessing.launch(raw_u8, self.crop_rows, out, self.stream)
+
   def l2_loss_eval(self, weight_decay):
     """The same L2 term for an evaluation pass (test_step, main_tf2.py:105-117), added to cls_sums[3] WITHOUT touching the
     gradient arena, the clip factors or the gradient norm (optimizer_local adds weight_decay * w to the gradients): per-segment

@@ -6,7 +6,8 @@ hparams.py:249; 'momentum', 'sgd', 'adam'), the compiled loss ``CategoricalCross
 from_logits=True)`` with the ``acc_top1`` / ``acc_top5`` metrics (:199-207), and ``WarmupLearningRateSchedule``
 (``efficientnetv2/utils.py:78-131``).
 
-One step = [``V2Engine.randaug_batch``: RandAugment of the uint8 batch and its normalisation into the static image
+One step = [``V2Engine.crop_batch``: crop, bilinear resize and flip of the decoded uint8 images, with ``image_size`` set] ->
+[``V2Engine.randaug_batch``: RandAugment of the uint8 batch and its normalisation into the static image
 buffer, with ``augname='randaug'``] -> [``V2Engine.mix_batch``: mixup / cutmix of the images in place and of the labels into soft labels, when an
 alpha is non-zero] -> forward(training) with stochastic depth and head dropout -> ``edet_softmax_xent`` /
 ``edet_softmax_xent_soft`` (loss, d logits and the metric counts in one pass) -> ``V2Engine.backward`` -> ``LayerEngine.optimizer_local`` (the L2 term of ``_reg_l2_loss`` and the
@@ -22,6 +23,18 @@ hands ``distort_image`` after crop, resize, flip and the clip / cast of ``prepro
 (x - 128) / 128 itself; ``test_step`` only normalises.  The draws come from a third host generator seeded by the model's
 seed, whose state travels with the optimizer state under 'randaug_rng_state' (present only when ``augname`` is set).
 
+Crop, resize and flip on the device; staged sizes (``image_size``, ``eval_image_size``, ``transformations``;
+``automl_amd/v2_preprocessing.py``, the reference's ``preprocessing.py:22-70``): ``train_step`` then takes the **decoded uint8
+images** on a common canvas of any size, ``((raw [B, Hc, Wc, 3], sizes [B, 2]), labels)`` or ``({'image': raw, 'size':
+sizes}, {'label': ...})`` (``sizes`` may be left out when every image fills the canvas; ``v2_preprocessing.pad_batch`` makes
+both), draws one crop and one flip bit per image on the host from a fourth generator seeded by the model's seed
+('crop_rng_state' in the optimizer state, present only when ``image_size`` is set), and runs ``edet_crop_resize`` as the first
+launch of the step, in front of RandAugment and the mixing.  ``test_step`` on the same input does ``preprocess_for_eval``.
+``progressive_stages(model_name, epochs)`` restates the staged schedule of ``main_tf2.py:256-275`` and ``set_stage`` /
+``set_image_size`` apply it between steps: a new size builds a new executor on the same variable arena and the step is captured
+again.  The crop sampler's random stream and the float32 staircase of ``tf.image.resize`` are not pinned against TensorFlow
+(``v2_preprocessing``'s docstring).
+
 Labels are the reference's dense float labels [B, C] (``datasets.py:321-323``: one-hot, or mixed by the caller's own
 pipeline; used as they are) or sparse integer class ids [B].  Mixup / cutmix (``datasets.py:191-301``; ``mixup_alpha`` /
 ``cutmix_alpha`` of the constructor, ``set_mix_alphas`` between steps, ``mix_alphas(model_name)`` for a named model's
@@ -31,8 +44,7 @@ seeded by the model's seed whose state travels with the optimizer state.  Mixing
 (a ``ValueError``).
 
 Single GPU.  Not built, and raising or absent rather than ignored: data-parallel classifier training, ``conv_dropout``,
-AutoAugment v0 and ``ra_aa``, the legacy ``effnetv1_*`` preprocessing, the random crop / resize / flip in front of
-RandAugment, progressive resizing, the TF1 trainer's EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
+AutoAugment v0 and ``ra_aa``, the legacy ``effnetv1_*`` preprocessing, the TF1 trainer's EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
 reference's TF2 trainer, keeps none).
 """
 import math
@@ -42,6 +54,7 @@ import torch
 
 from automl_amd import autoaugment
 from automl_amd import effnetv2_model
+from automl_amd import v2_preprocessing
 from automl_amd.layer_engine import LayerEngine, Update, capture_graph
 
 OPTIMIZERS = ('rmsprop', 'momentum', 'sgd', 'adam')
@@ -122,6 +135,44 @@ def randaug_params(model_name):
   return data.get('augname') or None, int(data.get('ra_num_layers') or 2), 15 if ram is None else ram
 
 
+IBASE = 128      # data.ibase of the reference's base configuration (hparams.py:284)
+
+
+def progressive_stages(model_name, epochs, stages=None, ibase=None, sched=None):
+  """The staged schedule of main_tf2.py:256-275 for a named model's recipe (effnetv2_configs: train.isize, train.stages,
+  train.sched, data.ram, data.mixup_alpha, data.cutmix_alpha) over `epochs` epochs -> a list of dicts {start_epoch,
+  end_epoch, image_size, ra_magnitude, mixup_alpha, cutmix_alpha}, one per stage, for TrainableModel.set_stage.
+  Stage k of n: ratio = (k + 1) / n, epochs [int(k / n * epochs), int(ratio * epochs)), image_size = int(ibase +
+  (train_size - ibase) * ratio); with `sched` the magnitude ramps np.linspace(5, ram, n) and both alphas np.linspace(0,
+  alpha, n), else every stage keeps the model's own values.  ibase: None = IBASE; a falsy value = train_size / 2 (:258).
+  stages == 0 (:248-255): one stage at train.isize with the model's own values."""
+  from automl_amd import effnetv2_configs
+  cfg = effnetv2_configs.get_model_config(model_name).as_dict()
+  train, data = cfg.get('train') or {}, cfg.get('data') or {}
+  train_size = int(train['isize'])
+  total = int(train.get('stages') or 0) if stages is None else int(stages)
+  sched = bool(train.get('sched')) if sched is None else bool(sched)
+  ram = data.get('ram')
+  ram = 15 if ram is None else ram
+  mixup, cutmix = float(data.get('mixup_alpha') or 0.0), float(data.get('cutmix_alpha') or 0.0)
+  if total < 0:
+    raise ValueError('stages %r must be >= 0' % (stages,))
+  if not total:
+    return [dict(start_epoch=0, end_epoch=int(epochs), image_size=train_size, ra_magnitude=float(ram), mixup_alpha=mixup,
+                 cutmix_alpha=cutmix)]
+  ibase = (IBASE if ibase is None else ibase) or (train_size / 2)
+  ram_list = np.linspace(5, ram, total) if sched else [ram] * total
+  mixup_list = np.linspace(0, mixup, total) if sched else [mixup] * total
+  cutmix_list = np.linspace(0, cutmix, total) if sched else [cutmix] * total
+  out = []
+  for stage in range(total):
+    ratio = float(stage + 1) / float(total)
+    out.append(dict(start_epoch=int(float(stage) / float(total) * epochs), end_epoch=int(ratio * epochs),
+                    image_size=int(ibase + (train_size - ibase) * ratio), ra_magnitude=float(ram_list[stage]),
+                    mixup_alpha=float(mixup_list[stage]), cutmix_alpha=float(cutmix_list[stage])))
+  return out
+
+
 def mix_split(batch, mixup_alpha, cutmix_alpha):
   """Rows [0, n_mixup) are mixed by mixup, rows [n_mixup, batch) by cutmix (datasets.py:287-300: both -> batch // 2, mixup
   only -> batch, cutmix only -> 0); None = no mixing."""
@@ -197,11 +248,17 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   the unmixed one); a named model's own pair is mix_alphas(model_name).
   augname: None (the default: nothing changes) or 'randaug' -- RandAugment of ra_num_layers layers at ra_magnitude on the
   device (the reference's defaults, preprocessing.py:115-116; a named model's own are randaug_params(model_name));
-  train_step then takes uint8 images.  The other names of the reference raise."""
+  train_step then takes uint8 images.  The other names of the reference raise.
+  image_size: None (the default: nothing changes) or the training size -- train_step then takes decoded uint8 images on a
+  canvas of any size (with their sizes) and crops, resizes and flips them on the device (`transformations`, the
+  reference's 'crop|flip'; '' = the whole image, unflipped); test_step centre-crops and resizes them to eval_image_size
+  (default: image_size).  The captured step is keyed on the canvas shape: a new one makes the next step eager and the one
+  after it captured again, so a fixed canvas (pad_batch(images, canvas)) keeps the graph."""
 
   def __init__(self, model_name='efficientnetv2-s', model_config=None, name=None, weight_decay=0.0, optimizer='rmsprop',
                learning_rate=0.016, label_smoothing=0.0, ema_decay=None, momentum=0.9, use_graph=True, check_device_labels=False,
-               mixup_alpha=0.0, cutmix_alpha=0.0, augname=None, ra_num_layers=2, ra_magnitude=15, **kwargs):
+               mixup_alpha=0.0, cutmix_alpha=0.0, augname=None, ra_num_layers=2, ra_magnitude=15, image_size=None,
+               eval_image_size=None, transformations='crop|flip', **kwargs):
     super().__init__(model_name=model_name, model_config=model_config, include_top=True, name=name or model_name, **kwargs)
     optimizer = str(optimizer).lower()
     if optimizer not in OPTIMIZERS:
@@ -234,6 +291,39 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.ra_magnitude = autoaugment.check_magnitude(ra_magnitude)
     self._ra_rng = autoaugment.randaug_rng(self._seed)
     self._ra_forced = None
+    self.image_size = None if image_size is None else self._check_size(image_size)
+    self.eval_image_size = None if eval_image_size is None else self._check_size(eval_image_size)
+    self.transformations = 'crop|flip' if transformations is None else str(transformations)
+    self._crop_rng = v2_preprocessing.crop_rng(self._seed)
+    self._crop_forced = None
+
+  @staticmethod
+  def _check_size(size):
+    if int(size) != size or int(size) < 1:
+      raise ValueError('image size %r must be a positive integer' % (size,))
+    return int(size)
+
+  def set_image_size(self, size):
+    """A new training size from the next step on (the reference trains each progressive stage at its own size,
+    main_tf2.py:265-284).  The next step builds a new executor for it on the same variable arena and runs eager, the one
+    after it is captured again; optimizer slots, EMA shadows, the iteration count and every generator carry over."""
+    if self.image_size is None:
+      raise ValueError('set_image_size on a model built without image_size')
+    self.image_size = self._check_size(size)
+    self._graph = None
+
+  def set_stage(self, stage):
+    """One entry of progressive_stages: its image size, its RandAugment magnitude (when augname is set) and its mixup /
+    cutmix alphas, from the next step on."""
+    self.set_image_size(stage['image_size'])
+    if self.augname is not None:
+      self.set_randaug(stage['ra_magnitude'])
+    self.set_mix_alphas(stage['mixup_alpha'], stage['cutmix_alpha'])
+
+  def force_crop_rows(self, rows):
+    """Use these rows (v2_preprocessing.train_rows' int32 [batch, 8]) for every following train_step instead of drawing;
+    None = draw again.  For tests and debugging."""
+    self._crop_forced = rows
 
   def set_randaug(self, magnitude):
     """A new RandAugment magnitude from the next step on (the reference ramps it per progressive-training stage,
@@ -264,7 +354,12 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   # ---- plumbing ------------------------------------------------------------------------------------------------------
   def _ensure_engine(self, batch, height, width):
+    old = self.engine
     eng = super()._ensure_engine(batch, height, width)
+    if self.image_size is not None and old is not None and eng is not old:
+      # a new size is a stage of one run (set_image_size; test_step at eval_image_size): the dropout / stochastic-depth
+      # generator goes on where the previous executor's stopped
+      eng._rng.set_state(old._rng.get_state())
     eng.head_dropout = float(self._mconfig.dropout_rate or 0.0)
     if self.optimizer in ('rmsprop', 'adam'):
       eng.arena.use_second_slot('rms' if self.optimizer == 'rmsprop' else 'adam_v')
@@ -277,18 +372,44 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     lr = self.learning_rate
     return float(lr(self.iterations)) if callable(lr) else float(lr)
 
-  def _prepare(self, data, mixing=False, augment=False):
-    """(images, labels) or the reference's ({'image': ...}, {'label': ...}) -> (executor, device images, device labels).
-    Labels: integer class ids [batch] -> int32, or float [batch, num_classes] (one-hot or already mixed rows, used as they
-    are) -> float32.  mixing: the step will mix this batch on the device -- integer labels only.  augment: the step will
-    RandAugment this batch -- uint8 images only; with augname set uint8 images stay uint8 (the engine normalises them)."""
+  @staticmethod
+  def _split(data):
+    """(images, labels), ((raw, sizes), labels) or the reference's ({'image': ..., ['size': ...]}, {'label': ...})
+    -> (images, sizes or None, labels)."""
     images, labels = data
+    sizes = None
     if isinstance(images, dict):
-      images, labels = images['image'], labels['label']
+      sizes, images, labels = images.get('size'), images['image'], labels['label']
+    elif isinstance(images, (tuple, list)):
+      images, sizes = images
     if isinstance(images, np.ndarray):
       images = torch.from_numpy(images)
+    return images, sizes, labels
+
+  @staticmethod
+  def _raw_sizes(sizes, raw):
+    """(height, width) of every image on its canvas, int [batch, 2]; None = every image fills the canvas."""
+    b, hc, wc = int(raw.shape[0]), int(raw.shape[1]), int(raw.shape[2])
+    if sizes is None:
+      return np.tile(np.array([hc, wc], np.int32), (b, 1))
+    s = np.asarray(sizes.cpu() if isinstance(sizes, torch.Tensor) else sizes)
+    if s.shape != (b, 2) or (s < 1).any() or (s[:, 0] > hc).any() or (s[:, 1] > wc).any():
+      raise ValueError('sizes must be [batch, 2] = (height, width) inside the %d x %d canvas, got %s' % (hc, wc, s.tolist()))
+    return s.astype(np.int32)
+
+  def _prepare(self, data, mixing=False, augment=False, crop_size=None):
+    """(images, labels) -> (executor, device images, device labels).
+    Labels: integer class ids [batch] -> int32, or float [batch, num_classes] (one-hot or already mixed rows, used as they
+    are) -> float32.  mixing: the step will mix this batch on the device -- integer labels only.  augment: the step will
+    RandAugment this batch -- uint8 images only; with augname set uint8 images stay uint8 (the engine normalises them).
+    crop_size: the step will crop and resize this batch to that size on the device -- uint8 images on a canvas of any
+    size, which stay as they are; the executor is the one for (crop_size, crop_size)."""
+    images, labels = data
     if images.dim() != 4 or images.shape[-1] != 3:
       raise ValueError('images must be [batch, height, width, 3], got %s' % (tuple(images.shape),))
+    if crop_size is not None and images.dtype != torch.uint8:
+      raise ValueError('image_size=%r: the step takes the decoded uint8 images [batch, canvas_h, canvas_w, 3] that the '
+                       'reference crops, resizes and flips itself (preprocessing.py:22-55), got %s' % (self.image_size, images.dtype))
     if augment and images.dtype != torch.uint8:
       raise ValueError('augname=%r: train_step takes uint8 images [batch, height, width, 3] (what the reference hands '
                        'distort_image, preprocessing.py:49-50,107-111), got %s' % (self.augname, images.dtype))
@@ -308,12 +429,15 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
         # (labels already on the device are the caller's promise unless check_device_labels: the check waits for the device)
         if int(labels.min()) < 0 or int(labels.max()) >= self.spec.num_classes:
           raise ValueError('labels outside [0, %d)' % self.spec.num_classes)
-    eng = self._ensure_engine(int(images.shape[0]), int(images.shape[1]), int(images.shape[2]))
-    if self.augname is not None and images.dtype == torch.uint8:
+    if crop_size is not None:
+      eng = self._ensure_engine(int(images.shape[0]), crop_size, crop_size)
+    else:
+      eng = self._ensure_engine(int(images.shape[0]), int(images.shape[1]), int(images.shape[2]))
+    if crop_size is not None or (self.augname is not None and images.dtype == torch.uint8):
       dev_images = images.to(device=eng.device).contiguous()
     else:
       dev_images = images.to(device=eng.device, dtype=eng.tdtype).contiguous()
-    if mixing and not self.use_graph and dev_images.data_ptr() == images.data_ptr():
+    if crop_size is None and mixing and not self.use_graph and dev_images.data_ptr() == images.data_ptr():
       dev_images = dev_images.clone()      # the eager step mixes in place: never in the caller's own tensor
     return eng, dev_images, labels.to(device=eng.device, dtype=torch.float32 if soft else torch.int32).contiguous()
 
@@ -328,6 +452,9 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   # ---- the step ------------------------------------------------------------------------------------------------------
   def _step_body(self, eng, images, labels):
+    if self.image_size is not None:
+      # decoded uint8 canvases -> the training size: uint8 for RandAugment, else the normalised network input
+      images = eng.crop_batch(images, to_u8=self.augname is not None)
     if self.augname is not None:
       images = eng.randaug_batch(images)      # uint8 -> the engine's own normalised buffer (mixed in place below)
     if self.mixing:
@@ -340,7 +467,8 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   def _graph_step(self, eng, images, labels):
     g = self._graph
-    if g is None or g['engine'] is not eng or g['labels'].dtype != labels.dtype or g['labels'].shape != labels.shape:
+    if g is None or g['engine'] is not eng or g['labels'].dtype != labels.dtype or g['labels'].shape != labels.shape or \
+        g['images'].shape != images.shape:      # (a new canvas shape, with image_size set: captured again)
       g = self._graph = {'engine': eng, 'steps': 0, 'graph': None, 'images': torch.empty_like(images),
                          'labels': torch.empty_like(labels)}
     # (refilled every step: the in-place mixing of a step never sees an already mixed buffer)
@@ -375,7 +503,11 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     already DEVICE tensors are not looked at (that would synchronise every step) unless the model was built with
     check_device_labels=True: an out-of-range device label is then the caller's error, and the kernel -- which reads
     nothing out of bounds for it -- returns a finite loss for a row without a hot class, with no signal."""
-    eng, images, labels = self._prepare(data, mixing=self.mixing, augment=self.augname is not None)
+    images, sizes, labels = self._split(data)
+    eng, images, labels = self._prepare((images, labels), mixing=self.mixing,
+                                        augment=self.augname is not None and self.image_size is None, crop_size=self.image_size)
+    if self.image_size is not None:
+      sizes = self._raw_sizes(sizes, images)      # (checked before any generator moves)
     lr = self._lr()
     eng.set_hyper(lr, self.ema_decay)
     if eng.drop_masks or eng.dropout_mask is not None:
@@ -390,6 +522,11 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       if draws is None:
         draws = autoaugment.randaug_draws(self._ra_rng, eng.batch, self.ra_num_layers)
       eng.set_randaug_draws(*autoaugment.randaug_args(draws, self.ra_magnitude, h, w))
+    if self.image_size is not None:
+      rows = self._crop_forced
+      if rows is None:
+        rows = v2_preprocessing.train_rows(self._crop_rng, sizes, self.transformations)
+      eng.set_crop_rows(rows)
     if self.use_graph:
       self._graph_step(eng, images, labels)
     else:
@@ -401,9 +538,18 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   def test_step(self, data):
     """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117).  Never mixes and never augments; both
-    label kinds; with augname set, uint8 images are normalised (x - 128) / 128 on the way in."""
-    eng, images, labels = self._prepare(data)
-    if images.dtype == torch.uint8:
+    label kinds; with augname set, uint8 images are normalised (x - 128) / 128 on the way in.  With image_size set, uint8
+    images are decoded images on a canvas (train_step's input): preprocess_for_eval's centre crop and resize to
+    eval_image_size or image_size (v2_preprocessing.eval_rows), never flipped, then normalised."""
+    images, sizes, labels = self._split(data)
+    size = None
+    if self.image_size is not None and images.dtype == torch.uint8:
+      size = self.eval_image_size or self.image_size
+    eng, images, labels = self._prepare((images, labels), crop_size=size)
+    if size is not None:
+      eng.set_crop_rows(v2_preprocessing.eval_rows(self._raw_sizes(sizes, images), size))
+      images = eng.crop_batch(images, to_u8=False)
+    elif images.dtype == torch.uint8:
       images = eng.randaug_batch(images, augment=False)
     eng.forward(images, training=False)
     eng.softmax_loss(labels, self.label_smoothing)
@@ -416,7 +562,8 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     """Optimizer slots ('velocity' = the momentum slot, 'rms' = RMSprop's mean square or 'adam_v'), EMA shadows, the
     iteration count (it drives the learning-rate schedule) and the states of the two generators -- 'rng_state' behind the
     dropout and stochastic-depth draws, 'mix_rng_state' behind the mixup / cutmix draws and, only when augname is set,
-    'randaug_rng_state' behind the RandAugment draws -- so that a resumed run continues the uninterrupted one bit for bit."""
+    'randaug_rng_state' behind the RandAugment draws and, only when image_size is set, 'crop_rng_state' behind the crop and
+    flip draws -- so that a resumed run continues the uninterrupted one bit for bit."""
     if self.engine is None:
       raise RuntimeError('the network has not been built yet (call it once)')
     state = self.engine.arena.get_optimizer_state()
@@ -425,6 +572,8 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     state['mix_rng_state'] = _pack_rng_state(self._mix_rng)
     if self.augname is not None:
       state['randaug_rng_state'] = _pack_rng_state(self._ra_rng)
+    if self.image_size is not None:
+      state['crop_rng_state'] = _pack_rng_state(self._crop_rng)
     return state
 
   def set_optimizer_state(self, state):
@@ -443,3 +592,5 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       _unpack_rng_state(self._mix_rng, state['mix_rng_state'])
     if self.augname is not None and 'randaug_rng_state' in state:
       _unpack_rng_state(self._ra_rng, state['randaug_rng_state'])
+    if self.image_size is not None and 'crop_rng_state' in state:
+      _unpack_rng_state(self._crop_rng, state['crop_rng_state'])

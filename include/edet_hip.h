@@ -488,6 +488,23 @@ int edet_randaug_stats(const uint8_t* src, int batch, int height, int width, con
 int edet_randaug_apply(const uint8_t* src, void* dst, int batch, int height, int width, const int32_t* ops,
                        const int32_t* iargs, const float* fargs, const uint8_t* luts, int out_dtype, void* stream);
 
+/* ---- crop, resize and flip of decoded images (efficientnetv2/preprocessing.py:22-70) ----
+ * raw uint8 [batch][canvas_h][canvas_w][3]; image b occupies the top-left height x width of its canvas.  Per image:
+ * tf.image.resize(tf.slice(image, crop), [out_h, out_w]) -- bilinear, half-pixel centres, no antialiasing, the taps clamped
+ * at the CROP edges -- then, with flip != 0, the left-right mirror of the OUTPUT (column x = column out_w - 1 - x of the
+ * resized crop).  out [batch][out_h][out_w][3]: out_dtype EDET_U8 = clip(v, 0, 255) truncated (preprocessing.py:49-50, the
+ * input of edet_randaug_*); EDET_F32 / EDET_BF16 = (v - 128) / 128 (:153), bf16 rounded to nearest even.  The fp32 arithmetic
+ * is that of edet_preprocess_infer, restated in tests/crop_ref.py and compared bit for bit.  Every field of per_image_dev is
+ * clamped in the kernel: height into [1, canvas_h], width into [1, canvas_w], crop_y into [0, height - 1], crop_h into
+ * [1, height - crop_y], likewise for x.  batch <= 65535, canvas_h * canvas_w * 3 < 2^31. */
+typedef struct edet_crop_image { /* 32 bytes, one per image, read from DEVICE memory */
+  int32_t height, width;         /* valid extent of the raw image inside its canvas  */
+  int32_t crop_y, crop_x, crop_h, crop_w;
+  int32_t flip, reserved;
+} edet_crop_image_t;
+int edet_crop_resize(const uint8_t* raw, int batch, int canvas_h, int canvas_w, const edet_crop_image_t* per_image_dev,
+                     void* out, int out_h, int out_w, int out_dtype, void* stream);
+
 /* ---- optimizer -----------------------------------------------------------------
  * train_lib.py:486-491 (L2), :675-682 (per-tensor clip_by_norm then
  * clip_by_global_norm), Keras SGD momentum, TFA MovingAverage (:176-199).

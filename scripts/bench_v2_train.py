@@ -7,12 +7,17 @@
   step   ms per TrainableModel.train_step (RMSprop, default dropout and stochastic depth, hipGraph replay); with
          `--mix ALPHA` mixup and cutmix are on at that alpha (half the batch each) and the static image buffer is refilled
          from the caller's batch every step, as a mixing step needs; with `--randaug` RandAugment is on at the model's own
-         magnitude (uint8 images, refilled every step);
+         magnitude (uint8 images, refilled every step); with `--crop CANVAS` the step takes decoded uint8 images on a
+         CANVAS x CANVAS canvas and crops, resizes and flips them to `--size` on the device first (image_size = --size);
   mix    the mix pass alone (edet_mix_images + edet_mix_labels on the step's buffers): HIP events around `--launches`
          passes, `--reps` repetitions -> median, spread, bytes moved and implied GB/s;
   randaug the RandAugment pass alone (V2Engine.randaug_batch: the layers' edet_randaug_stats + edet_randaug_apply, the last
          one storing the normalised bf16 input) with the drawn mix of operations, then the whole batch one operation for each
          of the 16: HIP events around `--launches` passes, `--reps` repetitions -> median, spread, bytes moved, implied GB/s;
+  crop   the crop / resize / flip pass alone (V2Engine.crop_batch: edet_crop_resize from a `--crop CANVAS` canvas to `--size`,
+         with one step's drawn rows), into uint8 (what RandAugment reads) and into the normalised bf16 input: HIP events
+         around `--launches` passes, `--reps` repetitions -> median, spread, bytes read (sum of the crop areas x 3) and
+         written, implied GB/s and its share of the 8 TB/s HBM peak;
   fwdbwd ms per forward(training) + backward of EffNetV2Model with dropout_rate=0, launched eagerly: what the step had
          before the loss, the dropout and the update existed."""
 import argparse
@@ -27,6 +32,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from automl_amd import _lib, autoaugment, effnetv2_configs, effnetv2_model, effnetv2_train, engine as engine_lib  # noqa: E402
+from automl_amd import v2_preprocessing  # noqa: E402
 from automl_amd._lib import call, ptr  # noqa: E402
 
 
@@ -88,18 +94,30 @@ def _data_u8(args):
   return images.to('cuda:0').contiguous(), torch.from_numpy(rng.integers(0, 1000, args.batch)).to('cuda:0', torch.int32)
 
 
+def _data_raw(args):
+  """Decoded images that fill a --crop x --crop canvas."""
+  rng = np.random.default_rng(2)
+  images = torch.from_numpy(rng.integers(0, 256, (args.batch, args.crop, args.crop, 3), dtype=np.uint8))
+  return images.to('cuda:0').contiguous(), torch.from_numpy(rng.integers(0, 1000, args.batch)).to('cuda:0', torch.int32)
+
+
+HBM_PEAK = 8e12      # bytes / s
+
+
 def bench_step(args):
   extra = {}
+  if args.crop:
+    extra['image_size'] = args.size
   if args.randaug:
     name, layers, ram = effnetv2_train.randaug_params(args.model)
-    extra = dict(augname=name, ra_num_layers=layers, ra_magnitude=ram)
+    extra.update(augname=name, ra_num_layers=layers, ra_magnitude=ram)
   net = effnetv2_train.TrainableModel(args.model, dtype='bf16', learning_rate=1e-4, weight_decay=1e-5, label_smoothing=0.1,
                                       use_graph=True, mixup_alpha=args.mix, cutmix_alpha=args.mix, **extra)
-  images, labels = _data_u8(args) if args.randaug else _data(args)
+  images, labels = _data_raw(args) if args.crop else _data_u8(args) if args.randaug else _data(args)
   first = net.train_step((images, labels))
   for _ in range(max(args.warmup, 2)):
     net.train_step((images, labels), sync_loss=False)
-  if not args.mix and not args.randaug:      # (a mixing step mixes the static buffer in place: it is refilled from `images` every step)
+  if not args.mix and not args.randaug and not args.crop:      # (a mixing step mixes the static buffer in place: it is refilled from `images` every step)
     images, labels = net.input_buffers()
   torch.cuda.synchronize()
   t0 = time.perf_counter()
@@ -112,7 +130,8 @@ def bench_step(args):
                     'hipGraph replay%s' % (args.model, args.size, args.size, args.batch, net.cfg_model.dropout_rate,
                                           (', mixup + cutmix alpha %g' % args.mix if args.mix else '') +
                                           (', RandAugment %d layers M=%g' % (extra['ra_num_layers'], extra['ra_magnitude'])
-                                           if args.randaug else '')),
+                                           if args.randaug else '') +
+                                          (', crop / resize / flip from a %dx%d uint8 canvas' % (args.crop, args.crop) if args.crop else '')),
                     'ms_per_step': round(dt * 1e3, 3), 'images_per_sec': round(args.batch / dt, 1),
                     'first_loss': first['loss'], 'last_loss': last['loss'], 'steps': args.steps}))
 
@@ -195,6 +214,38 @@ def bench_randaug(args):
   print(json.dumps(out))
 
 
+def bench_crop(args):
+  if not args.crop:
+    raise SystemExit('the crop phase needs --crop CANVAS')
+  net = effnetv2_train.TrainableModel(args.model, dtype='bf16', use_graph=False, image_size=args.size)
+  images, _ = _data_raw(args)
+  eng = net._ensure_engine(args.batch, args.size, args.size)
+  rows = v2_preprocessing.train_rows(net._crop_rng, [[args.crop, args.crop]] * args.batch)
+  eng.set_crop_rows(rows)
+  read = int((rows[:, 4].astype(np.int64) * rows[:, 5]).sum()) * 3
+  out = {'phase': 'crop', 'workload': '%s batch %d, crop / resize / flip from a %dx%d uint8 canvas to %dx%d' % (
+      args.model, args.batch, args.crop, args.crop, args.size, args.size), 'launches': args.launches, 'reps': args.reps,
+      'bytes_read': read, 'mean_crop_area_fraction': round(read / 3 / (args.batch * args.crop * args.crop), 4)}
+  for key, to_u8, esize in (('to_uint8', True, 1), ('to_bf16', False, 2)):
+    for _ in range(3):
+      eng.crop_batch(images, to_u8)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(args.reps):
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(args.launches):
+        eng.crop_batch(images, to_u8)
+      e1.record()
+      torch.cuda.synchronize()
+      times.append(e0.elapsed_time(e1) / args.launches)
+    med, written = float(np.median(times)), args.batch * args.size * args.size * 3 * esize
+    out[key] = {'median_ms': round(med, 5), 'spread_ms': round(max(times) - min(times), 5), 'min_ms': round(min(times), 5),
+                'bytes_written': written, 'GBps': round((read + written) / (med * 1e-3) / 1e9, 1),
+                'share_of_hbm_peak': round((read + written) / (med * 1e-3) / HBM_PEAK, 4)}
+  print(json.dumps(out))
+
+
 def bench_fwdbwd(args):
   net = effnetv2_model.EffNetV2Model(args.model, 'dropout_rate=0', dtype='bf16')
   images, _ = _data(args)
@@ -219,7 +270,7 @@ def bench_fwdbwd(args):
 
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument('phase', choices=['opt', 'step', 'mix', 'randaug', 'fwdbwd'])
+  ap.add_argument('phase', choices=['opt', 'step', 'mix', 'randaug', 'crop', 'fwdbwd'])
   ap.add_argument('--model', default='efficientnetv2-s')
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--size', type=int, default=224)
@@ -229,11 +280,13 @@ def main():
   ap.add_argument('--reps', type=int, default=11)
   ap.add_argument('--mix', type=float, default=0.0, help='mixup_alpha = cutmix_alpha of the step / mix phases (0 = off)')
   ap.add_argument('--randaug', action='store_true', help='step phase: RandAugment on, at the named model\'s layers and magnitude')
+  ap.add_argument('--crop', type=int, default=0, metavar='CANVAS',
+                  help='step / crop phases: decoded uint8 images on a CANVAS x CANVAS canvas, cropped and resized to --size on the device')
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('bench_v2_train.py needs an MI355X: there is no CPU path and no CPU timing')
   _lib.load()
-  {'opt': bench_opt, 'step': bench_step, 'mix': bench_mix, 'randaug': bench_randaug, 'fwdbwd': bench_fwdbwd}[args.phase](args)
+  {'opt': bench_opt, 'step': bench_step, 'mix': bench_mix, 'randaug': bench_randaug, 'crop': bench_crop, 'fwdbwd': bench_fwdbwd}[args.phase](args)
 
 
 if __name__ == '__main__':
