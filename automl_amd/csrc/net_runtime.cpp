@@ -5,16 +5,23 @@
 //
 // A plan holds no code and no host pointers: every device pointer is (buffer, offset), every structure / array argument is
 // a byte blob with relocation entries, every stream an index (0 = the caller's stream), every fork / join an event
-// operation.  File layout: automl_amd/plan.py (docstring).
+// operation.  File layout: automl_amd/plan.py (docstring).  The files are decoded and checked in plan_file.cpp, which knows
+// nothing of the device; nothing here reads a file's bytes except to copy checked ranges of them.
+#include <fcntl.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdlib.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
+#include <deque>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "plan_file.h"
 #include "../../include/edet_net.h"
 
 namespace {
@@ -27,9 +34,14 @@ union PlanSlot {
 
 #include "plan_stubs.inc"
 
-constexpr uint32_t NULL_BUF = 0xffffffffu;
-enum OpKind : uint8_t { OP_CALL = 0, OP_EVENT_RECORD = 1, OP_STREAM_WAIT = 2, OP_ALLREDUCE = 3 };
-enum ArgType : uint8_t { A_INT = 0, A_DOUBLE = 1, A_DEVPTR = 2, A_STREAM = 3, A_BLOB = 4, A_NULL = 5 };
+using plan_file::kSlotArenas;
+using plan_file::kSlotNames;
+using plan_file::NUM_SLOTS;
+using plan_file::OP_ALLREDUCE;
+using plan_file::OP_CALL;
+using plan_file::OP_EVENT_RECORD;
+using plan_file::OP_STREAM_WAIT;
+using plan_file::Var;
 
 struct Op {
   uint8_t kind;
@@ -55,30 +67,17 @@ struct Named {
   uint64_t off, bytes;
 };
 
-// One entry of the plan's variable table: `off` / `count` are ELEMENTS inside the variable's fp32 arena ("params" and the
-// slot arenas of the same layout for a trainable variable, "bn_state" for a moving statistic).
-struct Var {
-  std::string name;
-  int trainable = 0;
-  int rank = 0;
-  int64_t dims[4] = {0, 0, 0, 0};
-  uint64_t off = 0, count = 0;
-};
-constexpr int NUM_SLOTS = 4;
-const char* const kSlotNames[NUM_SLOTS] = {"value", "ema", "momentum", "adam_v"};
-
 }  // namespace
 
 struct edet_net {
   std::vector<void*> bufs;
-  std::vector<uint64_t> buf_bytes;
   std::vector<std::string> name_list;
   std::map<std::string, Named> names;
   std::map<std::string, int64_t> props;
   std::vector<Program> programs;
   std::vector<hipStream_t> streams;      // [0] unused (the caller's stream)
   std::vector<hipEvent_t> events;
-  std::vector<std::vector<unsigned char>*> blobs;
+  std::deque<std::vector<unsigned char>> blobs;      // patched structure / array arguments; a deque: stable addresses
   bool use_graph = false;
   std::vector<Var> vars;                 // the variable table, in the Python arena's creation order
   std::map<std::string, int64_t> var_index;
@@ -92,20 +91,28 @@ struct edet_net {
 
 namespace {
 
-struct Reader {
-  FILE* f;
-  bool ok = true;
-  template <class T> T get() {
-    T v{};
-    if (fread(&v, sizeof(T), 1, f) != 1) ok = false;
-    return v;
+// A whole file mapped read-only for the time of a load (an empty file: ok, no bytes).
+struct MappedFile {
+  const unsigned char* data = nullptr;
+  size_t size = 0;
+  bool ok = false;
+  explicit MappedFile(const char* path) {
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return;
+    struct stat st;
+    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) {
+      size = (size_t)st.st_size;
+      void* p = size ? mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+      ok = p != MAP_FAILED;
+      data = ok ? (const unsigned char*)p : nullptr;
+    }
+    close(fd);
   }
-  std::string str() {
-    const uint16_t n = get<uint16_t>();
-    std::string s(n, '\0');
-    if (n && fread(&s[0], 1, n, f) != n) ok = false;
-    return s;
+  ~MappedFile() {
+    if (data) munmap((void*)data, size);
   }
+  MappedFile(const MappedFile&) = delete;
+  MappedFile& operator=(const MappedFile&) = delete;
 };
 
 void free_net(edet_net* net) {
@@ -120,25 +127,7 @@ void free_net(edet_net* net) {
     if (e) (void)hipEventDestroy(e);
   for (auto b : net->bufs)
     if (b) (void)hipFree(b);
-  for (auto b : net->blobs) delete b;
   delete net;
-}
-
-#define NET_CHECK(cond, ...)          \
-  do {                                \
-    if (!(cond)) {                    \
-      edet_set_error(__VA_ARGS__);    \
-      free_net(net);                  \
-      if (f) fclose(f);               \
-      return -1;                      \
-    }                                 \
-  } while (0)
-
-int find_fn(const std::string& name) {
-  const int n = (int)(sizeof(kPlanFnNames) / sizeof(kPlanFnNames[0]));
-  for (int i = 0; i < n; ++i)
-    if (name == kPlanFnNames[i]) return i;
-  return -1;
 }
 
 Program* find_program(edet_net* net, const char* name) {
@@ -233,238 +222,131 @@ int run_program(edet_net* net, const char* name, void* stream) {
   return rc;
 }
 
+void* dev_ptr(const edet_net* net, const plan_file::DevRef& r) {      // bounds: checked by parse_plan
+  return r.buf == plan_file::NULL_BUF ? nullptr : (void*)((char*)net->bufs[r.buf] + r.off);
+}
+
+// Buffers, streams and events of a parsed plan, and its programs with every (buffer, offset) turned into a pointer.
+int instantiate(edet_net* net, const plan_file::PlanFile& pf) {
+  net->bufs.assign(pf.buffers.size(), nullptr);
+  for (size_t i = 0; i < pf.buffers.size(); ++i) {
+    const uint64_t bytes = pf.buffers[i].bytes;
+    const hipError_t e = hipMalloc(&net->bufs[i], bytes ? bytes : 1);
+    EDET_CHECK(e == hipSuccess, "edet_create: hipMalloc(%llu bytes) for buffer %u: %s", (unsigned long long)bytes, (unsigned)i,
+               hipGetErrorString(e));
+    if (!pf.buffers[i].init_offset) {
+      const hipError_t m = hipMemset(net->bufs[i], 0, bytes);
+      EDET_CHECK(m == hipSuccess, "edet_create: hipMemset: %s", hipGetErrorString(m));
+    }
+  }
+  net->streams.assign(pf.nstreams, nullptr);
+  for (uint32_t i = 1; i < pf.nstreams; ++i) {
+    const hipError_t e = hipStreamCreateWithFlags(&net->streams[i], hipStreamNonBlocking);
+    EDET_CHECK(e == hipSuccess, "edet_create: hipStreamCreate: %s", hipGetErrorString(e));
+  }
+  net->events.assign(pf.nevents, nullptr);
+  for (uint32_t i = 0; i < pf.nevents; ++i) {
+    const hipError_t e = hipEventCreateWithFlags(&net->events[i], hipEventDisableTiming);
+    EDET_CHECK(e == hipSuccess, "edet_create: hipEventCreate: %s", hipGetErrorString(e));
+  }
+  for (const plan_file::Name& n : pf.names) {
+    if (n.buf == plan_file::NULL_BUF) {
+      net->props[n.name] = (int64_t)n.off;
+    } else {
+      net->names[n.name] = Named{n.buf, n.off, n.bytes};
+      net->name_list.push_back(n.name);
+    }
+  }
+  net->vars = pf.vars;
+  for (size_t i = 0; i < net->vars.size(); ++i) net->var_index[net->vars[i].name] = (int64_t)i;
+  net->has_vars = pf.has_vars;
+  net->optimizer = pf.optimizer;
+  net->iterations = pf.iterations;
+  net->beta1 = pf.beta1;
+  net->beta2 = pf.beta2;
+  net->programs.resize(pf.programs.size());
+  for (size_t pi = 0; pi < pf.programs.size(); ++pi) {
+    Program& prog = net->programs[pi];
+    prog.name = pf.programs[pi].name;
+    prog.ops.resize(pf.programs[pi].ops.size());
+    for (size_t oi = 0; oi < prog.ops.size(); ++oi) {
+      const plan_file::Op& src = pf.programs[pi].ops[oi];
+      Op& op = prog.ops[oi];
+      op.kind = src.kind;
+      op.fn = src.fn;
+      op.a = src.kind == OP_EVENT_RECORD ? src.event : src.stream;
+      op.b = src.kind == OP_EVENT_RECORD ? src.stream : src.event;
+      op.ptr = src.kind == OP_ALLREDUCE ? dev_ptr(net, src.ptr) : nullptr;
+      op.count = src.count;
+      op.args.resize(src.args.size());
+      for (size_t k = 0; k < src.args.size(); ++k) {
+        const plan_file::Arg& a = src.args[k];
+        PlanSlot& s = op.args[k];
+        s.i = 0;
+        if (a.type == plan_file::A_INT) {
+          s.i = a.i;
+        } else if (a.type == plan_file::A_DOUBLE) {
+          s.f = a.f;
+        } else if (a.type == plan_file::A_DEVPTR) {
+          s.p = dev_ptr(net, a.ptr);
+        } else if (a.type == plan_file::A_STREAM) {
+          op.stream_args.push_back(((int)k << 8) | (int)a.stream);
+        } else if (a.type == plan_file::A_BLOB) {
+          net->blobs.emplace_back((a.blob_bytes + 15) / 8 * 8);      // padded to 8 bytes, plus slack
+          unsigned char* blob = net->blobs.back().data();
+          if (a.blob_bytes) memcpy(blob, a.blob, a.blob_bytes);
+          for (const plan_file::BlobReloc& q : a.relocs) {
+            void* p = dev_ptr(net, q.to);
+            memcpy(blob + q.at, &p, 8);
+          }
+          s.p = blob;
+        }
+      }
+    }
+  }
+  return 0;
+}
+
+// Initial contents through one pinned staging buffer, then the device pointers stored inside them.
+int upload(edet_net* net, const plan_file::PlanFile& pf, const unsigned char* file) {
+  const size_t CH = 64u << 20;
+  void* stage = nullptr;
+  EDET_CHECK(hipHostMalloc(&stage, CH, hipHostMallocDefault) == hipSuccess, "edet_create: hipHostMalloc failed");
+  bool good = true;
+  for (size_t i = 0; i < pf.buffers.size() && good; ++i) {
+    const plan_file::Buffer& b = pf.buffers[i];
+    if (!b.init_offset) continue;
+    for (uint64_t done = 0; good && done < b.bytes; done += CH) {
+      const size_t n = (size_t)(b.bytes - done < CH ? b.bytes - done : CH);
+      memcpy(stage, file + b.init_offset + done, n);      // inside the file: checked by parse_plan
+      good = hipMemcpy((char*)net->bufs[i] + done, stage, n, hipMemcpyHostToDevice) == hipSuccess;
+    }
+  }
+  (void)hipHostFree(stage);
+  EDET_CHECK(good, "edet_create: could not read / upload the initial contents");
+  for (const plan_file::DevReloc& d : pf.dev_relocs) {
+    void* p = dev_ptr(net, d.to);
+    EDET_CHECK(hipMemcpy((char*)net->bufs[d.buf] + d.at, &p, 8, hipMemcpyHostToDevice) == hipSuccess,
+               "edet_create: device relocation upload failed");
+  }
+  EDET_CHECK(hipDeviceSynchronize() == hipSuccess, "edet_create: hipDeviceSynchronize failed");
+  return 0;
+}
+
 }  // namespace
 
+// The file is decoded and checked as a whole (plan_file.cpp) before anything is allocated on the device.
 extern "C" int edet_create(const char* plan_path, edet_net_t** net_out) {
-  edet_net* net = nullptr;
-  FILE* f = nullptr;
-  NET_CHECK(plan_path && net_out, "edet_create: null argument");
+  EDET_CHECK(plan_path && net_out, "edet_create: null argument");
   *net_out = nullptr;
-  f = fopen(plan_path, "rb");
-  NET_CHECK(f, "edet_create: cannot open %s", plan_path);
-  net = new edet_net();
-  Reader r{f};
-  char magic[8];
-  NET_CHECK(fread(magic, 1, 8, f) == 8 && memcmp(magic, "EDETPLAN", 8) == 0, "edet_create: %s is not a plan file", plan_path);
-  const uint32_t version = r.get<uint32_t>(), nbuf = r.get<uint32_t>(), nnames = r.get<uint32_t>(),
-                 nstreams = r.get<uint32_t>(), nevents = r.get<uint32_t>(), nprog = r.get<uint32_t>(),
-                 nfn = r.get<uint32_t>(), ndevreloc = r.get<uint32_t>();
-  NET_CHECK(r.ok && version == 1, "edet_create: plan version %u (this library reads version 1)", version);
-  NET_CHECK(nstreams >= 1 && nstreams <= 255, "edet_create: bad stream count %u", nstreams);
-  std::vector<int> fn_map(nfn);
-  for (uint32_t i = 0; i < nfn; ++i) {
-    const std::string name = r.str();
-    fn_map[i] = find_fn(name);
-    NET_CHECK(fn_map[i] >= 0, "edet_create: the plan calls %s, which this library does not export", name.c_str());
-  }
-  std::vector<uint64_t> init_at(nbuf);
-  net->bufs.assign(nbuf, nullptr);
-  net->buf_bytes.assign(nbuf, 0);
-  for (uint32_t i = 0; i < nbuf; ++i) {
-    net->buf_bytes[i] = r.get<uint64_t>();
-    init_at[i] = r.get<uint64_t>();
-  }
-  NET_CHECK(r.ok, "edet_create: truncated plan (buffer table)");
-  for (uint32_t i = 0; i < nbuf; ++i) {
-    const hipError_t e = hipMalloc(&net->bufs[i], net->buf_bytes[i] ? net->buf_bytes[i] : 1);
-    NET_CHECK(e == hipSuccess, "edet_create: hipMalloc(%llu bytes) for buffer %u: %s",
-              (unsigned long long)net->buf_bytes[i], i, hipGetErrorString(e));
-    if (!init_at[i]) {
-      const hipError_t m = hipMemset(net->bufs[i], 0, net->buf_bytes[i]);
-      NET_CHECK(m == hipSuccess, "edet_create: hipMemset: %s", hipGetErrorString(m));
-    }
-  }
-  auto dev = [&](uint32_t b, uint64_t off) -> void* {
-    return b == NULL_BUF ? nullptr : (void*)((char*)net->bufs[b] + off);
-  };
-  for (uint32_t i = 0; i < nnames; ++i) {
-    const std::string name = r.str();
-    Named n;
-    n.buf = r.get<uint32_t>();
-    n.off = r.get<uint64_t>();
-    n.bytes = r.get<uint64_t>();
-    NET_CHECK(r.ok && (n.buf == NULL_BUF || (n.buf < nbuf && n.off + n.bytes <= net->buf_bytes[n.buf])),
-              "edet_create: bad named buffer '%s'", name.c_str());
-    if (n.buf == NULL_BUF) {
-      net->props[name] = (int64_t)n.off;
-    } else {
-      net->names[name] = n;
-      net->name_list.push_back(name);
-    }
-  }
-  struct DevReloc { uint32_t buf; uint64_t at; uint32_t tbuf; uint64_t toff; };
-  std::vector<DevReloc> devreloc(ndevreloc);
-  for (auto& d : devreloc) {
-    d.buf = r.get<uint32_t>(); d.at = r.get<uint64_t>(); d.tbuf = r.get<uint32_t>(); d.toff = r.get<uint64_t>();
-    NET_CHECK(r.ok && d.buf < nbuf && d.tbuf < nbuf && d.at + 8 <= net->buf_bytes[d.buf] && d.toff <= net->buf_bytes[d.tbuf],
-              "edet_create: bad device relocation");
-  }
-  net->streams.assign(nstreams, nullptr);
-  for (uint32_t i = 1; i < nstreams; ++i) {
-    const hipError_t e = hipStreamCreateWithFlags(&net->streams[i], hipStreamNonBlocking);
-    NET_CHECK(e == hipSuccess, "edet_create: hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  net->events.assign(nevents, nullptr);
-  for (uint32_t i = 0; i < nevents; ++i) {
-    const hipError_t e = hipEventCreateWithFlags(&net->events[i], hipEventDisableTiming);
-    NET_CHECK(e == hipSuccess, "edet_create: hipEventCreate: %s", hipGetErrorString(e));
-  }
-  net->programs.resize(nprog);
-  for (uint32_t pi = 0; pi < nprog; ++pi) {
-    Program& prog = net->programs[pi];
-    prog.name = r.str();
-    const uint32_t nops = r.get<uint32_t>();
-    NET_CHECK(r.ok, "edet_create: truncated plan (program header)");
-    prog.ops.resize(nops);
-    for (uint32_t oi = 0; oi < nops; ++oi) {
-      Op& op = prog.ops[oi];
-      op.kind = r.get<uint8_t>();
-      if (op.kind == OP_CALL) {
-        const uint16_t fid = r.get<uint16_t>();
-        const uint8_t nargs = r.get<uint8_t>();
-        NET_CHECK(r.ok && fid < nfn, "edet_create: bad entry-point index in program '%s'", prog.name.c_str());
-        op.fn = fn_map[fid];
-        NET_CHECK(nargs == kPlanFnArgs[op.fn], "edet_create: %s takes %d arguments, the plan passes %d (plan from another "
-                  "version of the library?)", kPlanFnNames[op.fn], kPlanFnArgs[op.fn], (int)nargs);
-        op.args.resize(nargs);
-        for (int k = 0; k < nargs; ++k) {
-          const uint8_t t = r.get<uint8_t>();
-          PlanSlot s;
-          s.i = 0;
-          if (t == A_INT) {
-            s.i = r.get<int64_t>();
-          } else if (t == A_DOUBLE) {
-            s.f = r.get<double>();
-          } else if (t == A_DEVPTR) {
-            const uint32_t b = r.get<uint32_t>();
-            const uint64_t off = r.get<uint64_t>();
-            NET_CHECK(r.ok && (b == NULL_BUF || (b < nbuf && off <= net->buf_bytes[b])), "edet_create: bad device pointer");
-            s.p = dev(b, off);
-          } else if (t == A_STREAM) {
-            const uint32_t idx = r.get<uint32_t>();
-            NET_CHECK(r.ok && idx < nstreams, "edet_create: bad stream index");
-            op.stream_args.push_back((k << 8) | (int)idx);
-          } else if (t == A_BLOB) {
-            const uint32_t nbytes = r.get<uint32_t>();
-            NET_CHECK(r.ok && nbytes <= (1u << 20), "edet_create: bad argument blob");
-            auto* blob = new std::vector<unsigned char>((nbytes + 15) / 8 * 8);
-            net->blobs.push_back(blob);
-            if (nbytes) NET_CHECK(fread(blob->data(), 1, nbytes, f) == nbytes, "edet_create: truncated plan (blob)");
-            const uint16_t nreloc = r.get<uint16_t>();
-            for (int q = 0; q < nreloc; ++q) {
-              const uint32_t at = r.get<uint32_t>(), b = r.get<uint32_t>();
-              const uint64_t off = r.get<uint64_t>();
-              NET_CHECK(r.ok && at + 8 <= nbytes && b < nbuf && off <= net->buf_bytes[b], "edet_create: bad blob relocation");
-              void* p = dev(b, off);
-              memcpy(blob->data() + at, &p, 8);
-            }
-            s.p = blob->data();
-          } else {
-            NET_CHECK(t == A_NULL, "edet_create: unknown argument type %d", (int)t);
-          }
-          op.args[k] = s;
-        }
-      } else if (op.kind == OP_EVENT_RECORD || op.kind == OP_STREAM_WAIT) {
-        op.a = r.get<uint32_t>();
-        op.b = r.get<uint32_t>();
-        const uint32_t ev = op.kind == OP_EVENT_RECORD ? op.a : op.b, st = op.kind == OP_EVENT_RECORD ? op.b : op.a;
-        NET_CHECK(r.ok && ev < nevents && st < nstreams, "edet_create: bad event operation");
-      } else if (op.kind == OP_ALLREDUCE) {
-        const uint32_t b = r.get<uint32_t>();
-        const uint64_t off = r.get<uint64_t>();
-        op.count = r.get<uint64_t>();
-        op.a = r.get<uint32_t>();
-        NET_CHECK(r.ok && b < nbuf && off + 4 * op.count <= net->buf_bytes[b] && op.a < nstreams, "edet_create: bad all-reduce operation");
-        op.ptr = dev(b, off);
-      } else {
-        NET_CHECK(false, "edet_create: unknown operation %d", (int)op.kind);
-      }
-    }
-    NET_CHECK(r.ok, "edet_create: truncated plan (program '%s')", prog.name.c_str());
-  }
-  // the variable table (optional section behind the last program; layout: automl_amd/plan.py)
-  if (net->props.count("num_variables")) {
-    char vmagic[8];
-    NET_CHECK(fread(vmagic, 1, 8, f) == 8 && memcmp(vmagic, "EDETVARS", 8) == 0,
-              "edet_create: the plan announces a variable table and holds none");
-    const uint32_t nvars = r.get<uint32_t>();
-    NET_CHECK(r.ok && (int64_t)nvars == net->props["num_variables"], "edet_create: bad variable table (count)");
-    auto arena_elems = [&](const char* arena) -> int64_t {
-      auto it = net->names.find(arena);
-      return it == net->names.end() ? -1 : (int64_t)(it->second.bytes / 4);
-    };
-    const int64_t cap_train = arena_elems("params"), cap_state = arena_elems("bn_state");
-    for (const char* slot : {"ema", "velocity", "adam_v"}) {
-      const int64_t c = arena_elems(slot);
-      NET_CHECK(c < 0 || c == cap_train, "edet_create: bad variable table (the '%s' arena is not of the size of 'params')", slot);
-    }
-    net->vars.reserve(nvars < 65536 ? nvars : 65536);
-    for (uint32_t i = 0; i < nvars; ++i) {
-      Var v;
-      v.name = r.str();
-      v.trainable = r.get<uint8_t>() ? 1 : 0;
-      v.rank = r.get<uint8_t>();
-      NET_CHECK(r.ok && v.rank <= 4, "edet_create: bad variable table (entry %u)", i);
-      uint64_t prod = 1;
-      bool fits = true;
-      for (int d = 0; d < v.rank; ++d) {
-        const uint64_t dim = r.get<uint64_t>();
-        fits = fits && dim <= (1ull << 40) && (dim == 0 || prod <= (1ull << 40) / dim);
-        if (fits) prod *= dim;
-        v.dims[d] = (int64_t)dim;
-      }
-      v.off = r.get<uint64_t>();
-      v.count = r.get<uint64_t>();
-      const int64_t cap = v.trainable ? cap_train : cap_state;
-      NET_CHECK(r.ok && fits && v.count == prod && cap >= 0 && v.count <= (uint64_t)cap && v.off <= (uint64_t)cap - v.count,
-                "edet_create: bad variable table (variable '%s' does not fit its arena)", v.name.c_str());
-      NET_CHECK(net->var_index.emplace(v.name, (int64_t)i).second, "edet_create: bad variable table ('%s' twice)", v.name.c_str());
-      net->vars.push_back(v);
-    }
-    net->has_vars = true;
-  }
-  {
-    auto prop = [&](const char* name, int64_t fallback) {
-      auto it = net->props.find(name);
-      return it == net->props.end() ? fallback : it->second;
-    };
-    net->optimizer = (int)prop("optimizer", -1);
-    net->iterations = prop("iterations", 0);
-    NET_CHECK(net->optimizer >= -1 && net->optimizer <= 1 && net->iterations >= 0, "edet_create: bad optimizer properties");
-    if (net->optimizer == 1) {
-      NET_CHECK(net->props.count("adam_beta1_bits") && net->props.count("adam_beta2_bits"),
-                "edet_create: an Adam plan without its beta properties");
-      const int64_t b1 = net->props["adam_beta1_bits"], b2 = net->props["adam_beta2_bits"];
-      memcpy(&net->beta1, &b1, 8);
-      memcpy(&net->beta2, &b2, 8);
-      NET_CHECK(net->beta1 >= 0.0 && net->beta1 < 1.0 && net->beta2 >= 0.0 && net->beta2 < 1.0, "edet_create: bad Adam betas");
-    }
-  }
-  // initial contents, through one pinned staging buffer
-  {
-    const size_t CH = 64u << 20;
-    void* stage = nullptr;
-    NET_CHECK(hipHostMalloc(&stage, CH, hipHostMallocDefault) == hipSuccess, "edet_create: hipHostMalloc failed");
-    bool good = true;
-    for (uint32_t i = 0; i < nbuf && good; ++i) {
-      if (!init_at[i]) continue;
-      good = fseek(f, (long)init_at[i], SEEK_SET) == 0;
-      for (uint64_t done = 0; good && done < net->buf_bytes[i]; done += CH) {
-        const size_t n = (size_t)(net->buf_bytes[i] - done < CH ? net->buf_bytes[i] - done : CH);
-        good = fread(stage, 1, n, f) == n && hipMemcpy((char*)net->bufs[i] + done, stage, n, hipMemcpyHostToDevice) == hipSuccess;
-      }
-    }
-    (void)hipHostFree(stage);
-    NET_CHECK(good, "edet_create: could not read / upload the initial contents");
-  }
-  for (const auto& d : devreloc) {
-    void* p = dev(d.tbuf, d.toff);
-    NET_CHECK(hipMemcpy((char*)net->bufs[d.buf] + d.at, &p, 8, hipMemcpyHostToDevice) == hipSuccess,
-              "edet_create: device relocation upload failed");
-  }
-  NET_CHECK(hipDeviceSynchronize() == hipSuccess, "edet_create: hipDeviceSynchronize failed");
-  fclose(f);
-  *net_out = net;
+  const MappedFile file(plan_path);
+  EDET_CHECK(file.ok, "edet_create: cannot open %s", plan_path);
+  plan_file::PlanFile pf;
+  std::string err;
+  EDET_CHECK(plan_file::parse_plan(file.data, file.size, &pf, &err), "edet_create: %s: %s", plan_path, err.c_str());
+  std::unique_ptr<edet_net, void (*)(edet_net*)> net(new edet_net(), free_net);      // released on every failure below
+  if (instantiate(net.get(), pf) != 0 || upload(net.get(), pf, file.data) != 0) return -1;
+  *net_out = net.release();
   return 0;
 }
 
@@ -554,6 +436,11 @@ extern "C" int edet_train_step(edet_net_t* net, float learning_rate, float ema_d
 // ---- variables by name ------------------------------------------------------------------------------------------------
 namespace {
 
+// The named arena that holds a slot of a variable, at the variable's element offset (the table: plan_file.h).
+const char* slot_arena(const Var& v, int slot) {
+  return slot == EDET_SLOT_VALUE && !v.trainable ? plan_file::kStateArena : kSlotArenas[slot];
+}
+
 // Device address of a variable's slot, or nullptr with the error text set (the message names the variable).
 float* slot_ptr(edet_net* net, const Var& v, int slot, const char* who) {
   if (slot < 0 || slot >= NUM_SLOTS) {
@@ -564,22 +451,19 @@ float* slot_ptr(edet_net* net, const Var& v, int slot, const char* who) {
     edet_set_error("%s: variable '%s' is not trainable: it has no %s slot", who, v.name.c_str(), kSlotNames[slot]);
     return nullptr;
   }
-  const char* arena = slot == EDET_SLOT_VALUE ? (v.trainable ? "params" : "bn_state")
-                      : slot == EDET_SLOT_EMA ? "ema" : slot == EDET_SLOT_MOMENTUM ? "velocity" : "adam_v";
-  auto it = net->names.find(arena);
+  auto it = net->names.find(slot_arena(v, slot));
   if (it == net->names.end() || (slot == EDET_SLOT_ADAM_V && net->optimizer != 1)) {
     edet_set_error("%s: variable '%s' has no %s slot in this plan%s", who, v.name.c_str(), kSlotNames[slot],
                    slot == EDET_SLOT_ADAM_V ? " (its optimizer is not Adam)" : "");
     return nullptr;
   }
-  return (float*)((char*)net->bufs[it->second.buf] + it->second.off) + v.off;      // bounds: checked by edet_create
+  return (float*)((char*)net->bufs[it->second.buf] + it->second.off) + v.off;      // bounds: checked by parse_plan
 }
 
 bool has_slot(edet_net* net, const Var& v, int slot) {
   if (slot == EDET_SLOT_VALUE) return true;
-  if (!v.trainable) return false;
-  if (slot == EDET_SLOT_ADAM_V) return net->optimizer == 1 && net->names.count("adam_v");
-  return net->names.count(slot == EDET_SLOT_EMA ? "ema" : "velocity") != 0;
+  if (!v.trainable || (slot == EDET_SLOT_ADAM_V && net->optimizer != 1)) return false;
+  return net->names.count(slot_arena(v, slot)) != 0;
 }
 
 const Var* find_var(edet_net* net, const char* name, const char* who) {
@@ -710,67 +594,43 @@ extern "C" int edet_net_save_state(edet_net_t* net, const char* path) {
 extern "C" int edet_net_load_state(edet_net_t* net, const char* path) {
   EDET_CHECK(net && path, "edet_net_load_state: null argument");
   EDET_CHECK(net->has_vars, "edet_net_load_state: the plan was recorded without a variable table");
-  FILE* f = fopen(path, "rb");
-  EDET_CHECK(f, "edet_net_load_state: cannot open %s", path);
-  struct Rec { const Var* v; int slot; std::vector<float> data; };
-  std::vector<Rec> recs;
+  const MappedFile file(path);
+  EDET_CHECK(file.ok, "edet_net_load_state: cannot open %s", path);
+  plan_file::StateFile sf;
+  std::string err;
+  EDET_CHECK(plan_file::parse_state(file.data, file.size, &sf, &err), "edet_net_load_state: %s: %s", path, err.c_str());
+  // pass 1: every record against the plan; nothing on the device changes unless the whole file is good
   std::vector<char> seen(net->vars.size() * NUM_SLOTS, 0);
-  Reader r{f};
-  char magic[8];
-  int64_t iterations = 0;
-  // pass 1: read and check everything; nothing on the device changes unless the whole file is good
-#define STATE_CHECK(cond, ...)       \
-  do {                               \
-    if (!(cond)) {                   \
-      edet_set_error(__VA_ARGS__);   \
-      fclose(f);                     \
-      return -1;                     \
-    }                                \
-  } while (0)
-  STATE_CHECK(fread(magic, 1, 8, f) == 8 && memcmp(magic, "EDETSTAT", 8) == 0, "edet_net_load_state: %s is not a state file", path);
-  const uint32_t version = r.get<uint32_t>(), nrec = r.get<uint32_t>();
-  iterations = r.get<int64_t>();
-  STATE_CHECK(r.ok && version == 1, "edet_net_load_state: state file version %u (this library reads version 1)", version);
-  STATE_CHECK(iterations >= 0 && nrec <= seen.size(), "edet_net_load_state: %s holds %u records, the plan has %llu variable "
-              "slots", path, nrec, (unsigned long long)seen.size());
-  recs.reserve(nrec);
-  for (uint32_t i = 0; i < nrec; ++i) {
-    const std::string name = r.str();
-    const int slot = r.get<uint8_t>(), rank = r.get<uint8_t>();
-    STATE_CHECK(r.ok && rank <= 4, "edet_net_load_state: truncated or bad record %u", i);
-    uint64_t dims[4] = {0, 0, 0, 0};
-    for (int d = 0; d < rank; ++d) dims[d] = r.get<uint64_t>();
-    const uint64_t count = r.get<uint64_t>();
-    STATE_CHECK(r.ok, "edet_net_load_state: truncated state file (variable '%s')", name.c_str());
-    auto it = net->var_index.find(name);
-    STATE_CHECK(it != net->var_index.end(), "edet_net_load_state: the plan has no variable '%s'", name.c_str());
+  EDET_CHECK(sf.records.size() <= seen.size(), "edet_net_load_state: %s holds %u records, the plan has %llu variable slots", path,
+             (unsigned)sf.records.size(), (unsigned long long)seen.size());
+  std::vector<const Var*> var_of;
+  for (const plan_file::StateRecord& rec : sf.records) {
+    const char* name = rec.name.c_str();
+    auto it = net->var_index.find(rec.name);
+    EDET_CHECK(it != net->var_index.end(), "edet_net_load_state: the plan has no variable '%s'", name);
     const Var& v = net->vars[(size_t)it->second];
-    STATE_CHECK(slot < NUM_SLOTS && has_slot(net, v, slot), "edet_net_load_state: variable '%s' has no slot %d in this plan",
-                name.c_str(), slot);
-    STATE_CHECK(count == v.count, "edet_net_load_state: variable '%s' has %llu elements, the file holds %llu", name.c_str(),
-                (unsigned long long)v.count, (unsigned long long)count);
-    bool same = rank == v.rank;
-    for (int d = 0; same && d < rank; ++d) same = dims[d] == (uint64_t)v.dims[d];
-    STATE_CHECK(same, "edet_net_load_state: variable '%s': the shape in the file differs from the plan's", name.c_str());
-    char& mark = seen[(size_t)it->second * NUM_SLOTS + slot];
-    STATE_CHECK(!mark, "edet_net_load_state: variable '%s' comes twice in slot %s", name.c_str(), kSlotNames[slot]);
+    EDET_CHECK(rec.slot < NUM_SLOTS && has_slot(net, v, rec.slot), "edet_net_load_state: variable '%s' has no slot %d in this plan",
+               name, rec.slot);
+    EDET_CHECK(rec.count == v.count, "edet_net_load_state: variable '%s' has %llu elements, the file holds %llu", name,
+               (unsigned long long)v.count, (unsigned long long)rec.count);
+    bool same = rec.rank == v.rank;
+    for (int d = 0; same && d < rec.rank; ++d) same = rec.dims[d] == (uint64_t)v.dims[d];
+    EDET_CHECK(same, "edet_net_load_state: variable '%s': the shape in the file differs from the plan's", name);
+    char& mark = seen[(size_t)it->second * NUM_SLOTS + rec.slot];
+    EDET_CHECK(!mark, "edet_net_load_state: variable '%s' comes twice in slot %s", name, kSlotNames[rec.slot]);
     mark = 1;
-    recs.push_back(Rec{&v, slot, std::vector<float>((size_t)count)});      // count == v.count: bounded by the arena
-    STATE_CHECK(count == 0 || fread(recs.back().data.data(), 4, (size_t)count, f) == (size_t)count,
-                "edet_net_load_state: truncated state file (variable '%s')", name.c_str());
+    var_of.push_back(&v);
   }
-  STATE_CHECK(fgetc(f) == EOF, "edet_net_load_state: %s carries bytes after its last record", path);
   for (size_t i = 0; i < net->vars.size(); ++i)
     for (int slot = 0; slot < NUM_SLOTS; ++slot)
-      STATE_CHECK(seen[i * NUM_SLOTS + slot] || !has_slot(net, net->vars[i], slot),
-                  "edet_net_load_state: %s does not hold the %s of variable '%s'", path, kSlotNames[slot], net->vars[i].name.c_str());
-#undef STATE_CHECK
-  fclose(f);
-  for (const Rec& rec : recs) {
-    float* p = slot_ptr(net, *rec.v, rec.slot, "edet_net_load_state");
-    if (!p || edet_copy_to_device(p, rec.data.data(), rec.data.size() * 4) != 0) return -1;
+      EDET_CHECK(seen[i * NUM_SLOTS + slot] || !has_slot(net, net->vars[i], slot),
+                 "edet_net_load_state: %s does not hold the %s of variable '%s'", path, kSlotNames[slot], net->vars[i].name.c_str());
+  // pass 2: the payloads, straight from the mapped file
+  for (size_t i = 0; i < sf.records.size(); ++i) {
+    float* p = slot_ptr(net, *var_of[i], sf.records[i].slot, "edet_net_load_state");
+    if (!p || edet_copy_to_device(p, sf.records[i].data, (size_t)sf.records[i].count * 4) != 0) return -1;
   }
-  net->iterations = iterations;
+  net->iterations = sf.iterations;
   return 0;
 }
 

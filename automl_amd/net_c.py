@@ -1,5 +1,5 @@
 """ctypes binding of the network-level C ABI (include/edet_net.h): a recorded step plan replayed by the library's own
-host runtime (csrc/net_runtime.cpp).  What a compiled host would call; here for the parity tests and for Python callers
+host runtime (csrc/plan_file.cpp, csrc/net_runtime.cpp).  What a compiled host would call; here for the parity tests and for Python callers
 that want a step without the engine (no tape, no per-launch Python)."""
 import ctypes
 

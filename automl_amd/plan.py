@@ -1,5 +1,6 @@
 """Step plans: the launches of an engine pass, recorded at the C ABI and written to a file that a host WITHOUT a Python
-interpreter replays (csrc/net_runtime.cpp behind include/edet_net.h: edet_create / edet_forward / edet_train_step).
+interpreter replays (behind include/edet_net.h: edet_create / edet_forward / edet_train_step; csrc/plan_file.cpp decodes and
+checks the whole file on the host before csrc/net_runtime.cpp allocates anything on the device, then replays it).
 
 Why a recorded plan and not a second engine in C++: every launch of a step already goes through `_lib.call` (the layers,
 and since round 6 the clears, the side chain's gradient join and the loss normalizer: edet_zero / edet_axpy_clear /
@@ -45,6 +46,7 @@ import bisect
 import contextlib
 import ctypes
 import gc
+import mmap
 import os
 import re
 import struct
@@ -346,118 +348,169 @@ class Recorder(object):
             'entry_points': len(fn_ids), 'streams': len(self.streams), 'events': self.nevents}
 
 
-def _read_header(path):
-  with open(path, 'rb') as f:
-    raw = f.read(8 + 32)
-    assert raw[:8] == MAGIC, 'not a plan file'
-    version, nbuf, nnames, nstreams, nevents, nprog, nfn, ndevreloc = struct.unpack('<IIIIIIII', raw[8:])
+class _Cursor(object):
+  """The one reader of plan and state files: forward through a file's bytes, every read checked against what remains.
+  ValueError (path, what was being read) for a read past the end."""
 
-    def s16():
-      (n,) = struct.unpack('<H', f.read(2))
-      return f.read(n).decode()
-    fns = [s16() for _ in range(nfn)]
-    bufs = [struct.unpack('<QQ', f.read(16)) for _ in range(nbuf)]
-    names = {}
-    for _ in range(nnames):
-      n = s16()
-      names[n] = struct.unpack('<IQQ', f.read(20))
-  return {'version': version, 'entry_points': fns, 'buffers': bufs, 'names': names, 'streams': nstreams,
-          'events': nevents, 'programs': nprog, 'device_relocations': ndevreloc}
+  def __init__(self, path, kind):
+    self.path, self.kind, self.pos = path, kind, 0
+    with open(path, 'rb') as f:      # mapped, not read: a plan carries its initial contents, of which nothing is decoded
+      self.size = os.fstat(f.fileno()).st_size
+      self.data = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if self.size else b''
+
+  def fail(self, what):
+    return ValueError('%s: %s' % (self.path, what))
+
+  def raw(self, n, what):
+    if n > len(self.data) - self.pos:
+      raise self.fail('truncated %s (%s)' % (self.kind, what))
+    self.pos += n
+    return self.data[self.pos - n:self.pos]
+
+  def take(self, fmt, what):
+    vals = struct.unpack('<' + fmt, self.raw(struct.calcsize('<' + fmt), what))
+    return vals if len(vals) > 1 else vals[0]
+
+  def s16(self, what):
+    return self.raw(self.take('H', what), what).decode(errors='replace')
+
+  def count(self, n, min_record, what):
+    """n records of at least min_record bytes each must fit what remains (asked before anything loops n times)."""
+    if n > (len(self.data) - self.pos) // min_record:
+      raise self.fail('truncated %s (%s)' % (self.kind, what))
+    return n
 
 
-def read_summary(path):
-  """Header of a plan file (CPU: the format test and `python -m automl_amd.plan FILE`); 'variables': the variable table
-  (see read_plan), empty for a plan written without one."""
-  out = _read_header(path)
-  out['variables'] = read_plan(path)['variables'] if 'num_variables' in out['names'] else []
-  return out
+def _fits(off, n, cap):
+  return n <= cap and off <= cap - n
 
 
 def read_plan(path):
-  """The whole plan decoded (CPU; the mirror of csrc/net_runtime.cpp's loader): summary + 'ops': program -> list of
-  ('call', entry point, [args]) / ('evrec', event, stream) / ('wait', stream, event) / ('allreduce', buf, off, count, stream);
-  args: ('i', v) ('f', v) ('p', buf, off) ('s', idx) ('b', bytes, [(at, buf, off)]) ('n',); 'variables': the variable table
-  as [{'name', 'shape', 'trainable', 'offset', 'count'}] (offset / count in elements of the variable's arena), empty for
-  a plan written without one."""
-  out = _read_header(path)
-  with open(path, 'rb') as f:
-    # everything in front of the initial contents (which start at the smallest offset the buffer table names)
-    first = min([b[1] for b in out['buffers'] if b[1]] or [0])
-    data = f.read(first) if first else f.read()
-  pos = [8 + 32]
+  """The whole plan decoded and checked (CPU; the mirror of csrc/plan_file.cpp, except that the variable table is not held
+  against its arenas and the optimizer properties are not read): 'version', 'entry_points', 'buffers' [(bytes, init offset)],
+  'names' {name: (buf, offset, bytes)}, 'streams', 'events', 'programs', 'device_relocations' (counts); 'ops': program ->
+  list of ('call', entry point, [args]) / ('evrec', event, stream) / ('wait', stream, event) / ('allreduce', buf, off, count,
+  stream); args: ('i', v) ('f', v) ('p', buf, off) ('s', idx) ('b', bytes, [(at, buf, off)]) ('n',);
+  'device_relocation_table' [(buf, at, target buf, target offset)]; 'variables': the variable table as [{'name', 'shape',
+  'trainable', 'offset', 'count'}] (offset / count in elements of the variable's arena), empty for a plan written without
+  one.  ValueError for a file that is not a plan or that the library's loader would refuse for its structure."""
+  c = _Cursor(path, 'plan')
+  if c.data[:8] != MAGIC:
+    raise c.fail('not a plan file')
+  c.pos = 8
+  version, nbuf, nnames, nstreams, nevents, nprog, nfn, ndevreloc = c.take('IIIIIIII', 'header')
+  if version != VERSION:
+    raise c.fail('plan version %d (this reader knows version %d)' % (version, VERSION))
+  if not 1 <= nstreams <= 255:
+    raise c.fail('bad stream count %d' % nstreams)
+  arity = {name: len(args) for name, args in header_prototypes().items()}
+  fns = [c.s16('entry-point names') for _ in range(c.count(nfn, 2, 'entry-point names'))]
+  for name in fns:
+    if name not in arity:
+      raise c.fail('the plan calls %s, which this library does not export' % name)
+  bufs = [c.take('QQ', 'buffer table') for _ in range(c.count(nbuf, 16, 'buffer table'))]
 
-  def take(fmt):
-    vals = struct.unpack_from('<' + fmt, data, pos[0])
-    pos[0] += struct.calcsize('<' + fmt)
-    return vals if len(vals) > 1 else vals[0]
-
-  def s16():
-    n = take('H')
-    v = data[pos[0]:pos[0] + n].decode()
-    pos[0] += n
-    return v
-  for _ in out['entry_points']:
-    s16()
-  pos[0] += 16 * len(out['buffers'])
-  for _ in range(len(out['names'])):
-    s16()
-    pos[0] += 20
-  devrel = [take('IQIQ') for _ in range(out['device_relocations'])]
+  def ref(b, off, null=False):
+    return (null and b == NULL_BUF) or (b < nbuf and off <= bufs[b][0])
+  names = {}
+  for _ in range(c.count(nnames, 22, 'names')):
+    n = c.s16('names')
+    b, off, nbytes = names[n] = c.take('IQQ', 'names')
+    if b != NULL_BUF and not (b < nbuf and _fits(off, nbytes, bufs[b][0])):
+      raise c.fail("bad named buffer '%s'" % n)
+  devrel = [c.take('IQIQ', 'device relocations') for _ in range(c.count(ndevreloc, 24, 'device relocations'))]
+  for b, at, tb, toff in devrel:
+    if not (b < nbuf and _fits(at, 8, bufs[b][0]) and ref(tb, toff)):
+      raise c.fail('bad device relocation')
   progs = {}
-  for _ in range(out['programs']):
-    name = s16()
+  for _ in range(c.count(nprog, 6, 'programs')):
+    name = c.s16('program header')
+    what = "program '%s'" % name
     ops = []
-    for _ in range(take('I')):
-      kind = take('B')
+    for _ in range(c.count(c.take('I', 'program header'), 4, 'program header')):
+      kind = c.take('B', what)
       if kind == 0:
-        fid, nargs = take('HB')
+        fid, nargs = c.take('HB', what)
+        if fid >= nfn:
+          raise c.fail('bad entry-point index in %s' % what)
+        if nargs != arity[fns[fid]]:
+          raise c.fail('%s takes %d arguments, the plan passes %d' % (fns[fid], arity[fns[fid]], nargs))
         args = []
         for _ in range(nargs):
-          t = take('B')
+          t = c.take('B', what)
           if t == 0:
-            args.append(('i', take('q')))
+            args.append(('i', c.take('q', what)))
           elif t == 1:
-            args.append(('f', take('d')))
+            args.append(('f', c.take('d', what)))
           elif t == 2:
-            args.append(('p',) + take('IQ'))
+            args.append(('p',) + c.take('IQ', what))
+            if not ref(*args[-1][1:], null=True):
+              raise c.fail('bad device pointer')
           elif t == 3:
-            args.append(('s', take('I')))
+            args.append(('s', c.take('I', what)))
+            if args[-1][1] >= nstreams:
+              raise c.fail('bad stream index')
           elif t == 4:
-            n = take('I')
-            raw = data[pos[0]:pos[0] + n]
-            pos[0] += n
-            args.append(('b', raw, [take('IIQ') for _ in range(take('H'))]))
-          else:
-            assert t == 5, t
+            n = c.take('I', what)
+            if n > 1 << 20:
+              raise c.fail('bad argument blob')
+            raw = c.raw(n, 'blob')
+            relocs = [c.take('IIQ', what) for _ in range(c.count(c.take('H', what), 16, 'blob relocations'))]
+            if not all(_fits(at, 8, n) and ref(b, off) for at, b, off in relocs):
+              raise c.fail('bad blob relocation')
+            args.append(('b', raw, relocs))
+          elif t == 5:
             args.append(('n',))
-        ops.append(('call', out['entry_points'][fid], args))
-      elif kind == 1:
-        ops.append(('evrec',) + take('II'))
-      elif kind == 2:
-        ops.append(('wait',) + take('II'))
+          else:
+            raise c.fail('unknown argument type %d' % t)
+        ops.append(('call', fns[fid], args))
+      elif kind in (1, 2):
+        a, b = c.take('II', what)
+        ev, st = (a, b) if kind == 1 else (b, a)
+        if ev >= nevents or st >= nstreams:
+          raise c.fail('bad event operation')
+        ops.append(('evrec' if kind == 1 else 'wait', a, b))
+      elif kind == 3:
+        b, off, count, stream = c.take('IQQI', what)
+        if not (b < nbuf and count <= bufs[b][0] // 4 and _fits(off, 4 * count, bufs[b][0]) and stream < nstreams):
+          raise c.fail('bad all-reduce operation')
+        ops.append(('allreduce', b, off, count, stream))
       else:
-        assert kind == 3, kind
-        ops.append(('allreduce',) + take('IQQI'))
+        raise c.fail('unknown operation %d' % kind)
     progs[name] = ops
-  out['ops'] = progs
-  out['device_relocation_table'] = devrel
   variables = []
-  if 'num_variables' in out['names']:
-    if data[pos[0]:pos[0] + 8] != VARS_MAGIC:
-      raise ValueError('%s: the plan announces a variable table and holds none' % path)
-    pos[0] += 8
-    nvars = take('I')
-    if nvars != out['names']['num_variables'][1]:
-      raise ValueError('%s: variable table of %d entries, property num_variables = %d' % (path, nvars, out['names']['num_variables'][1]))
+  if 'num_variables' in names:
+    if c.data[c.pos:c.pos + 8] != VARS_MAGIC:
+      raise c.fail('the plan announces a variable table and holds none')
+    c.pos += 8
+    nvars = c.count(c.take('I', 'variable table'), 20, 'variable table')
+    if nvars != names['num_variables'][1]:
+      raise c.fail('variable table of %d entries, property num_variables = %d' % (nvars, names['num_variables'][1]))
+    seen = set()
     for _ in range(nvars):
-      name = s16()
-      trainable, rank = take('BB')
+      name = c.s16('variable table')
+      trainable, rank = c.take('BB', name)
       if rank > MAX_RANK:
-        raise ValueError('%s: variable %s of rank %d' % (path, name, rank))
-      shape = tuple(take('Q') for _ in range(rank))
-      off, count = take('QQ')
+        raise c.fail('bad variable table (variable %s of rank %d)' % (name, rank))
+      shape = tuple(c.take('Q', name) for _ in range(rank))
+      off, count = c.take('QQ', name)
+      if count != int(np.prod(shape, dtype=object)) or name in seen:
+        raise c.fail("bad variable table (variable '%s': count %d of shape %s, or twice)" % (name, count, shape))
+      seen.add(name)
       variables.append({'name': name, 'shape': shape, 'trainable': bool(trainable), 'offset': off, 'count': count})
-  out['variables'] = variables
+  for i, (nbytes, at) in enumerate(bufs):
+    if at and not _fits(at, nbytes, c.size):
+      raise c.fail('truncated plan (the initial contents of buffer %d lie outside the file)' % i)
+  return {'version': version, 'entry_points': fns, 'buffers': bufs, 'names': names, 'streams': nstreams, 'events': nevents,
+          'programs': nprog, 'device_relocations': ndevreloc, 'ops': progs, 'device_relocation_table': devrel,
+          'variables': variables}
+
+
+def read_summary(path):
+  """read_plan without the operations and the device relocation table (the format test and `python -m automl_amd.plan
+  FILE`)."""
+  out = read_plan(path)
+  del out['ops'], out['device_relocation_table']
   return out
 
 
@@ -483,45 +536,29 @@ def write_state(path, variables, ema=None, momentum=None, adam_v=None, iteration
 def read_state(path):
   """-> {'variables': {name: array}, 'ema': {...}, 'momentum': {...}, 'adam_v': {...}, 'iterations': n} of a state file;
   ValueError for a file that is not one, is truncated or carries bytes after its last record."""
-  with open(path, 'rb') as f:
-    data = f.read()
-  if data[:8] != STATE_MAGIC:
+  c = _Cursor(path, 'state file')
+  if c.data[:8] != STATE_MAGIC:
     raise ValueError('%s is not a state file' % path)
-  pos = [8]
-
-  def take(fmt, what):
-    n = struct.calcsize('<' + fmt)
-    if n > len(data) - pos[0]:
-      raise ValueError('%s: truncated state file (%s)' % (path, what))
-    vals = struct.unpack_from('<' + fmt, data, pos[0])
-    pos[0] += n
-    return vals if len(vals) > 1 else vals[0]
-  version, nrec, iterations = take('IIq', 'header')
+  c.pos = 8
+  version, nrec, iterations = c.take('IIq', 'header')
   if version != STATE_VERSION:
-    raise ValueError('%s: state file version %d (this reader knows version %d)' % (path, version, STATE_VERSION))
+    raise c.fail('state file version %d (this reader knows version %d)' % (version, STATE_VERSION))
   out = {k: {} for k in STATE_SLOTS}
-  for _ in range(nrec):
-    n = take('H', 'name')
-    if n > len(data) - pos[0]:
-      raise ValueError('%s: truncated state file (name)' % path)
-    name = data[pos[0]:pos[0] + n].decode()
-    pos[0] += n
-    slot, rank = take('BB', name)
+  for _ in range(c.count(nrec, 12, 'records')):
+    name = c.s16('name')
+    slot, rank = c.take('BB', name)
     if slot >= len(STATE_SLOTS) or rank > MAX_RANK:
-      raise ValueError('%s: variable %s: bad slot %d / rank %d' % (path, name, slot, rank))
-    shape = tuple(take('Q', name) for _ in range(rank))
-    count = take('Q', name)
-    want = 1
-    for d in shape:
-      want *= d
-    if count != want or count > (len(data) - pos[0]) // 4:
-      raise ValueError('%s: truncated state file or bad count (variable %s, %d elements)' % (path, name, count))
+      raise c.fail('variable %s: bad slot %d / rank %d' % (name, slot, rank))
+    shape = tuple(c.take('Q', name) for _ in range(rank))
+    count = c.take('Q', name)
+    if count != int(np.prod(shape, dtype=object)):
+      raise c.fail('bad count (variable %s, %d elements of shape %s)' % (name, count, shape))
     if name in out[STATE_SLOTS[slot]]:
-      raise ValueError('%s: variable %s twice in slot %s' % (path, name, STATE_SLOTS[slot]))
-    out[STATE_SLOTS[slot]][name] = np.frombuffer(data, '<f4', count, pos[0]).reshape(shape).copy()
-    pos[0] += 4 * count
-  if pos[0] != len(data):
-    raise ValueError('%s: %d bytes after the last record' % (path, len(data) - pos[0]))
+      raise c.fail('variable %s twice in slot %s' % (name, STATE_SLOTS[slot]))
+    payload = c.raw(4 * c.count(count, 4, name), name)
+    out[STATE_SLOTS[slot]][name] = np.frombuffer(payload, '<f4').reshape(shape).copy()
+  if c.pos != len(c.data):
+    raise c.fail('%d bytes after the last record' % (len(c.data) - c.pos))
   out['iterations'] = iterations
   return out
 

@@ -2,6 +2,7 @@
 edet_train_step) equals the Python host's own passes BIT FOR BIT: in process through ctypes (eager and as a captured
 hipGraph), and from a C99 host program with no interpreter (tests/c_host/edet_host.c, built here with gcc).  Reference
 interfaces: efficientdet/tf2/efficientdet_keras.py:790-799, 893-915; efficientdet/tf2/train_lib.py:606-684."""
+import ctypes
 import os
 import shutil
 import subprocess
@@ -142,6 +143,27 @@ def test_replay_in_process_equals_the_python_host(recorded):
       want = recorded['expected'][k].reshape(-1)
       assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), '%s: %d of %d elements differ' % (
           k, int((got.view(np.uint32) != want.view(np.uint32)).sum()), want.size)
+  finally:
+    cnet.close()
+
+
+def test_a_plan_cut_inside_its_initial_contents_is_refused_and_the_whole_one_loads_afterwards(recorded, tmp_path):
+  """The loader checks the whole file before it allocates: the first half of the initial contents is not a plan, and the
+  refusal leaves the process able to load and replay the intact one."""
+  inits = [(at, n) for n, at in plan.read_summary(recorded['path'])['buffers'] if at]
+  first, end = min(at for at, _ in inits), max(at + n for at, n in inits)
+  assert end == os.path.getsize(recorded['path'])
+  bad = tmp_path / 'half.plan'
+  with open(recorded['path'], 'rb') as f:
+    bad.write_bytes(f.read(first + (end - first) // 2))
+  lib = net_c._lib_net()
+  h = ctypes.c_void_p()
+  assert lib.edet_create(str(bad).encode(), ctypes.byref(h)) != 0 and not h.value
+  assert b'truncated plan' in lib.edet_last_error(), lib.edet_last_error()
+  cnet = net_c.CNet(recorded['path'])
+  try:
+    cnet.forward()
+    _logits_equal(cnet, recorded['expected'], recorded['config'])
   finally:
     cnet.close()
 
