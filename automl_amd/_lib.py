@@ -52,6 +52,12 @@ class CropImage(ctypes.Structure):
               ('crop_h', ctypes.c_int32), ('crop_w', ctypes.c_int32), ('flip', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class GridMaskImage(ctypes.Structure):
+  """edet_gridmask_image_t: one row of edet_gridmask's per-image array (gridmask.gridmask_args)."""
+  _fields_ = [('apply', ctypes.c_int32), ('size', ctypes.c_int32), ('d', ctypes.c_int32), ('l', ctypes.c_int32),
+              ('s1', ctypes.c_int32), ('s2', ctypes.c_int32), ('coef', ctypes.c_float * 6)]
+
+
 NMS_HARD, NMS_GAUSSIAN, NMS_LINEAR = 0, 1, 2
 NMS_TF_V5, NMS_NUMPY = 0, 1
 NMS_PAD_INDEX0, NMS_PAD_ZERO, NMS_PAD_DUMMY = 0, 1, 2
@@ -163,6 +169,7 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     'edet_nms_gather': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    'edet_gridmask': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 
 _lib = None

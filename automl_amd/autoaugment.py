@@ -92,8 +92,13 @@ def identity_draws(batch, num_layers):
 
 def rotate_coefficients(degrees, h, w):
   """TFA rotate -> angles_to_projective_transforms in float32: [cos, -sin, xoff, sin, cos, yoff]."""
+  return angle_coefficients(np.float32(degrees * (math.pi / 180.0)), h, w)
+
+
+def angle_coefficients(angle, h, w):
+  """angles_to_projective_transforms for a float32 angle in radians (gridmask.py forms its own angle, gridmask.py:53-54)."""
   f = np.float32
-  angle = f(degrees * (math.pi / 180.0))
+  angle = f(angle)
   c, s = np.cos(angle), np.sin(angle)
   wm, hm = f(w - 1), f(h - 1)
   xoff = (wm - (c * wm - s * hm)) / f(2.0)

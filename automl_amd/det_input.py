@@ -1,0 +1,194 @@
+"""The detector's training input on the device, from a raw batch to the train step's static buffers.
+
+Restates the training branch of ``InputReader.dataset_parser`` plus ``process_example`` (dataloader.py:301-338, :369-382)
+for a batch of equally sized decoded images with padded boxes:
+
+  1. ``gridmask.gridmask`` if ``config.grid_mask`` (:308-310)                                  edet_gridmask
+  2. ``normalize_image``, 3. ``random_horizontal_flip`` if ``input_rand_hflip``,
+  4. ``set_training_random_scale_factors(jitter_min, jitter_max, target_size)``,
+  5. ``resize_and_crop_image``, 6. ``resize_and_crop_boxes`` (:321-334)                        edet_preprocess_train
+  7. ``anchor_labeler.label_anchors`` (:337-338)                                               edet_label_anchors
+  8. ``mean_num_positives``: the batch mean of num_positives tiled to [B, 1] (:371-375)
+
+The three launches write into destinations the CALLER supplies -- the captured step's ``input_buffers()`` -- so nothing is
+staged; the labelling workspace, the per-image argument arrays and the GridMask scratch image are allocated once, here.  The
+draws are made on the host (``draw``), turned into the kernels' per-image rows by the same float32 arithmetic as
+``preprocess.DetectionInputProcessor`` (``preprocess.training_scale_factors`` is shared) and copied from pinned memory.
+
+``skip_crowd_during_training`` (:303-306) is the caller's filtering of ``boxes`` / ``counts``: crowd boxes are left out of the
+padded rows before they get here.  ``autoaugment_policy`` (:312-319) is not built; ``EfficientDetNetTrain.train_step_raw``
+raises for it.
+"""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from automl_amd import _lib
+from automl_amd import gridmask as gridmask_lib
+from automl_amd import labeling
+from automl_amd import preprocess
+from automl_amd import utils
+from automl_amd._lib import call, ptr
+
+Draws = collections.namedtuple('Draws', ['flip', 'scale', 'gridmask'])
+
+
+def input_rng(seed):
+  """The generator behind the input draws of a model built with `seed`."""
+  return np.random.Generator(np.random.PCG64([int(seed), 0x64657469]))
+
+
+def mean_num_positives(num_positives):
+  """dataloader.py:371-375: reduce_mean over the batch, tiled to [B, 1].  num_positives are integer-valued floats, so their
+  sum is exact in any order and the mean is one rounded division (by a tensor: torch turns a division by a host scalar
+  into a product with its reciprocal, a second rounding)."""
+  b = int(num_positives.shape[0])
+  count = torch.full((), float(b), dtype=num_positives.dtype, device=num_positives.device)
+  return torch.div(num_positives.sum(), count).reshape(1, 1).expand(b, 1)
+
+
+class DetectionInput(object):
+  """The input launches of one (batch, raw size, box rows) shape for `config` on `device`."""
+
+  def __init__(self, config, anchors, batch, height, width, max_boxes, dtype=torch.float32, device='cuda:0'):
+    if dtype not in (torch.float32, torch.bfloat16):
+      raise ValueError('dtype must be float32 or bfloat16')
+    if not 1 <= int(max_boxes) <= preprocess.MAX_BOXES:
+      raise ValueError('between 1 and %d box rows per image (edet_preprocess_train keeps them in LDS), got %d'
+                       % (preprocess.MAX_BOXES, max_boxes))
+    self.config = config
+    self.batch, self.height, self.width, self.max_boxes = int(batch), int(height), int(width), int(max_boxes)
+    self.dtype, self.device = dtype, torch.device(device)
+    self.output_size = utils.parse_image_size(config.image_size)
+    target = getattr(config, 'target_size', None)
+    self.target_size = utils.parse_image_size(target) if target else self.output_size
+    self.grid_mask = bool(getattr(config, 'grid_mask', None))
+    if self.grid_mask:
+      gridmask_lib.block_range(self.height, self.width)      # a raw size the reference could not mask: raises
+    self.labeler = labeling.AnchorLabeler(anchors, config.num_classes, device=device)
+    self.levels = list(self.labeler._levels)
+    f = np.float32
+    self._mean = (ctypes.c_float * 3)(*[float(v) for v in np.broadcast_to(np.asarray(config.mean_rgb, f).reshape(-1), (3,))])
+    self._std = (ctypes.c_float * 3)(*[float(v) for v in np.broadcast_to(np.asarray(config.stddev_rgb, f).reshape(-1), (3,))])
+    b, m, dev = self.batch, self.max_boxes, self.device
+    # allocated once: argument rows, the masked image, the boxes between the two kernels, the labelling workspace
+    self.prep_rows = torch.zeros((b, 5), dtype=torch.int32, device=dev)              # edet_prep_image_t
+    self.mask_rows = self.masked = None
+    if self.grid_mask:
+      self.mask_rows = torch.zeros((b, gridmask_lib.ARGS_BYTES), dtype=torch.uint8, device=dev)      # edet_gridmask_image_t
+      self.masked = torch.empty((b, self.height, self.width, 3), dtype=torch.uint8, device=dev)
+    self.boxes = torch.empty((b, m, 4), dtype=torch.float32, device=dev)
+    self.classes = torch.empty((b, m), dtype=torch.float32, device=dev)
+    self.labels = torch.empty((b, m), dtype=torch.int32, device=dev)
+    self.counts = torch.empty((b,), dtype=torch.int32, device=dev)
+    self.num_positives = torch.empty((b,), dtype=torch.float32, device=dev)
+    need = ctypes.c_size_t(0)
+    call('edet_label_anchors_workspace_bytes', b, int(self.labeler._boxes.shape[0]), ctypes.byref(need))
+    self._ws_bytes = need.value
+    self.workspace = torch.empty((max(need.value, 1),), dtype=torch.uint8, device=dev)
+    self._level_anchors = (ctypes.c_int * len(self.levels))(*self.labeler._lanch)
+    self._own = None
+
+  # ---- draws ----------------------------------------------------------------------------------------------------------
+  def draw(self, rng):
+    """One step's draws from a numpy generator: flip [B] and scale [B, 3] uniform float32 in [0, 1) (what
+    DetectionInputProcessor's setters take as `draws`), gridmask = gridmask_draws' five arrays (None without grid_mask)."""
+    b = self.batch
+    flip = rng.random((b, 1)).astype(np.float32)[:, 0]
+    scale = rng.random((b, 3)).astype(np.float32)
+    gm = gridmask_lib.gridmask_draws(rng, b, self.height, self.width) if self.grid_mask else None
+    return Draws(flip, scale, gm)
+
+  def rows(self, draws):
+    """draws -> (edet_prep_image_t rows int32 [B, 5], edet_gridmask_image_t rows or None), on the host."""
+    c = self.config
+    flip, scale, gm = draws
+    u = np.asarray(scale, np.float32).reshape(self.batch, 3)
+    per = np.zeros((self.batch, 5), np.int32)
+    if c.input_rand_hflip:
+      per[:, 0] = preprocess.flip_decisions(np.asarray(flip, np.float32).reshape(self.batch))
+    for i in range(self.batch):
+      _, per[i, 1:3], per[i, 3:5] = preprocess.training_scale_factors(
+          u[i], c.jitter_min, c.jitter_max, self.target_size, self.output_size, self.height, self.width)
+    if int(per[:, 1:3].min()) < 1:
+      raise ValueError('the scaled image is empty')
+    mask = None
+    if self.grid_mask:
+      if gm is None:
+        raise ValueError('config.grid_mask is set: draws need the five GridMask arrays (gridmask.gridmask_draws)')
+      mask = gridmask_lib.gridmask_args(gm, self.height, self.width)      # gridmask.gridmask's defaults (dataloader.py:310)
+      if mask.shape[0] != self.batch:
+        raise ValueError('GridMask draws for %d images, batch %d' % (mask.shape[0], self.batch))
+    return per, mask
+
+  # ---- destinations ---------------------------------------------------------------------------------------------------
+  def label_shapes(self):
+    """{label name: (shape, dtype)} of what run() fills, the train step's label layout (dataloader.py:369-382)."""
+    b, a = self.batch, self.labeler._a
+    out = collections.OrderedDict()
+    for level, (h, w) in zip(self.levels, self.labeler._hw):
+      out['cls_targets_%d' % level] = ((b, h, w, a), torch.int32)
+      out['box_targets_%d' % level] = ((b, h, w, a * 4), torch.float32)
+    out['mean_num_positives'] = ((b, 1), torch.float32)
+    return out
+
+  def own_buffers(self):
+    """(images, labels) buffers of this object's own, allocated at the first call: the destinations of a step that has no
+    captured graph's buffers to write into."""
+    if self._own is None:
+      oh, ow = self.output_size
+      images = torch.empty((self.batch, oh, ow, 3), dtype=self.dtype, device=self.device)
+      labels = {k: torch.empty(shape, dtype=dt, device=self.device) for k, (shape, dt) in self.label_shapes().items()}
+      self._own = (images, labels)
+    return self._own
+
+  def _check_destinations(self, images, labels):
+    oh, ow = self.output_size
+    if tuple(images.shape) != (self.batch, oh, ow, 3) or images.dtype != self.dtype or not images.is_contiguous():
+      raise ValueError('images destination must be a dense %s %s, got %s %s'
+                       % (self.dtype, (self.batch, oh, ow, 3), images.dtype, tuple(images.shape)))
+    for k, (shape, dt) in self.label_shapes().items():
+      t = labels.get(k)
+      n = int(np.prod(shape))
+      if t is None or t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != images.device:
+        raise ValueError('labels destination %r must be a dense %s tensor of %d elements on %s'
+                         % (k, dt, n, images.device))
+
+  # ---- the launches ---------------------------------------------------------------------------------------------------
+  def run(self, raw_images, boxes, classes, counts, draws, images, labels, stream=None):
+    """raw_images uint8 [B, H, W, 3], boxes float32 [B, M, 4] normalised (ymin, xmin, ymax, xmax), classes [B, M], counts
+    [B] (device tensors, or host arrays that are copied over) -> fills `images` [B, h, w, 3] and `labels`
+    {'cls_targets_<l>', 'box_targets_<l>', 'mean_num_positives'} in place, on torch's current stream."""
+    b, m, dev = self.batch, self.max_boxes, self.device
+    raw = torch.as_tensor(raw_images)
+    if raw.dtype != torch.uint8 or tuple(raw.shape) != (b, self.height, self.width, 3):
+      raise ValueError('raw images must be uint8 %s, got %s %s' % ((b, self.height, self.width, 3), raw.dtype, tuple(raw.shape)))
+    raw = raw.to(dev).contiguous()
+    boxes = torch.as_tensor(boxes, dtype=torch.float32).to(dev).reshape(b, m, 4).contiguous()
+    classes = torch.as_tensor(classes).to(dev).to(torch.float32).reshape(b, m).contiguous()
+    counts = torch.as_tensor(counts).to(dev).to(torch.int32).reshape(b).contiguous()
+    self._check_destinations(images, labels)
+    per, mask = self.rows(draws)
+    if stream is None:
+      stream = torch.cuda.current_stream(dev).cuda_stream
+    self.prep_rows.copy_(torch.from_numpy(per).pin_memory(), non_blocking=True)
+    src = raw
+    if self.grid_mask:
+      self.mask_rows.copy_(gridmask_lib.args_tensor(mask, pin=True), non_blocking=True)
+      src = gridmask_lib.apply_mask(raw, self.masked, self.mask_rows, stream)
+    call('edet_preprocess_train', ptr(src), 0, b, self.height, self.width, self.output_size[0], self.output_size[1],
+         self._mean, self._std, ptr(self.prep_rows), ptr(images), ptr(boxes), ptr(classes), ptr(counts), m,
+         ptr(self.boxes), ptr(self.classes), ptr(self.counts),
+         _lib.EDET_BF16 if self.dtype == torch.bfloat16 else _lib.EDET_F32, stream)
+    self.labels.copy_(self.classes)      # float class ids (-1 padded) -> int32, as label_anchors_batch takes them
+    nlev = len(self.levels)
+    cp = (ctypes.c_void_p * nlev)(*[labels['cls_targets_%d' % l].data_ptr() for l in self.levels])
+    bp = (ctypes.c_void_p * nlev)(*[labels['box_targets_%d' % l].data_ptr() for l in self.levels])
+    call('edet_label_anchors', ptr(self.labeler._boxes), self._level_anchors, nlev, ptr(self.boxes), ptr(self.labels),
+         ptr(self.counts), b, m, float(self.labeler._match_threshold), ptr(self.workspace), self._ws_bytes, cp, bp,
+         ptr(self.num_positives), stream)
+    labels['mean_num_positives'].view(b, 1).copy_(mean_num_positives(self.num_positives))
+    self._keep_alive = (raw, boxes, classes, counts)
+    return images, labels

@@ -54,6 +54,7 @@ import torch
 
 from automl_amd import autoaugment
 from automl_amd import effnetv2_model
+from automl_amd import utils
 from automl_amd import v2_preprocessing
 from automl_amd.layer_engine import LayerEngine, Update, capture_graph
 
@@ -223,18 +224,7 @@ def draw_mix(rng, batch, h, w, mixup_alpha, cutmix_alpha):
   return weights, boxes
 
 
-def _pack_rng_state(rng):
-  """PCG64 state -> uint64 [6] (state and increment as two words each, the buffered 32-bit half)."""
-  st = rng.bit_generator.state
-  m = (1 << 64) - 1
-  s, inc = int(st['state']['state']), int(st['state']['inc'])
-  return np.array([s & m, s >> 64, inc & m, inc >> 64, int(st['has_uint32']), int(st['uinteger'])], dtype=np.uint64)
-
-
-def _unpack_rng_state(rng, words):
-  v = [int(x) for x in np.asarray(words, dtype=np.uint64)]
-  rng.bit_generator.state = {'bit_generator': 'PCG64', 'state': {'state': v[0] | (v[1] << 64), 'inc': v[2] | (v[3] << 64)},
-                             'has_uint32': v[4], 'uinteger': v[5]}
+_pack_rng_state, _unpack_rng_state = utils.pack_rng_state, utils.unpack_rng_state
 
 
 class TrainableModel(effnetv2_model.EffNetV2Model):

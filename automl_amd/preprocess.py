@@ -38,6 +38,27 @@ F = np.float32
 MAX_BOXES = 1024      # PREP_MAX_BOXES of csrc/preprocess.hip
 
 
+def flip_decisions(u):
+  """random_horizontal_flip's decision per uniform draw (object_detection/preprocessor.py:113-199): flipped when > 0.5."""
+  return (np.asarray(u, np.float32) > F(0.5)).astype(np.int32)
+
+
+def training_scale_factors(u, scale_min, scale_max, target, output_size, height, width):
+  """set_training_random_scale_factors for one image (dataloader.py:66-111), float32 statement by statement, the int casts
+  truncating: u = the three uniform [0, 1) float32 values behind (scale factor, offset y, offset x); target, output_size =
+  (height, width) pairs -> (image_scale float32, (scaled_h, scaled_w), (offset_y, offset_x)).  DetectionInputProcessor and
+  the detector's raw-batch step (det_input.py) both call this."""
+  oh, ow = output_size
+  factor = F(scale_min) + u[0] * (F(scale_max) - F(scale_min))        # tf.random.uniform([], min, max)
+  scaled_y, scaled_x = int(F(factor * F(target[0]))), int(F(factor * F(target[1])))
+  h, w = F(height), F(width)
+  scale = min(F(scaled_x) / w, F(scaled_y) / h)
+  sh, sw = int(F(h * scale)), int(F(w * scale))
+  oy = max(F(0), F(sh - oh)) * u[1]
+  ox = max(F(0), F(sw - ow)) * u[2]
+  return scale, (sh, sw), (int(F(oy)), int(F(ox)))
+
+
 class DetectionInputProcessor(object):
   """``dataloader.DetectionInputProcessor`` (dataloader.py:144-200, base class :36-141) for a BATCH of equally sized raw
   images, same method names and call order as ``InputReader.process_example`` uses them (:321-336)::
@@ -102,23 +123,16 @@ class DetectionInputProcessor(object):
   def random_horizontal_flip(self, draws=None):
     """preprocessor.random_horizontal_flip (object_detection/preprocessor.py:113-199): one uniform draw per image,
     flipped when it is > 0.5; image and boxes together."""
-    self._flip = (self._uniform(draws, 1)[:, 0] > F(0.5)).astype(np.int32)
+    self._flip = flip_decisions(self._uniform(draws, 1)[:, 0])
     self._result = None
 
   def set_training_random_scale_factors(self, scale_min, scale_max, target_size=None, draws=None):
     """dataloader.py:66-111; draws [B, 3] = the uniform [0, 1) values behind (scale factor, offset y, offset x)."""
     target = utils.parse_image_size(target_size) if target_size else self._output_size
     u = self._uniform(draws, 3)
-    oh, ow = self._output_size
     for i in range(self._batch):
-      factor = F(scale_min) + u[i, 0] * (F(scale_max) - F(scale_min))        # tf.random.uniform([], min, max)
-      scaled_y, scaled_x = int(F(factor * F(target[0]))), int(F(factor * F(target[1])))
-      h, w = F(self._height), F(self._width)
-      scale = min(F(scaled_x) / w, F(scaled_y) / h)
-      sh, sw = int(F(h * scale)), int(F(w * scale))
-      oy = max(F(0), F(sh - oh)) * u[i, 1]
-      ox = max(F(0), F(sw - ow)) * u[i, 2]
-      self._image_scale[i], self._scaled[i], self._offset[i] = scale, (sh, sw), (int(F(oy)), int(F(ox)))
+      self._image_scale[i], self._scaled[i], self._offset[i] = training_scale_factors(
+          u[i], scale_min, scale_max, target, self._output_size, self._height, self._width)
     self._scales_set = True
     self._result = None
 

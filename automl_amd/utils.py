@@ -1,4 +1,6 @@
-"""Shape helpers of the detection path (reference efficientdet/utils.py:484-526)."""
+"""Shape helpers of the detection path (reference efficientdet/utils.py:484-526) and the packing of a host generator's state
+that both trainers put into their optimizer state."""
+import numpy as np
 
 
 def parse_image_size(image_size):
@@ -34,3 +36,17 @@ def same_padding(in_size, kernel, stride):
   out = -(-in_size // stride)
   total = max((out - 1) * stride + kernel - in_size, 0)
   return out, total // 2, total - total // 2
+
+
+def pack_rng_state(rng):
+  """PCG64 state -> uint64 [6] (state and increment as two words each, the buffered 32-bit half)."""
+  st = rng.bit_generator.state
+  m = (1 << 64) - 1
+  s, inc = int(st['state']['state']), int(st['state']['inc'])
+  return np.array([s & m, s >> 64, inc & m, inc >> 64, int(st['has_uint32']), int(st['uinteger'])], dtype=np.uint64)
+
+
+def unpack_rng_state(rng, words):
+  v = [int(x) for x in np.asarray(words, dtype=np.uint64)]
+  rng.bit_generator.state = {'bit_generator': 'PCG64', 'state': {'state': v[0] | (v[1] << 64), 'inc': v[2] | (v[3] << 64)},
+                             'has_uint32': v[4], 'uinteger': v[5]}

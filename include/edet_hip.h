@@ -664,6 +664,31 @@ int edet_preprocess_train(const void* raw_images, int raw_is_float, int batch, i
                           const float* classes_in, const int* counts_in, int max_boxes, float* boxes_out,
                           float* classes_out, int* counts_out, int dtype, void* stream);
 
+/* ---- GridMask of a training batch (efficientdet/aug/gridmask.py:22-136) ------------------------
+ * src, dst uint8 [batch][height][width][3], src != dst.  Per image (DEVICE array): apply != 0 -> dst = src * mask, else the
+ * copy.  The S x S mask of the reference (S = size) is never stored; every output pixel (y, x) evaluates it at mask
+ * position (Y, X) = (y + (S - height) / 2, x + (S - width) / 2), floor divisions (crop, :58-63):
+ *   stripes (:92-102)   m[r][c] = stripe(r; s1) | stripe(c; s2), stripe(t; s) = 1 iff 0 <= t < S, q = t - s >= 0,
+ *                       q / d < S / d (integer divisions) and q % d < l.  1 = kept: the image survives on the stripes.
+ *   rotation (:50-55)   ImageProjectiveTransformV2, BILINEAR, constant fill 0, on int32: source position
+ *                       (coef[0] X + coef[1] Y + coef[2], coef[3] X + coef[4] Y + coef[5]) in fp32, left to right; the
+ *                       low taps are floor(), the high taps floor() + 1, each 0 outside [0, S); row blend
+ *                       (x_ceil - x) v00 + (x - x_floor) v01, the column blend likewise; the result truncated to int32.
+ * The caller makes the draws and the coefficients (automl_amd/gridmask.py: sine and cosine are numpy float32 on the host).
+ * Every field is clamped in the kernel: size into [0, 2^30], d >= 1, l into [0, d], s1 and s2 into [0, d]; a source
+ * position that is not finite, or whose four taps all lie outside the mask, gives 0.  The arithmetic (single fp32
+ * operations in the stated order) is restated in tests/gridmask_ref.py and compared bit for bit.
+ * batch <= 65535, height * width * 3 < 2^31. */
+typedef struct edet_gridmask_image { /* 48 bytes, one per image, read from DEVICE memory */
+  int32_t apply;                 /* the occurrence draw (:116)                                          */
+  int32_t size;                  /* S, the side of the square mask (:70-73)                             */
+  int32_t d, l;                  /* gridblock and length (:76-90)                                       */
+  int32_t s1, s2;                /* the two stripe starts: s1 lands on rows, s2 on columns (:92-102)    */
+  float coef[6];                 /* angles_to_projective_transforms of the drawn angle on an S x S image */
+} edet_gridmask_image_t;
+int edet_gridmask(const uint8_t* src, uint8_t* dst, int batch, int height, int width,
+                  const edet_gridmask_image_t* per_image_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
