@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(_HERE, 'libedet_hip.so')
-SOURCES = ['pw_gemm.hip', 'pw_stream.hip', 'pw_big.hip', 'pw_glds.hip', 'pw_tile_bwd.hip', 'conv.hip', 'conv_halo.hip', 'dwconv.hip', 'dw_march.hip', 'mbconv_fused.hip', 'stem.hip', 'bn_se.hip', 'fuse.hip', 'loss_opt.hip', 'mix.hip', 'randaug.hip', 'crop_resize.hip', 'gridmask.hip', 'postprocess.hip', 'labeling.hip', 'preprocess.hip', 'error.cpp', 'plan_file.cpp', 'net_runtime.cpp']
+SOURCES = ['pw_gemm.hip', 'pw_stream.hip', 'pw_big.hip', 'pw_glds.hip', 'pw_tile_bwd.hip', 'conv.hip', 'conv_halo.hip', 'dwconv.hip', 'dw_march.hip', 'mbconv_fused.hip', 'stem.hip', 'bn_se.hip', 'fuse.hip', 'loss_opt.hip', 'mix.hip', 'randaug.hip', 'crop_resize.hip', 'gridmask.hip', 'det_autoaug.hip', 'postprocess.hip', 'labeling.hip', 'preprocess.hip', 'error.cpp', 'plan_file.cpp', 'net_runtime.cpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result']
 # files that restate float32 numpy / TensorFlow expressions operation by operation (argmax ties, 1e-6 parities):
@@ -15,7 +15,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-res
 # plain operators, not contraction barriers)
 EXTRA_FLAGS = {'labeling.hip': ['-ffp-contract=off'], 'preprocess.hip': ['-ffp-contract=off'],
                'randaug.hip': ['-ffp-contract=off'], 'crop_resize.hip': ['-ffp-contract=off'],
-               'gridmask.hip': ['-ffp-contract=off']}
+               'gridmask.hip': ['-ffp-contract=off'], 'det_autoaug.hip': ['-ffp-contract=off']}
 
 
 def _stale(target, deps):
@@ -28,6 +28,7 @@ def _stale(target, deps):
 def build_library(force=False, verbose=False):
   """Compiles every HIP source for gfx950 and links libedet_hip.so; returns its path."""
   hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pw_impl.h'), os.path.join(CSRC, 'dw_impl.h'),
+          os.path.join(CSRC, 'randaug_impl.h'),
           os.path.join(_HERE, '..', 'include', 'edet_hip.h'),
           os.path.join(_HERE, '..', 'include', 'edet_net.h'), os.path.join(CSRC, 'plan_stubs.inc'),
           os.path.join(CSRC, 'plan_file.h')]

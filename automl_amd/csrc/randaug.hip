@@ -16,6 +16,7 @@
 // needs no statistics pass.  Solarize compares in int32: a threshold >= 256 leaves every pixel as it is (what TensorFlow's
 // conversion of an out-of-range Python integer to uint8 would do is pinned by nothing here).
 #include "common.h"
+#include "randaug_impl.h"
 
 namespace {
 
@@ -25,25 +26,10 @@ constexpr int OP_AUTOCONTRAST = 0, OP_EQUALIZE = 1, OP_INVERT = 2, OP_ROTATE = 3
               OP_CUTOUT = 14, OP_SOLARIZE_ADD = 15, OP_IDENTITY = 16;
 constexpr int OUT_U8 = 2;      // EDET_U8
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-// clip to [0, 255] then truncate (NaN -> 0)
-__device__ __forceinline__ int clip_u8(float t) { return (int)fminf(fmaxf(t, 0.f), 255.f); }
-
-// autoaugment.py:79-119 for one value: a + f (b - a) as a subtract, a multiply and an add
-__device__ __forceinline__ int blend(int a, int b, float f) {
-  if (f == 0.f) return a;
-  if (f == 1.f) return b;
-  const float fa = (float)a;
-  const float t = fa + f * ((float)b - fa);
-  return clip_u8(t);      // (0 < f < 1 stays inside [0, 255]: the clip changes nothing there)
-}
-
-// tf.image.rgb_to_grayscale on uint8: v / 255 as a product, the three weights left to right, * 255.5, saturate, truncate
-__device__ __forceinline__ int gray_of(int r, int g, int b) {
-  const float k = 1.0f / 255.0f;
-  const float s = ((float)r * k) * 0.2989f + ((float)g * k) * 0.5870f + ((float)b * k) * 0.1140f;
-  return clip_u8(s * 255.5f);
-}
+using raug::blend;
+using raug::clampi;
+using raug::clip_u8;
+using raug::gray_of;
 
 // ---- statistics: one workgroup per image --------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void k_randaug_stats(const uint8_t* __restrict__ src, int n, const int32_t* __restrict__ ops,

@@ -4,20 +4,30 @@ Restates the training branch of ``InputReader.dataset_parser`` plus ``process_ex
 for a batch of equally sized decoded images with padded boxes:
 
   1. ``gridmask.gridmask`` if ``config.grid_mask`` (:308-310)                                  edet_gridmask
+  1a. ``distort_image_with_autoaugment`` / ``..._randaugment`` (:312-319) if the ``autoaugment`` switch is on
+                                                     edet_autoaug_boxes, edet_randaug_stats, edet_autoaug_contrast_lut,
+                                                     edet_randaug_apply per layer (det_autoaugment.py)
   2. ``normalize_image``, 3. ``random_horizontal_flip`` if ``input_rand_hflip``,
   4. ``set_training_random_scale_factors(jitter_min, jitter_max, target_size)``,
   5. ``resize_and_crop_image``, 6. ``resize_and_crop_boxes`` (:321-334)                        edet_preprocess_train
   7. ``anchor_labeler.label_anchors`` (:337-338)                                               edet_label_anchors
   8. ``mean_num_positives``: the batch mean of num_positives tiled to [B, 1] (:371-375)
 
-The three launches write into destinations the CALLER supplies -- the captured step's ``input_buffers()`` -- so nothing is
-staged; the labelling workspace, the per-image argument arrays and the GridMask scratch image are allocated once, here.  The
+The launches write into destinations the CALLER supplies -- the captured step's ``input_buffers()`` -- so nothing is
+staged; the labelling workspace, the per-image argument arrays, the GridMask scratch image and AutoAugment's scratch images,
+boxes, tables and argument buffer are allocated once, here.  The
 draws are made on the host (``draw``), turned into the kernels' per-image rows by the same float32 arithmetic as
 ``preprocess.DetectionInputProcessor`` (``preprocess.training_scale_factors`` is shared) and copied from pinned memory.
 
 ``skip_crowd_during_training`` (:303-306) is the caller's filtering of ``boxes`` / ``counts``: crowd boxes are left out of the
-padded rows before they get here.  ``autoaugment_policy`` (:312-319) is not built; ``EfficientDetNetTrain.train_step_raw``
-raises for it.
+padded rows before they get here.
+
+The box-aware AutoAugment / RandAugment of ``aug/autoaugment.py`` is reached through the constructor's ``autoaugment`` switch
+(``EfficientDetNetTrain.set_autoaugment``): ``'randaug'`` (the data loader's num_layers=1, magnitude=15, :315-316), ``'v2'``,
+``'v3'`` or ``'test'``.  ``'v0'``, ``'v1'`` and the ``*_Only_BBoxes`` operations they need are not built.  The
+``config.autoaugment_policy`` key itself is still refused by ``train_step_raw``.  What is not pinned against TensorFlow
+(TFA's rounding rule, float32 sine and cosine, the random streams, ``reduce_mean``'s order beyond a grey sum of 2^24) is
+listed in det_autoaugment.py.
 """
 import collections
 import ctypes
@@ -26,13 +36,15 @@ import numpy as np
 import torch
 
 from automl_amd import _lib
+from automl_amd import det_autoaugment
 from automl_amd import gridmask as gridmask_lib
 from automl_amd import labeling
 from automl_amd import preprocess
 from automl_amd import utils
 from automl_amd._lib import call, ptr
 
-Draws = collections.namedtuple('Draws', ['flip', 'scale', 'gridmask'])
+Draws = collections.namedtuple('Draws', ['flip', 'scale', 'gridmask', 'autoaug'], defaults=(None,))
+RANDAUG_NUM_LAYERS, RANDAUG_MAGNITUDE = 1, 15      # dataloader.py:315-316
 
 
 def input_rng(seed):
@@ -52,7 +64,8 @@ def mean_num_positives(num_positives):
 class DetectionInput(object):
   """The input launches of one (batch, raw size, box rows) shape for `config` on `device`."""
 
-  def __init__(self, config, anchors, batch, height, width, max_boxes, dtype=torch.float32, device='cuda:0'):
+  def __init__(self, config, anchors, batch, height, width, max_boxes, dtype=torch.float32, device='cuda:0',
+               autoaugment=None):
     if dtype not in (torch.float32, torch.bfloat16):
       raise ValueError('dtype must be float32 or bfloat16')
     if not 1 <= int(max_boxes) <= preprocess.MAX_BOXES:
@@ -67,6 +80,8 @@ class DetectionInput(object):
     self.grid_mask = bool(getattr(config, 'grid_mask', None))
     if self.grid_mask:
       gridmask_lib.block_range(self.height, self.width)      # a raw size the reference could not mask: raises
+    self.autoaugment = autoaugment      # None, 'randaug', 'v2', 'v3' or 'test' (det_autoaugment.available_policy)
+    self._aa_policy = det_autoaugment.available_policy(autoaugment) if autoaugment is not None else None
     self.labeler = labeling.AnchorLabeler(anchors, config.num_classes, device=device)
     self.levels = list(self.labeler._levels)
     f = np.float32
@@ -79,6 +94,17 @@ class DetectionInput(object):
     if self.grid_mask:
       self.mask_rows = torch.zeros((b, gridmask_lib.ARGS_BYTES), dtype=torch.uint8, device=dev)      # edet_gridmask_image_t
       self.masked = torch.empty((b, self.height, self.width, 3), dtype=torch.uint8, device=dev)
+    self.aa_layers = 0
+    if self._aa_policy is not None:
+      self.aa_layers = det_autoaugment.num_layers_of(self._aa_policy, RANDAUG_NUM_LAYERS)
+      self._aa_layout, nbytes = det_autoaugment.args_layout(self.aa_layers, b)
+      self.aa_rows = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)      # one step's arguments, one copy
+      self.aa_args = det_autoaugment.unpack_args(self.aa_rows, self._aa_layout)
+      shape = (b, self.height, self.width, 3)
+      self.aa_images = torch.empty(shape, dtype=torch.uint8, device=dev)
+      self.aa_scratch = [torch.empty(shape, dtype=torch.uint8, device=dev) for _ in range(min(self.aa_layers - 1, 2))]
+      self.aa_boxes = torch.empty((b, m, 4), dtype=torch.float32, device=dev)
+      self.aa_luts = torch.zeros((b, 3, 256), dtype=torch.uint8, device=dev)
     self.boxes = torch.empty((b, m, 4), dtype=torch.float32, device=dev)
     self.classes = torch.empty((b, m), dtype=torch.float32, device=dev)
     self.labels = torch.empty((b, m), dtype=torch.int32, device=dev)
@@ -94,17 +120,23 @@ class DetectionInput(object):
   # ---- draws ----------------------------------------------------------------------------------------------------------
   def draw(self, rng):
     """One step's draws from a numpy generator: flip [B] and scale [B, 3] uniform float32 in [0, 1) (what
-    DetectionInputProcessor's setters take as `draws`), gridmask = gridmask_draws' five arrays (None without grid_mask)."""
+    DetectionInputProcessor's setters take as `draws`), gridmask = gridmask_draws' five arrays (None without grid_mask),
+    autoaug = det_autoaugment.autoaug_draws' tuple (None without the switch; taken last, so that the stream of a model
+    without it does not move)."""
     b = self.batch
     flip = rng.random((b, 1)).astype(np.float32)[:, 0]
     scale = rng.random((b, 3)).astype(np.float32)
     gm = gridmask_lib.gridmask_draws(rng, b, self.height, self.width) if self.grid_mask else None
-    return Draws(flip, scale, gm)
+    aa = None
+    if self._aa_policy is not None:
+      aa = det_autoaugment.autoaug_draws(rng, b, self._aa_policy, RANDAUG_NUM_LAYERS)
+    return Draws(flip, scale, gm, aa)
 
   def rows(self, draws):
-    """draws -> (edet_prep_image_t rows int32 [B, 5], edet_gridmask_image_t rows or None), on the host."""
+    """draws -> (edet_prep_image_t rows int32 [B, 5], edet_gridmask_image_t rows or None, AutoAugment's packed argument
+    arrays uint8 or None -- det_autoaugment.pack_args of autoaug_args), on the host."""
     c = self.config
-    flip, scale, gm = draws
+    flip, scale, gm, aa = Draws(*draws)
     u = np.asarray(scale, np.float32).reshape(self.batch, 3)
     per = np.zeros((self.batch, 5), np.int32)
     if c.input_rand_hflip:
@@ -121,7 +153,16 @@ class DetectionInput(object):
       mask = gridmask_lib.gridmask_args(gm, self.height, self.width)      # gridmask.gridmask's defaults (dataloader.py:310)
       if mask.shape[0] != self.batch:
         raise ValueError('GridMask draws for %d images, batch %d' % (mask.shape[0], self.batch))
-    return per, mask
+    packed = None
+    if self._aa_policy is not None:
+      if aa is None:
+        raise ValueError('the autoaugment switch is on (%r): draws need det_autoaugment.autoaug_draws\' tuple' % (self.autoaugment,))
+      packed, layout = det_autoaugment.pack_args(det_autoaugment.autoaug_args(
+          aa, self._aa_policy, self.height, self.width, magnitude=RANDAUG_MAGNITUDE))
+      if layout != self._aa_layout:
+        raise ValueError('AutoAugment draws for %s, want [layers, batch] = %s'
+                         % (layout['policy'][1], self._aa_layout['policy'][1]))
+    return per, mask, packed
 
   # ---- destinations ---------------------------------------------------------------------------------------------------
   def label_shapes(self):
@@ -170,7 +211,7 @@ class DetectionInput(object):
     classes = torch.as_tensor(classes).to(dev).to(torch.float32).reshape(b, m).contiguous()
     counts = torch.as_tensor(counts).to(dev).to(torch.int32).reshape(b).contiguous()
     self._check_destinations(images, labels)
-    per, mask = self.rows(draws)
+    per, mask, packed = self.rows(draws)
     if stream is None:
       stream = torch.cuda.current_stream(dev).cuda_stream
     self.prep_rows.copy_(torch.from_numpy(per).pin_memory(), non_blocking=True)
@@ -178,6 +219,10 @@ class DetectionInput(object):
     if self.grid_mask:
       self.mask_rows.copy_(gridmask_lib.args_tensor(mask, pin=True), non_blocking=True)
       src = gridmask_lib.apply_mask(raw, self.masked, self.mask_rows, stream)
+    if self._aa_policy is not None:      # dataloader.py:312-319: after GridMask, on the uint8 image and the boxes
+      self.aa_rows.copy_(torch.from_numpy(packed).pin_memory(), non_blocking=True)
+      src, boxes = det_autoaugment.apply_layers(src, self.aa_images, boxes, self.aa_boxes, counts, self.aa_args, self.aa_luts,
+                                                self.aa_scratch, stream)
     call('edet_preprocess_train', ptr(src), 0, b, self.height, self.width, self.output_size[0], self.output_size[1],
          self._mean, self._std, ptr(self.prep_rows), ptr(images), ptr(boxes), ptr(classes), ptr(counts), m,
          ptr(self.boxes), ptr(self.classes), ptr(self.counts),

@@ -11,6 +11,7 @@ import os
 
 import torch
 
+from automl_amd import det_autoaugment
 from automl_amd import det_input
 from automl_amd import efficientdet_net
 from automl_amd import engine as engine_lib
@@ -175,6 +176,17 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     # first train_step_raw, so a model that never calls it keeps its state keys
     self._det_input = None
     self._input_rng = None
+    self.autoaugment = None      # set_autoaugment: the box-aware AutoAugment / RandAugment in front of train_step_raw's crop
+
+  def set_autoaugment(self, policy):
+    """Switches the box-aware AutoAugment / RandAugment of aug/autoaugment.py (dataloader.py:312-319) on for train_step_raw:
+    'randaug' (num_layers=1, magnitude=15), 'v2', 'v3' or 'test'; None switches it off.  'v0' and 'v1' need the
+    *_Only_BBoxes operations, which are not built, and raise.  Needs no device; the input stage is rebuilt by the next
+    train_step_raw.  The draws come from the generator behind 'input_rng_state', after the step's other draws."""
+    if policy is not None:
+      det_autoaugment.available_policy(policy)
+    self.autoaugment = policy
+    self._det_input = None
 
   def get_optimizer_state(self):
     """Optimizer slots, iteration count and -- with positives_momentum > 0 -- the moving loss normalizer.  (The reference
@@ -411,12 +423,17 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     The draws (per image: flip, three scale draws, the five GridMask draws) come from a host generator seeded from the
     model's seed, whose state joins get_optimizer_state() as 'input_rng_state' once this method has been used; draws =
     det_input.Draws(flip [B], scale [B, 3], gridmask five arrays [B] or None) hands the values in instead.
-    skip_crowd_during_training (dataloader.py:303-306) is the caller's filtering of boxes / counts.  autoaugment_policy
-    (dataloader.py:312-319) is not built and raises."""
+    skip_crowd_during_training (dataloader.py:303-306) is the caller's filtering of boxes / counts.
+
+    The box-aware AutoAugment / RandAugment of aug/autoaugment.py (dataloader.py:312-319) runs between GridMask and the crop
+    once set_autoaugment(policy) has switched it on ('randaug', 'v2', 'v3', 'test'; 'v0', 'v1' and the *_Only_BBoxes
+    operations are not built); its draws then follow the others in the same generator, or come as the fourth field of
+    det_input.Draws (det_autoaugment.autoaug_draws).  The config key autoaugment_policy itself is still refused."""
     c = self.config
     if getattr(c, 'autoaugment_policy', None):
       raise ValueError('autoaugment_policy=%r is not built (the box-aware AutoAugment / RandAugment of aug/autoaugment.py, '
-                       'dataloader.py:312-319); train_step_raw would have to ignore it' % (c.autoaugment_policy,))
+                       'dataloader.py:312-319); train_step_raw would have to ignore it -- the part that is built is switched '
+                       'on with set_autoaugment(policy)' % (c.autoaugment_policy,))
     raw, boxes, classes, counts = data
     raw = torch.as_tensor(raw)
     if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
@@ -427,10 +444,10 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     b, m = int(raw.shape[0]), int(boxes.shape[1])
     h, w = utils.parse_image_size(c.image_size)
     eng = self._ensure_engine(b, h, w)
-    key = (b, int(raw.shape[1]), int(raw.shape[2]), m, h, w)
+    key = (b, int(raw.shape[1]), int(raw.shape[2]), m, h, w, self.autoaugment)
     if self._det_input is None or self._det_input[0] != key:
       self._det_input = (key, det_input.DetectionInput(c, self.anchors((h, w)), b, key[1], key[2], m, dtype=eng.tdtype,
-                                                       device=eng.device))
+                                                       device=eng.device, autoaugment=self.autoaugment))
     inp = self._det_input[1]
     if draws is None:
       if self._input_rng is None:

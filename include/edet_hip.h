@@ -689,6 +689,33 @@ typedef struct edet_gridmask_image { /* 48 bytes, one per image, read from DEVIC
 int edet_gridmask(const uint8_t* src, uint8_t* dst, int batch, int height, int width,
                   const edet_gridmask_image_t* per_image_dev, void* stream);
 
+/* ---- box-aware AutoAugment / RandAugment of the detector's input (efficientdet/aug/autoaugment.py) ----------------------
+ * The image operations are edet_randaug_stats / edet_randaug_apply above; the two calls here make the boxes follow and write
+ * what those read.  Per layer and image the caller gives, in DEVICE memory: policy int32 [batch], the reference's operation
+ * (NAME_TO_FUNC, :1350-1372): 0 AutoContrast, 1 Equalize, 2 Posterize, 3 Solarize, 4 SolarizeAdd, 5 Color, 6 Contrast,
+ * 7 Brightness, 8 Sharpness, 9 Cutout, 10 BBox_Cutout, 11 Rotate_BBox, 12 TranslateX_BBox, 13 TranslateY_BBox, 14 ShearX_BBox,
+ * 15 ShearY_BBox, anything else = none; and ops / iargs / fargs in edet_randaug_apply's layout, with the apply id of the
+ * image kernel: *_BBox -> Rotate / Translate / Shear with the host-made coefficients, Cutout and BBox_Cutout -> Cutout,
+ * Contrast -> 16 (copy) until edet_autoaug_contrast_lut has made its table.  Launch order of one layer:
+ * edet_autoaug_boxes, edet_randaug_stats, edet_autoaug_contrast_lut, edet_randaug_apply.
+ * edet_autoaug_boxes: boxes, boxes_out fp32 [batch][max_boxes][4] normalised (ymin, xmin, ymax, xmax), the same buffer or
+ * two, 16-byte aligned; rows at or past counts[b] are copied.  Rotate_BBox reads cos = fargs[0], sin = fargs[3] (no
+ * trigonometry on the device), TranslateX/Y_BBox the pixels fargs[2] / fargs[5], ShearX/Y_BBox the level fargs[1] / fargs[3]:
+ * _rotate_bbox (:785-835), _shift_bbox (:881-919), _shear_bbox (:978-1025), _clip_bbox and _check_bbox_area with delta 0.05
+ * (:435-483) in fp32 -- to_int32 truncates, every entry of the 2 x 4 matrix product is two rounded products and one rounded
+ * add, one rounded division.  BBox_Cutout leaves the boxes alone and writes the rectangle of _cutout_inside_bbox
+ * (:1245-1281) into the image's iargs row {lower, left, height - upper, width - right}: dargs fp64 [batch][4] = {pad_fraction,
+ * box draw, centre draw y, centre draw x}, draws in [0, 1); the box is int(u count), a centre lo + int(u (hi + 1 - lo)), the
+ * pad sizes int(pad_fraction * (extent / 2)) in fp64; counts[b] == 0: the empty rectangle (:1344).
+ * edet_autoaug_contrast_lut: for the images whose policy is Contrast (:267-280) the grey levels (the rgb_to_grayscale of
+ * Color) are summed as integers, mean = fp32(sum) / fp32(height width) clipped and truncated to uint8, luts[b][c][v] =
+ * blend(mean, v, fargs[b][6]) and ops[b] = 1, the table look-up of edet_randaug_apply.  Beyond a grey sum of 2^24 this exact
+ * sum is the definition (reduce_mean's summation order is not).  Restated in tests/det_autoaug_ref.py, compared bit for bit. */
+int edet_autoaug_boxes(const float* boxes, float* boxes_out, const int32_t* counts, int batch, int max_boxes, int height,
+                       int width, const int32_t* policy, int32_t* iargs, const float* fargs, const double* dargs, void* stream);
+int edet_autoaug_contrast_lut(const uint8_t* src, int batch, int height, int width, const int32_t* policy, int32_t* ops,
+                              const float* fargs, uint8_t* luts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

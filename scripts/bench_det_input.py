@@ -7,7 +7,7 @@
             they reuse one batch of 126 MB in and 126 MB out, which the cache holds -- say which one a figure is;
   step      ms per EfficientDetNetTrain step of `--model` at its own image size, batch `--batch`, bf16, hipGraph replay:
             train_step_raw from a raw uint8 batch of `--height` x `--width` with `--boxes` box rows per image (GridMask on with
-            `--grid-mask`), next to train_step fed from input_buffers() (no input work at all), alternating, `--reps`
+            `--grid-mask`, the box-aware AutoAugment with `--autoaugment v2`), next to train_step fed from input_buffers() (no input work at all), alternating, `--reps`
             repetitions of `--steps` steps each -> medians and spreads."""
 import argparse
 import json
@@ -67,6 +67,8 @@ def bench_step(args):
     config.override('grid_mask=true')
   net = train_lib.EfficientDetNetTrain(config=config, dtype='bf16', steps_per_epoch=1000, global_batch_size=args.batch,
                                        use_graph=True)
+  if args.autoaugment:
+    net.set_autoaugment(args.autoaugment)
   b, m = args.batch, args.boxes
   rng = np.random.default_rng(2)
   raw = torch.from_numpy(rng.integers(0, 256, (b, args.height, args.width, 3), dtype=np.uint8)).to('cuda:0')
@@ -94,7 +96,7 @@ def bench_step(args):
     times['train_step_raw'].append(timed(lambda: net.train_step_raw(data, sync_loss=False)))
     times['train_step'].append(timed(lambda: net.train_step(fed, sync_loss=False)))
   out = {'phase': 'step', 'model': args.model, 'batch': b, 'image_size': config.image_size, 'raw': [args.height, args.width],
-         'box_rows': m, 'grid_mask': bool(args.grid_mask), 'steps': args.steps, 'reps': args.reps,
+         'box_rows': m, 'grid_mask': bool(args.grid_mask), 'autoaugment': args.autoaugment or None, 'steps': args.steps, 'reps': args.reps,
          'first_loss': round(float(first['loss']), 4)}
   for name, t in times.items():
     out[name] = {'median_ms': round(float(np.median(t)), 3), 'spread_ms': round(max(t) - min(t), 3), 'min_ms': round(min(t), 3)}
@@ -111,6 +113,7 @@ if __name__ == '__main__':
   ap.add_argument('--width', type=int, default=640)
   ap.add_argument('--boxes', type=int, default=100)
   ap.add_argument('--grid-mask', action='store_true')
+  ap.add_argument('--autoaugment', default='')
   ap.add_argument('--rotate', type=int, default=1)
   ap.add_argument('--launches', type=int, default=20)
   ap.add_argument('--reps', type=int, default=9)
