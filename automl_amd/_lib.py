@@ -172,6 +172,9 @@ SIGNATURES = {
     'edet_gridmask': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     'edet_autoaug_boxes': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     'edet_autoaug_contrast_lut': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    'edet_coco_match': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    'edet_coco_accumulate': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p],
 }
 
 _lib = None

@@ -716,6 +716,39 @@ int edet_autoaug_boxes(const float* boxes, float* boxes_out, const int32_t* coun
 int edet_autoaug_contrast_lut(const uint8_t* src, int batch, int height, int width, const int32_t* policy, int32_t* ops,
                               const float* fargs, uint8_t* luts, void* stream);
 
+/* ---- COCO box AP / AR of an evaluator state (efficientdet/coco_metric.py; COCOeval for iouType 'bbox') ----------------------
+ * The images of the state in ascending image id, padded: dets fp32 [n_images][max_dets][6] rows {x, y, width, height, score,
+ * class}, gts fp32 [n_images][max_gts][7] rows {x, y, width, height, is_crowd (0 or 1), area, class}; a row whose class is not
+ * > -1 is padding.  Classes are compared as the fp32 values they are.  1 <= max_dets <= 100, 1 <= max_gts <= 128.
+ * edet_coco_match (one wave per image, lanes = the 40 (area range, IoU threshold) pairs): rank int32 [n_images][max_dets], the
+ * row's position among the kept rows of its image and class by descending score, equal scores in row order, -1 for padding;
+ * matched, ignored uint16 [n_images][4][max_dets], bit t = IoU threshold t.  iou_thrs fp64 [10], area_rng fp64 [4][2] {lo, hi}
+ * in DEVICE memory.  IoU in fp64 from the fp32 values: w = min(d.x + d.w, g.x + g.w) - max(d.x, g.x), 0 if w <= 0, h likewise,
+ * i = w h, u = d.w d.h for a crowd, else (d.w d.h + g.w g.h) - i, iou = i / u.  A ground truth is ignored in an area range when
+ * it is a crowd or its area is < lo or > hi; per threshold the rows are visited by descending score, best = min(t, 1 - 1e-10),
+ * the ground truths of the row's class not ignored first, then ignored, each in row order: skip one already matched unless a
+ * crowd, stop at an ignored one once a not ignored one is held, skip iou < best, else take it (an equal IoU replaces).  A
+ * matched row inherits the ground truth's ignore flag; an unmatched row is ignored when fp32(width height) is < lo or > hi.
+ * edet_coco_accumulate (one workgroup per (category, area range, cap, threshold)): perm int32 [n_images max_dets] = the rows
+ * ordered by (category, descending score, image, rank), seg int32 [n_cats + 1] = where each category starts in perm, npig int32
+ * [n_cats][4] = the not ignored ground truths, caps int32 [3] = maxDets, rec_thrs fp64 [101], all DEVICE memory.  precision
+ * fp64 [10][101][n_cats][4][3] and recall fp64 [10][n_cats][4][3] are the caller's, pre-set to -1: a cell with npig = 0 is
+ * left alone.  tp = matched & ~ignored and fp = ~matched & ~ignored of the rows with rank < cap, summed as integers along the
+ * segment; rc = tp / npig, pr = tp / ((fp + tp) + 2^-52), pr made non-increasing from the right; recall = the last rc,
+ * precision[r] = pr at the first row with rc >= rec_thrs[r], 0 past the end.  No atomics; the same bits on every run.
+ * Restated in tests/coco_ref.py and compared bit for bit.  n_images * max_dets < 2^29. */
+#define EDET_COCO_THRS 10
+#define EDET_COCO_RECS 101
+#define EDET_COCO_AREAS 4
+#define EDET_COCO_CAPS 3
+#define EDET_COCO_MAX_DETS 100
+#define EDET_COCO_MAX_GTS 128
+int edet_coco_match(const float* dets, const float* gts, int n_images, int max_dets, int max_gts, const double* iou_thrs,
+                    const double* area_rng, int32_t* rank, uint16_t* matched, uint16_t* ignored, void* stream);
+int edet_coco_accumulate(const int32_t* perm, const int32_t* seg, const int32_t* rank, const uint16_t* matched,
+                         const uint16_t* ignored, const int32_t* npig, int n_images, int max_dets, int n_cats,
+                         const double* rec_thrs, const int32_t* caps, double* precision, double* recall, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
