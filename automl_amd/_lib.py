@@ -175,6 +175,8 @@ SIGNATURES = {
     'edet_coco_match': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     'edet_coco_accumulate': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p],
+    'edet_wbf_cluster': [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    'edet_wbf_order': [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
 }
 
 _lib = None

@@ -749,6 +749,30 @@ int edet_coco_accumulate(const int32_t* perm, const int32_t* seg, const int32_t*
                          const uint16_t* ignored, const int32_t* npig, int n_images, int max_dets, int n_cats,
                          const double* rec_thrs, const int32_t* caps, double* precision, double* recall, void* stream);
 
+/* ---- weighted box fusion of the detections of several passes (efficientdet/tf2/wbf.py:70-95) ------------------------------
+ * dets fp32 [batch][rows][7], rows {image id, x1, y1, x2, y2, score, class} (the corner form of generate_detections), counts
+ * int32 [batch] = the rows of each image that count (NULL: all; clamped to 0..rows), 1 <= rows <= 1024, num_models >= 1.
+ * Finite coordinates and scores only.
+ * edet_wbf_cluster (one wave per (image, class)): for cid in 0 .. num_classes - 1 the rows with class == (float)cid, in input
+ * order; any other class value is dropped.  A row founds a cluster when its class has none yet or when the largest IoU with the
+ * clusters' current averages is < 0.55f; else it joins the cluster of that IoU, the lowest index among equals.  A NaN IoU (0 / 0:
+ * two boxes without area) is not below 0.55 and beats every number, the lowest such index first (numpy's max / argmax).  IoU in
+ * fp32: xa = max(x11, x21), ya, xb = min(x12, x22), yb likewise, inter = max(xb - xa, 0) max(yb - ya, 0), iou = inter /
+ * ((area_a + area_b) - inter).  Per cluster five running fp32 sums that start at +0 and take the members in order: x1 s, y1 s,
+ * x2 s, y2 s (each product rounded, then added) and s; the average of a coordinate is its sum / the sum of s.  When the class
+ * is done the cluster's row {image id of the first member, the four averages, (sum of s / (float)n) * (float)min(1, (double)n
+ * / num_models), class of the first member} is written to scratch fp32 [batch][rows][7] at the row of its first member and
+ * flags int32 [batch][rows] is set to 1 there.  flags must be ZERO on entry; scratch need not be initialised.  No atomics.
+ * edet_wbf_order (one workgroup per image): the flagged rows of scratch by descending score, equal scores by (class, row)
+ * ascending -- rank = the number of flagged rows ahead, by counting -- written densely to fused fp32 [batch][rows][7]; the rows
+ * at or past fused_counts[b] (int32 [batch], the number of clusters) are zero.
+ * Restated in tests/wbf_ref.py and compared bit for bit. */
+#define EDET_WBF_MAX_ROWS 1024
+int edet_wbf_cluster(const float* dets, const int32_t* counts, int batch, int rows, int num_classes, int num_models,
+                     float* scratch, int32_t* flags, void* stream);
+int edet_wbf_order(const float* scratch, const int32_t* flags, int batch, int rows, float* fused, int32_t* fused_counts,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
