@@ -128,6 +128,11 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p],
     'edet_box_loss': [c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_void_p,
                       c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p],
+    'edet_focal_loss_eval': [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_float, c_float,
+                             c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p],
+    'edet_box_loss_eval': [c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                           ctypes.c_size_t, c_int, c_void_p],
+    'edet_l2_loss': [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],
     'edet_opt_l2_norms': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p],
     'edet_opt_clip_factors': [c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     'edet_opt_scale': [c_void_p, c_void_p, c_void_p, c_int, c_void_p],
@@ -167,6 +172,8 @@ SIGNATURES = {
                               c_void_p, c_int, c_void_p],
     'edet_preprocess_train': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    'edet_pack_groundtruth': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                              c_void_p, c_void_p],
     'edet_nms_gather': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     'edet_gridmask': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],

@@ -33,6 +33,9 @@ inline RowMap row_map_ld(int ld) {
 // workgroup writes its row [nch | 1] there and edet_reduce_partials2 adds the rows in order (the same loss and bias gradient on
 // every run); without one the kernel is launched as ONE workgroup, which adds into the destinations itself -- no atomics.
 // LDS: scr[THREADS * 8] floats (dynamic).
+// GRAD = false (the loss-only kernels of the evaluation step, edet_focal_loss_eval / edet_box_loss_eval): the same loss sum in
+// the same order, no bias-gradient rows -- a partial row is the workgroup's loss alone.
+template <bool GRAD = true>
 __device__ __forceinline__ void loss_tail(float loss_acc, const float (&db)[8], bool ok, int nch, const RowMap& m, float* scr,
                                           float* part, float* sum_dst, float* dbias) {
   __shared__ float wsum[THREADS / 64];
@@ -42,16 +45,18 @@ __device__ __forceinline__ void loss_tail(float loss_acc, const float (&db)[8], 
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) loss_acc += __shfl_down(loss_acc, off, 64);
   if ((tid & 63) == 0) wsum[tid >> 6] = loss_acc;
+  if (GRAD) {
 #pragma unroll
-  for (int e = 0; e < 8; ++e) scr[rr * width + cv * 8 + e] = ok ? db[e] : 0.f;
+    for (int e = 0; e < 8; ++e) scr[rr * width + cv * 8 + e] = ok ? db[e] : 0.f;
+  }
   __syncthreads();
-  float* row = part ? part + (size_t)blockIdx.x * (1 + nch) : nullptr;      // [bias gradient (nch) | loss]
+  float* row = part ? part + (size_t)blockIdx.x * (GRAD ? 1 + nch : 1) : nullptr;      // [bias gradient (nch) | loss]
   if (tid == 0) {
     float t = 0.f;
     for (int w = 0; w < THREADS / 64; ++w) t += wsum[w];
-    if (row) row[nch] = t; else *sum_dst += t;          // (no partial buffer: the kernel runs as ONE workgroup)
+    if (row) row[GRAD ? nch : 0] = t; else *sum_dst += t;          // (no partial buffer: the kernel runs as ONE workgroup)
   }
-  if (dbias || row) {
+  if (GRAD && (dbias || row)) {
     for (int i = tid; i < nch; i += THREADS) {
       float t = 0.f;
       for (int r = 0; r < m.rpp; ++r) t += scr[r * width + i];
@@ -60,7 +65,7 @@ __device__ __forceinline__ void loss_tail(float loss_acc, const float (&db)[8], 
   }
 }
 
-template <typename T, bool G15, bool LS>
+template <typename T, bool G15, bool LS, bool GRAD = true>
 __device__ __forceinline__ void focal_body(const T* __restrict__ logits, int ld,
                                                   const int32_t* __restrict__ tgt, int64_t positions,
                                                   int na, int nc, float alpha, float gamma, float inv_norm_h,
@@ -99,17 +104,19 @@ __device__ __forceinline__ void focal_body(const T* __restrict__ logits, int ld,
           const float af = pos ? alpha : 1.f - alpha;
           const float mod = G15 ? sg * __builtin_amdgcn_sqrtf(sg) : __powf(sg, gamma);
           loss_acc = fmaf(af * mod, sp * inv_norm, loss_acc);
-          const float dldu = af * mod * fmaf(gamma * (1.f - sg), sp, LS ? sg - half_ls : sg) * inv_norm;
-          g[e] = pos ? -dldu : dldu;
+          if (GRAD) {
+            const float dldu = af * mod * fmaf(gamma * (1.f - sg), sp, LS ? sg - half_ls : sg) * inv_norm;
+            g[e] = pos ? -dldu : dldu;
+          }
         }
-        db[e] += g[e];
+        if (GRAD) db[e] += g[e];
         if (++k == nc) {
           k = 0;
           ++a;
           t = a < na ? tgt[p * na + a] : -2;
         }
       }
-      store8<T>(dlogits + p * ld + j0, g);
+      if (GRAD) store8<T>(dlogits + p * ld + j0, g);
     }
   } else if (ok) {
     // One row per step, the next row's logits and targets requested before this row is worked on (r03: the first
@@ -157,12 +164,14 @@ __device__ __forceinline__ void focal_body(const T* __restrict__ logits, int ld,
         const float mod = G15 ? sg * __builtin_amdgcn_sqrtf(sg) : __powf(sg, gamma);
         const float wgt = valid ? af * mod * inv_norm : 0.f;
         loss_acc = fmaf(wgt, sp, loss_acc);
-        // d/du [sg^gamma * softplus(u)] = sg^gamma * (gamma*(1-sg)*sp + sg)
-        const float dldu = wgt * fmaf(gamma * (1.f - sg), sp, LS ? sg - half_ls : sg);
-        g[e] = pos ? -dldu : dldu;
-        db[e] += g[e];
+        if (GRAD) {
+          // d/du [sg^gamma * softplus(u)] = sg^gamma * (gamma*(1-sg)*sp + sg)
+          const float dldu = wgt * fmaf(gamma * (1.f - sg), sp, LS ? sg - half_ls : sg);
+          g[e] = pos ? -dldu : dldu;
+          db[e] += g[e];
+        }
       }
-      store8<T>(dlogits + p * ld + j0, g);
+      if (GRAD) store8<T>(dlogits + p * ld + j0, g);
 #pragma unroll
       for (int e = 0; e < 8; ++e) x[e] = xn[e];
       t0 = t0n; t1 = t1n;
@@ -170,7 +179,7 @@ __device__ __forceinline__ void focal_body(const T* __restrict__ logits, int ld,
     }
   }
   extern __shared__ float red[];  // [THREADS * 8]
-  loss_tail(loss_acc, db, ok, nch, m, red, part, &sums[0], dbias);
+  loss_tail<GRAD>(loss_acc, db, ok, nch, m, red, part, &sums[0], dbias);
 }
 
 template <typename T, bool G15>
@@ -191,12 +200,20 @@ __global__ __launch_bounds__(THREADS) void k_focal_ls(const T* __restrict__ logi
   focal_body<T, G15, true>(logits, ld, tgt, positions, na, nc, alpha, gamma, inv_norm_h, norm_scale, dlogits, dbias, sums, part, m, half_ls);
 }
 
-template <typename T>
-__global__ __launch_bounds__(THREADS) void k_box(const T* __restrict__ out, int ld,
-                                                const float* __restrict__ tgt, int64_t positions, int nch,
-                                                float delta, float inv_norm_h, float grad_scale,
-                                                const float* __restrict__ norm_scale,
-                                                T* __restrict__ dbox, float* dbias, float* sums, float* part, RowMap m) {
+// the loss alone (GRAD = false): the arithmetic and the summation order of k_focal / k_focal_ls, no gradient stores
+template <typename T, bool G15, bool LS>
+__global__ __launch_bounds__(THREADS) void k_focal_eval(const T* __restrict__ logits, int ld,
+                                                       const int32_t* __restrict__ tgt, int64_t positions,
+                                                       int na, int nc, float alpha, float gamma, float inv_norm_h,
+                                                       const float* __restrict__ norm_scale, float* sums, float* part, RowMap m,
+                                                       float half_ls) {
+  focal_body<T, G15, LS, false>(logits, ld, tgt, positions, na, nc, alpha, gamma, inv_norm_h, norm_scale, nullptr, nullptr, sums, part, m, half_ls);
+}
+
+template <typename T, bool GRAD>
+__device__ __forceinline__ void box_body(const T* out, int ld, const float* tgt, int64_t positions, int nch,
+                                         float delta, float inv_norm_h, float grad_scale, const float* norm_scale,
+                                         T* dbox, float* dbias, float* sums, float* part, RowMap m) {
   const float inv_norm = norm_scale ? inv_norm_h * norm_scale[0] : inv_norm_h;
   const int tid = threadIdx.x;
   const int cv = tid % m.tpr, rr = tid / m.tpr;
@@ -220,16 +237,32 @@ __global__ __launch_bounds__(THREADS) void k_box(const T* __restrict__ out, int 
             const float ae = fabsf(err);
             const bool quad = ae <= delta;
             loss_acc += (quad ? 0.5f * err * err : delta * ae - 0.5f * delta * delta) * inv_norm;
-            g[e] = (quad ? err : (err > 0.f ? delta : -delta)) * inv_norm * grad_scale;
+            if (GRAD) g[e] = (quad ? err : (err > 0.f ? delta : -delta)) * inv_norm * grad_scale;
           }
         }
-        db[e] += g[e];
+        if (GRAD) db[e] += g[e];
       }
-      store8<T>(dbox + p * ld + j0, g);
+      if (GRAD) store8<T>(dbox + p * ld + j0, g);
     }
   }
   extern __shared__ float red[];  // [THREADS * 8]
-  loss_tail(loss_acc, db, ok, nch, m, red, part, &sums[1], dbias);
+  loss_tail<GRAD>(loss_acc, db, ok, nch, m, red, part, &sums[1], dbias);
+}
+
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_box(const T* __restrict__ out, int ld,
+                                                const float* __restrict__ tgt, int64_t positions, int nch,
+                                                float delta, float inv_norm_h, float grad_scale,
+                                                const float* __restrict__ norm_scale,
+                                                T* __restrict__ dbox, float* dbias, float* sums, float* part, RowMap m) {
+  box_body<T, true>(out, ld, tgt, positions, nch, delta, inv_norm_h, grad_scale, norm_scale, dbox, dbias, sums, part, m);
+}
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_box_eval(const T* __restrict__ out, int ld,
+                                                     const float* __restrict__ tgt, int64_t positions, int nch,
+                                                     float delta, float inv_norm_h,
+                                                     const float* __restrict__ norm_scale, float* sums, float* part, RowMap m) {
+  box_body<T, false>(out, ld, tgt, positions, nch, delta, inv_norm_h, 0.f, norm_scale, nullptr, nullptr, sums, part, m);
 }
 
 // ----------------------------------------------------------------------------------- optimizer
@@ -258,7 +291,10 @@ __device__ __forceinline__ bool slice_range(const int64_t* seg_off, int s, int j
   return b < e;
 }
 
-__global__ __launch_bounds__(THREADS) void k_l2_norms(float* grads, const float* params,
+// GRAD = false (k_l2_loss_slices, the evaluation step): the wsq sums alone, in the same order -- the gradient arena is neither
+// read nor written, seg_sqnorm is [nseg][OPT_SPLIT] L2 shares
+template <bool GRAD>
+__device__ __forceinline__ void l2_norms_body(float* grads, const float* params,
                                                      const int64_t* seg_off, const int32_t* seg_flags,
                                                      float wd, float* seg_sqnorm, int nseg) {
   __shared__ float sh[THREADS / 64];
@@ -270,42 +306,70 @@ __global__ __launch_bounds__(THREADS) void k_l2_norms(float* grads, const float*
   float gsq = 0.f, wsq = 0.f;
   if (any && frozen) {
     // a frozen variable (config.var_freeze_expr) has no gradient: zeroed here, no share in the norms, skipped by the update
-    for (int64_t i = b + threadIdx.x; i < e; i += THREADS) grads[i] = 0.f;
+    if (GRAD) {
+      for (int64_t i = b + threadIdx.x; i < e; i += THREADS) grads[i] = 0.f;
+    }
   } else if (any) {
     if ((b & 3) == 0) {
       const int64_t nv = (e - b) >> 2;
-      float4* g4 = reinterpret_cast<float4*>(grads + b);
+      float4* g4 = GRAD ? reinterpret_cast<float4*>(grads + b) : nullptr;
       const float4* w4 = reinterpret_cast<const float4*>(params + b);
       for (int64_t i = threadIdx.x; i < nv; i += THREADS) {
-        float4 g = g4[i];
+        float4 g = GRAD ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
         if (reg) {
           const float4 w = w4[i];
-          g.x = fmaf(wd, w.x, g.x); g.y = fmaf(wd, w.y, g.y); g.z = fmaf(wd, w.z, g.z); g.w = fmaf(wd, w.w, g.w);
-          g4[i] = g;
+          if (GRAD) {
+            g.x = fmaf(wd, w.x, g.x); g.y = fmaf(wd, w.y, g.y); g.z = fmaf(wd, w.z, g.z); g.w = fmaf(wd, w.w, g.w);
+            g4[i] = g;
+          }
           wsq += w.x * w.x + w.y * w.y + w.z * w.z + w.w * w.w;
         }
-        gsq += g.x * g.x + g.y * g.y + g.z * g.z + g.w * g.w;
+        if (GRAD) gsq += g.x * g.x + g.y * g.y + g.z * g.z + g.w * g.w;
       }
       b += nv << 2;
     }
     for (int64_t i = b + threadIdx.x; i < e; i += THREADS) {
-      float g = grads[i];
+      float g = GRAD ? grads[i] : 0.f;
       if (reg) {
         const float w = params[i];
-        g = fmaf(wd, w, g);
-        grads[i] = g;
+        if (GRAD) {
+          g = fmaf(wd, w, g);
+          grads[i] = g;
+        }
         wsq = fmaf(w, w, wsq);
       }
-      gsq = fmaf(g, g, gsq);
+      if (GRAD) gsq = fmaf(g, g, gsq);
     }
   }
-  const float tg = block_sum(gsq, sh);
+  const float tg = GRAD ? block_sum(gsq, sh) : 0.f;
   const float tw = block_sum(wsq, sh);
   if (threadIdx.x == 0) {
-    seg_sqnorm[(size_t)s * OPT_SPLIT + j] = tg;
+    if (GRAD) seg_sqnorm[(size_t)s * OPT_SPLIT + j] = tg;
     // this slice's share of the L2 loss, summed in a fixed order by k_clip_factors (r04: no atomics)
-    seg_sqnorm[((size_t)nseg + s) * OPT_SPLIT + j] = (any && reg) ? 0.5f * wd * tw : 0.f;
+    seg_sqnorm[((size_t)(GRAD ? nseg : 0) + s) * OPT_SPLIT + j] = (any && reg) ? 0.5f * wd * tw : 0.f;
   }
+}
+
+__global__ __launch_bounds__(THREADS) void k_l2_norms(float* grads, const float* params,
+                                                     const int64_t* seg_off, const int32_t* seg_flags,
+                                                     float wd, float* seg_sqnorm, int nseg) {
+  l2_norms_body<true>(grads, params, seg_off, seg_flags, wd, seg_sqnorm, nseg);
+}
+__global__ __launch_bounds__(THREADS) void k_l2_loss_slices(const float* params, const int64_t* seg_off,
+                                                           const int32_t* seg_flags, float wd, float* seg_l2, int nseg) {
+  l2_norms_body<false>(nullptr, params, seg_off, seg_flags, wd, seg_l2, nseg);
+}
+// the L2 half of k_clip_factors: the slices' shares added in its order (segments strided over the lanes, a segment's slices
+// in order, block_sum), WRITTEN to l2_out[0]
+__global__ __launch_bounds__(THREADS) void k_l2_loss_sum(const float* seg_l2, int nseg, float* l2_out) {
+  __shared__ float sh[THREADS / 64];
+  float l2 = 0.f;
+  for (int s = threadIdx.x; s < nseg; s += THREADS) {
+#pragma unroll
+    for (int j = 0; j < OPT_SPLIT; ++j) l2 += seg_l2[(size_t)s * OPT_SPLIT + j];
+  }
+  const float l2tot = block_sum(l2, sh);
+  if (threadIdx.x == 0) l2_out[0] = l2tot;
 }
 
 // tf.clip_by_norm per tensor, then tf.clip_by_global_norm over the clipped tensors
@@ -554,6 +618,87 @@ extern "C" int edet_box_loss(const void* box_out, int ld, const float* box_targe
   else EDET_CHECK(false, "edet_box_loss: bad dtype %d", dtype);
   if (part && edet_reduce_partials2(part, (int)g, 1 + nch, dbias, nch, &sums[1], to_stream(stream)) != 0) return -2;
   EDET_LAUNCH_CHECK("edet_box_loss");
+  return 0;
+}
+
+// ---- the evaluation step's losses (tf2/train_lib.py:686-732, test_step): the sums of the entry points above, bit for bit, with
+// no gradient written anywhere.  Same grids (the partial rows line up), GRAD = false instantiations of the same bodies.
+extern "C" int edet_focal_loss_eval(const void* logits, int ld, const int32_t* cls_targets,
+                                    int64_t positions, int num_anchors, int num_classes,
+                                    float alpha, float gamma, float label_smoothing, float inv_normalizer,
+                                    const float* norm_scale_dev, float* sums, void* workspace, size_t workspace_bytes,
+                                    int dtype, void* stream) {
+  EDET_CHECK(logits && cls_targets && sums, "edet_focal_loss_eval: null pointer");
+  EDET_CHECK(ld % 8 == 0 && ld >= num_anchors * num_classes && ld <= 2048, "edet_focal_loss_eval: bad ld %d", ld);
+  EDET_CHECK(num_classes >= 1 && num_anchors >= 1 && positions >= 0, "edet_focal_loss_eval: bad shape");
+  EDET_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "edet_focal_loss_eval: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_focal_loss_eval: bad dtype %d", dtype);
+  const RowMap m = row_map_ld(ld);
+  int64_t g = (positions + m.rpp - 1) / m.rpp;
+  g = (g + 3) / 4;
+  const size_t lds = (size_t)THREADS * 8 * sizeof(float);
+  const bool g15 = gamma == 1.5f;
+  const bool ls = label_smoothing != 0.f;
+  const float half_ls = 0.5f * label_smoothing;
+  {   // the training entry point's cap: the residency of ITS kernel, so that both run the same grid
+    const void* fn = dtype == EDET_BF16 ? (g15 ? reinterpret_cast<const void*>(&k_focal<bf16_t, true>) : reinterpret_cast<const void*>(&k_focal<bf16_t, false>))
+                                        : (g15 ? reinterpret_cast<const void*>(&k_focal<float, true>) : reinterpret_cast<const void*>(&k_focal<float, false>));
+    const int slots = edet_resident_wgs(fn, THREADS, lds);
+    const int64_t cap = slots > 0 ? slots : 4096;
+    if (g > cap) g = cap;
+  }
+  if (g < 1) g = 1;
+  // the training entry point goes to ONE workgroup when the workspace cannot hold its rows [g][1 + nch]: the same rule here
+  const int nch_ = num_anchors * num_classes;
+  float* part = (workspace && workspace_bytes >= (size_t)g * (1 + nch_) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
+  if (!part) g = 1;
+#define FOCAL_EVAL(T, G, L)                                                                                \
+  edet_launch(k_focal_eval<T, G, L>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const T*)logits, ld, cls_targets, positions, \
+      num_anchors, num_classes, alpha, gamma, inv_normalizer, norm_scale_dev, sums, part, m, half_ls)
+#define FOCAL_EVAL_T(T)                                                    \
+  do {                                                                     \
+    if (g15) { if (ls) FOCAL_EVAL(T, true, true); else FOCAL_EVAL(T, true, false); }     \
+    else { if (ls) FOCAL_EVAL(T, false, true); else FOCAL_EVAL(T, false, false); }       \
+  } while (0)
+  if (dtype == EDET_BF16) FOCAL_EVAL_T(bf16_t);
+  else FOCAL_EVAL_T(float);
+#undef FOCAL_EVAL_T
+#undef FOCAL_EVAL
+  if (part && edet_reduce_partials2(part, (int)g, 1, nullptr, 0, &sums[0], to_stream(stream)) != 0) return -2;
+  EDET_LAUNCH_CHECK("edet_focal_loss_eval");
+  return 0;
+}
+
+extern "C" int edet_box_loss_eval(const void* box_out, int ld, const float* box_targets,
+                                  int64_t positions, int nch, float delta, float inv_normalizer,
+                                  const float* norm_scale_dev, float* sums, void* workspace, size_t workspace_bytes,
+                                  int dtype, void* stream) {
+  EDET_CHECK(box_out && box_targets && sums, "edet_box_loss_eval: null pointer");
+  EDET_CHECK(ld % 8 == 0 && nch >= 1 && ld >= nch && ld <= 2048 && positions >= 0, "edet_box_loss_eval: bad ld %d", ld);
+  EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_box_loss_eval: bad dtype %d", dtype);
+  const RowMap m = row_map_ld(ld);
+  int64_t g = (positions + m.rpp - 1) / m.rpp;
+  g = (g + 3) / 4;
+  if (g > 2048) g = 2048;
+  if (g < 1) g = 1;
+  const size_t lds = (size_t)THREADS * 8 * sizeof(float);
+  float* part = (workspace && workspace_bytes >= (size_t)g * (1 + nch) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
+  if (!part) g = 1;
+  if (dtype == EDET_BF16)
+    edet_launch(k_box_eval<bf16_t>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const bf16_t*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, norm_scale_dev, sums, part, m);
+  else
+    edet_launch(k_box_eval<float>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const float*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, norm_scale_dev, sums, part, m);
+  if (part && edet_reduce_partials2(part, (int)g, 1, nullptr, 0, &sums[1], to_stream(stream)) != 0) return -2;
+  EDET_LAUNCH_CHECK("edet_box_loss_eval");
+  return 0;
+}
+
+extern "C" int edet_l2_loss(const float* params, const int64_t* seg_offsets, const int32_t* seg_flags, int nseg,
+                            float weight_decay, float* seg_l2, float* l2_out, void* stream) {
+  EDET_CHECK(params && seg_offsets && seg_flags && seg_l2 && l2_out && nseg > 0, "edet_l2_loss: bad arguments");
+  edet_launch(k_l2_loss_slices, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, seg_offsets, seg_flags, weight_decay, seg_l2, nseg);
+  edet_launch(k_l2_loss_sum, dim3(1), dim3(THREADS), 0, to_stream(stream), (const float*)seg_l2, nseg, l2_out);
+  EDET_LAUNCH_CHECK("edet_l2_loss");
   return 0;
 }
 

@@ -64,6 +64,8 @@ def mean_num_positives(num_positives):
 class DetectionInput(object):
   """The input launches of one (batch, raw size, box rows) shape for `config` on `device`."""
 
+  TRAINING = True      # DetectionEvalInput: no GridMask, no AutoAugment, no draws
+
   def __init__(self, config, anchors, batch, height, width, max_boxes, dtype=torch.float32, device='cuda:0',
                autoaugment=None):
     if dtype not in (torch.float32, torch.bfloat16):
@@ -77,7 +79,7 @@ class DetectionInput(object):
     self.output_size = utils.parse_image_size(config.image_size)
     target = getattr(config, 'target_size', None)
     self.target_size = utils.parse_image_size(target) if target else self.output_size
-    self.grid_mask = bool(getattr(config, 'grid_mask', None))
+    self.grid_mask = self.TRAINING and bool(getattr(config, 'grid_mask', None))
     if self.grid_mask:
       gridmask_lib.block_range(self.height, self.width)      # a raw size the reference could not mask: raises
     self.autoaugment = autoaugment      # None, 'randaug', 'v2', 'v3' or 'test' (det_autoaugment.available_policy)
@@ -223,6 +225,14 @@ class DetectionInput(object):
       self.aa_rows.copy_(torch.from_numpy(packed).pin_memory(), non_blocking=True)
       src, boxes = det_autoaugment.apply_layers(src, self.aa_images, boxes, self.aa_boxes, counts, self.aa_args, self.aa_luts,
                                                 self.aa_scratch, stream)
+    self._launch(src, boxes, classes, counts, images, labels, stream)
+    self._keep_alive = (raw, boxes, classes, counts)
+    return images, labels
+
+  def _launch(self, src, boxes, classes, counts, images, labels, stream):
+    """edet_preprocess_train with the rows in prep_rows, edet_label_anchors, mean_num_positives: what the training and the
+    evaluation stage share."""
+    b, m = self.batch, self.max_boxes
     call('edet_preprocess_train', ptr(src), 0, b, self.height, self.width, self.output_size[0], self.output_size[1],
          self._mean, self._std, ptr(self.prep_rows), ptr(images), ptr(boxes), ptr(classes), ptr(counts), m,
          ptr(self.boxes), ptr(self.classes), ptr(self.counts),
@@ -235,5 +245,88 @@ class DetectionInput(object):
          ptr(self.counts), b, m, float(self.labeler._match_threshold), ptr(self.workspace), self._ws_bytes, cp, bp,
          ptr(self.num_positives), stream)
     labels['mean_num_positives'].view(b, 1).copy_(mean_num_positives(self.num_positives))
+
+
+def parse_source_ids(source_ids):
+  """dataloader.py:340-342: an empty source id is -1, the others tf.strings.to_number's float32.  Numbers pass through."""
+  a = np.asarray(source_ids)
+  if a.dtype.kind in 'USO':
+    a = np.asarray([float(v) if str(v) != '' else -1.0 for v in a.reshape(-1).tolist()])
+  return a.astype(np.float32).reshape(-1)
+
+
+class DetectionEvalInput(DetectionInput):
+  """The evaluation branch of ``InputReader.dataset_parser`` plus ``process_example`` (dataloader.py:321-323, :331-353,
+  :369-392) for one (batch, raw size, box rows) shape: ``normalize_image``, ``set_scale_factors_to_output_size`` -- no flip,
+  no crop offset, no draws, neither GridMask nor AutoAugment --, ``resize_and_crop_image`` / ``resize_and_crop_boxes``
+  (edet_preprocess_train), ``label_anchors`` (edet_label_anchors), ``mean_num_positives``, and the ground truth of the batch
+  (edet_pack_groundtruth): 3 launches of this library plus the small copies.  The per-image rows and ``image_scales`` are
+  constants of the shape: computed and uploaded once, here.
+
+  ``labels`` gets what the training stage writes plus ``source_ids`` float32 [B] (an empty id is -1, :340-342),
+  ``image_scales`` float32 [B] = image_scale_to_original (:345) and ``groundtruth_data`` float32 [B,
+  max_instances_per_image, 7], rows [y1, x1, y2, x2, is_crowd, area, class] in pixels of the ORIGINAL image.
+
+  Kept as the reference is written: ``resize_and_crop_boxes`` drops zero-area boxes together with their classes (:186-190)
+  but ``is_crowds`` and ``areas`` are not filtered, so after a dropped box columns 4 and 5 of the later rows belong to a
+  different annotation than columns 0-3 and 6.  ``pad_to_fixed_size`` asserts instances < max_instances_per_image (:228, a
+  strict less); more box ROWS than max_instances_per_image raise here, on the host, and an image that fills every row is
+  packed without padding rows instead of failing."""
+
+  TRAINING = False
+
+  def __init__(self, config, anchors, batch, height, width, max_boxes, dtype=torch.float32, device='cuda:0'):
+    self.max_instances = int(getattr(config, 'max_instances_per_image', None) or 100)
+    if int(max_boxes) > self.max_instances:
+      raise ValueError('ERROR: please increase config.max_instances_per_image (%d box rows, max_instances_per_image %d; '
+                       'dataloader.pad_to_fixed_size)' % (max_boxes, self.max_instances))
+    super().__init__(config, anchors, batch, height, width, max_boxes, dtype=dtype, device=device)
+    b, m, dev = self.batch, self.max_boxes, self.device
+    scale, scaled = preprocess.output_size_scale_factors(self.output_size, self.height, self.width)
+    if min(scaled) < 1:
+      raise ValueError('the scaled image is empty')
+    per = np.zeros((b, 5), np.int32)      # flip 0, offsets 0
+    per[:, 1:3] = scaled
+    self.prep_rows.copy_(torch.from_numpy(per))
+    self.image_scale = scale
+    self.image_scales = torch.full((b,), float(np.float32(1.0) / scale), dtype=torch.float32, device=dev)
+    self.is_crowds = torch.empty((b, m), dtype=torch.float32, device=dev)
+    self.areas = torch.empty((b, m), dtype=torch.float32, device=dev)
+
+  def draw(self, rng):
+    raise TypeError('the evaluation input makes no draws')
+
+  def label_shapes(self):
+    out = super().label_shapes()
+    b = self.batch
+    out['source_ids'] = ((b,), torch.float32)
+    out['image_scales'] = ((b,), torch.float32)
+    out['groundtruth_data'] = ((b, self.max_instances, 7), torch.float32)
+    return out
+
+  def run(self, raw_images, boxes, classes, counts, is_crowds, areas, source_ids, images, labels, stream=None):
+    """raw_images uint8 [B, H, W, 3], boxes float32 [B, M, 4] normalised (ymin, xmin, ymax, xmax), classes [B, M], counts [B],
+    is_crowds [B, M] (bool or 0 / 1), areas [B, M], source_ids [B] (numbers, or strings with '' for none) -> fills `images`
+    and `labels` in place, on torch's current stream."""
+    b, m, dev = self.batch, self.max_boxes, self.device
+    raw = torch.as_tensor(raw_images)
+    if raw.dtype != torch.uint8 or tuple(raw.shape) != (b, self.height, self.width, 3):
+      raise ValueError('raw images must be uint8 %s, got %s %s' % ((b, self.height, self.width, 3), raw.dtype, tuple(raw.shape)))
+    raw = raw.to(dev).contiguous()
+    boxes = torch.as_tensor(boxes, dtype=torch.float32).to(dev).reshape(b, m, 4).contiguous()
+    classes = torch.as_tensor(classes).to(dev).to(torch.float32).reshape(b, m).contiguous()
+    counts = torch.as_tensor(counts).to(dev).to(torch.int32).reshape(b).contiguous()
+    self._check_destinations(images, labels)
+    if stream is None:
+      stream = torch.cuda.current_stream(dev).cuda_stream
+    self.is_crowds.copy_(torch.as_tensor(is_crowds).reshape(b, m), non_blocking=True)      # tf.cast(is_crowds, float32), :347
+    self.areas.copy_(torch.as_tensor(areas).reshape(b, m), non_blocking=True)
+    if not torch.is_tensor(source_ids):
+      source_ids = torch.from_numpy(parse_source_ids(source_ids))
+    labels['source_ids'].view(b).copy_(source_ids.reshape(b), non_blocking=True)
+    labels['image_scales'].view(b).copy_(self.image_scales)
+    self._launch(raw, boxes, classes, counts, images, labels, stream)
+    call('edet_pack_groundtruth', ptr(self.boxes), ptr(self.classes), ptr(self.counts), ptr(self.is_crowds), ptr(self.areas),
+         ptr(counts), ptr(self.image_scales), b, m, self.max_instances, ptr(labels['groundtruth_data']), stream)
     self._keep_alive = (raw, boxes, classes, counts)
     return images, labels

@@ -432,6 +432,56 @@ class Engine(LayerEngine):
       rb.grad_written = True
     self.backward()
 
+  def loss_only(self, labels):
+    """test_step's losses (train_lib.py:717-732) of the last forward pass into eval_sums [cls, box, L2, -]: per level
+    edet_focal_loss_eval and edet_box_loss_eval -- the training kernels' sums bit for bit, nothing of the size of the logits
+    written -- then edet_l2_loss.  Nothing the training step owns is touched: the sums, the reciprocal normalizer
+    (eval_inv_norm, read when labels['normalizer'] == 'device') and the L2 scratch are buffers of their own, the gradient
+    arena is neither read nor written.  The logits are read in the dtype they were stored in (an inference pass with bf16
+    storage keeps them in fp32, _head_level)."""
+    c = self.config
+    sums = self.eval_sums
+    call('edet_zero', ptr(sums), sums.numel() * 4, self.stream)
+    norm_dev = None
+    if labels.get('normalizer') == 'device':
+      normalizer, norm_dev = 1.0, ptr(self.eval_inv_norm)
+    elif 'normalizer' in labels:
+      normalizer = float(labels['normalizer'])
+    else:
+      normalizer = float(labels['mean_num_positives'].sum().item()) + 1.0
+    na = self.spec.num_anchors
+    ls = float(getattr(c, 'label_smoothing', 0.0) or 0.0)
+    for li, (cv, bv) in enumerate(zip(self.cls_views, self.box_views)):
+      level = c.min_level + li
+      ct = labels['cls_targets_%d' % level]
+      bt = labels['box_targets_%d' % level]
+      assert ct.dtype == torch.int32 and ct.is_contiguous() and bt.dtype == torch.float32 and bt.is_contiguous()
+      r, rb = cv.raw, bv.raw
+      call('edet_focal_loss_eval', ptr(r.data), r.ld, ptr(ct), r.rows, na, c.num_classes, c.alpha, c.gamma, ls,
+           1.0 / normalizer, norm_dev, ptr(sums), *self._ws(), _lib.EDET_F32 if r.data.dtype == torch.float32 else EDET_BF16,
+           self.stream, nbytes=r.rows * r.c * r.data.element_size())
+      call('edet_box_loss_eval', ptr(rb.data), rb.ld, ptr(bt), rb.rows, 4 * na, c.delta, 1.0 / (normalizer * 4.0), norm_dev,
+           ptr(sums), *self._ws(), _lib.EDET_F32 if rb.data.dtype == torch.float32 else EDET_BF16, self.stream)
+    seg_l2 = self.buf('eval:seg_l2', (self.nseg * _lib.OPT_SPLIT,), torch.float32)
+    call('edet_l2_loss', ptr(self.params_flat), ptr(self.seg_offsets), ptr(self.seg_flags), self.nseg, float(c.weight_decay),
+         ptr(seg_l2), sums.data_ptr() + 8, self.stream)
+
+  @property
+  def eval_sums(self):
+    return self.buf('eval:loss_sums', (4,), torch.float32)
+
+  @property
+  def eval_inv_norm(self):
+    """1 / normalizer of the evaluation step, a device scalar of its own (the training step's is hyper[2])."""
+    return self.buf('eval:inv_norm', (1,), torch.float32)
+
+  def eval_loss_values(self):
+    s = self.eval_sums.detach().cpu().numpy()
+    c = self.config
+    det = float(s[0] + c.box_loss_weight * s[1])
+    return {'cls_loss': float(s[0]), 'box_loss': float(s[1]), 'det_loss': det, 'reg_l2_loss': float(s[2]),
+            'loss': det + float(s[2])}
+
   def backward(self):
     """The base pass; with set_overlap_reduce, every range of the arena is handed to the reduce as soon as the tape entry
     that completes it (_reduce_marks) has run."""

@@ -185,7 +185,7 @@ class Config(object):
 _DEFAULT_GROUPS = (
     ('identity', dict(name='efficientdet-d1', act_type='swish')),
     # input pipeline: read by EfficientDetNetTrain.train_step_raw (det_input.py); autoaugment_policy raises there, sample_image
-    # and map_freq are kept for interface completeness
+    # is kept for interface completeness, map_freq is what a caller hands to train_lib.COCOCallback(update_freq=)
     ('input', dict(image_size=640, target_size=None, input_rand_hflip=True, jitter_min=0.1, jitter_max=2.0,
                    autoaugment_policy=None, grid_mask=False, sample_image=None, map_freq=5)),
     ('dataset', dict(num_classes=90, seg_num_classes=3, heads=['object_detection'], skip_crowd_during_training=True,

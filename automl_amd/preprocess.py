@@ -59,6 +59,15 @@ def training_scale_factors(u, scale_min, scale_max, target, output_size, height,
   return scale, (sh, sw), (int(F(oy)), int(F(ox)))
 
 
+def output_size_scale_factors(output_size, height, width):
+  """set_scale_factors_to_output_size for one raw size (dataloader.py:113-124), float32 statement by statement ->
+  (image_scale float32, (scaled_h, scaled_w)).  DetectionInputProcessor and the detector's evaluation input (det_input.py)
+  both call this."""
+  h, w = F(height), F(width)
+  scale = min(F(output_size[1]) / w, F(output_size[0]) / h)
+  return scale, (int(F(h * scale)), int(F(w * scale)))
+
+
 class DetectionInputProcessor(object):
   """``dataloader.DetectionInputProcessor`` (dataloader.py:144-200, base class :36-141) for a BATCH of equally sized raw
   images, same method names and call order as ``InputReader.process_example`` uses them (:321-336)::
@@ -138,10 +147,9 @@ class DetectionInputProcessor(object):
 
   def set_scale_factors_to_output_size(self):
     """dataloader.py:113-124 (evaluation: the whole image into the top-left corner, no offset)."""
-    h, w = F(self._height), F(self._width)
-    scale = min(F(self._output_size[1]) / w, F(self._output_size[0]) / h)
+    scale, scaled = output_size_scale_factors(self._output_size, self._height, self._width)
     self._image_scale[:] = scale
-    self._scaled[:] = (int(F(h * scale)), int(F(w * scale)))
+    self._scaled[:] = scaled
     self._offset[:] = 0
     self._scales_set = True
     self._result = None

@@ -11,6 +11,7 @@ import os
 
 import torch
 
+from automl_amd import _lib
 from automl_amd import det_autoaugment
 from automl_amd import det_input
 from automl_amd import efficientdet_net
@@ -176,6 +177,9 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     # first train_step_raw, so a model that never calls it keeps its state keys
     self._det_input = None
     self._input_rng = None
+    # test_step / test_step_raw: the evaluation input stage of the last raw shape and the captured evaluation pass per engine
+    self._det_eval_input = None
+    self._eval_graphs = {}
     self.autoaugment = None      # set_autoaugment: the box-aware AutoAugment / RandAugment in front of train_step_raw's crop
 
   def set_autoaugment(self, policy):
@@ -509,3 +513,182 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     vals = eng.loss_values()
     vals['learning_rate'] = lr
     return vals
+
+
+  # ---- test_step: the losses of a batch, nothing moved (tf2/train_lib.py:686-732) ---------------------------------------
+  def _eval_normalizer(self, eng, labels):
+    """1 / normalizer of an evaluation step into eng.eval_inv_norm, as the training step forms it (_host_normalizer /
+    _device_normalizer) -- except that with positives_momentum > 0 the moving average is READ, v * m + x * (1 - m), and not
+    stored."""
+    m = self._positives_momentum()
+    if 'normalizer' in labels:
+      norm = float(labels['normalizer'])
+      if m > 0:
+        norm = moving_normalizer_update(float(self._moving_normalizer or 0.0), norm, m)
+      elif m < 0 and self.use_dist:
+        norm = self._host_normalizer(norm)      # the replica mean: a collective, no state
+      eng.eval_inv_norm.copy_(torch.tensor([1.0 / norm], dtype=torch.float32), non_blocking=True)
+      return
+    if 'mean_num_positives' not in labels:
+      raise KeyError("labels need 'mean_num_positives' (dataloader.py:393) or a host 'normalizer'")
+    mnp = labels['mean_num_positives'].reshape(-1)
+    if mnp.dtype != torch.float32 or not mnp.is_contiguous():
+      mnp = mnp.float().contiguous()
+    if m == 0 or (m < 0 and not self.use_dist):
+      _lib.call('edet_loss_normalizer', _lib.ptr(mnp), mnp.numel(), _lib.ptr(eng.eval_inv_norm), eng.stream)
+      return
+    s = mnp.sum() + 1.0
+    if m > 0:
+      v = self._moving_normalizer
+      if not torch.is_tensor(v):
+        v = torch.full((), float(v or 0.0), dtype=torch.float32, device=s.device)
+      s = moving_normalizer_update(v.clone(), s, m)      # the training step's arithmetic on a copy
+    else:
+      import torch.distributed as dist
+      s = s.clone()
+      dist.all_reduce(s, group=self.process_group)
+      s = s / dist.get_world_size(self.process_group)
+    torch.reciprocal(s, out=eng.eval_inv_norm[0])
+
+  def _eval_pass(self, eng, images, labels):
+    """forward(training=False) and the loss-only kernels; with use_graph the first call per engine is eager, the second
+    captures the pass -- separately from the train step's graph -- and later calls replay it.  images / labels: device
+    tensors, with use_graph the static buffers of that capture."""
+    self._eval_normalizer(eng, labels)
+    glabels = {k: v for k, v in labels.items() if k != 'normalizer'}
+    glabels['normalizer'] = 'device'
+
+    def body():
+      eng.forward(images, training=False)
+      eng.loss_only(glabels)
+
+    g = self._eval_graphs.get((eng.batch,) + tuple(eng.image_size)) if self.use_graph else None
+    if g is None or g['steps'] == 0:
+      body()
+    else:
+      if g['graph'] is None:
+        torch.cuda.synchronize()
+        eng._cast_version = -1      # the captured pass makes its own compute copies and BatchNorm vectors: variables move
+        g['graph'] = engine_lib.capture_graph(eng.arena, body)
+      g['graph'].replay()
+    if g is not None:
+      g['steps'] += 1
+    # the next pass of this engine -- a training step, perhaps the one that is captured -- makes its compute copies again
+    eng._cast_version = -1
+
+  def _eval_graph_state(self, eng, make_buffers):
+    """The captured evaluation pass of `eng` (by its shape; a state whose engine has been dropped is dropped with it)."""
+    self._eval_graphs = {k: v for k, v in self._eval_graphs.items() if self._engines.get(k) is v['engine']}
+    key = (eng.batch,) + tuple(eng.image_size)
+    g = self._eval_graphs.get(key)
+    if g is None:
+      images, labels = make_buffers()
+      g = self._eval_graphs[key] = {'engine': eng, 'steps': 0, 'graph': None, 'images': images, 'labels': labels}
+    return g
+
+  def test_step(self, data, sync_loss=True):
+    """tf2/train_lib.py:686-732: data = (images, labels) as train_step takes them -> {'cls_loss', 'box_loss', 'det_loss',
+    'reg_l2_loss', 'loss'} of a forward pass with training=False (BatchNorm moving statistics, no stochastic depth) on the
+    model's CURRENT variables, config.label_smoothing honoured as in training, the normalizer sum(mean_num_positives) + 1 on
+    the device or a host 'normalizer'.  The loss kernels are the training kernels without their gradient half
+    (edet_focal_loss_eval, edet_box_loss_eval: the same sums bit for bit) and edet_l2_loss, which reads the variables only:
+    reg_l2_loss is what the next train_step reports.
+
+    Nothing moves: no variable, optimizer slot, BatchNorm moving statistic, iteration count, input_rng_state or gradient
+    buffer.  That includes the moving loss normalizer of positives_momentum > 0: the step uses v * m + x * (1 - m) from the
+    stored value v and does NOT store it -- a deliberate difference from the reference, whose _detection_loss runs Keras'
+    moving_average_update in test_step too, so that validation never moves the training state.
+
+    With use_graph the first call per batch shape is eager and later calls replay a captured graph of their own (static
+    buffers: evaluation copies, or the evaluation input stage's destinations for test_step_raw).  The values are not
+    averaged over batches; that is the caller's."""
+    images, labels = data
+    b, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    eng = self._ensure_engine(b, h, w)
+    images, labels = self._to_device_images(images, eng), self._labels_to_device(labels, eng)
+    if self.use_graph:
+      g = self._eval_graph_state(eng, lambda: (torch.empty_like(images),
+                                               {k: torch.empty_like(v) for k, v in labels.items() if torch.is_tensor(v)}))
+      if images.data_ptr() != g['images'].data_ptr():
+        g['images'].copy_(images, non_blocking=True)
+      for k, v in labels.items():
+        if torch.is_tensor(v) and k in g['labels'] and v.data_ptr() != g['labels'][k].data_ptr():
+          g['labels'][k].copy_(v, non_blocking=True)
+      static = dict(g['labels'])
+      if 'normalizer' in labels:
+        static['normalizer'] = labels['normalizer']
+      images, labels = g['images'], static
+    self._eval_pass(eng, images, labels)
+    return eng.eval_loss_values() if sync_loss else {}
+
+  def test_step_raw(self, data, sync_loss=True):
+    """test_step from a raw batch: data = (raw_images uint8 [B, H, W, 3], boxes float32 [B, M, 4] normalised, classes [B, M],
+    counts [B], is_crowds [B, M], areas [B, M], source_ids [B]).  The evaluation branch of the input pipeline
+    (det_input.DetectionEvalInput: no draws, no GridMask, no AutoAugment) runs on the device in front of the pass, straight
+    into the captured pass's static buffers.  -> (loss values, labels): labels also holds 'source_ids', 'image_scales' and
+    'groundtruth_data', so a caller can go on to detections without a second input pass (the buffers are reused by the next
+    call)."""
+    raw, boxes, classes, counts, is_crowds, areas, source_ids = data
+    raw = torch.as_tensor(raw)
+    if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
+      raise ValueError('raw images must be uint8 [batch, height, width, 3], got %s %s' % (raw.dtype, tuple(raw.shape)))
+    boxes = torch.as_tensor(boxes)
+    if boxes.dim() != 3 or boxes.shape[0] != raw.shape[0] or boxes.shape[-1] != 4:
+      raise ValueError('boxes must be [batch, max_boxes, 4], got %s' % (tuple(boxes.shape),))
+    c = self.config
+    b, m = int(raw.shape[0]), int(boxes.shape[1])
+    h, w = utils.parse_image_size(c.image_size)
+    if m > int(getattr(c, 'max_instances_per_image', None) or 100):
+      det_input.DetectionEvalInput(c, None, b, int(raw.shape[1]), int(raw.shape[2]), m)      # raises, before any device work
+    eng = self._ensure_engine(b, h, w)
+    key = (b, int(raw.shape[1]), int(raw.shape[2]), m, h, w, eng.tdtype)
+    if self._det_eval_input is None or self._det_eval_input[0] != key:
+      self._det_eval_input = (key, det_input.DetectionEvalInput(c, self.anchors((h, w)), b, key[1], key[2], m, dtype=eng.tdtype,
+                                                                device=eng.device))
+    inp = self._det_eval_input[1]
+    if self.use_graph:
+      g = self._eval_graph_state(eng, inp.own_buffers)
+      images, labels = g['images'], g['labels']
+      for k, (shape, dt) in inp.label_shapes().items():      # a capture that test_step made: without the ground-truth keys
+        if k not in labels:
+          labels[k] = torch.empty(shape, dtype=dt, device=eng.device)
+    else:
+      images, labels = inp.own_buffers()
+    inp.run(raw, boxes, classes, counts, is_crowds, areas, source_ids, images, labels)
+    self._eval_pass(eng, images, labels)
+    return (eng.eval_loss_values() if sync_loss else {}), labels
+
+
+class COCOCallback(object):
+  """tf2/train_lib.py:202-250: COCO AP of the model on a test set every `update_freq` epochs.  test_batches: an iterable of
+  the raw tuples eval_lib.evaluate takes.  set_model(model) builds the evaluator from the model's config (val_json_file,
+  label_map); on_epoch_end(epoch, logs) follows :232-248 as written -- epoch += 1, then `update_freq and epoch % update_freq
+  == 0` -- resets the evaluator, runs config.eval_samples // config.batch_size batches when both are set (:237-238; all of
+  them otherwise) and puts the metrics into `logs` under evaluator.metric_names.  No summary writer.  update_freq is
+  config.map_freq in the reference's get_callbacks (:343-346)."""
+
+  def __init__(self, test_batches, update_freq=None):
+    self.test_dataset = test_batches
+    self.update_freq = update_freq
+    self.model = self.config = self.evaluator = None
+
+  def set_model(self, model):
+    from automl_amd import coco_metric
+    self.model = model
+    self.config = model.config
+    self.evaluator = coco_metric.EvaluationMetric(filename=getattr(self.config, 'val_json_file', None),
+                                                  label_map=getattr(self.config, 'label_map', None))
+
+  def on_epoch_end(self, epoch, logs=None):
+    from automl_amd import eval_lib
+    epoch += 1
+    if self.update_freq and epoch % self.update_freq == 0:
+      self.evaluator.reset_states()
+      samples, batch = getattr(self.config, 'eval_samples', None), getattr(self.config, 'batch_size', None)
+      count = samples // batch if samples and batch else None
+      metrics = eval_lib.evaluate(self.model, self.test_dataset, evaluator=self.evaluator, max_batches=count)
+      eval_results = {name: metrics[name] for name in self.evaluator.metric_names}
+      if logs is not None:
+        logs.update(eval_results)
+      return eval_results
+    return None

@@ -415,6 +415,29 @@ int edet_box_loss(const void* box_out, int ld, const float* box_targets,
                   float grad_scale, const float* norm_scale_dev, void* dbox, float* dbias, float* sums,
                   void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
+/* ---- the evaluation step's losses (train_lib.py:686-732, test_step): loss only, nothing else written -----------------------
+ * edet_focal_loss_eval / edet_box_loss_eval add into sums[0] / sums[1] EXACTLY what edet_focal_loss (label_smoothing == 0) or
+ * edet_focal_loss_smooth, and edet_box_loss, add for the same logits, targets, normalizer arguments and workspace size, bit for
+ * bit: the same per-element arithmetic (instantiations of the same kernel bodies without the gradient), the same grid, the
+ * same order of the sums (wave shuffles, waves in order, the workgroups' partial values in order).  No dlogits, no dbias: the
+ * logits are read once and nothing of their size is written.  workspace: as above ([workgroups][1 + channels] floats decide
+ * between the grid and ONE workgroup exactly as in training, although only one float per workgroup is used).
+ * edet_l2_loss: l2_out[0] = weight_decay * sum over the segments with EDET_SEG_L2 and without EDET_SEG_FROZEN of sum(w^2) / 2
+ * (train_lib.py:486-491), the value edet_opt_l2_norms + edet_opt_clip_factors add into l2_sum for the same variables, bit for
+ * bit (the same slices, the same sums, the same final order) -- written, not added, and the gradient arena is not touched.
+ * seg_l2: scratch [nseg][EDET_OPT_SPLIT] floats.  */
+int edet_focal_loss_eval(const void* logits, int ld, const int32_t* cls_targets,
+                         int64_t positions, int num_anchors, int num_classes,
+                         float alpha, float gamma, float label_smoothing, float inv_normalizer,
+                         const float* norm_scale_dev, float* sums, void* workspace, size_t workspace_bytes,
+                         int dtype, void* stream);
+int edet_box_loss_eval(const void* box_out, int ld, const float* box_targets,
+                       int64_t positions, int nch, float delta, float inv_normalizer,
+                       const float* norm_scale_dev, float* sums, void* workspace, size_t workspace_bytes,
+                       int dtype, void* stream);
+int edet_l2_loss(const float* params, const int64_t* seg_offsets, const int32_t* seg_flags, int nseg,
+                 float weight_decay, float* seg_l2, float* l2_out, void* stream);
+
 /* ---- EfficientNetV2 classifier loss and head dropout (efficientnetv2/main_tf2.py:89-117,199-207) ----
  * edet_softmax_xent: tf.keras.losses.CategoricalCrossentropy(label_smoothing, from_logits=True) with the default mean over
  * the batch (main_tf2.py:201-202), its gradient, and the counts behind TopKCategoricalAccuracy(k=1) / (k=5) (:203-206), in
@@ -663,6 +686,20 @@ int edet_preprocess_train(const void* raw_images, int raw_is_float, int batch, i
                           const edet_prep_image_t* per_image_dev, void* out, const float* boxes_in,
                           const float* classes_in, const int* counts_in, int max_boxes, float* boxes_out,
                           float* classes_out, int* counts_out, int dtype, void* stream);
+
+/* ---- ground truth of an evaluation batch (dataloader.py:344-353, :389) ----------------------------------------------------
+ * boxes [batch][max_boxes][4], classes [batch][max_boxes], kept_counts [batch]: what edet_preprocess_train leaves (the kept
+ * boxes in pixels of the output image, compacted, classes padded with -1).  is_crowds, areas fp32 [batch][max_boxes] and
+ * counts [batch]: the caller's annotations as given.  image_scales [batch] = image_scale_to_original.  All DEVICE memory.
+ * groundtruth_data fp32 [batch][max_instances][7], rows {y1, x1, y2, x2, is_crowd, area, class}: a coordinate is one rounded
+ * fp32 product with the scale; box and class columns of the rows at or past kept_counts[b] are -1; is_crowd is 0 and area -1
+ * at or past counts[b].  As the reference is written: the zero-area filter drops boxes with their classes but not their
+ * is_crowd / area, so behind a dropped box columns 4-5 of a row belong to another annotation than columns 0-3 and 6.  Both
+ * counts are clamped to [0, max_boxes]; max_instances >= max_boxes.  One thread per row.  Restated in tests/det_eval_ref.py,
+ * compared bit for bit.  */
+int edet_pack_groundtruth(const float* boxes, const float* classes, const int32_t* kept_counts, const float* is_crowds,
+                          const float* areas, const int32_t* counts, const float* image_scales, int batch, int max_boxes,
+                          int max_instances, float* groundtruth_data, void* stream);
 
 /* ---- GridMask of a training batch (efficientdet/aug/gridmask.py:22-136) ------------------------
  * src, dst uint8 [batch][height][width][3], src != dst.  Per image (DEVICE array): apply != 0 -> dst = src * mask, else the
