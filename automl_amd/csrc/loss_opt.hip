@@ -6,6 +6,8 @@
 // :493-604 (_detection_loss), :486-491 (_reg_l2_loss), :675-683 (clip + apply), :176-199 (optimizer).
 #include "common.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int THREADS = 256;
@@ -533,6 +535,46 @@ __global__ __launch_bounds__(THREADS, 8) void k_rmsprop_ema(float* params, const
   update_walk(RmspropRule{rho, momentum, eps}, params, grads, ms, mom, ema, seg_off, seg_factor, seg_flags, hyper);
 }
 
+// ---- the launch rule of the loss kernels: ONE place, so that the evaluation entry points run the grid of the training ones
+// (their sums are promised bit for bit: the partial rows must line up).  Rows are strided over the grid: a quarter of the
+// passes, at most `cap` workgroups; ordered partial rows [g][1 + nch] -- the TRAINING row width, whoever asks -- when the
+// workspace holds them, else ONE workgroup that adds into the destinations itself.
+struct LossGrid { RowMap m; int g; float* part; size_t lds; };
+inline LossGrid loss_grid(int ld, int64_t positions, int nch, int64_t cap, void* workspace, size_t workspace_bytes) {
+  LossGrid L;
+  L.m = row_map_ld(ld);
+  L.lds = (size_t)THREADS * 8 * sizeof(float);
+  int64_t g = (positions + L.m.rpp - 1) / L.m.rpp;
+  g = (g + 3) / 4;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  L.part = (workspace && workspace_bytes >= (size_t)g * (1 + nch) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
+  L.g = L.part ? (int)g : 1;
+  return L;
+}
+constexpr int64_t BOX_GRID_CAP = 2048;
+
+// focal cap: one round of the workgroups the chip holds at once, asked of the training kernel k_focal<T, G15> (also with
+// label smoothing, and for the evaluation kernels)
+inline int64_t focal_grid_cap(int dtype, bool g15) {
+  const void* fn = dtype == EDET_BF16 ? (g15 ? reinterpret_cast<const void*>(&k_focal<bf16_t, true>) : reinterpret_cast<const void*>(&k_focal<bf16_t, false>))
+                                      : (g15 ? reinterpret_cast<const void*>(&k_focal<float, true>) : reinterpret_cast<const void*>(&k_focal<float, false>));
+  const int slots = edet_resident_wgs(fn, THREADS, (size_t)THREADS * 8 * sizeof(float));
+  return slots > 0 ? slots : 4096;
+}
+
+// f(T{}, bool_constant<G15>, bool_constant<LS>) for the runtime (dtype, gamma == 1.5, label smoothing on); dtype is checked
+template <typename T> struct type_tag { using type = T; };
+template <typename F>
+inline void focal_dispatch(int dtype, bool g15, bool ls, F&& f) {
+  auto by_flags = [&](auto t) {
+    if (g15) { if (ls) f(t, std::true_type{}, std::true_type{}); else f(t, std::true_type{}, std::false_type{}); }
+    else { if (ls) f(t, std::false_type{}, std::true_type{}); else f(t, std::false_type{}, std::false_type{}); }
+  };
+  if (dtype == EDET_BF16) by_flags(type_tag<bf16_t>{});
+  else by_flags(type_tag<float>{});
+}
+
 }  // namespace
 
 extern "C" int edet_focal_loss_smooth(const void* logits, int ld, const int32_t* cls_targets,
@@ -544,44 +586,23 @@ extern "C" int edet_focal_loss_smooth(const void* logits, int ld, const int32_t*
   EDET_CHECK(logits && cls_targets && dlogits && sums, "edet_focal_loss: null pointer");
   EDET_CHECK(ld % 8 == 0 && ld >= num_anchors * num_classes && ld <= 2048, "edet_focal_loss: bad ld %d", ld);
   EDET_CHECK(num_classes >= 1, "edet_focal_loss: num_classes must be positive");
+  EDET_CHECK(num_anchors >= 1 && positions >= 0, "edet_focal_loss: bad shape");
   EDET_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "edet_focal_loss: label_smoothing %g outside [0, 1]", (double)label_smoothing);
-  const RowMap m = row_map_ld(ld);
-  int64_t g = (positions + m.rpp - 1) / m.rpp;
-  g = (g + 3) / 4;
-  const size_t lds = (size_t)THREADS * 8 * sizeof(float);
+  EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_focal_loss: bad dtype %d", dtype);
   const bool g15 = gamma == 1.5f;
-  const bool ls = label_smoothing != 0.f;
   const float half_ls = 0.5f * label_smoothing;
-  {   // one round of the workgroups the chip holds at once (the rows are strided over the grid)
-    const void* fn = dtype == EDET_BF16 ? (g15 ? reinterpret_cast<const void*>(&k_focal<bf16_t, true>) : reinterpret_cast<const void*>(&k_focal<bf16_t, false>))
-                                        : (g15 ? reinterpret_cast<const void*>(&k_focal<float, true>) : reinterpret_cast<const void*>(&k_focal<float, false>));
-    const int slots = edet_resident_wgs(fn, THREADS, lds);
-    const int64_t cap = slots > 0 ? slots : 4096;
-    if (g > cap) g = cap;
-  }
-  if (g < 1) g = 1;
-  // ordered partial rows [g][1 + nch] when the workspace holds them (else: one workgroup)
-  const int nch_ = num_anchors * num_classes;
-  float* part = (workspace && workspace_bytes >= (size_t)g * (1 + nch_) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (!part) g = 1;
-#define FOCAL_LAUNCH(T, G)                                                                            \
-  edet_launch(k_focal<T, G>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const T*)logits, ld, cls_targets, positions, \
-      num_anchors, num_classes, alpha, gamma, inv_normalizer, norm_scale_dev, (T*)dlogits, dbias, sums, part, m)
-#define FOCAL_LAUNCH_LS(T, G)                                                                         \
-  edet_launch(k_focal_ls<T, G>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const T*)logits, ld, cls_targets, positions, \
-      num_anchors, num_classes, alpha, gamma, inv_normalizer, norm_scale_dev, (T*)dlogits, dbias, sums, part, m, half_ls)
-#define FOCAL_LAUNCH_T(T)                                                  \
-  do {                                                                     \
-    if (g15) { if (ls) FOCAL_LAUNCH_LS(T, true); else FOCAL_LAUNCH(T, true); }     \
-    else { if (ls) FOCAL_LAUNCH_LS(T, false); else FOCAL_LAUNCH(T, false); }       \
-  } while (0)
-  if (dtype == EDET_BF16) FOCAL_LAUNCH_T(bf16_t);
-  else if (dtype == EDET_F32) FOCAL_LAUNCH_T(float);
-#undef FOCAL_LAUNCH_T
-#undef FOCAL_LAUNCH_LS
-#undef FOCAL_LAUNCH
-  else EDET_CHECK(false, "edet_focal_loss: bad dtype %d", dtype);
-  if (part && edet_reduce_partials2(part, (int)g, 1 + nch_, dbias, nch_, &sums[0], to_stream(stream)) != 0) return -2;
+  const int nch = num_anchors * num_classes;
+  const LossGrid L = loss_grid(ld, positions, nch, focal_grid_cap(dtype, g15), workspace, workspace_bytes);
+  focal_dispatch(dtype, g15, label_smoothing != 0.f, [&](auto t, auto G, auto LS) {
+    using T = typename decltype(t)::type;
+    if constexpr (decltype(LS)::value)
+      edet_launch(k_focal_ls<T, decltype(G)::value>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const T*)logits, ld, cls_targets, positions,
+                  num_anchors, num_classes, alpha, gamma, inv_normalizer, norm_scale_dev, (T*)dlogits, dbias, sums, L.part, L.m, half_ls);
+    else
+      edet_launch(k_focal<T, decltype(G)::value>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const T*)logits, ld, cls_targets, positions,
+                  num_anchors, num_classes, alpha, gamma, inv_normalizer, norm_scale_dev, (T*)dlogits, dbias, sums, L.part, L.m);
+  });
+  if (L.part && edet_reduce_partials2(L.part, L.g, 1 + nch, dbias, nch, &sums[0], to_stream(stream)) != 0) return -2;
   EDET_LAUNCH_CHECK("edet_focal_loss");
   return 0;
 }
@@ -603,26 +624,20 @@ extern "C" int edet_box_loss(const void* box_out, int ld, const float* box_targe
                              float* sums, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
   EDET_CHECK(box_out && box_targets && dbox && sums, "edet_box_loss: null pointer");
   EDET_CHECK(ld % 8 == 0 && ld >= nch && ld <= 2048, "edet_box_loss: bad ld %d", ld);
-  const RowMap m = row_map_ld(ld);
-  int64_t g = (positions + m.rpp - 1) / m.rpp;
-  g = (g + 3) / 4;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  const size_t lds = (size_t)THREADS * 8 * sizeof(float);
-  float* part = (workspace && workspace_bytes >= (size_t)g * (1 + nch) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (!part) g = 1;
+  EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_box_loss: bad dtype %d", dtype);
+  const LossGrid L = loss_grid(ld, positions, nch, BOX_GRID_CAP, workspace, workspace_bytes);
   if (dtype == EDET_BF16)
-    edet_launch(k_box<bf16_t>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const bf16_t*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, grad_scale, norm_scale_dev, (bf16_t*)dbox, dbias, sums, part, m);
-  else if (dtype == EDET_F32)
-    edet_launch(k_box<float>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const float*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, grad_scale, norm_scale_dev, (float*)dbox, dbias, sums, part, m);
-  else EDET_CHECK(false, "edet_box_loss: bad dtype %d", dtype);
-  if (part && edet_reduce_partials2(part, (int)g, 1 + nch, dbias, nch, &sums[1], to_stream(stream)) != 0) return -2;
+    edet_launch(k_box<bf16_t>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const bf16_t*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, grad_scale, norm_scale_dev, (bf16_t*)dbox, dbias, sums, L.part, L.m);
+  else
+    edet_launch(k_box<float>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const float*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, grad_scale, norm_scale_dev, (float*)dbox, dbias, sums, L.part, L.m);
+  if (L.part && edet_reduce_partials2(L.part, L.g, 1 + nch, dbias, nch, &sums[1], to_stream(stream)) != 0) return -2;
   EDET_LAUNCH_CHECK("edet_box_loss");
   return 0;
 }
 
 // ---- the evaluation step's losses (tf2/train_lib.py:686-732, test_step): the sums of the entry points above, bit for bit, with
-// no gradient written anywhere.  Same grids (the partial rows line up), GRAD = false instantiations of the same bodies.
+// no gradient written anywhere.  The grids of loss_grid (a partial row is the workgroup's loss alone), GRAD = false
+// instantiations of the same bodies.
 extern "C" int edet_focal_loss_eval(const void* logits, int ld, const int32_t* cls_targets,
                                     int64_t positions, int num_anchors, int num_classes,
                                     float alpha, float gamma, float label_smoothing, float inv_normalizer,
@@ -633,38 +648,15 @@ extern "C" int edet_focal_loss_eval(const void* logits, int ld, const int32_t* c
   EDET_CHECK(num_classes >= 1 && num_anchors >= 1 && positions >= 0, "edet_focal_loss_eval: bad shape");
   EDET_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "edet_focal_loss_eval: label_smoothing %g outside [0, 1]", (double)label_smoothing);
   EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_focal_loss_eval: bad dtype %d", dtype);
-  const RowMap m = row_map_ld(ld);
-  int64_t g = (positions + m.rpp - 1) / m.rpp;
-  g = (g + 3) / 4;
-  const size_t lds = (size_t)THREADS * 8 * sizeof(float);
   const bool g15 = gamma == 1.5f;
-  const bool ls = label_smoothing != 0.f;
   const float half_ls = 0.5f * label_smoothing;
-  {   // the training entry point's cap: the residency of ITS kernel, so that both run the same grid
-    const void* fn = dtype == EDET_BF16 ? (g15 ? reinterpret_cast<const void*>(&k_focal<bf16_t, true>) : reinterpret_cast<const void*>(&k_focal<bf16_t, false>))
-                                        : (g15 ? reinterpret_cast<const void*>(&k_focal<float, true>) : reinterpret_cast<const void*>(&k_focal<float, false>));
-    const int slots = edet_resident_wgs(fn, THREADS, lds);
-    const int64_t cap = slots > 0 ? slots : 4096;
-    if (g > cap) g = cap;
-  }
-  if (g < 1) g = 1;
-  // the training entry point goes to ONE workgroup when the workspace cannot hold its rows [g][1 + nch]: the same rule here
-  const int nch_ = num_anchors * num_classes;
-  float* part = (workspace && workspace_bytes >= (size_t)g * (1 + nch_) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (!part) g = 1;
-#define FOCAL_EVAL(T, G, L)                                                                                \
-  edet_launch(k_focal_eval<T, G, L>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const T*)logits, ld, cls_targets, positions, \
-      num_anchors, num_classes, alpha, gamma, inv_normalizer, norm_scale_dev, sums, part, m, half_ls)
-#define FOCAL_EVAL_T(T)                                                    \
-  do {                                                                     \
-    if (g15) { if (ls) FOCAL_EVAL(T, true, true); else FOCAL_EVAL(T, true, false); }     \
-    else { if (ls) FOCAL_EVAL(T, false, true); else FOCAL_EVAL(T, false, false); }       \
-  } while (0)
-  if (dtype == EDET_BF16) FOCAL_EVAL_T(bf16_t);
-  else FOCAL_EVAL_T(float);
-#undef FOCAL_EVAL_T
-#undef FOCAL_EVAL
-  if (part && edet_reduce_partials2(part, (int)g, 1, nullptr, 0, &sums[0], to_stream(stream)) != 0) return -2;
+  const LossGrid L = loss_grid(ld, positions, num_anchors * num_classes, focal_grid_cap(dtype, g15), workspace, workspace_bytes);
+  focal_dispatch(dtype, g15, label_smoothing != 0.f, [&](auto t, auto G, auto LS) {
+    using T = typename decltype(t)::type;
+    edet_launch(k_focal_eval<T, decltype(G)::value, decltype(LS)::value>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const T*)logits, ld, cls_targets,
+                positions, num_anchors, num_classes, alpha, gamma, inv_normalizer, norm_scale_dev, sums, L.part, L.m, half_ls);
+  });
+  if (L.part && edet_reduce_partials2(L.part, L.g, 1, nullptr, 0, &sums[0], to_stream(stream)) != 0) return -2;
   EDET_LAUNCH_CHECK("edet_focal_loss_eval");
   return 0;
 }
@@ -676,19 +668,12 @@ extern "C" int edet_box_loss_eval(const void* box_out, int ld, const float* box_
   EDET_CHECK(box_out && box_targets && sums, "edet_box_loss_eval: null pointer");
   EDET_CHECK(ld % 8 == 0 && nch >= 1 && ld >= nch && ld <= 2048 && positions >= 0, "edet_box_loss_eval: bad ld %d", ld);
   EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_box_loss_eval: bad dtype %d", dtype);
-  const RowMap m = row_map_ld(ld);
-  int64_t g = (positions + m.rpp - 1) / m.rpp;
-  g = (g + 3) / 4;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  const size_t lds = (size_t)THREADS * 8 * sizeof(float);
-  float* part = (workspace && workspace_bytes >= (size_t)g * (1 + nch) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
-  if (!part) g = 1;
+  const LossGrid L = loss_grid(ld, positions, nch, BOX_GRID_CAP, workspace, workspace_bytes);
   if (dtype == EDET_BF16)
-    edet_launch(k_box_eval<bf16_t>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const bf16_t*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, norm_scale_dev, sums, part, m);
+    edet_launch(k_box_eval<bf16_t>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const bf16_t*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, norm_scale_dev, sums, L.part, L.m);
   else
-    edet_launch(k_box_eval<float>, dim3((int)g), dim3(THREADS), lds, to_stream(stream), (const float*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, norm_scale_dev, sums, part, m);
-  if (part && edet_reduce_partials2(part, (int)g, 1, nullptr, 0, &sums[1], to_stream(stream)) != 0) return -2;
+    edet_launch(k_box_eval<float>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const float*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, norm_scale_dev, sums, L.part, L.m);
+  if (L.part && edet_reduce_partials2(L.part, L.g, 1, nullptr, 0, &sums[1], to_stream(stream)) != 0) return -2;
   EDET_LAUNCH_CHECK("edet_box_loss_eval");
   return 0;
 }

@@ -204,18 +204,9 @@ class DetectionInput(object):
     """raw_images uint8 [B, H, W, 3], boxes float32 [B, M, 4] normalised (ymin, xmin, ymax, xmax), classes [B, M], counts
     [B] (device tensors, or host arrays that are copied over) -> fills `images` [B, h, w, 3] and `labels`
     {'cls_targets_<l>', 'box_targets_<l>', 'mean_num_positives'} in place, on torch's current stream."""
-    b, m, dev = self.batch, self.max_boxes, self.device
-    raw = torch.as_tensor(raw_images)
-    if raw.dtype != torch.uint8 or tuple(raw.shape) != (b, self.height, self.width, 3):
-      raise ValueError('raw images must be uint8 %s, got %s %s' % ((b, self.height, self.width, 3), raw.dtype, tuple(raw.shape)))
-    raw = raw.to(dev).contiguous()
-    boxes = torch.as_tensor(boxes, dtype=torch.float32).to(dev).reshape(b, m, 4).contiguous()
-    classes = torch.as_tensor(classes).to(dev).to(torch.float32).reshape(b, m).contiguous()
-    counts = torch.as_tensor(counts).to(dev).to(torch.int32).reshape(b).contiguous()
+    raw, boxes, classes, counts, stream = self._canonical(raw_images, boxes, classes, counts, stream)
     self._check_destinations(images, labels)
     per, mask, packed = self.rows(draws)
-    if stream is None:
-      stream = torch.cuda.current_stream(dev).cuda_stream
     self.prep_rows.copy_(torch.from_numpy(per).pin_memory(), non_blocking=True)
     src = raw
     if self.grid_mask:
@@ -226,8 +217,24 @@ class DetectionInput(object):
       src, boxes = det_autoaugment.apply_layers(src, self.aa_images, boxes, self.aa_boxes, counts, self.aa_args, self.aa_luts,
                                                 self.aa_scratch, stream)
     self._launch(src, boxes, classes, counts, images, labels, stream)
-    self._keep_alive = (raw, boxes, classes, counts)
     return images, labels
+
+  def _canonical(self, raw_images, boxes, classes, counts, stream):
+    """The arguments run() takes, checked and on the device -> (raw uint8 [B, H, W, 3], boxes float32 [B, M, 4], classes
+    float32 [B, M], counts int32 [B], stream handle: torch's current stream unless one was given).  They are kept alive
+    until the next call: the launches that read them are asynchronous."""
+    b, m, dev = self.batch, self.max_boxes, self.device
+    raw = torch.as_tensor(raw_images)
+    if raw.dtype != torch.uint8 or tuple(raw.shape) != (b, self.height, self.width, 3):
+      raise ValueError('raw images must be uint8 %s, got %s %s' % ((b, self.height, self.width, 3), raw.dtype, tuple(raw.shape)))
+    raw = raw.to(dev).contiguous()
+    boxes = torch.as_tensor(boxes, dtype=torch.float32).to(dev).reshape(b, m, 4).contiguous()
+    classes = torch.as_tensor(classes).to(dev).to(torch.float32).reshape(b, m).contiguous()
+    counts = torch.as_tensor(counts).to(dev).to(torch.int32).reshape(b).contiguous()
+    if stream is None:
+      stream = torch.cuda.current_stream(dev).cuda_stream
+    self._keep_alive = (raw, boxes, classes, counts)
+    return raw, boxes, classes, counts, stream
 
   def _launch(self, src, boxes, classes, counts, images, labels, stream):
     """edet_preprocess_train with the rows in prep_rows, edet_label_anchors, mean_num_positives: what the training and the
@@ -255,6 +262,16 @@ def parse_source_ids(source_ids):
   return a.astype(np.float32).reshape(-1)
 
 
+def check_max_instances(config, max_boxes):
+  """-> config.max_instances_per_image (100 when unset); more box ROWS than that raise, on the host (dataloader.py:228,
+  pad_to_fixed_size)."""
+  max_instances = int(getattr(config, 'max_instances_per_image', None) or 100)
+  if int(max_boxes) > max_instances:
+    raise ValueError('ERROR: please increase config.max_instances_per_image (%d box rows, max_instances_per_image %d; '
+                     'dataloader.pad_to_fixed_size)' % (max_boxes, max_instances))
+  return max_instances
+
+
 class DetectionEvalInput(DetectionInput):
   """The evaluation branch of ``InputReader.dataset_parser`` plus ``process_example`` (dataloader.py:321-323, :331-353,
   :369-392) for one (batch, raw size, box rows) shape: ``normalize_image``, ``set_scale_factors_to_output_size`` -- no flip,
@@ -276,10 +293,7 @@ class DetectionEvalInput(DetectionInput):
   TRAINING = False
 
   def __init__(self, config, anchors, batch, height, width, max_boxes, dtype=torch.float32, device='cuda:0'):
-    self.max_instances = int(getattr(config, 'max_instances_per_image', None) or 100)
-    if int(max_boxes) > self.max_instances:
-      raise ValueError('ERROR: please increase config.max_instances_per_image (%d box rows, max_instances_per_image %d; '
-                       'dataloader.pad_to_fixed_size)' % (max_boxes, self.max_instances))
+    self.max_instances = check_max_instances(config, max_boxes)
     super().__init__(config, anchors, batch, height, width, max_boxes, dtype=dtype, device=device)
     b, m, dev = self.batch, self.max_boxes, self.device
     scale, scaled = preprocess.output_size_scale_factors(self.output_size, self.height, self.width)
@@ -308,17 +322,9 @@ class DetectionEvalInput(DetectionInput):
     """raw_images uint8 [B, H, W, 3], boxes float32 [B, M, 4] normalised (ymin, xmin, ymax, xmax), classes [B, M], counts [B],
     is_crowds [B, M] (bool or 0 / 1), areas [B, M], source_ids [B] (numbers, or strings with '' for none) -> fills `images`
     and `labels` in place, on torch's current stream."""
-    b, m, dev = self.batch, self.max_boxes, self.device
-    raw = torch.as_tensor(raw_images)
-    if raw.dtype != torch.uint8 or tuple(raw.shape) != (b, self.height, self.width, 3):
-      raise ValueError('raw images must be uint8 %s, got %s %s' % ((b, self.height, self.width, 3), raw.dtype, tuple(raw.shape)))
-    raw = raw.to(dev).contiguous()
-    boxes = torch.as_tensor(boxes, dtype=torch.float32).to(dev).reshape(b, m, 4).contiguous()
-    classes = torch.as_tensor(classes).to(dev).to(torch.float32).reshape(b, m).contiguous()
-    counts = torch.as_tensor(counts).to(dev).to(torch.int32).reshape(b).contiguous()
+    b, m = self.batch, self.max_boxes
+    raw, boxes, classes, counts, stream = self._canonical(raw_images, boxes, classes, counts, stream)
     self._check_destinations(images, labels)
-    if stream is None:
-      stream = torch.cuda.current_stream(dev).cuda_stream
     self.is_crowds.copy_(torch.as_tensor(is_crowds).reshape(b, m), non_blocking=True)      # tf.cast(is_crowds, float32), :347
     self.areas.copy_(torch.as_tensor(areas).reshape(b, m), non_blocking=True)
     if not torch.is_tensor(source_ids):
@@ -328,5 +334,4 @@ class DetectionEvalInput(DetectionInput):
     self._launch(raw, boxes, classes, counts, images, labels, stream)
     call('edet_pack_groundtruth', ptr(self.boxes), ptr(self.classes), ptr(self.counts), ptr(self.is_crowds), ptr(self.areas),
          ptr(counts), ptr(self.image_scales), b, m, self.max_instances, ptr(labels['groundtruth_data']), stream)
-    self._keep_alive = (raw, boxes, classes, counts)
     return images, labels

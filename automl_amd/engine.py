@@ -389,6 +389,28 @@ class Engine(LayerEngine):
     return cls, box
 
   # ------------------------------------------------------------------ loss + backward + update
+  def _loss_front(self, labels, inv_norm_dev):
+    """What loss_backward and loss_only open with -> (normalizer, norm_dev, levels).  labels['normalizer'] == 'device':
+    1 / normalizer lives in the device scalar `inv_norm_dev` (hyper[2:], set_normalizer; eval_inv_norm), nothing of the step
+    depends on a host value, so its launches can be captured once and replayed for every batch; a host float supplied by the
+    caller: no device sync; else sum(mean_num_positives) + 1 through the host.  levels: per level (cls_raw, box_raw,
+    cls_targets, box_targets), the targets checked."""
+    c = self.config
+    norm_dev = None
+    if labels.get('normalizer') == 'device':
+      normalizer, norm_dev = 1.0, ptr(inv_norm_dev)
+    elif 'normalizer' in labels:
+      normalizer = float(labels['normalizer'])
+    else:
+      normalizer = float(labels['mean_num_positives'].sum().item()) + 1.0
+    levels = []
+    for li, (cv, bv) in enumerate(zip(self.cls_views, self.box_views)):
+      ct = labels['cls_targets_%d' % (c.min_level + li)]
+      bt = labels['box_targets_%d' % (c.min_level + li)]
+      assert ct.dtype == torch.int32 and ct.is_contiguous() and bt.dtype == torch.float32 and bt.is_contiguous()
+      levels.append((cv.raw, bv.raw, ct, bt))
+    return normalizer, norm_dev, levels
+
   def loss_backward(self, labels):
     """Detection loss forward+backward (train_lib.py:493-604) then the tape in reverse.
 
@@ -397,23 +419,10 @@ class Engine(LayerEngine):
     """
     c = self.config
     assert self.training
-    norm_dev = None
-    if labels.get('normalizer') == 'device':
-      # 1/normalizer lives in self.hyper[2] (set_normalizer): nothing of the step depends on a host value,
-      # so the launches below can be captured once and replayed for every batch
-      normalizer, norm_dev = 1.0, ptr(self.hyper[2:])
-    elif 'normalizer' in labels:   # host float supplied by the caller: no device sync
-      normalizer = float(labels['normalizer'])
-    else:
-      normalizer = float(labels['mean_num_positives'].sum().item()) + 1.0
+    normalizer, norm_dev, levels = self._loss_front(labels, self.hyper[2:])
     na = self.spec.num_anchors
-    for li, (cv, bv) in enumerate(zip(self.cls_views, self.box_views)):
-      level = c.min_level + li
-      ct = labels['cls_targets_%d' % level]
-      bt = labels['box_targets_%d' % level]
-      assert ct.dtype == torch.int32 and ct.is_contiguous() and bt.dtype == torch.float32 and bt.is_contiguous()
-      r = cv.raw
-      ls = float(getattr(c, 'label_smoothing', 0.0) or 0.0)
+    ls = float(getattr(c, 'label_smoothing', 0.0) or 0.0)
+    for r, rb, ct, bt in levels:
       if ls:      # FocalLoss(label_smoothing), train_lib.py:400-402
         call('edet_focal_loss_smooth', ptr(r.data), r.ld, ptr(ct), r.rows, na, c.num_classes, c.alpha, c.gamma, ls,
              1.0 / normalizer, norm_dev, ptr(r.ensure_grad()), ptr(self.grad('class_net/class-predict/bias')),
@@ -425,7 +434,6 @@ class Engine(LayerEngine):
              ptr(self.loss_sums), *self._ws(), self.dtype, self.stream,
              nbytes=2 * r.rows * r.c * self.esize)
       r.grad_written = True
-      rb = bv.raw
       call('edet_box_loss', ptr(rb.data), rb.ld, ptr(bt), rb.rows, 4 * na, c.delta, 1.0 / (normalizer * 4.0),
            float(c.box_loss_weight), norm_dev, ptr(rb.ensure_grad()), ptr(self.grad('box_net/box-predict/bias')),
            ptr(self.loss_sums), *self._ws(), self.dtype, self.stream)
@@ -442,21 +450,10 @@ class Engine(LayerEngine):
     c = self.config
     sums = self.eval_sums
     call('edet_zero', ptr(sums), sums.numel() * 4, self.stream)
-    norm_dev = None
-    if labels.get('normalizer') == 'device':
-      normalizer, norm_dev = 1.0, ptr(self.eval_inv_norm)
-    elif 'normalizer' in labels:
-      normalizer = float(labels['normalizer'])
-    else:
-      normalizer = float(labels['mean_num_positives'].sum().item()) + 1.0
+    normalizer, norm_dev, levels = self._loss_front(labels, self.eval_inv_norm)
     na = self.spec.num_anchors
     ls = float(getattr(c, 'label_smoothing', 0.0) or 0.0)
-    for li, (cv, bv) in enumerate(zip(self.cls_views, self.box_views)):
-      level = c.min_level + li
-      ct = labels['cls_targets_%d' % level]
-      bt = labels['box_targets_%d' % level]
-      assert ct.dtype == torch.int32 and ct.is_contiguous() and bt.dtype == torch.float32 and bt.is_contiguous()
-      r, rb = cv.raw, bv.raw
+    for r, rb, ct, bt in levels:
       call('edet_focal_loss_eval', ptr(r.data), r.ld, ptr(ct), r.rows, na, c.num_classes, c.alpha, c.gamma, ls,
            1.0 / normalizer, norm_dev, ptr(sums), *self._ws(), _lib.EDET_F32 if r.data.dtype == torch.float32 else EDET_BF16,
            self.stream, nbytes=r.rows * r.c * r.data.element_size())

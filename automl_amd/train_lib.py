@@ -276,24 +276,33 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
   def _new_graph_state(eng, images, labels):
     return {'engine': eng, 'steps': 0, 'graphs': None, 'images': images, 'labels': labels}
 
+  @staticmethod
+  def _static_like(images, labels):
+    """Static buffers for device (images, labels): a host 'normalizer' has none."""
+    return torch.empty_like(images), {k: torch.empty_like(v) for k, v in labels.items() if torch.is_tensor(v)}
+
+  @staticmethod
+  def _stage(g, images, labels):
+    """Device (images, labels) into the static buffers of the graph state `g` -- a tensor that already IS its buffer is not
+    copied, one the buffers have no place for is left out -- -> (images, labels) of static tensors; a host 'normalizer'
+    passes through."""
+    if images.data_ptr() != g['images'].data_ptr():
+      g['images'].copy_(images, non_blocking=True)
+    static = dict(g['labels'])
+    for k, v in labels.items():
+      if not torch.is_tensor(v):
+        static[k] = v
+      elif k in static and v.data_ptr() != static[k].data_ptr():
+        static[k].copy_(v, non_blocking=True)
+    return g['images'], static
+
   def _graph_step(self, eng, images, labels, lr, decay):
     g = self._graph
     if g is None or g['engine'] is not eng:
-      g = self._graph = self._new_graph_state(eng, torch.empty_like(images),
-                                              {k: torch.empty_like(v) for k, v in labels.items() if torch.is_tensor(v)})
-    if images.data_ptr() != g['images'].data_ptr():
-      g['images'].copy_(images, non_blocking=True)
-    for k, buf in g['labels'].items():
-      if labels[k].data_ptr() != buf.data_ptr():
-        buf.copy_(labels[k], non_blocking=True)
+      g = self._graph = self._new_graph_state(eng, *self._static_like(images, labels))
+    _, labels = self._stage(g, images, labels)
     eng.set_hyper(lr, decay)
-    if 'normalizer' in labels:                         # host value supplied by the caller
-      norm = self._host_normalizer(float(labels['normalizer']))
-      eng.hyper[2:3].copy_(torch.tensor([1.0 / norm], dtype=torch.float32), non_blocking=True)
-    elif 'mean_num_positives' in g['labels']:
-      self._device_normalizer(eng, g['labels']['mean_num_positives'])
-    else:
-      raise KeyError("labels need 'mean_num_positives' (dataloader.py:393) or a host 'normalizer'")
+    self._inv_normalizer(eng, labels, eng.hyper[2:3], store=True)
     glabels = dict(g['labels'])
     glabels['normalizer'] = 'device'
     reduce_fn = make_grad_all_reduce(self.process_group) if self.use_dist else None
@@ -378,43 +387,102 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
   def _positives_momentum(self):
     return float(getattr(self.config, 'positives_momentum', None) or 0.0)
 
-  def _host_normalizer(self, value):
-    """sum(mean_num_positives) + 1 as the reference uses it (train_lib.py:517-534): the moving average over the steps for
-    positives_momentum > 0, the mean over the replicas for positives_momentum < 0, the value itself otherwise."""
-    m = self._positives_momentum()
-    if m > 0:
-      if torch.is_tensor(self._moving_normalizer):      # one representation: the device scalar, once it exists
-        return float(moving_normalizer_update(self._moving_normalizer, float(value), m))
-      self._moving_normalizer = moving_normalizer_update(
-          0.0 if self._moving_normalizer is None else float(self._moving_normalizer), value, m)
-      return self._moving_normalizer
-    if m < 0 and self.use_dist:
-      import torch.distributed as dist
-      t = torch.tensor([value], dtype=torch.float32)
-      if dist.get_backend(self.process_group) == 'nccl':
-        t = t.cuda()
-      dist.all_reduce(t, group=self.process_group)
-      return float(t.item()) / dist.get_world_size(self.process_group)
-    return value
+  def _normalizer(self, value, dest, store, eng=None):
+    """The loss normalizer sum(mean_num_positives) + 1 as the reference uses it (train_lib.py:517-534): the moving average
+    over the steps for positives_momentum > 0, the mean over the replicas for positives_momentum < 0 (a collective, no
+    state), the value itself otherwise.
 
-  def _device_normalizer(self, eng, mean_num_positives):
-    """The same on the device (no host synchronisation; runs eagerly in front of the replayed graph): hyper[2] =
-    1 / normalizer."""
+    value: the sum + 1 of this step as a host float supplied by the caller, or the device tensor mean_num_positives (then
+    `eng` launches edet_loss_normalizer where no average is asked for, and nothing waits for the host: no .item()).
+    dest: a one-element device tensor that receives 1 / normalizer (eng.hyper[2:3], eng.eval_inv_norm), or None: the
+    normalizer comes back as a host float (host values only).
+    store: True, the training step: the moving average v <- v * m + x * (1 - m) is stored.  False, the evaluation step: it
+    is READ, v * m + x * (1 - m), and v stays.
+
+    The stored average is a python float only until a device value arrives; from then on the 0-d device tensor is its one
+    representation, updated in place.  A state without the key restarts at 0."""
     m = self._positives_momentum()
+    v = self._moving_normalizer
+    if not torch.is_tensor(value):
+      norm = value
+      if m > 0 and store and torch.is_tensor(v):
+        norm = float(moving_normalizer_update(v, float(value), m))
+      elif m > 0:
+        norm = moving_normalizer_update(float(v or 0.0), value, m)
+        if store:
+          self._moving_normalizer = norm
+      elif m < 0 and self.use_dist:
+        import torch.distributed as dist
+        t = torch.tensor([value], dtype=torch.float32)
+        if dist.get_backend(self.process_group) == 'nccl':
+          t = t.cuda()
+        dist.all_reduce(t, group=self.process_group)
+        norm = float(t.item()) / dist.get_world_size(self.process_group)
+      if dest is None:
+        return norm
+      dest.copy_(torch.tensor([1.0 / norm], dtype=torch.float32), non_blocking=True)
+      return None
+    mnp = value.reshape(-1)
+    if mnp.dtype != torch.float32 or not mnp.is_contiguous():
+      mnp = mnp.float().contiguous()
     if m == 0 or (m < 0 and not self.use_dist):
-      eng.set_normalizer(mean_num_positives)
-      return
-    s = mean_num_positives.reshape(-1).float().sum() + 1.0
+      _lib.call('edet_loss_normalizer', _lib.ptr(mnp), mnp.numel(), _lib.ptr(dest), eng.stream)
+      return None
+    s = mnp.sum() + 1.0
     if m > 0:
-      if not torch.is_tensor(self._moving_normalizer):
-        self._moving_normalizer = torch.full((), float(self._moving_normalizer or 0.0), dtype=torch.float32, device=s.device)
-      s = moving_normalizer_update(self._moving_normalizer, s, m)
+      if not torch.is_tensor(v):
+        v = torch.full((), float(v or 0.0), dtype=torch.float32, device=s.device)
+      if store:
+        self._moving_normalizer = v
+      s = moving_normalizer_update(v if store else v.clone(), s, m)
     else:
       import torch.distributed as dist
       s = s.clone()
       dist.all_reduce(s, group=self.process_group)
       s = s / dist.get_world_size(self.process_group)
-    torch.reciprocal(s, out=eng.hyper[2])
+    torch.reciprocal(s, out=dest[0])
+    return None
+
+  def _host_normalizer(self, value):
+    return self._normalizer(value, None, store=True)
+
+  def _device_normalizer(self, eng, mean_num_positives):
+    return self._normalizer(mean_num_positives, eng.hyper[2:3], store=True, eng=eng)
+
+  def _inv_normalizer(self, eng, labels, dest, store):
+    """1 / normalizer of a step whose launches read it from the device, into `dest`: runs eagerly in front of the replayed
+    graph."""
+    if 'normalizer' in labels:                         # host value supplied by the caller
+      self._normalizer(float(labels['normalizer']), dest, store)
+    elif 'mean_num_positives' in labels:
+      self._normalizer(labels['mean_num_positives'], dest, store, eng)
+    else:
+      raise KeyError("labels need 'mean_num_positives' (dataloader.py:393) or a host 'normalizer'")
+
+  def _raw_input(self, raw, boxes, training):
+    """What train_step_raw and test_step_raw open with: the raw batch checked on the host -> (engine, the input stage of this
+    shape: det_input.DetectionInput / DetectionEvalInput, built when the shape, the dtype or the AutoAugment switch moved)."""
+    raw = torch.as_tensor(raw)
+    if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
+      raise ValueError('raw images must be uint8 [batch, height, width, 3], got %s %s' % (raw.dtype, tuple(raw.shape)))
+    boxes = torch.as_tensor(boxes)
+    if boxes.dim() != 3 or boxes.shape[0] != raw.shape[0] or boxes.shape[-1] != 4:
+      raise ValueError('boxes must be [batch, max_boxes, 4], got %s' % (tuple(boxes.shape),))
+    c = self.config
+    b, rh, rw, m = int(raw.shape[0]), int(raw.shape[1]), int(raw.shape[2]), int(boxes.shape[1])
+    h, w = utils.parse_image_size(c.image_size)
+    if not training:
+      det_input.check_max_instances(c, m)      # raises, before any device work
+    eng = self._ensure_engine(b, h, w)
+    attr = '_det_input' if training else '_det_eval_input'
+    key = (b, rh, rw, m, h, w, eng.tdtype, self.autoaugment if training else None)
+    cached = getattr(self, attr)
+    if cached is None or cached[0] != key:
+      extra = {'autoaugment': self.autoaugment} if training else {}
+      stage = det_input.DetectionInput if training else det_input.DetectionEvalInput
+      cached = (key, stage(c, self.anchors((h, w)), b, rh, rw, m, dtype=eng.tdtype, device=eng.device, **extra))
+      setattr(self, attr, cached)
+    return eng, cached[1]
 
   def train_step_raw(self, data, sync_loss=True, draws=None):
     """One training step from a raw batch: data = (raw_images uint8 [B, H, W, 3], boxes float32 [B, M, 4] normalised (ymin,
@@ -439,20 +507,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
                        'dataloader.py:312-319); train_step_raw would have to ignore it -- the part that is built is switched '
                        'on with set_autoaugment(policy)' % (c.autoaugment_policy,))
     raw, boxes, classes, counts = data
-    raw = torch.as_tensor(raw)
-    if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
-      raise ValueError('raw images must be uint8 [batch, height, width, 3], got %s %s' % (raw.dtype, tuple(raw.shape)))
-    boxes = torch.as_tensor(boxes)
-    if boxes.dim() != 3 or boxes.shape[0] != raw.shape[0] or boxes.shape[-1] != 4:
-      raise ValueError('boxes must be [batch, max_boxes, 4], got %s' % (tuple(boxes.shape),))
-    b, m = int(raw.shape[0]), int(boxes.shape[1])
-    h, w = utils.parse_image_size(c.image_size)
-    eng = self._ensure_engine(b, h, w)
-    key = (b, int(raw.shape[1]), int(raw.shape[2]), m, h, w, self.autoaugment)
-    if self._det_input is None or self._det_input[0] != key:
-      self._det_input = (key, det_input.DetectionInput(c, self.anchors((h, w)), b, key[1], key[2], m, dtype=eng.tdtype,
-                                                       device=eng.device, autoaugment=self.autoaugment))
-    inp = self._det_input[1]
+    eng, inp = self._raw_input(raw, boxes, training=True)
     if draws is None:
       if self._input_rng is None:
         self._input_rng = det_input.input_rng(self._seed)
@@ -479,34 +534,26 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
       import torch.distributed as dist
       eng.sync_bn = (make_grad_all_reduce(self.process_group), dist.get_world_size(self.process_group))
     lr = self._lr(b)
-    if self.use_graph:
-      decay = None
-      if self.config.moving_average_decay:
-        decay = ema_decay_dynamic(self.config.moving_average_decay, self.iterations)
-      self._graph_step(eng, self._to_device_images(images, eng), self._labels_to_device(labels, eng), lr, decay)
-      self.iterations += 1
-      if not sync_loss:
-        return {'learning_rate': lr}
-      vals = eng.loss_values()
-      vals['learning_rate'] = lr
-      return vals
-    reduce_fn = make_grad_all_reduce(self.process_group) if self.use_dist else None
-    eng.set_overlap_reduce(reduce_fn if self.overlap_grad_reduce else None, self.overlap_buckets)
-    eng.forward(self._to_device_images(images, eng), training=True)
-    dlabels = self._labels_to_device(labels, eng)
-    if self._positives_momentum() != 0:
-      if 'normalizer' in dlabels:
-        # the caller supplied this step's sum(mean_num_positives) + 1 as a host float: moving average / replica mean on the host
-        dlabels['normalizer'] = self._host_normalizer(dlabels['normalizer'])
-      else:
-        # on the device, as the captured step does it (no .item(): the eager step does not wait for the host either)
-        self._device_normalizer(eng, dlabels['mean_num_positives'])
-        dlabels['normalizer'] = 'device'
-    eng.loss_backward(dlabels)
     decay = None
     if self.config.moving_average_decay:
       decay = ema_decay_dynamic(self.config.moving_average_decay, self.iterations)
-    eng.optimizer_step(lr, decay, reduce_fn)
+    if self.use_graph:
+      self._graph_step(eng, self._to_device_images(images, eng), self._labels_to_device(labels, eng), lr, decay)
+    else:
+      reduce_fn = make_grad_all_reduce(self.process_group) if self.use_dist else None
+      eng.set_overlap_reduce(reduce_fn if self.overlap_grad_reduce else None, self.overlap_buckets)
+      eng.forward(self._to_device_images(images, eng), training=True)
+      dlabels = self._labels_to_device(labels, eng)
+      if self._positives_momentum() != 0:
+        if 'normalizer' in dlabels:
+          # the caller supplied this step's sum(mean_num_positives) + 1 as a host float: moving average / replica mean on the host
+          dlabels['normalizer'] = self._host_normalizer(dlabels['normalizer'])
+        else:
+          # on the device, as the captured step does it (no .item(): the eager step does not wait for the host either)
+          self._device_normalizer(eng, dlabels['mean_num_positives'])
+          dlabels['normalizer'] = 'device'
+      eng.loss_backward(dlabels)
+      eng.optimizer_step(lr, decay, reduce_fn)
     self.iterations += 1
     if not sync_loss:
       return {'learning_rate': lr}
@@ -514,47 +561,13 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     vals['learning_rate'] = lr
     return vals
 
-
   # ---- test_step: the losses of a batch, nothing moved (tf2/train_lib.py:686-732) ---------------------------------------
-  def _eval_normalizer(self, eng, labels):
-    """1 / normalizer of an evaluation step into eng.eval_inv_norm, as the training step forms it (_host_normalizer /
-    _device_normalizer) -- except that with positives_momentum > 0 the moving average is READ, v * m + x * (1 - m), and not
-    stored."""
-    m = self._positives_momentum()
-    if 'normalizer' in labels:
-      norm = float(labels['normalizer'])
-      if m > 0:
-        norm = moving_normalizer_update(float(self._moving_normalizer or 0.0), norm, m)
-      elif m < 0 and self.use_dist:
-        norm = self._host_normalizer(norm)      # the replica mean: a collective, no state
-      eng.eval_inv_norm.copy_(torch.tensor([1.0 / norm], dtype=torch.float32), non_blocking=True)
-      return
-    if 'mean_num_positives' not in labels:
-      raise KeyError("labels need 'mean_num_positives' (dataloader.py:393) or a host 'normalizer'")
-    mnp = labels['mean_num_positives'].reshape(-1)
-    if mnp.dtype != torch.float32 or not mnp.is_contiguous():
-      mnp = mnp.float().contiguous()
-    if m == 0 or (m < 0 and not self.use_dist):
-      _lib.call('edet_loss_normalizer', _lib.ptr(mnp), mnp.numel(), _lib.ptr(eng.eval_inv_norm), eng.stream)
-      return
-    s = mnp.sum() + 1.0
-    if m > 0:
-      v = self._moving_normalizer
-      if not torch.is_tensor(v):
-        v = torch.full((), float(v or 0.0), dtype=torch.float32, device=s.device)
-      s = moving_normalizer_update(v.clone(), s, m)      # the training step's arithmetic on a copy
-    else:
-      import torch.distributed as dist
-      s = s.clone()
-      dist.all_reduce(s, group=self.process_group)
-      s = s / dist.get_world_size(self.process_group)
-    torch.reciprocal(s, out=eng.eval_inv_norm[0])
-
   def _eval_pass(self, eng, images, labels):
     """forward(training=False) and the loss-only kernels; with use_graph the first call per engine is eager, the second
     captures the pass -- separately from the train step's graph -- and later calls replay it.  images / labels: device
     tensors, with use_graph the static buffers of that capture."""
-    self._eval_normalizer(eng, labels)
+    # as the training step forms it, except that the moving average of positives_momentum > 0 is read and not stored
+    self._inv_normalizer(eng, labels, eng.eval_inv_norm, store=False)
     glabels = {k: v for k, v in labels.items() if k != 'normalizer'}
     glabels['normalizer'] = 'device'
 
@@ -607,17 +620,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     eng = self._ensure_engine(b, h, w)
     images, labels = self._to_device_images(images, eng), self._labels_to_device(labels, eng)
     if self.use_graph:
-      g = self._eval_graph_state(eng, lambda: (torch.empty_like(images),
-                                               {k: torch.empty_like(v) for k, v in labels.items() if torch.is_tensor(v)}))
-      if images.data_ptr() != g['images'].data_ptr():
-        g['images'].copy_(images, non_blocking=True)
-      for k, v in labels.items():
-        if torch.is_tensor(v) and k in g['labels'] and v.data_ptr() != g['labels'][k].data_ptr():
-          g['labels'][k].copy_(v, non_blocking=True)
-      static = dict(g['labels'])
-      if 'normalizer' in labels:
-        static['normalizer'] = labels['normalizer']
-      images, labels = g['images'], static
+      images, labels = self._stage(self._eval_graph_state(eng, lambda: self._static_like(images, labels)), images, labels)
     self._eval_pass(eng, images, labels)
     return eng.eval_loss_values() if sync_loss else {}
 
@@ -629,23 +632,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     'groundtruth_data', so a caller can go on to detections without a second input pass (the buffers are reused by the next
     call)."""
     raw, boxes, classes, counts, is_crowds, areas, source_ids = data
-    raw = torch.as_tensor(raw)
-    if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
-      raise ValueError('raw images must be uint8 [batch, height, width, 3], got %s %s' % (raw.dtype, tuple(raw.shape)))
-    boxes = torch.as_tensor(boxes)
-    if boxes.dim() != 3 or boxes.shape[0] != raw.shape[0] or boxes.shape[-1] != 4:
-      raise ValueError('boxes must be [batch, max_boxes, 4], got %s' % (tuple(boxes.shape),))
-    c = self.config
-    b, m = int(raw.shape[0]), int(boxes.shape[1])
-    h, w = utils.parse_image_size(c.image_size)
-    if m > int(getattr(c, 'max_instances_per_image', None) or 100):
-      det_input.DetectionEvalInput(c, None, b, int(raw.shape[1]), int(raw.shape[2]), m)      # raises, before any device work
-    eng = self._ensure_engine(b, h, w)
-    key = (b, int(raw.shape[1]), int(raw.shape[2]), m, h, w, eng.tdtype)
-    if self._det_eval_input is None or self._det_eval_input[0] != key:
-      self._det_eval_input = (key, det_input.DetectionEvalInput(c, self.anchors((h, w)), b, key[1], key[2], m, dtype=eng.tdtype,
-                                                                device=eng.device))
-    inp = self._det_eval_input[1]
+    eng, inp = self._raw_input(raw, boxes, training=False)
     if self.use_graph:
       g = self._eval_graph_state(eng, inp.own_buffers)
       images, labels = g['images'], g['labels']

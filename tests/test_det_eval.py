@@ -105,6 +105,52 @@ def test_more_box_rows_than_max_instances_raise_on_the_host():
   assert net.engine is None      # refused before anything was built
 
 
+def test_max_instances_check_is_a_function_of_its_own():
+  """det_input.check_max_instances: what DetectionEvalInput and test_step_raw both call, before any device work."""
+  config = eval_config()
+  n = config.max_instances_per_image
+  assert det_input.check_max_instances(config, n) == n and det_input.check_max_instances(config, 1) == n
+  with pytest.raises(ValueError, match=r'please increase config.max_instances_per_image \(%d box rows, max_instances_per_image %d'
+                     % (n + 1, n)):
+    det_input.check_max_instances(config, n + 1)
+  config.max_instances_per_image = None      # the reference's default
+  assert det_input.check_max_instances(config, 100) == 100
+  with pytest.raises(ValueError, match='max_instances_per_image'):
+    det_input.check_max_instances(config, 101)
+
+
+def test_one_normalizer_reads_or_stores():
+  """EfficientDetNetTrain._normalizer on a net without an engine (host value, host result).  store=False is the evaluation
+  step's: v * m + x * (1 - m) from the stored v -- a float, a 0-d tensor, or nothing yet (0) -- and v stays.  store=True is
+  the training step's: the sequence tests/test_hparams_config.py checks through _host_normalizer."""
+  m, xs = 0.9, [101.0, 57.0, 230.5, 1.0, 88.0]
+  net = train_lib.EfficientDetNetTrain(config=eval_config(',positives_momentum=%r' % m))
+  assert net._normalizer(7.0, None, store=False) == 0.0 * m + 7.0 * (1 - m) and net._moving_normalizer is None
+  net._moving_normalizer = 5.0
+  assert net._normalizer(7.0, None, store=False) == 5.0 * m + 7.0 * (1 - m)
+  assert net._moving_normalizer == 5.0 and not torch.is_tensor(net._moving_normalizer)
+  state = net._moving_normalizer = torch.full((), 5.0, dtype=torch.float32)
+  assert net._normalizer(7.0, None, store=False) == 5.0 * m + 7.0 * (1 - m)
+  assert net._moving_normalizer is state and float(state) == 5.0
+  want, v = [], 0.0
+  for x in xs:
+    v = v - (v - x) * (1.0 - m)
+    want.append(v)
+  for start in (None, torch.zeros((), dtype=torch.float32)):
+    net._moving_normalizer = start
+    got = [net._normalizer(x, None, store=True) for x in xs]
+    np.testing.assert_allclose(got, want, rtol=1e-12 if start is None else 1e-6)
+    assert torch.is_tensor(net._moving_normalizer) == (start is not None) and abs(float(net._moving_normalizer) - want[-1]) < 1e-3
+    assert start is None or net._moving_normalizer is start
+  # ... and _host_normalizer is that call
+  net._moving_normalizer = None
+  np.testing.assert_allclose([net._host_normalizer(x) for x in xs], want, rtol=1e-12)
+  np.testing.assert_allclose(float(net._moving_normalizer), want[-1], rtol=1e-12)
+  off = train_lib.EfficientDetNetTrain(config=eval_config())
+  assert off._normalizer(101.0, None, store=True) == 101.0 == off._normalizer(101.0, None, store=False)
+  assert off._moving_normalizer is None
+
+
 class StubEvaluator(object):
   metric_names = ['AP', 'AP50']
   label_map = None
@@ -170,7 +216,64 @@ def _loss_inputs(positions, na, nc, tdt, seed):
 # 40: 37 positions are no multiple of the rows per workgroup and make 5 (class) / 1 (box) workgroups, 301 make 38 / 3.  3
 # classes: focal_body's branch for fewer than 8 classes (rows of 32, 64 rows per pass, 2 workgroups).  8 classes: a chunk is
 # exactly one anchor.
-LOSS_GEOMETRIES = [(37, 9, 90), (301, 9, 90), (301, 9, 3), (70, 3, 8)]
+# Past each cap of the grid rule (the smallest shapes that get there): 33000 positions of 816-wide class rows ask for
+# ceil(ceil(33000 / 2) / 4) = 4125 workgroups, above the 4096 fallback and above any residency of 256-thread workgroups, so the
+# class cap is taken whatever its value (box: 258, uncapped); 262200 positions of 40-wide box rows (32 rows per pass) ask for
+# ceil(ceil(262200 / 32) / 4) = 2049 > 2048, the box cap (class: rows of 32, 64 per pass, 1025).
+LOSS_GEOMETRIES = [(37, 9, 90), (301, 9, 90), (301, 9, 3), (70, 3, 8), (33000, 9, 90), (262200, 9, 3)]
+THREADS = 256      # of the loss kernels
+
+
+def loss_grid(ld, positions):
+  """The documented grid rule of the loss kernels before its cap: rows per pass from the row width (one thread per 8
+  elements, rounded up to a power of two), then (positions + rpp - 1) / rpp, then (g + 3) / 4."""
+  tpr = 1
+  while tpr < ld // 8 and tpr < THREADS:
+    tpr *= 2
+  rpp = THREADS // tpr
+  return max(((positions + rpp - 1) // rpp + 3) // 4, 1)
+
+
+def loss_inputs(geom, tdt):
+  """_loss_inputs of the geometry, made once per geometry (the cases of one geometry follow each other)."""
+  if _CACHE.get('loss_geom') != geom:
+    _CACHE['loss_geom'], _CACHE['loss_inputs'] = geom, {}
+  if tdt not in _CACHE['loss_inputs']:
+    _CACHE['loss_inputs'][tdt] = _loss_inputs(*geom, tdt, 11)
+  return _CACHE['loss_inputs'][tdt]
+
+
+def four_losses(inputs, geom, edt, smoothing, ws, bytes_cls, bytes_box, inv_c, inv_b, nd_c, nd_b):
+  """The two training and the two evaluation entry points on the same inputs -> (training sums, evaluation sums) as numpy
+  [4]; `ws` with bytes_cls / bytes_box as the workspace size of the class / box calls."""
+  logits, box, ct, bt = inputs
+  positions, na, nc = geom
+  dev = logits.device
+  st = torch.cuda.current_stream().cuda_stream
+  train, evl = torch.zeros(4, device=dev), torch.zeros(4, device=dev)
+  dl, db = torch.empty_like(logits), torch.empty_like(box)
+  dbc, dbb = torch.zeros(na * nc, device=dev), torch.zeros(4 * na, device=dev)
+  if smoothing:
+    call('edet_focal_loss_smooth', ptr(logits), logits.shape[1], ptr(ct), positions, na, nc, 0.25, 1.5, smoothing, inv_c,
+         ptr(nd_c), ptr(dl), ptr(dbc), ptr(train), ptr(ws), bytes_cls, edt, st)
+  else:
+    call('edet_focal_loss', ptr(logits), logits.shape[1], ptr(ct), positions, na, nc, 0.25, 1.5, inv_c, ptr(nd_c), ptr(dl),
+         ptr(dbc), ptr(train), ptr(ws), bytes_cls, edt, st)
+  call('edet_box_loss', ptr(box), box.shape[1], ptr(bt), positions, 4 * na, 0.1, inv_b, 50.0, ptr(nd_b), ptr(db), ptr(dbb),
+       ptr(train), ptr(ws), bytes_box, edt, st)
+  call('edet_focal_loss_eval', ptr(logits), logits.shape[1], ptr(ct), positions, na, nc, 0.25, 1.5, smoothing, inv_c,
+       ptr(nd_c), ptr(evl), ptr(ws), bytes_cls, edt, st)
+  call('edet_box_loss_eval', ptr(box), box.shape[1], ptr(bt), positions, 4 * na, 0.1, inv_b, ptr(nd_b), ptr(evl), ptr(ws),
+       bytes_box, edt, st)
+  torch.cuda.synchronize()
+  return train.cpu().numpy(), evl.cpu().numpy()
+
+
+def normalizer_conventions(dev, norm=37.0):
+  """(inv class, inv box, device class, device box): a host value; 1.0 with a device scalar."""
+  inv_dev = torch.tensor([1.0 / norm], dtype=torch.float32, device=dev)
+  inv_box = torch.tensor([1.0 / (norm * 4.0)], dtype=torch.float32, device=dev)
+  return ((1.0 / norm, 1.0 / (norm * 4.0), None, None), (1.0, 1.0, inv_dev, inv_box))
 
 
 @pytest.mark.gpu
@@ -180,36 +283,19 @@ LOSS_GEOMETRIES = [(37, 9, 90), (301, 9, 90), (301, 9, 3), (70, 3, 8)]
 def test_loss_only_kernels_equal_the_training_kernels_bit_for_bit(dt, smoothing, geom):
   """sums[0:2] of edet_focal_loss_eval / edet_box_loss_eval against edet_focal_loss(_smooth) / edet_box_loss as uint32, for
   the grid with a partial buffer and for ONE workgroup (no workspace), and for both normalizer conventions (a host value;
-  1.0 with a device scalar); the logits are left as they were."""
+  1.0 with a device scalar); the logits are left as they were.  The partial buffer holds the rows of the uncapped grid, so
+  the two large geometries run their capped grids and not one workgroup."""
   _, edt, tdt = dt
   positions, na, nc = geom
-  logits, box, ct, bt = _loss_inputs(positions, na, nc, tdt, 11)
+  inputs = loss_inputs(geom, tdt)
+  logits, box = inputs[:2]
   dev = logits.device
-  st = torch.cuda.current_stream().cuda_stream
-  norm = 37.0
-  inv_dev = torch.tensor([1.0 / norm], dtype=torch.float32, device=dev)
-  inv_box = torch.tensor([1.0 / (norm * 4.0)], dtype=torch.float32, device=dev)
-  wsp = torch.empty(1024 * 1024, dtype=torch.float32, device=dev)
+  rows = max(loss_grid(logits.shape[1], positions) * (1 + na * nc), loss_grid(box.shape[1], positions) * (1 + 4 * na))
+  wsp = torch.empty(max(1024 * 1024, rows), dtype=torch.float32, device=dev)
   logits0, box0 = logits.clone(), box.clone()
   for ws, wsb in ((wsp, wsp.numel() * 4), (None, 0)):
-    for inv_c, inv_b, nd_c, nd_b in ((1.0 / norm, 1.0 / (norm * 4.0), None, None), (1.0, 1.0, inv_dev, inv_box)):
-      train, evl = torch.zeros(4, device=dev), torch.zeros(4, device=dev)
-      dl, db = torch.empty_like(logits), torch.empty_like(box)
-      dbc, dbb = torch.zeros(na * nc, device=dev), torch.zeros(4 * na, device=dev)
-      if smoothing:
-        call('edet_focal_loss_smooth', ptr(logits), logits.shape[1], ptr(ct), positions, na, nc, 0.25, 1.5, smoothing, inv_c,
-             ptr(nd_c), ptr(dl), ptr(dbc), ptr(train), ptr(ws), wsb, edt, st)
-      else:
-        call('edet_focal_loss', ptr(logits), logits.shape[1], ptr(ct), positions, na, nc, 0.25, 1.5, inv_c, ptr(nd_c), ptr(dl),
-             ptr(dbc), ptr(train), ptr(ws), wsb, edt, st)
-      call('edet_box_loss', ptr(box), box.shape[1], ptr(bt), positions, 4 * na, 0.1, inv_b, 50.0, ptr(nd_b), ptr(db), ptr(dbb),
-           ptr(train), ptr(ws), wsb, edt, st)
-      call('edet_focal_loss_eval', ptr(logits), logits.shape[1], ptr(ct), positions, na, nc, 0.25, 1.5, smoothing, inv_c,
-           ptr(nd_c), ptr(evl), ptr(ws), wsb, edt, st)
-      call('edet_box_loss_eval', ptr(box), box.shape[1], ptr(bt), positions, 4 * na, 0.1, inv_b, ptr(nd_b), ptr(evl), ptr(ws),
-           wsb, edt, st)
-      torch.cuda.synchronize()
-      t, e = train.cpu().numpy(), evl.cpu().numpy()
+    for inv_c, inv_b, nd_c, nd_b in normalizer_conventions(dev):
+      t, e = four_losses(inputs, geom, edt, smoothing, ws, wsb, wsb, inv_c, inv_b, nd_c, nd_b)
       print(geom, dt[0], smoothing, 'workspace' if ws is not None else 'one workgroup', 'device' if nd_c is not None else 'host',
             t[:2], e[:2])
       assert np.isfinite(t[:2]).all() and t[0] > 0 and t[1] > 0
@@ -218,6 +304,35 @@ def test_loss_only_kernels_equal_the_training_kernels_bit_for_bit(dt, smoothing,
       assert torch.equal(logits.view(torch.int16 if tdt == torch.bfloat16 else torch.int32),
                          logits0.view(torch.int16 if tdt == torch.bfloat16 else torch.int32))
       assert torch.equal(box.float(), box0.float())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dt', [('f32', _lib.EDET_F32, torch.float32), ('bf16', _lib.EDET_BF16, torch.bfloat16)], ids=lambda d: d[0])
+@pytest.mark.parametrize('smoothing', [0.0, 0.1], ids=['hard', 'ls0.1'])
+@pytest.mark.parametrize('geom', [(37, 9, 90), (301, 9, 90)], ids=lambda g: 'x'.join(map(str, g)))
+def test_loss_workspace_boundary_is_the_training_rows_for_all_four(dt, smoothing, geom):
+  """A workspace of exactly g * (1 + nch) floats -- the TRAINING rows of the (here uncapped) grid, sized per call -- just
+  holds them: all four entry points give the huge-workspace sums.  One float less and the training entry points go to one
+  workgroup, and so must the evaluation ones, although their own g floats would fit: the no-workspace sums, bit for bit."""
+  _, edt, tdt = dt
+  positions, na, nc = geom
+  inputs = loss_inputs(geom, tdt)
+  logits, box = inputs[:2]
+  dev = logits.device
+  fit_c = loss_grid(logits.shape[1], positions) * (1 + na * nc) * 4
+  fit_b = loss_grid(box.shape[1], positions) * (1 + 4 * na) * 4
+  assert loss_grid(logits.shape[1], positions) == {37: 5, 301: 38}[positions] and fit_c > 4 and fit_b > 4
+  wsp = torch.empty(1024 * 1024, dtype=torch.float32, device=dev)
+  for conv in normalizer_conventions(dev):
+    huge = four_losses(inputs, geom, edt, smoothing, wsp, wsp.numel() * 4, wsp.numel() * 4, *conv)
+    none = four_losses(inputs, geom, edt, smoothing, None, 0, 0, *conv)
+    fits = four_losses(inputs, geom, edt, smoothing, wsp, fit_c, fit_b, *conv)
+    short = four_losses(inputs, geom, edt, smoothing, wsp, fit_c - 4, fit_b - 4, *conv)
+    print(geom, dt[0], smoothing, fit_c, fit_b, huge[0][:2], fits[0][:2], none[0][:2], short[0][:2])
+    for (t, e), (wt, we), what in ((fits, huge, 'rows just fit'), (short, none, 'one float short')):
+      assert np.array_equal(bits(t[:2]), bits(wt[:2])), (what, 'training', t[:2], wt[:2])
+      assert np.array_equal(bits(e[:2]), bits(we[:2])), (what, 'evaluation', e[:2], we[:2])
+      assert np.array_equal(bits(e[:2]), bits(t[:2])), (what, 'evaluation against training', e[:2], t[:2])
 
 
 @pytest.mark.gpu
@@ -425,6 +540,35 @@ def test_replayed_test_step_equals_the_eager_one(dtype):
   images, labels = eager._det_eval_input[1].own_buffers()
   again = eager.test_step((images.clone(), {k: v.clone() for k, v in labels.items() if k.split('_')[0] in ('cls', 'box', 'mean')}))
   assert again == e[2][0]
+
+
+@pytest.mark.gpu
+def test_test_step_raw_after_a_capture_that_test_step_made():
+  """use_graph, mixed order: test_step twice (eager, then the capture) on tensors of its own, then test_step_raw of the same
+  shape.  The capture's static labels have no ground-truth keys; test_step_raw adds them, writes into the captured buffers and
+  replays the graph test_step captured."""
+  config = eval_config()
+  ev = raw_tuple(case_arrays('rows_at_max'))
+  graph, eager = new_net(config, 'bf16', True), new_net(config, 'bf16', False)
+  want, want_labels = eager.test_step_raw(ev)
+  images, labels = eager._det_eval_input[1].own_buffers()
+  data = (images.clone(), {k: v.clone() for k, v in labels.items() if k.split('_')[0] in ('cls', 'box', 'mean')})
+  first = [graph.test_step(data) for _ in range(2)]
+  state = graph._eval_graphs[(BATCH, SIZE, SIZE)]
+  captured = state['graph']
+  assert captured is not None and state['steps'] == 2 and 'groundtruth_data' not in state['labels']
+  assert first[0] == first[1] == want
+  state['images'].zero_()      # the raw call fills the captured buffers itself
+  got, got_labels = graph.test_step_raw(ev)
+  assert sorted(got) == sorted(LOSS_KEYS)
+  for k in LOSS_KEYS:
+    assert got[k] == want[k], (k, got[k], want[k])
+  assert graph._eval_graphs[(BATCH, SIZE, SIZE)]['graph'] is captured and state['steps'] == 3
+  torch.cuda.synchronize()
+  assert {'groundtruth_data', 'source_ids', 'image_scales'} <= set(got_labels)
+  for k in ('groundtruth_data', 'source_ids', 'image_scales'):
+    assert np.array_equal(bits(got_labels[k].cpu().numpy()), bits(want_labels[k].cpu().numpy())), k
+  assert np.array_equal(bits(got_labels['groundtruth_data'].cpu().numpy()), bits(case_arrays('rows_at_max')['groundtruth_data']))
 
 
 @pytest.mark.gpu
