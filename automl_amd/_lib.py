@@ -58,6 +58,23 @@ class GridMaskImage(ctypes.Structure):
               ('s1', ctypes.c_int32), ('s2', ctypes.c_int32), ('coef', ctypes.c_float * 6)]
 
 
+class JpegInfo(ctypes.Structure):
+  """edet_jpeg_info_t: what edet_jpeg_info reads in front of the first scan."""
+  _fields_ = [('height', ctypes.c_int32), ('width', ctypes.c_int32), ('components', ctypes.c_int32),
+              ('precision', ctypes.c_int32), ('kind', ctypes.c_int32), ('restart_interval', ctypes.c_int32),
+              ('sof', ctypes.c_int32), ('jfif', ctypes.c_int32), ('adobe_transform', ctypes.c_int32),
+              ('reserved', ctypes.c_int32), ('h_samp', ctypes.c_uint8 * 4), ('v_samp', ctypes.c_uint8 * 4),
+              ('quant_id', ctypes.c_uint8 * 4), ('comp_id', ctypes.c_uint8 * 4)]
+
+
+class JpegImage(ctypes.Structure):
+  """edet_jpeg_image_t: one row of the JPEG decoder's per-image array (written by edet_jpeg_entropy_decode)."""
+  _fields_ = [('status', ctypes.c_int32), ('height', ctypes.c_int32), ('width', ctypes.c_int32),
+              ('components', ctypes.c_int32), ('h_max', ctypes.c_int32), ('v_max', ctypes.c_int32),
+              ('blocks_w', ctypes.c_int32 * 3), ('blocks_h', ctypes.c_int32 * 3), ('quant_id', ctypes.c_int32 * 3),
+              ('first_block', ctypes.c_int32 * 3), ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 NMS_HARD, NMS_GAUSSIAN, NMS_LINEAR = 0, 1, 2
 NMS_TF_V5, NMS_NUMPY = 0, 1
 NMS_PAD_INDEX0, NMS_PAD_ZERO, NMS_PAD_DUMMY = 0, 1, 2
@@ -184,6 +201,11 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_void_p],
     'edet_wbf_cluster': [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     'edet_wbf_order': [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    'edet_jpeg_info': [c_void_p, ctypes.c_size_t, ctypes.POINTER(JpegInfo)],
+    'edet_jpeg_entropy_decode': [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t), c_int, c_int, c_int, c_void_p,
+                                 ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_int],
+    'edet_jpeg_idct': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
+    'edet_jpeg_color': [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p],
 }
 
 _lib = None

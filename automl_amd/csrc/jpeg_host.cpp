@@ -1,0 +1,456 @@
+// The host stage of the JPEG decoder (include/edet_hip.h, "baseline JPEG decode"): the marker walk and the Huffman decode of
+// SOF0 / SOF1 streams into int16 coefficients.  Plain C++17 -- no device call and no device header, so the same file builds
+// with a host compiler alone (tests/c_host/jpeg_host_check.cpp runs it under the address and undefined-behaviour sanitizers).
+// Everything behind it -- dequantisation, inverse DCT, upsampling, colour -- is csrc/jpeg.hip.
+//
+// The statuses, the order in which a file is refused and every stored coefficient are those of tests/jpeg_ref.py (walk,
+// check_frame, parse), statement for statement.  Every read of the input goes through a length check, every table index is
+// validated before use: a hostile file gives a status.  Arithmetic that a corrupt stream can drive out of range (the DC
+// predictor) is unsigned and wraps.
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <atomic>
+#include <thread>
+#include <vector>
+
+#include "../../include/edet_hip.h"
+
+void edet_set_error(const char* fmt, ...);      // error.cpp (the stand-alone checker brings its own)
+
+namespace {
+
+constexpr int MAX_THREADS = 16;
+constexpr int LOOK_BITS = 10;
+
+const uint8_t NATURAL[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct RawHuff {
+  bool present = false;
+  uint8_t counts[16];
+  uint8_t vals[256];
+  int total = 0;
+};
+
+// what the walk up to SOS leaves: the frame, the tables and where the scan starts
+struct Parsed {
+  edet_jpeg_info_t info;
+  bool have_frame = false;
+  bool have_qt[4] = {false, false, false, false};
+  uint16_t qt[4][64];
+  RawHuff huff[2][4];
+  const uint8_t* sos = nullptr;      // the SOS segment behind its length
+  size_t sos_len = 0;
+  size_t scan = 0;                   // position of the entropy-coded data
+};
+
+// jpeg_ref.walk: the markers up to the first SOS -> 0, or EDET_JPEG_MALFORMED
+int walk(const uint8_t* d, size_t n, Parsed& P) {
+  memset(&P.info, 0, sizeof(P.info));
+  memset(P.qt, 0, sizeof(P.qt));
+  P.info.adobe_transform = -1;
+  if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return EDET_JPEG_MALFORMED;
+  size_t p = 2;
+  for (;;) {
+    if (p >= n || d[p] != 0xFF) return EDET_JPEG_MALFORMED;
+    while (p < n && d[p] == 0xFF) ++p;
+    if (p >= n) return EDET_JPEG_MALFORMED;
+    const int m = d[p++];
+    if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+    if (m == 0xD9) return EDET_JPEG_MALFORMED;
+    if (n - p < 2) return EDET_JPEG_MALFORMED;
+    const size_t len = ((size_t)d[p] << 8) | d[p + 1];
+    if (len < 2 || len > n - p) return EDET_JPEG_MALFORMED;
+    const uint8_t* seg = d + p + 2;
+    const size_t sl = len - 2;
+    if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+      if (P.have_frame || sl < 6) return EDET_JPEG_MALFORMED;
+      const int nc = seg[5];
+      if (sl != (size_t)6 + 3 * (size_t)nc) return EDET_JPEG_MALFORMED;
+      P.have_frame = true;
+      P.info.precision = seg[0];
+      P.info.height = (seg[1] << 8) | seg[2];
+      P.info.width = (seg[3] << 8) | seg[4];
+      P.info.components = nc;
+      P.info.sof = m;
+      P.info.kind = m == 0xC0 ? EDET_JPEG_KIND_BASELINE : m == 0xC1 ? EDET_JPEG_KIND_EXTENDED
+                    : m == 0xC2 ? EDET_JPEG_KIND_PROGRESSIVE : EDET_JPEG_KIND_OTHER;
+      for (int i = 0; i < nc && i < 4; ++i) {
+        P.info.comp_id[i] = seg[6 + 3 * i];
+        P.info.h_samp[i] = seg[7 + 3 * i] >> 4;
+        P.info.v_samp[i] = seg[7 + 3 * i] & 15;
+        P.info.quant_id[i] = seg[8 + 3 * i];
+      }
+    } else if (m == 0xDB) {
+      size_t q = 0;
+      while (q < sl) {
+        const int pq = seg[q] >> 4, tq = seg[q] & 15;
+        const size_t size = pq ? 128 : 64;
+        if (pq > 1 || tq > 3 || q + 1 + size > sl) return EDET_JPEG_MALFORMED;
+        const uint8_t* v = seg + q + 1;
+        for (int i = 0; i < 64; ++i) P.qt[tq][NATURAL[i]] = pq ? (uint16_t)((v[2 * i] << 8) | v[2 * i + 1]) : v[i];
+        P.have_qt[tq] = true;
+        q += 1 + size;
+      }
+    } else if (m == 0xC4) {
+      size_t q = 0;
+      while (q < sl) {
+        if (q + 17 > sl) return EDET_JPEG_MALFORMED;
+        const int tc = seg[q] >> 4, th = seg[q] & 15;
+        int total = 0;
+        for (int i = 0; i < 16; ++i) total += seg[q + 1 + i];
+        if (tc > 1 || th > 3 || total > 256 || q + 17 + (size_t)total > sl) return EDET_JPEG_MALFORMED;
+        RawHuff& H = P.huff[tc][th];
+        H.present = true;
+        H.total = total;
+        memcpy(H.counts, seg + q + 1, 16);
+        memcpy(H.vals, seg + q + 17, (size_t)total);
+        q += 17 + (size_t)total;
+      }
+    } else if (m == 0xDD) {
+      if (sl != 2) return EDET_JPEG_MALFORMED;
+      P.info.restart_interval = (seg[0] << 8) | seg[1];
+    } else if (m == 0xE0) {
+      if (sl >= 5 && memcmp(seg, "JFIF\0", 5) == 0) P.info.jfif = 1;
+    } else if (m == 0xEE) {
+      if (sl >= 12 && memcmp(seg, "Adobe", 5) == 0) P.info.adobe_transform = seg[11];
+    } else if (m == 0xDA) {
+      if (!P.have_frame) return EDET_JPEG_MALFORMED;
+      P.sos = seg;
+      P.sos_len = sl;
+      P.scan = p + len;
+      return 0;
+    }
+    p += len;
+  }
+}
+
+// jpeg_ref.check_frame
+int check_frame(const edet_jpeg_info_t& f, int canvas_h, int canvas_w) {
+  if (f.kind == EDET_JPEG_KIND_PROGRESSIVE) return EDET_JPEG_PROGRESSIVE;
+  if (f.kind == EDET_JPEG_KIND_OTHER)
+    return (f.sof == 0xC9 || f.sof == 0xCA || f.sof == 0xCB || f.sof == 0xCD || f.sof == 0xCE || f.sof == 0xCF)
+               ? EDET_JPEG_ARITHMETIC : EDET_JPEG_UNSUPPORTED;
+  if (f.precision != 8) return EDET_JPEG_PRECISION;
+  if (f.components != 1 && f.components != 3) return EDET_JPEG_COMPONENTS;
+  if (f.components == 3) {
+    const bool chroma = f.h_samp[1] == 1 && f.v_samp[1] == 1 && f.h_samp[2] == 1 && f.v_samp[2] == 1;
+    const bool luma = (f.h_samp[0] == 1 && f.v_samp[0] == 1) || (f.h_samp[0] == 2 && f.v_samp[0] == 1) ||
+                      (f.h_samp[0] == 2 && f.v_samp[0] == 2);
+    if (!chroma || !luma) return EDET_JPEG_SAMPLING;
+    const bool rgb_ids = f.comp_id[0] == 'R' && f.comp_id[1] == 'G' && f.comp_id[2] == 'B';
+    if (f.adobe_transform == 0 || (f.adobe_transform < 0 && !f.jfif && rgb_ids)) return EDET_JPEG_UNSUPPORTED;
+  } else if (f.h_samp[0] < 1 || f.h_samp[0] > 4 || f.v_samp[0] < 1 || f.v_samp[0] > 4) {
+    return EDET_JPEG_MALFORMED;
+  }
+  if (f.height < 1 || f.width < 1) return EDET_JPEG_MALFORMED;
+  if (f.height > canvas_h || f.width > canvas_w) return EDET_JPEG_TOO_LARGE;
+  return 0;
+}
+
+// the scan header against the frame (jpeg_ref.parse up to the tables): the Huffman table ids per component
+int check_scan(const Parsed& P, int td[3], int ta[3]) {
+  const edet_jpeg_info_t& f = P.info;
+  const int nc = f.components;
+  const uint8_t* s = P.sos;
+  if (P.sos_len < 1 || P.sos_len != (size_t)4 + 2 * (size_t)s[0]) return EDET_JPEG_MALFORMED;
+  const int ns = s[0];
+  for (int i = 0; i < ns; ++i) {
+    bool known = false;
+    for (int c = 0; c < nc; ++c) known |= s[1 + 2 * i] == f.comp_id[c];
+    if (!known) return EDET_JPEG_MALFORMED;
+  }
+  if (ns != nc) return EDET_JPEG_UNSUPPORTED;
+  for (int i = 0; i < nc; ++i)
+    if (s[1 + 2 * i] != f.comp_id[i]) return EDET_JPEG_UNSUPPORTED;
+  if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0) return EDET_JPEG_MALFORMED;
+  for (int i = 0; i < nc; ++i) {
+    td[i] = s[2 + 2 * i] >> 4;
+    ta[i] = s[2 + 2 * i] & 15;
+    if (td[i] > 3 || ta[i] > 3 || !P.huff[0][td[i]].present || !P.huff[1][ta[i]].present) return EDET_JPEG_MALFORMED;
+    if (f.quant_id[i] > 3 || !P.have_qt[f.quant_id[i]]) return EDET_JPEG_MALFORMED;
+  }
+  return 0;
+}
+
+// jdhuff.c's derived table: a look-up for codes of up to LOOK_BITS bits, the canonical ranges for longer ones
+struct Huff {
+  uint16_t look[1 << LOOK_BITS];      // (length << 8) | symbol, 0 = no code of <= LOOK_BITS bits starts like this
+  int32_t mincode[17], count[17], valptr[17];
+  uint8_t vals[256];
+
+  bool build(const RawHuff& R, bool is_dc) {
+    memset(look, 0, sizeof(look));
+    memcpy(vals, R.vals, sizeof(vals));
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+      count[len] = R.counts[len - 1];
+      mincode[len] = (int32_t)code;
+      valptr[len] = k;
+      for (int i = 0; i < count[len]; ++i) {
+        if (code >= ((uint32_t)1 << len)) return false;      // more codes than the length has
+        if (k >= R.total) return false;
+        const int sym = R.vals[k];
+        if (is_dc && sym > 15) return false;
+        if (len <= LOOK_BITS) {
+          const uint32_t lo = code << (LOOK_BITS - len);
+          for (uint32_t j = 0; j < ((uint32_t)1 << (LOOK_BITS - len)); ++j) look[lo + j] = (uint16_t)((len << 8) | sym);
+        }
+        ++code;
+        ++k;
+      }
+      code <<= 1;
+    }
+    return true;
+  }
+};
+
+// the entropy-coded bytes from `p` up to the next marker, unstuffed on the fly; bits come from the top of `acc`
+struct Bits {
+  const uint8_t* d;
+  size_t n, p;
+  uint64_t acc = 0;
+  int have = 0;
+  bool stopped = false;
+
+  Bits(const uint8_t* data, size_t size, size_t pos) : d(data), n(size), p(pos) {}
+
+  void fill() {
+    while (have <= 56 && !stopped) {
+      if (p >= n) { stopped = true; break; }
+      const uint8_t b = d[p];
+      if (b == 0xFF) {
+        if (p + 1 < n && d[p + 1] == 0) { p += 2; }
+        else { stopped = true; break; }      // a marker or the end: p stays on the 0xFF
+      } else {
+        ++p;
+      }
+      acc = (acc << 8) | b;
+      have += 8;
+    }
+  }
+
+  // the next 16 bits, zero-filled past the end
+  uint32_t peek16() {
+    if (have < 16) fill();
+    return have >= 16 ? (uint32_t)(acc >> (have - 16)) & 0xFFFFu : (uint32_t)(acc << (16 - have)) & 0xFFFFu;
+  }
+
+  // -> symbol, or -1: no such code, or the code runs past the data
+  int symbol(const Huff& H) {
+    const uint32_t peek = peek16();
+    const uint16_t e = H.look[peek >> (16 - LOOK_BITS)];
+    int len = e >> 8, sym = e & 0xFF;
+    if (!len) {
+      for (int l = LOOK_BITS + 1; l <= 16; ++l) {
+        const int32_t code = (int32_t)(peek >> (16 - l));
+        if (H.count[l] && code >= H.mincode[l] && code - H.mincode[l] < H.count[l]) {
+          const int at = H.valptr[l] + (code - H.mincode[l]);
+          if (at > 255) return -1;
+          len = l;
+          sym = H.vals[at];
+          break;
+        }
+      }
+      if (!len) return -1;
+    }
+    if (len > have) return -1;
+    have -= len;
+    return sym;
+  }
+
+  // `s` bits (1 .. 15) as jdhuff.c's HUFF_EXTEND -> value; ok = false when the data ends first
+  int receive_extend(int s, bool& ok) {
+    if (have < s) fill();
+    if (have < s) { ok = false; return 0; }
+    const int v = (int)((acc >> (have - s)) & (((uint64_t)1 << s) - 1));
+    have -= s;
+    return v >= (1 << (s - 1)) ? v : v - (1 << s) + 1;
+  }
+};
+
+// the scan of one image -> coefficients; 0 or EDET_JPEG_MALFORMED
+int decode_scan(const uint8_t* d, size_t n, const Parsed& P, const int td[3], const int ta[3], const edet_jpeg_image_t& im,
+                int16_t* coef) {
+  const int nc = im.components;
+  std::vector<Huff> tables(2 * (size_t)nc);
+  for (int c = 0; c < nc; ++c) {
+    if (!tables[2 * c].build(P.huff[0][td[c]], true)) return EDET_JPEG_MALFORMED;
+    if (!tables[2 * c + 1].build(P.huff[1][ta[c]], false)) return EDET_JPEG_MALFORMED;
+  }
+  memset(coef + (size_t)64 * im.first_block[0], 0, sizeof(int16_t) * 64 * (size_t)im.total_blocks);
+  const int hs[3] = {im.h_max, 1, 1}, vs[3] = {im.v_max, 1, 1};
+  const int mcus_w = im.blocks_w[0] / hs[0], mcus_h = im.blocks_h[0] / vs[0];
+  uint32_t pred[3] = {0, 0, 0};
+  Bits bits(d, n, P.scan);
+  const int ri = P.info.restart_interval;
+  int todo = ri, next_rst = 0;
+  for (int my = 0; my < mcus_h; ++my) {
+    for (int mx = 0; mx < mcus_w; ++mx) {
+      if (ri && todo == 0) {
+        // the bits left in this interval are padding; the reader stopped on (or in front of) the marker's 0xFF
+        bits.fill();
+        size_t q = bits.p;
+        if (!bits.stopped) {      // a full accumulator: the interval has bytes it never needed; go to the next marker
+          while (q < n && !(d[q] == 0xFF && !(q + 1 < n && d[q + 1] == 0))) q += (d[q] == 0xFF) ? 2 : 1;
+        }
+        if (q >= n || d[q] != 0xFF) return EDET_JPEG_MALFORMED;
+        while (q < n && d[q] == 0xFF) ++q;
+        if (q >= n || d[q] != 0xD0 + next_rst) return EDET_JPEG_MALFORMED;
+        next_rst = (next_rst + 1) & 7;
+        bits = Bits(d, n, q + 1);
+        pred[0] = pred[1] = pred[2] = 0;
+        todo = ri;
+      }
+      --todo;
+      for (int c = 0; c < nc; ++c) {
+        const Huff& dc = tables[2 * c];
+        const Huff& ac = tables[2 * c + 1];
+        for (int yy = 0; yy < vs[c]; ++yy) {
+          for (int xx = 0; xx < hs[c]; ++xx) {
+            const size_t at = (size_t)im.first_block[c] + (size_t)(my * vs[c] + yy) * im.blocks_w[c] + (mx * hs[c] + xx);
+            int16_t* blk = coef + 64 * at;
+            bool ok = true;
+            int s = bits.symbol(dc);
+            if (s < 0) return EDET_JPEG_MALFORMED;
+            if (s) pred[c] += (uint32_t)bits.receive_extend(s, ok);
+            if (!ok) return EDET_JPEG_MALFORMED;
+            blk[0] = (int16_t)(uint16_t)(pred[c] & 0xFFFFu);
+            int k = 1;
+            while (k < 64) {
+              const int rs = bits.symbol(ac);
+              if (rs < 0) return EDET_JPEG_MALFORMED;
+              const int r = rs >> 4;
+              s = rs & 15;
+              if (s == 0) {
+                if (r != 15) break;
+                k += 16;
+                continue;
+              }
+              k += r;
+              if (k > 63) return EDET_JPEG_MALFORMED;
+              blk[NATURAL[k]] = (int16_t)bits.receive_extend(s, ok);
+              if (!ok) return EDET_JPEG_MALFORMED;
+              ++k;
+            }
+          }
+        }
+      }
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int edet_jpeg_info(const uint8_t* data, size_t n, edet_jpeg_info_t* out) {
+  if (!data || !out) {
+    edet_set_error("edet_jpeg_info: null pointer");
+    return -1;
+  }
+  Parsed P;
+  if (walk(data, n, P) != 0) {
+    memset(out, 0, sizeof(*out));
+    edet_set_error("edet_jpeg_info: not a JPEG stream with a frame and a scan (%zu bytes)", n);
+    return -1;
+  }
+  *out = P.info;
+  return 0;
+}
+
+extern "C" int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h,
+                                        int canvas_w, int16_t* coef_host, size_t coef_capacity,
+                                        edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status,
+                                        int threads) {
+  if (!datas || !sizes || !coef_host || !images_host || !qtables_host || !status || batch < 1) {
+    edet_set_error("edet_jpeg_entropy_decode: null pointer or batch %d < 1", batch);
+    return -1;
+  }
+  if (threads <= 0) threads = batch < MAX_THREADS ? batch : MAX_THREADS;
+  if (threads > MAX_THREADS) threads = MAX_THREADS;
+  if (threads > batch) threads = batch;
+
+  struct Job {
+    Parsed P;
+    int td[3], ta[3];
+  };
+  std::vector<Job> jobs((size_t)batch);
+  // the headers, one image after the other: the place of an image in the arena depends on the images in front of it
+  size_t next_block = 0;
+  const size_t cap_blocks = coef_capacity / 64;
+  for (int b = 0; b < batch; ++b) {
+    Job& J = jobs[(size_t)b];
+    edet_jpeg_image_t& im = images_host[b];
+    memset(&im, 0, sizeof(im));
+    memset(qtables_host + (size_t)b * 256, 0, 256 * sizeof(uint16_t));
+    int st = walk(datas[b], sizes[b], J.P);
+    if (!st) st = check_frame(J.P.info, canvas_h, canvas_w);
+    if (!st) st = check_scan(J.P, J.td, J.ta);
+    if (!st) {
+      const edet_jpeg_info_t& f = J.P.info;
+      im.height = f.height;
+      im.width = f.width;
+      im.components = f.components;
+      im.h_max = f.components == 3 ? f.h_samp[0] : 1;
+      im.v_max = f.components == 3 ? f.v_samp[0] : 1;
+      const int mw = (f.width + 8 * im.h_max - 1) / (8 * im.h_max), mh = (f.height + 8 * im.v_max - 1) / (8 * im.v_max);
+      size_t total = 0;
+      for (int c = 0; c < f.components; ++c) {
+        im.blocks_w[c] = c == 0 ? mw * im.h_max : mw;
+        im.blocks_h[c] = c == 0 ? mh * im.v_max : mh;
+        im.quant_id[c] = f.quant_id[c];
+        total += (size_t)im.blocks_w[c] * (size_t)im.blocks_h[c];      // <= 3 * 8192 * 8192
+      }
+      if (total > cap_blocks || next_block > cap_blocks - total || next_block + total > (size_t)INT32_MAX) {
+        st = EDET_JPEG_TOO_LARGE;
+      } else {
+        size_t at = next_block;
+        for (int c = 0; c < f.components; ++c) {
+          im.first_block[c] = (int32_t)at;
+          at += (size_t)im.blocks_w[c] * (size_t)im.blocks_h[c];
+        }
+        im.total_blocks = (int32_t)total;
+        next_block += total;
+        memcpy(qtables_host + (size_t)b * 256, J.P.qt, sizeof(J.P.qt));
+      }
+    }
+    if (st) {
+      memset(&im, 0, sizeof(im));
+    }
+    im.status = st;
+    status[b] = st;
+  }
+
+  // the scans, in parallel: an image refused here keeps its place in the arena, unused
+  std::atomic<int> next(0);
+  auto work = [&]() {
+    for (;;) {
+      const int b = next.fetch_add(1);
+      if (b >= batch) return;
+      edet_jpeg_image_t& im = images_host[b];
+      if (im.status) continue;
+      const Job& J = jobs[(size_t)b];
+      const int st = decode_scan(datas[b], sizes[b], J.P, J.td, J.ta, im, coef_host);
+      if (st) {
+        memset(&im, 0, sizeof(im));
+        memset(qtables_host + (size_t)b * 256, 0, 256 * sizeof(uint16_t));
+        im.status = st;
+        status[b] = st;
+      }
+    }
+  };
+  if (threads == 1) {
+    work();
+  } else {
+    std::vector<std::thread> pool;
+    pool.reserve((size_t)threads - 1);
+    for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+  }
+  return 0;
+}

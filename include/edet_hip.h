@@ -810,6 +810,87 @@ int edet_wbf_cluster(const float* dets, const int32_t* counts, int batch, int ro
 int edet_wbf_order(const float* scratch, const int32_t* flags, int batch, int rows, float* fused, int32_t* fused_counts,
                    void* stream);
 
+/* ---- baseline JPEG decode (tf.io.decode_jpeg / decode_image(channels=3): object_detection/tf_example_decoder.py:57,
+ * inference.py:63, tf2/train_lib.py:258, efficientnetv2/preprocessing.py:142, efficientnetv2/datasets.py:328,502) ----------
+ * libjpeg's default decoder -- the integer-accurate inverse DCT (jidctint.c), fancy chroma upsampling (jdsample.c), YCbCr ->
+ * RGB (jdcolor.c) -- split in two: the serial entropy stage on the HOST (csrc/jpeg_host.cpp: plain C++, no device call, the
+ * only entry points of this header that take host pointers and block), everything behind it on the device (csrc/jpeg.hip).
+ * Decoded are 8-bit Huffman streams of SOF0 / SOF1 with one interleaved scan: one component, or three (YCbCr) whose chroma
+ * is sampled 1x1 and whose luma is 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0).  Everything else is a status, never a guess.
+ * Restated in tests/jpeg_ref.py; both stages are compared with it, and it with Pillow's libjpeg-turbo, byte for byte. */
+#define EDET_JPEG_OK 0
+#define EDET_JPEG_PROGRESSIVE 1   /* SOF2                                                                                   */
+#define EDET_JPEG_ARITHMETIC 2    /* SOF9 .. SOF11, SOF13 .. SOF15                                                          */
+#define EDET_JPEG_PRECISION 3     /* a sample precision other than 8 bits (12-bit files)                                    */
+#define EDET_JPEG_COMPONENTS 4    /* neither one component nor three (CMYK / YCCK)                                          */
+#define EDET_JPEG_SAMPLING 5      /* sampling factors outside the supported set (4:4:0, 4:1:1, subsampled luma, ...)        */
+#define EDET_JPEG_TOO_LARGE 6     /* higher or wider than the canvas                                                        */
+#define EDET_JPEG_MALFORMED 7     /* truncated; a bad marker, segment, table, code, restart marker or coefficient index     */
+#define EDET_JPEG_UNSUPPORTED 8   /* lossless / hierarchical frames, several or non-interleaved scans, RGB-coded components */
+#define EDET_JPEG_KIND_BASELINE 0      /* SOF0 */
+#define EDET_JPEG_KIND_EXTENDED 1      /* SOF1: extended sequential, Huffman */
+#define EDET_JPEG_KIND_PROGRESSIVE 2   /* SOF2 */
+#define EDET_JPEG_KIND_OTHER 3         /* every other frame marker; `sof` tells which */
+typedef struct edet_jpeg_info { /* 56 bytes: the frame header and what precedes the first SOS marker */
+  int32_t height, width;         /* of the frame; 0 is possible in the file (DNL) and is refused by the decoder            */
+  int32_t components;            /* as the frame header says (the arrays below hold the first four)                        */
+  int32_t precision;             /* bits per sample                                                                        */
+  int32_t kind;                  /* EDET_JPEG_KIND_*                                                                       */
+  int32_t restart_interval;      /* of the last DRI segment in front of SOS, 0 = none                                      */
+  int32_t sof;                   /* the frame marker's second byte, 0xC0 .. 0xCF                                           */
+  int32_t jfif;                  /* 1 if an APP0 JFIF segment was seen                                                     */
+  int32_t adobe_transform;       /* the transform byte of an APP14 Adobe segment, -1 if there is none                      */
+  int32_t reserved;
+  uint8_t h_samp[4], v_samp[4];  /* per component: sampling factors                                                        */
+  uint8_t quant_id[4];           /* per component: the quantisation table it names                                         */
+  uint8_t comp_id[4];            /* per component: its identifier                                                          */
+} edet_jpeg_info_t;
+typedef struct edet_jpeg_image { /* 80 bytes, one per image: written by the host stage, read by the kernels from DEVICE memory */
+  int32_t status;                /* EDET_JPEG_*; not 0: the other fields are 0 and the image's canvas comes out all zero    */
+  int32_t height, width;
+  int32_t components;            /* 1 or 3                                                                                 */
+  int32_t h_max, v_max;          /* the luma sampling factors, 1 or 2 (chroma is 1x1; one component: 1, 1)                 */
+  int32_t blocks_w[3], blocks_h[3]; /* per component: its 8x8-block grid, padded to whole MCUs                             */
+  int32_t quant_id[3];           /* per component: row 0 .. 3 of the image's [4][64] quantisation tables                   */
+  int32_t first_block[3];        /* per component: where its blocks start in BOTH arenas, in blocks: coefficient element
+                                    64 first_block, plane byte 64 first_block.  The components of an image are adjacent.  */
+  int32_t total_blocks;          /* of the image: the sum of blocks_w blocks_h                                             */
+  int32_t reserved;
+} edet_jpeg_image_t;
+/* edet_jpeg_info (host): walks the markers of `data` up to the first SOS.  Fails (-1) on a stream without SOI, with a bad
+ * segment length, with two frame headers, or that ends before SOS; every read is bounds-checked.
+ * edet_jpeg_entropy_decode (host, blocks until done): the Huffman stage of `batch` streams on `threads` worker threads
+ * (clamped to 1 .. 16; <= 0: min(16, batch); never derived from the machine's core count).  Per image a descriptor, its
+ * status (the descriptor's, repeated in status[batch]) and its quantisation tables uint16 [4][64] in natural order (zero where
+ * the file defines none) in qtables_host [batch][4][64]; the coefficients int16, NOT dequantised, 64 per block in natural
+ * order, per image and component in raster order over the block grid, densely packed in image order (first_block).  The DC
+ * predictor wraps: its low 16 bits are stored.  coef_capacity counts int16 elements; an image that no longer fits gets
+ * EDET_JPEG_TOO_LARGE.  A refused image occupies no blocks.  The call itself fails only on a null pointer or batch < 1.
+ * edet_jpeg_idct (device, one launch): coef, images, qtables as the host stage wrote them, copied to DEVICE memory; planes
+ * uint8, per image and component [blocks_h 8][blocks_w 8] at byte 64 first_block, padding blocks included.  Per block:
+ * coefficient x table entry, jidctint.c's column pass, then its row pass (CONST_BITS 13, PASS1_BITS 2; descale by
+ * (x + (1 << (s - 1))) >> s with s = 11, then 18), + 128, clamped to 0 .. 255.  All sums, products and left shifts wrap at
+ * 32 bits and the right shifts are arithmetic, so a corrupt stream gives the restatement's bytes.  max_blocks >= every
+ * image's total_blocks sizes the grid.  plane_capacity is the size of planes in bytes, and coef holds at least as many
+ * ELEMENTS: a descriptor that does not lie inside them, or that the host stage could not have written, is treated as refused
+ * before anything is read or written.  coef and qtables 16-byte aligned, planes 8-byte aligned.
+ * edet_jpeg_color (device, one launch): planes -> raw uint8 [batch][canvas_h][canvas_w][3].  Chroma: h2v1 -- first output
+ * of a row in[0], last in[last], even (3 cur + prev + 1) >> 2, odd (3 cur + next + 2) >> 2; h2v2 -- per output row colsum =
+ * 3 near + far, far = the chroma row above for the upper output row of a pair and below for the lower, clamped to the
+ * ceil(height / 2) real rows; even (3 this + last + 8) >> 4, (4 this + 8) >> 4 at the first column, odd (3 this + next + 7)
+ * >> 4, (4 this + 7) >> 4 at the last of the ceil(width / 2) real columns.  R = Y + ((91881 cr + 32768) >> 16), G = Y +
+ * ((-22554 cb - 46802 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16), cb and cr minus 128, clamped; one component:
+ * R = G = B = Y.  Every canvas pixel outside height x width, and the whole canvas of an image whose status is not 0, is
+ * written 0: raw needs no memset and equals v2_preprocessing.pad_batch of the decoded images.  batch <= 65535. */
+int edet_jpeg_info(const uint8_t* data, size_t n, edet_jpeg_info_t* out);
+int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
+                             int16_t* coef_host, size_t coef_capacity, edet_jpeg_image_t* images_host,
+                             uint16_t* qtables_host, int32_t* status, int threads);
+int edet_jpeg_idct(const int16_t* coef, const edet_jpeg_image_t* images_dev, const uint16_t* qtables_dev, int batch,
+                   int max_blocks, uint8_t* planes, size_t plane_capacity, void* stream);
+int edet_jpeg_color(const uint8_t* planes, const edet_jpeg_image_t* images_dev, int batch, int canvas_h, int canvas_w,
+                    size_t plane_capacity, uint8_t* raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

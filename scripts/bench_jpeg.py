@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""The JPEG decoder on one MI355X and its host, for LABNOTES.md (NOT the bench.py line).  A batch of `--batch` copies of the
+640x480 4:2:0 file of tests/golden/jpeg_cases.npz -- or of `--file`, any JPEG the decoder takes: the fixture is mostly flat
+tiles (16 KB), so its Huffman stage is far shorter than a photograph's --, one JSON line:
+  host_ms        the host stage alone (edet_jpeg_entropy_decode into pinned memory) at 1, 4 and 16 threads: wall clock,
+                 median and spread of `--reps` batches;
+  copy_ms        the three host-to-device copies of one batch, HIP events;
+  idct_ms, color_ms   each kernel alone, HIP events around `--launches` launches;
+  end_to_end     JpegDecoder(depth=2).decode in a loop at `--threads` threads, the device stage of one batch under the host
+                 stage of the next: wall clock per batch with one synchronisation at the end -> images per second;
+  pillow         where Pillow is importable: Image.open(...).convert('RGB') of the same bytes on a pool of as many worker
+                 threads (its decoder releases the interpreter lock), the independent baseline -> images per second.
+No ratio is asserted: the numbers are the result."""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from automl_amd import jpeg  # noqa: E402
+from automl_amd._lib import call, ptr  # noqa: E402
+
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'jpeg_cases.npz')
+
+
+def stats(times):
+  return {'median_ms': round(float(np.median(times)), 3), 'spread_ms': round(max(times) - min(times), 3),
+          'min_ms': round(min(times), 3)}
+
+
+def events(fn, launches, reps):
+  times = []
+  for _ in range(reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(launches):
+      fn()
+    e1.record()
+    torch.cuda.synchronize()
+    times.append(e0.elapsed_time(e1) / launches)
+  return stats(times)
+
+
+def main(args):
+  if args.file:
+    data = open(args.file, 'rb').read()
+    info = jpeg.jpeg_info(data)
+    rgb, h, w = None, info.height, info.width
+  else:
+    g = np.load(GOLDEN)
+    data = g['big_480x640_420/bytes'].tobytes()
+    rgb = g['big_480x640_420/rgb']
+    h, w = rgb.shape[:2]
+  b = args.batch
+  datas = [data] * b
+  out = {'batch': b, 'height': h, 'width': w, 'file': os.path.basename(args.file) if args.file else 'big_480x640_420',
+         'file_bytes': len(data), 'reps': args.reps}
+  dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2)
+  slot = dec._slots[0]
+  out['host_ms'] = {}
+  for threads in (1, 4, 16):
+    times = []
+    for _ in range(args.reps + 1):
+      t0 = time.perf_counter()
+      jpeg.entropy_decode(datas, h, w, slot.coef_host, slot.images_host, slot.qtables_host, slot.status, threads)
+      times.append((time.perf_counter() - t0) * 1e3)
+    out['host_ms'][str(threads)] = dict(stats(times[1:]), images_per_s=round(b / (float(np.median(times[1:])) * 1e-3), 1))
+  desc = jpeg.descriptors(slot.images_host, b)
+  assert not slot.status.any()
+  used = max(d.first_block[0] + d.total_blocks for d in desc)
+  most = max(d.total_blocks for d in desc)
+  out['coefficient_bytes'] = used * 128
+
+  def copy():
+    slot.coef[:used * 64].copy_(slot.coef_host[:used * 64], non_blocking=True)
+    slot.images.copy_(slot.images_host, non_blocking=True)
+    slot.qtables.copy_(slot.qtables_host, non_blocking=True)
+  raw = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dec.device)
+  st = torch.cuda.current_stream().cuda_stream
+  copy()
+  torch.cuda.synchronize()
+  out['copy_ms'] = events(copy, 1, args.reps)
+  out['copy_GBps'] = round(used * 128 / (out['copy_ms']['median_ms'] * 1e-3) / 1e9, 1)
+  out['idct_ms'] = events(lambda: call('edet_jpeg_idct', ptr(slot.coef), ptr(slot.images), ptr(slot.qtables), b, most,
+                                       ptr(slot.planes), dec.blocks * 64, st), args.launches, args.reps)
+  out['color_ms'] = events(lambda: call('edet_jpeg_color', ptr(slot.planes), ptr(slot.images), b, h, w, dec.blocks * 64,
+                                        ptr(raw), st), args.launches, args.reps)
+  assert rgb is None or np.array_equal(raw[b - 1].cpu().numpy(), rgb), 'the decoded batch differs from the fixture'
+  sizes = np.zeros((b, 2), np.int32)
+  for _ in range(2):
+    dec.decode(datas, out=raw, sizes_out=sizes)
+  torch.cuda.synchronize()
+  times = []
+  for _ in range(args.reps):
+    t0 = time.perf_counter()
+    for _ in range(args.batches):
+      dec.decode(datas, out=raw, sizes_out=sizes)
+    torch.cuda.synchronize()
+    times.append((time.perf_counter() - t0) * 1e3 / args.batches)
+  out['end_to_end'] = dict(stats(times), threads=args.threads, depth=2, batches_per_rep=args.batches,
+                           images_per_s=round(b / (float(np.median(times)) * 1e-3), 1))
+  try:
+    from PIL import Image
+  except ImportError:
+    out['pillow'] = None
+  else:
+    def one(d):
+      return np.asarray(Image.open(io.BytesIO(d)).convert('RGB'))
+    with ThreadPoolExecutor(max_workers=args.threads) as pool:
+      times = []
+      for _ in range(args.reps + 1):
+        t0 = time.perf_counter()
+        done = list(pool.map(one, datas))
+        times.append((time.perf_counter() - t0) * 1e3)
+    assert np.array_equal(done[0], raw[0].cpu().numpy()), 'Pillow and the decoder differ'
+    out['pillow'] = dict(stats(times[1:]), threads=args.threads,
+                         images_per_s=round(b / (float(np.median(times[1:])) * 1e-3), 1))
+  print(json.dumps(out))
+
+
+if __name__ == '__main__':
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--file', default='')
+  ap.add_argument('--batch', type=int, default=128)
+  ap.add_argument('--threads', type=int, default=16)
+  ap.add_argument('--reps', type=int, default=7)
+  ap.add_argument('--launches', type=int, default=10)
+  ap.add_argument('--batches', type=int, default=6)
+  a = ap.parse_args()
+  if not torch.cuda.is_available():
+    sys.exit('bench_jpeg.py needs an MI355X: nothing is measured without one')
+  main(a)
