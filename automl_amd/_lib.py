@@ -17,6 +17,13 @@ ACT_CODES = {'swish': ACT_SWISH, 'silu': ACT_SWISH, 'swish_native': ACT_SWISH, '
 RS_IDENTITY, RS_UP2, RS_POOL = 0, 1, 2
 MAX_PARTS = 1024
 OPT_SPLIT = 16   # EDET_OPT_SPLIT: partial squared norms per tensor segment
+
+
+def se_bwd_scratch_floats(n, c, se):
+  """fp32 elements of edet_se_fc_bwd's scratch (include/edet_hip.h; SeBwdScratch::total() in csrc/se.hip)."""
+  return n * (c + (2 + (c + 127) // 128) * se) + 8 * (2 * c * se + c + se)
+
+
 SEG_L2, SEG_FROZEN = 1, 2   # EDET_SEG_L2 / EDET_SEG_FROZEN bits of seg_flags
 
 c_void_p, c_int, c_float, c_double, c_int64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float,

@@ -1,4 +1,5 @@
 """Builds the gfx950 shared library (C ABI in include/edet_hip.h) in-tree with hipcc."""
+import glob
 import os
 import subprocess
 import sys
@@ -7,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(_HERE, 'libedet_hip.so')
-SOURCES = ['pw_gemm.hip', 'pw_stream.hip', 'pw_big.hip', 'pw_glds.hip', 'pw_tile_bwd.hip', 'conv.hip', 'conv_halo.hip', 'dwconv.hip', 'dw_march.hip', 'mbconv_fused.hip', 'stem.hip', 'bn_se.hip', 'fuse.hip', 'loss_opt.hip', 'mix.hip', 'randaug.hip', 'crop_resize.hip', 'gridmask.hip', 'det_autoaug.hip', 'coco_eval.hip', 'wbf.hip', 'det_eval.hip', 'postprocess.hip', 'labeling.hip', 'preprocess.hip', 'jpeg.hip', 'error.cpp', 'jpeg_host.cpp', 'plan_file.cpp', 'net_runtime.cpp']
+SOURCES = ['pw_gemm.hip', 'pw_stream.hip', 'pw_big.hip', 'pw_glds.hip', 'pw_tile_bwd.hip', 'conv.hip', 'conv_halo.hip', 'dwconv.hip', 'dw_march.hip', 'mbconv_fused.hip', 'stem.hip', 'bn.hip', 'se.hip', 'reduce.hip', 'fuse.hip', 'loss_opt.hip', 'mix.hip', 'randaug.hip', 'crop_resize.hip', 'gridmask.hip', 'det_autoaug.hip', 'coco_eval.hip', 'wbf.hip', 'det_eval.hip', 'postprocess.hip', 'labeling.hip', 'preprocess.hip', 'jpeg.hip', 'error.cpp', 'jpeg_host.cpp', 'plan_file.cpp', 'net_runtime.cpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result']
 # files that restate float32 numpy / TensorFlow expressions operation by operation (argmax ties, 1e-6 parities):
@@ -29,11 +30,8 @@ def _stale(target, deps):
 
 def build_library(force=False, verbose=False):
   """Compiles every HIP source for gfx950 and links libedet_hip.so; returns its path."""
-  hdrs = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'pw_impl.h'), os.path.join(CSRC, 'dw_impl.h'),
-          os.path.join(CSRC, 'randaug_impl.h'),
-          os.path.join(_HERE, '..', 'include', 'edet_hip.h'),
-          os.path.join(_HERE, '..', 'include', 'edet_net.h'), os.path.join(CSRC, 'plan_stubs.inc'),
-          os.path.join(CSRC, 'plan_file.h')]
+  hdrs = (glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.inc')) +
+          glob.glob(os.path.join(_HERE, '..', 'include', '*.h')))
   objdir = os.path.join(CSRC, 'build')
   os.makedirs(objdir, exist_ok=True)
   jobs = []

@@ -262,7 +262,8 @@ __host__ __device__ inline int same_pad_before(int in, int k, int s) {
   return total / 2;
 }
 
-// dst[i] += sum_p ws[p*n + i]  (p < P): 16 elements x 16 partial-row slices per workgroup (bn_se.hip)
+// dst[i] += sum_p ws[p*n + i]  (p < P): 16 elements x 64 partial-row slices per workgroup (reduce.hip); recorded for one
+// batched launch instead while edet_reduce_defer is on for the stream
 int edet_reduce_partials(const float* ws, int P, int64_t n, float* dst, hipStream_t st);
 int edet_reduce_partials_set(const float* ws, int P, int64_t n, float* dst, hipStream_t st);
 // two destinations: dst_a[i] += column i for i < n_a (dst_a may be NULL), dst_b[i - n_a] += column i for n_a <= i < n
@@ -283,6 +284,14 @@ int edet_resident_wgs(const void* fn, int threads, size_t lds);
 static inline int edet_env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return (e && e[0]) ? atoi(e) : dflt;
+}
+
+// f(type_tag<T>{}) with T the storage type of the runtime `dtype`; false (nothing called) = not a dtype
+template <typename T> struct type_tag { using type = T; };
+template <typename F> inline bool dtype_dispatch(int dtype, F&& f) {
+  if (dtype == EDET_BF16) return f(type_tag<bf16_t>{}), true;
+  if (dtype == EDET_F32) return f(type_tag<float>{}), true;
+  return false;
 }
 
 static inline hipStream_t to_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

@@ -7,11 +7,12 @@
 // Reference: efficientdet/tf2/efficientdet_keras.py:75-121 (fuse_features: fastattn / sum),
 // :254-263 (MaxPooling2D pool=stride+1, 'SAME'), :272-281 (resize_nearest_neighbor),
 // :214-217 (activation before the separable conv); efficientdet/efficientdet_arch.py:418-475.
-#include "common.h"
+#include "rowmap_impl.h"
 
 namespace {
 
 constexpr int THREADS = 256;
+static_assert(THREADS == ROW_THREADS, "ew_grid sizes its grids for this workgroup size");
 
 struct FuseArgs {
   edet_tview_t in[3];
@@ -511,20 +512,6 @@ __global__ void k_fuse_weights_bwd(const float* w0, const float* w1, const float
   normalise_weights_bwd(w, nin, method, d, dw);
   for (int i = 0; i < nin; ++i)
     if (method == 2 || w[i] > 0.f) dwp[i][ch] += dw[i];
-}
-
-// grid of a grid-stride elementwise kernel: one thread per item up to ONE ROUND of what the chip holds of this kernel
-// (occupancy query; 4096 when unknown) -- with more workgroups than resident slots the last round runs partly empty
-inline int ew_grid(int64_t total, const void* fn = nullptr, size_t lds = 0) {
-  int64_t g = (total + THREADS - 1) / THREADS;
-  int cap = 4096;
-  if (fn) {
-    const int slots = edet_resident_wgs(fn, THREADS, lds);
-    if (slots > 0) cap = slots;
-  }
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 int fill_args(FuseArgs& a, const edet_tview_t* in0, const edet_tview_t* in1, const edet_tview_t* in2,

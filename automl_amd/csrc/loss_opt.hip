@@ -4,21 +4,14 @@
 //
 // Reference: efficientdet/tf2/train_lib.py:357-406 (FocalLoss), :409-437 (BoxLoss / Keras Huber),
 // :493-604 (_detection_loss), :486-491 (_reg_l2_loss), :675-683 (clip + apply), :176-199 (optimizer).
-#include "common.h"
+#include "rowmap_impl.h"
 
 #include <type_traits>
 
 namespace {
 
 constexpr int THREADS = 256;
-
-struct RowMap { int tpr, rpp; };
-inline RowMap row_map_ld(int ld) {
-  int nvec = ld / 8, tpr = 1;
-  while (tpr < nvec && tpr < THREADS) tpr <<= 1;
-  RowMap m; m.tpr = tpr; m.rpp = THREADS / tpr;
-  return m;
-}
+static_assert(THREADS == ROW_THREADS, "the row map is laid out for this workgroup size");
 
 // logits [positions][ld], channel j = anchor * num_classes + class.
 // Per element (train_lib.py:357-406 with label_smoothing 0): u = +-x, 1 - p_t = sigmoid(u),
@@ -542,7 +535,7 @@ __global__ __launch_bounds__(THREADS, 8) void k_rmsprop_ema(float* params, const
 struct LossGrid { RowMap m; int g; float* part; size_t lds; };
 inline LossGrid loss_grid(int ld, int64_t positions, int nch, int64_t cap, void* workspace, size_t workspace_bytes) {
   LossGrid L;
-  L.m = row_map_ld(ld);
+  L.m = row_map(ld);
   L.lds = (size_t)THREADS * 8 * sizeof(float);
   int64_t g = (positions + L.m.rpp - 1) / L.m.rpp;
   g = (g + 3) / 4;
@@ -564,15 +557,13 @@ inline int64_t focal_grid_cap(int dtype, bool g15) {
 }
 
 // f(T{}, bool_constant<G15>, bool_constant<LS>) for the runtime (dtype, gamma == 1.5, label smoothing on); dtype is checked
-template <typename T> struct type_tag { using type = T; };
 template <typename F>
 inline void focal_dispatch(int dtype, bool g15, bool ls, F&& f) {
   auto by_flags = [&](auto t) {
     if (g15) { if (ls) f(t, std::true_type{}, std::true_type{}); else f(t, std::true_type{}, std::false_type{}); }
     else { if (ls) f(t, std::false_type{}, std::true_type{}); else f(t, std::false_type{}, std::false_type{}); }
   };
-  if (dtype == EDET_BF16) by_flags(type_tag<bf16_t>{});
-  else by_flags(type_tag<float>{});
+  (void)dtype_dispatch(dtype, by_flags);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compares two `hipcc --cuda-device-only -S` outputs of one source kernel by kernel.
 
-usage: asm_kernels_equal.py PARENT.s CHANGE.s
+usage: asm_kernels_equal.py PARENT.s CHANGE.s [CHANGE2.s ...]
 
 The compiler emits the kernels of a file in the order in which the host code first names their instantiations, so a
 change that only reorders the host code's launch tables moves whole kernels in the assembly.  This script cuts both
@@ -10,6 +10,9 @@ each kernel and the rest of the file, drops the lines of the per-compilation `__
 ordinal from local labels and the comments that quote them (`.LBB<ordinal>_<block>`, `.Lfunc_end<ordinal>`; the comment
 column moves with the label's length), and compares the blocks by kernel name.  Prints the names that differ or exist on one side only; exit status 0 = every kernel and
 the rest of the file are identical.
+
+Several CHANGE files: the parent source was split.  Their kernels are compared with the parent's as one set; the parts that
+exist once per file (what precedes the first kernel, what follows the last, the metadata frame) are then left out.
 """
 import re
 import sys
@@ -49,9 +52,19 @@ def cut(path):
 
 
 def main():
-  a, b = cut(sys.argv[1]), cut(sys.argv[2])
+  per_file = ('HEAD', 'TAIL', 'META')
+  a, b = cut(sys.argv[1]), {}
+  for path in sys.argv[2:]:
+    part = cut(path)
+    twice = sorted(k for k in part if k in b and k not in per_file)
+    assert not twice, 'in more than one change file: %s' % twice
+    b.update(part)
+  if len(sys.argv) > 3:
+    for k in per_file:
+      a.pop(k, None)
+      b.pop(k, None)
   bad = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
-  kernels = [k for k in a if not k.startswith('meta:') and k not in ('HEAD', 'TAIL', 'META')]
+  kernels = [k for k in a if not k.startswith('meta:') and k not in per_file]
   same_order = [k for k in a] == [k for k in b]
   print('%d kernels in %s, %d blocks differ%s' % (len(kernels), sys.argv[1], len(bad), '' if same_order else ' (emission order differs)'))
   for k in bad[:10]:

@@ -456,6 +456,74 @@ def test_pw_bwd_weight(dt, shape, mode, use_ws, pw_impl, ws_mib=16):
   gu.check(dw, want, name, 'pw_bwd_weight %s %s' % (shape, mode), rtol=2e-2 if name == 'bf16' else 1e-3)
 
 
+# ------------------------------------------------------------------------------------ partial-sum reductions, exactly
+# edet_pw_bwd_weight in fp32 is the generic k_wgrad: row splits of 512 rows (launch_wgrad: at most 1024 / ceil(max(cin,
+# cout) / 64) splits of at least 512 rows), the fp32 MFMA, one partial row [cin][cout] per split in the workspace, and
+# edet_reduce_partials adds the P = ceil(rows / 512) partial rows into dweight.  On inputs in {-1, 0, 1} every partial and
+# every sum is an integer below 2^24: whatever the order, the result is the integer matrix product, bit for bit.
+def exact_wgrad_case(rows, cin, cout):
+  rng = np.random.default_rng(gu.seed_of('exact wgrad', rows, cin, cout))
+  x = torch.from_numpy(rng.integers(-1, 2, (1, 1, rows, cin)).astype(np.float32))
+  dy = torch.from_numpy(rng.integers(-1, 2, (1, 1, rows, cout)).astype(np.float32))
+  prod = (x.reshape(rows, cin).long().t() @ dy.reshape(rows, cout).long()).float()
+  tv = gu.tview(gu.to_dev(x, torch.float32), cin)
+  gv = gu.gview(gu.to_dev(dy, torch.float32), cout)
+  return tv, gv, prod
+
+
+# cout 24: 192 elements, twelve 16-element workgroups; cout 9: 72 elements, the last workgroup has lanes past the end
+@pytest.mark.parametrize('cout', [8, 24, 9])
+@pytest.mark.parametrize('rows', [475,          # P = 1: no partial rows, the one split adds into dweight itself
+                                  2011,         # P = 4
+                                  32731,        # P = 64: every slice of k_reduce_partials has one row
+                                  32769,        # P = 65: slice 0 takes a second row (the one-row tail)
+                                  66011])       # P = 129: the two-row loop, then the tail
+def test_reduce_partials_is_exact(rows, cout):
+  cin = 8
+  tv, gv, prod = exact_wgrad_case(rows, cin, cout)
+  rng = np.random.default_rng(rows)
+  dw0 = torch.from_numpy(rng.integers(-3, 4, (cin, cout)).astype(np.float32))      # dweight is accumulated into
+  dw = dw0.to(gu.DEV)
+  wsp = torch.full((1024 * 1024,), float('nan'), dtype=torch.float32, device=gu.DEV)
+  call('edet_pw_bwd_weight', ctypes.byref(tv), ctypes.byref(gv), ptr(dw), ptr(wsp), wsp.numel() * 4, _lib.EDET_F32, gu.stream())
+  torch.cuda.synchronize()
+  assert torch.equal(dw.cpu(), prod + dw0)
+
+
+def test_deferred_reduction_is_exact():
+  """edet_reduce_defer: 100 recorded sums of P = 4 rows, 98 into one destination and 2 into another, added by
+  edet_reduce_flush -- more than one batch of 96 table entries, a group cut over two launches, two groups in one launch."""
+  st = gu.stream()
+  tv, gv, prod = exact_wgrad_case(2011, 8, 8)       # P = 4; |98 * prod| <= 98 * 2011 < 2^24
+  A, B, C = (torch.zeros(8, 8, dtype=torch.float32, device=gu.DEV) for _ in range(3))
+  wsp = torch.full((256 * 1024,), float('nan'), dtype=torch.float32, device=gu.DEV)
+  base, nbytes = wsp.data_ptr(), wsp.numel() * 4
+
+  def wgrad(dst, off=0):
+    call('edet_pw_bwd_weight', ctypes.byref(tv), ctypes.byref(gv), ptr(dst), base + off, nbytes - off, _lib.EDET_F32, st)
+
+  call('edet_reduce_defer', st, 1)
+  try:
+    off = 0
+    for k in range(100):
+      wgrad(B if k in (40, 97) else A, off)
+      hi = ctypes.c_void_p()
+      call('edet_reduce_deferred_end', st, ctypes.byref(hi))       # the next call's workspace starts behind the recorded rows
+      assert hi.value == base + (k + 1) * 4 * 64 * 4
+      off = hi.value - base
+    torch.cuda.synchronize()
+    assert not bool(A.any()) and not bool(B.any()), 'a deferred sum was added before the flush'
+    call('edet_reduce_flush', st)
+    torch.cuda.synchronize()
+    assert torch.equal(A.cpu(), 98 * prod) and torch.equal(B.cpu(), 2 * prod)
+  finally:
+    call('edet_reduce_defer', st, 0)
+  wgrad(C)       # immediate again
+  torch.cuda.synchronize()
+  assert torch.equal(C.cpu(), prod)
+  assert torch.equal(A.cpu(), 98 * prod) and torch.equal(B.cpu(), 2 * prod)
+
+
 # ------------------------------------------------------------------------------------ depthwise
 DW_SHAPES = [(2, 9, 11, 16), (1, 16, 16, 40), (2, 7, 5, 144), (1, 20, 20, 96), (2, 33, 17, 32), (1, 9, 9, 2304),
              (2, 6, 6, 3840)]
@@ -691,10 +759,37 @@ def test_batchnorm_train_fwd_bwd(dt, shape):
   gu.check(acc, res + dz, name, 'edet_add')
 
 
+# the edges of partial_colsum's loops at its 64 row slices: the one-row tail (1, 2, 63, 64, 65), the two-row loop (128, 129,
+# 448, 449) and the eight-row loop (512, 513, 1024); c: not multiples of the 16 channels of a workgroup (lanes with ch >= c)
+@pytest.mark.parametrize('c', [8, 24, 40])
+@pytest.mark.parametrize('nparts', [1, 2, 63, 64, 65, 128, 129, 448, 449, 512, 513, 1024])
+def test_bn_finalize_column_sums_are_exact(nparts, c):
+  """The column sums both finalize kernels form of the [nparts][2][c] partial rows, on integers in [-3, 3]: every sum is an
+  integer, so dbeta / dgamma and the mean (count a power of two) are exact whatever the order of the additions."""
+  rng = np.random.default_rng(gu.seed_of('colsum', nparts, c))
+  parts = rng.integers(-3, 4, (nparts, 2, c))
+  col = torch.from_numpy(parts.sum(0))      # int64 [2][c]
+  pd = torch.from_numpy(parts.astype(np.float32)).to(gu.DEV).contiguous()
+  one = torch.ones(c, dtype=torch.float32, device=gu.DEV)
+  out = torch.zeros(7, c, dtype=torch.float32, device=gu.DEV)
+  count = 1024.0
+  call('edet_bn_bwd_finalize', ptr(pd), nparts, c, count, ptr(one), ptr(one), ptr(one), ptr(out[0]), ptr(out[1]), None,
+       ptr(out[2]), ptr(out[3]), ptr(out[4]), gu.stream())
+  call('edet_bn_finalize', ptr(pd), nparts, c, count, ptr(one), ptr(one), 1e-3, -1.0, 0, None, None, ptr(out[2]), ptr(out[3]),
+       ptr(out[5]), ptr(out[6]), gu.stream())
+  torch.cuda.synchronize()
+  assert torch.equal(out[1].cpu(), col[0].float()), 'dbeta != column sums of row 0'
+  assert torch.equal(out[0].cpu(), col[1].float()), 'dgamma != column sums of row 1'
+  assert torch.equal(out[5].cpu(), (col[0].double() / count).float()), 'mean != float32(column sum / count)'
+
+
 # ------------------------------------------------------------------------------------ SE
 @pytest.mark.parametrize('dt', gu.DTYPES, ids=lambda d: d[0])
 @pytest.mark.parametrize('shape', [(2, 9, 7, 32, 8), (3, 20, 20, 144, 6), (2, 5, 5, 1152, 48), (3, 5, 5, 2304, 96),
-                                   (2, 6, 6, 3840, 160), (2, 48, 43, 64, 16)])     # the last: three row chunks per image
+                                   (2, 6, 6, 3840, 160), (2, 48, 43, 64, 16),     # the last: three row chunks per image
+                                   # parameter gradients over image slices (n >= 16): 8 even slices; 8 asked, 6 uneven ones
+                                   # made; 66 images per slice (more than the 64-image LDS chunk), se beyond one 48-unit block
+                                   (16, 3, 3, 32, 8), (17, 3, 3, 32, 8), (521, 2, 2, 40, 52)])
 def test_squeeze_excite(dt, shape):
   name, edt, tdt = dt
   n, h, w, c, se = shape
@@ -765,7 +860,7 @@ def test_squeeze_excite(dt, shape):
   dgate = gu.fdev((dout * a.detach()).sum((1, 2)))
   grads = [torch.zeros_like(t) for t in (w1d, b1d, w2d, b2d)]
   dpool = torch.zeros(n, c, dtype=torch.float32, device=gu.DEV)
-  scratch = torch.zeros(n * (c + (2 + (c + 127) // 128) * se) + 8 * (2 * c * se + c + se), dtype=torch.float32, device=gu.DEV)
+  scratch = torch.zeros(_lib.se_bwd_scratch_floats(n, c, se), dtype=torch.float32, device=gu.DEV)
   call('edet_se_fc_bwd', ptr(pd), ptr(hd), ptr(gd), ptr(dgate), n, c, se, 1.0 / (h * w), ptr(w1d), ptr(w2d),
        ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(grads[3]), ptr(dpool), ptr(scratch), ACT_SWISH, gu.stream())
   parts = partial_buf(c)
