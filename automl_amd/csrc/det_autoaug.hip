@@ -112,12 +112,10 @@ __device__ __forceinline__ int draw_int(double u, int lo, int hi) {
   return lo + clampi((int)floor(u * (double)n), 0, n - 1);
 }
 
-// blockIdx.x = the image.  boxes / out: [batch][m][4], the same buffer or two.
-__global__ __launch_bounds__(THREADS) void k_autoaug_boxes(const float* boxes, float* out,
-                                                          const int32_t* __restrict__ counts, int m, int h, int w,
-                                                          const int32_t* __restrict__ policy, int32_t* __restrict__ iargs,
-                                                          const float* __restrict__ fargs, const double* __restrict__ dargs) {
-  const int img = blockIdx.x;
+// Image `img` of height h and width w.  boxes / out: [batch][m][4], the same buffer or two.
+__device__ __forceinline__ void boxes_image(const float* boxes, float* out, const int32_t* __restrict__ counts, int m, int h, int w,
+                                            int img, const int32_t* __restrict__ policy, int32_t* __restrict__ iargs,
+                                            const float* __restrict__ fargs, const double* __restrict__ dargs) {
   const int op = policy[img];
   const int count = clampi(counts[img], 0, m);
   const float H = (float)h, W = (float)w;
@@ -155,25 +153,57 @@ __global__ __launch_bounds__(THREADS) void k_autoaug_boxes(const float* boxes, f
   }
 }
 
-// blockIdx.x = the image; n = H W pixels.  Four pixels (three words) per thread and step where every image starts on a word.
-constexpr int LUT_THREADS = 1024;
-__global__ __launch_bounds__(LUT_THREADS) void k_autoaug_contrast_lut(const uint8_t* __restrict__ src, int n,
-                                                                     const int32_t* __restrict__ policy, int32_t* __restrict__ ops,
-                                                                     const float* __restrict__ fargs, uint8_t* __restrict__ luts) {
-  __shared__ unsigned long long part[LUT_THREADS];
+__global__ __launch_bounds__(THREADS) void k_autoaug_boxes(const float* boxes, float* out,
+                                                          const int32_t* __restrict__ counts, int m, int h, int w,
+                                                          const int32_t* __restrict__ policy, int32_t* __restrict__ iargs,
+                                                          const float* __restrict__ fargs, const double* __restrict__ dargs) {
+  boxes_image(boxes, out, counts, m, h, w, blockIdx.x, policy, iargs, fargs, dargs);
+}
+
+constexpr int MAX_EXTENT = (1 << 24) - 1;      // what the dense entry point accepts: every pixel coordinate is exact in fp32
+// The canvas batch: (h, w) = sizes[img], clamped (the boxes are normalised: no slot is indexed here, and a size is only a
+// factor)
+__global__ __launch_bounds__(THREADS) void k_autoaug_boxes_canvas(const float* boxes, float* out,
+                                                                 const int32_t* __restrict__ counts, int m,
+                                                                 const int32_t* __restrict__ sizes,
+                                                                 const int32_t* __restrict__ policy, int32_t* __restrict__ iargs,
+                                                                 const float* __restrict__ fargs, const double* __restrict__ dargs) {
   const int img = blockIdx.x;
-  if (policy[img] != AA_CONTRAST) return;      // (uniform over the workgroup)
-  const uint8_t* p = src + (size_t)img * n * 3;
+  boxes_image(boxes, out, counts, m, clampi(sizes[2 * img], 1, MAX_EXTENT), clampi(sizes[2 * img + 1], 1, MAX_EXTENT), img, policy,
+              iargs, fargs, dargs);
+}
+
+// The image at p of n = h w pixels, `pitch` pixels from row to row (dense: its pixels are consecutive and w is not used)
+// -> its table.  vec: four pixels (three words) per thread and step; p starts on a word and, with CANVAS, w and pitch are
+// multiples of 4.
+constexpr int LUT_THREADS = 1024;
+template <bool CANVAS>
+__device__ __forceinline__ void contrast_image(const uint8_t* __restrict__ p, int n, int w, int pitch, bool vec, int img,
+                                               int32_t* __restrict__ ops, const float* __restrict__ fargs,
+                                               uint8_t* __restrict__ luts) {
+  __shared__ unsigned long long part[LUT_THREADS];
   unsigned long long sum = 0;
-  if (n % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 4 == 0) {
+  if (vec) {
     const uint32_t* pw = reinterpret_cast<const uint32_t*>(p);
     for (int q = threadIdx.x; q < n / 4; q += LUT_THREADS) {
-      const uint32_t a = pw[q * 3], b = pw[q * 3 + 1], c = pw[q * 3 + 2];
+      int q3 = q * 3;
+      if (CANVAS) {
+        const int y = (q * 4) / w;
+        q3 = ((y * pitch + (q * 4 - y * w)) >> 2) * 3;
+      }
+      const uint32_t a = pw[q3], b = pw[q3 + 1], c = pw[q3 + 2];
       sum += (unsigned)(gray_of(a & 255, (a >> 8) & 255, (a >> 16) & 255) + gray_of(a >> 24, b & 255, (b >> 8) & 255) +
                         gray_of((b >> 16) & 255, b >> 24, c & 255) + gray_of((c >> 8) & 255, (c >> 16) & 255, c >> 24));
     }
   } else {
-    for (int i = threadIdx.x; i < n; i += LUT_THREADS) sum += (unsigned)gray_of(p[(size_t)i * 3], p[(size_t)i * 3 + 1], p[(size_t)i * 3 + 2]);
+    for (int i = threadIdx.x; i < n; i += LUT_THREADS) {
+      size_t o = (size_t)i * 3;
+      if (CANVAS) {
+        const int y = i / w;
+        o = (size_t)(y * pitch + (i - y * w)) * 3;
+      }
+      sum += (unsigned)gray_of(p[o], p[o + 1], p[o + 2]);
+    }
   }
   part[threadIdx.x] = sum;
   __syncthreads();
@@ -186,6 +216,32 @@ __global__ __launch_bounds__(LUT_THREADS) void k_autoaug_contrast_lut(const uint
   uint8_t* out = luts + (size_t)img * 768;
   if (threadIdx.x < 768) out[threadIdx.x] = (uint8_t)blend(mean, threadIdx.x & 255, f);
   if (threadIdx.x == 0) ops[img] = APPLY_LUT;
+}
+
+// blockIdx.x = the image; n = H W pixels.  The word path where every image starts on a word.
+__global__ __launch_bounds__(LUT_THREADS) void k_autoaug_contrast_lut(const uint8_t* __restrict__ src, int n,
+                                                                     const int32_t* __restrict__ policy, int32_t* __restrict__ ops,
+                                                                     const float* __restrict__ fargs, uint8_t* __restrict__ luts) {
+  const int img = blockIdx.x;
+  if (policy[img] != AA_CONTRAST) return;      // (uniform over the workgroup)
+  contrast_image<false>(src + (size_t)img * n * 3, n, 0, 0, n % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 4 == 0, img, ops, fargs,
+                        luts);
+}
+
+// The canvas batch: the grey levels of the h x w rectangle of the image's slot only, (h, w) = sizes[img] clamped into the
+// slot.  An image as wide as the canvas has consecutive pixels, as in the dense batch.
+__global__ __launch_bounds__(LUT_THREADS) void k_autoaug_contrast_lut_canvas(const uint8_t* __restrict__ src, int ch, int cw,
+                                                                            const int32_t* __restrict__ sizes,
+                                                                            const int32_t* __restrict__ policy,
+                                                                            int32_t* __restrict__ ops, const float* __restrict__ fargs,
+                                                                            uint8_t* __restrict__ luts) {
+  const int img = blockIdx.x;
+  if (policy[img] != AA_CONTRAST) return;      // (uniform over the workgroup)
+  const int h = clampi(sizes[2 * img], 1, ch), w = clampi(sizes[2 * img + 1], 1, cw);
+  const uint8_t* p = src + (size_t)img * ch * cw * 3;
+  const bool word = reinterpret_cast<uintptr_t>(p) % 4 == 0;
+  if (w == cw) contrast_image<false>(p, h * w, 0, 0, word && (h * w) % 4 == 0, img, ops, fargs, luts);
+  else contrast_image<true>(p, h * w, w, cw, word && w % 4 == 0 && cw % 4 == 0, img, ops, fargs, luts);
 }
 
 }  // namespace
@@ -214,5 +270,34 @@ extern "C" int edet_autoaug_contrast_lut(const uint8_t* src, int batch, int heig
   edet_launch(k_autoaug_contrast_lut, dim3(batch), dim3(LUT_THREADS), 0, to_stream(stream), src, height * width, policy, ops, fargs,
               luts);
   EDET_LAUNCH_CHECK("edet_autoaug_contrast_lut");
+  return 0;
+}
+
+extern "C" int edet_autoaug_boxes_canvas(const float* boxes, float* boxes_out, const int32_t* counts, int batch, int max_boxes,
+                                         const int32_t* sizes_dev, const int32_t* policy, int32_t* iargs, const float* fargs,
+                                         const double* dargs, void* stream) {
+  EDET_CHECK(boxes && boxes_out && counts && sizes_dev && policy && iargs && fargs && dargs,
+             "edet_autoaug_boxes_canvas: null pointer");
+  EDET_CHECK(batch > 0 && max_boxes > 0, "edet_autoaug_boxes_canvas: batch %d, %d box rows", batch, max_boxes);
+  EDET_CHECK(reinterpret_cast<uintptr_t>(boxes) % 16 == 0 && reinterpret_cast<uintptr_t>(boxes_out) % 16 == 0 &&
+                 reinterpret_cast<uintptr_t>(dargs) % 8 == 0,
+             "edet_autoaug_boxes_canvas: boxes need 16-byte, dargs 8-byte alignment");
+  edet_launch(k_autoaug_boxes_canvas, dim3(batch), dim3(THREADS), 0, to_stream(stream), boxes, boxes_out, counts, max_boxes,
+              sizes_dev, policy, iargs, fargs, dargs);
+  EDET_LAUNCH_CHECK("edet_autoaug_boxes_canvas");
+  return 0;
+}
+
+extern "C" int edet_autoaug_contrast_lut_canvas(const uint8_t* src, int batch, int canvas_h, int canvas_w,
+                                                const int32_t* sizes_dev, const int32_t* policy, int32_t* ops, const float* fargs,
+                                                uint8_t* luts, void* stream) {
+  EDET_CHECK(src && sizes_dev && policy && ops && fargs && luts, "edet_autoaug_contrast_lut_canvas: null pointer");
+  EDET_CHECK(batch > 0 && canvas_h > 0 && canvas_w > 0, "edet_autoaug_contrast_lut_canvas: batch %d, canvas %d x %d", batch,
+             canvas_h, canvas_w);
+  EDET_CHECK((int64_t)canvas_h * canvas_w * 3 < (int64_t)1 << 31, "edet_autoaug_contrast_lut_canvas: canvas %d x %d too large",
+             canvas_h, canvas_w);
+  edet_launch(k_autoaug_contrast_lut_canvas, dim3(batch), dim3(LUT_THREADS), 0, to_stream(stream), src, canvas_h, canvas_w,
+              sizes_dev, policy, ops, fargs, luts);
+  EDET_LAUNCH_CHECK("edet_autoaug_contrast_lut_canvas");
   return 0;
 }

@@ -54,13 +54,21 @@ __device__ __forceinline__ int mask_at(const Mask& m, int x, int y) {
   return (int)((yc - sy) * top + (sy - yf) * bot);
 }
 
-// blockIdx.y = the image (the apply bit is uniform over a workgroup).  P pixels per thread and step: 4 (12 bytes in as
-// dwords, three dword stores out) where H W is a multiple of 4 and both batches are 16-byte aligned, else 1 (byte by byte).
-template <int P>
-__global__ __launch_bounds__(THREADS) void k_gridmask(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int h, int w,
-                                                     const edet_gridmask_image_t* __restrict__ per_image) {
+// blockIdx.y = the image (the apply bit is uniform over a workgroup).  Dense batch (CANVAS = false): the image is h x w and its
+// pixels are consecutive.  Canvas batch: h x w is the canvas, the image is the top-left sizes[img] of its slot -- clamped into
+// the slot, so that no row of device memory can send an access outside it -- and only that rectangle is read and written.
+// P pixels per thread and step: 4 (12 bytes in as dwords, three dword stores out) or 1 (byte by byte).
+template <int P, bool CANVAS>
+__device__ __forceinline__ void mask_images(const uint8_t* src, uint8_t* dst, int h, int w, const int32_t* sizes,
+                                            const edet_gridmask_image_t* per_image) {
   const int img = blockIdx.y;
+  const int slot_h = h, pitch = w;      // pitch: pixels from one row of the image to the next
+  if constexpr (CANVAS) {
+    h = clampi(sizes[2 * img], 1, slot_h);
+    w = clampi(sizes[2 * img + 1], 1, pitch);
+  }
   const int npix = h * w;
+  const int slot = CANVAS ? slot_h * pitch : npix;      // pixels from one image to the next
   const edet_gridmask_image_t a = per_image[img];
   Mask m;
   // nothing in device memory may send a division by zero or an overflow into the stripe arithmetic
@@ -74,16 +82,18 @@ __global__ __launch_bounds__(THREADS) void k_gridmask(const uint8_t* __restrict_
   m.oy = (m.S - h) >> 1;      // floor division, as Python's //
   m.ox = (m.S - w) >> 1;
   m.c0 = a.coef[0]; m.c1 = a.coef[1]; m.c2 = a.coef[2]; m.c3 = a.coef[3]; m.c4 = a.coef[4]; m.c5 = a.coef[5];
-  const uint8_t* in = src + (size_t)img * npix * 3;
-  uint8_t* out = dst + (size_t)img * npix * 3;
+  const uint8_t* in = src + (size_t)img * slot * 3;
+  uint8_t* out = dst + (size_t)img * slot * 3;
   const int step = gridDim.x * THREADS;
   for (int q = blockIdx.x * THREADS + threadIdx.x; q * P < npix; q += step) {
     const int p0 = q * P;
     int y = p0 / w, x = p0 - y * w;
     if constexpr (P == 4) {
+      // the group's first dword: a canvas group never leaves its row (w and the pitch are multiples of 4)
+      const int q3 = CANVAS ? ((y * pitch + x) >> 2) * 3 : q * 3;
       uint32_t v[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] = reinterpret_cast<const uint32_t*>(in)[q * 3 + k];
+      for (int k = 0; k < 3; ++k) v[k] = reinterpret_cast<const uint32_t*>(in)[q3 + k];
       if (m.apply) {
         uint32_t keep[3] = {0u, 0u, 0u};      // byte masks: 0xff over the three bytes of a kept pixel
 #pragma unroll
@@ -97,13 +107,31 @@ __global__ __launch_bounds__(THREADS) void k_gridmask(const uint8_t* __restrict_
         for (int k = 0; k < 3; ++k) v[k] &= keep[k];
       }
 #pragma unroll
-      for (int k = 0; k < 3; ++k) reinterpret_cast<uint32_t*>(out)[q * 3 + k] = v[k];
+      for (int k = 0; k < 3; ++k) reinterpret_cast<uint32_t*>(out)[q3 + k] = v[k];
     } else {
       const int on = m.apply ? mask_at(m, x, y) : 1;
+      const size_t o = CANVAS ? (size_t)(y * pitch + x) * 3 : (size_t)p0 * 3;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) out[(size_t)p0 * 3 + c] = on ? in[(size_t)p0 * 3 + c] : (uint8_t)0;
+      for (int c = 0; c < 3; ++c) out[o + c] = on ? in[o + c] : (uint8_t)0;
     }
   }
+}
+
+// P = 4 where H W is a multiple of 4 and both batches are 16-byte aligned, else 1
+template <int P>
+__global__ __launch_bounds__(THREADS) void k_gridmask(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int h, int w,
+                                                     const edet_gridmask_image_t* __restrict__ per_image) {
+  mask_images<P, false>(src, dst, h, w, nullptr, per_image);
+}
+
+// The grid is sized from the canvas; the threads a smaller image does not need leave the loop at once.  vec_ok: cw is a
+// multiple of 4 and both batches are 16-byte aligned -- then the images whose own width is a multiple of 4 take the dword
+// path (a choice per image, uniform over the workgroup).
+__global__ __launch_bounds__(THREADS) void k_gridmask_canvas(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int ch,
+                                                            int cw, const int32_t* __restrict__ sizes, int vec_ok,
+                                                            const edet_gridmask_image_t* __restrict__ per_image) {
+  if (vec_ok && clampi(sizes[2 * blockIdx.y + 1], 1, cw) % 4 == 0) mask_images<4, true>(src, dst, ch, cw, sizes, per_image);
+  else mask_images<1, true>(src, dst, ch, cw, sizes, per_image);
 }
 
 }  // namespace
@@ -125,5 +153,24 @@ extern "C" int edet_gridmask(const uint8_t* src, uint8_t* dst, int batch, int he
   if (vec) edet_launch(k_gridmask<4>, grid, dim3(THREADS), 0, st, src, dst, height, width, per_image_dev);
   else edet_launch(k_gridmask<1>, grid, dim3(THREADS), 0, st, src, dst, height, width, per_image_dev);
   EDET_LAUNCH_CHECK("edet_gridmask");
+  return 0;
+}
+
+extern "C" int edet_gridmask_canvas(const uint8_t* src, uint8_t* dst, int batch, int canvas_h, int canvas_w,
+                                    const int32_t* sizes_dev, const edet_gridmask_image_t* per_image_dev, void* stream) {
+  EDET_CHECK(src && dst && sizes_dev && per_image_dev, "edet_gridmask_canvas: null pointer");
+  EDET_CHECK(src != dst, "edet_gridmask_canvas: in place");
+  EDET_CHECK(batch > 0 && batch <= 65535 && canvas_h > 0 && canvas_w > 0, "edet_gridmask_canvas: batch %d, canvas %d x %d", batch,
+             canvas_h, canvas_w);
+  EDET_CHECK((int64_t)canvas_h * canvas_w * 3 < (int64_t)1 << 31, "edet_gridmask_canvas: canvas %d x %d too large", canvas_h,
+             canvas_w);
+  const int npix = canvas_h * canvas_w;
+  const bool vec = canvas_w % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+  const int units = vec ? npix / 4 : npix;      // (an image on the byte path of a vec_ok batch takes four times the steps)
+  int gx = (units + THREADS * 4 - 1) / (THREADS * 4);
+  if (gx > 256) gx = 256;
+  edet_launch(k_gridmask_canvas, dim3((unsigned)gx, (unsigned)batch), dim3(THREADS), 0, to_stream(stream), src, dst, canvas_h,
+              canvas_w, sizes_dev, (int)vec, per_image_dev);
+  EDET_LAUNCH_CHECK("edet_gridmask_canvas");
   return 0;
 }

@@ -71,9 +71,11 @@ __global__ __launch_bounds__(256) void k_preprocess_infer(const PrepArgs a) {
 }
 
 // Training: output pixel (y, x) = pixel (y + offset_y, x + offset_x) of the image resized to [scaled_h, scaled_w]
-// (zero beyond it), the raw image mirrored left-right first when flip is set.
+// (zero beyond it), the raw image mirrored left-right first when flip is set.  The raw image is h x w, its first pixel at
+// pixel index `img` of a.raw and its rows `pitch` pixels apart (dense: img = b h w, pitch = w).
 template <typename T>
-__global__ __launch_bounds__(256) void k_preprocess_train(const PrepArgs a, const edet_prep_image_t* __restrict__ per) {
+__device__ __forceinline__ void train_pixel(const PrepArgs& a, const edet_prep_image_t* __restrict__ per, int h, int w, int pitch,
+                                            size_t img) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int b = blockIdx.z;
@@ -82,20 +84,19 @@ __global__ __launch_bounds__(256) void k_preprocess_train(const PrepArgs a, cons
   const int Y = y + p.offset_y, X = x + p.offset_x;
   float v[3] = {0.f, 0.f, 0.f};
   if (X < p.scaled_w && Y < p.scaled_h) {
-    const float sy = __fsub_rn(__fmul_rn(__fadd_rn((float)Y, 0.5f), (float)a.h / (float)p.scaled_h), 0.5f);
-    const float sx = __fsub_rn(__fmul_rn(__fadd_rn((float)X, 0.5f), (float)a.w / (float)p.scaled_w), 0.5f);
+    const float sy = __fsub_rn(__fmul_rn(__fadd_rn((float)Y, 0.5f), (float)h / (float)p.scaled_h), 0.5f);
+    const float sx = __fsub_rn(__fmul_rn(__fadd_rn((float)X, 0.5f), (float)w / (float)p.scaled_w), 0.5f);
     const float fy = floorf(sy), fx = floorf(sx);
-    const int y0 = max((int)fy, 0), y1 = min((int)ceilf(sy), a.h - 1);
-    int x0 = max((int)fx, 0), x1 = min((int)ceilf(sx), a.w - 1);
-    if (p.flip) { x0 = a.w - 1 - x0; x1 = a.w - 1 - x1; }       // taps of the mirrored image, read from the raw one
+    const int y0 = max((int)fy, 0), y1 = min((int)ceilf(sy), h - 1);
+    int x0 = max((int)fx, 0), x1 = min((int)ceilf(sx), w - 1);
+    if (p.flip) { x0 = w - 1 - x0; x1 = w - 1 - x1; }       // taps of the mirrored image, read from the raw one
     const float ly = __fsub_rn(sy, fy), lx = __fsub_rn(sx, fx);
-    const size_t img = (size_t)b * a.h * a.w;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float tl = __fsub_rn(raw_at(a, ((img + (size_t)y0 * a.w + x0) * 3) + c), a.mean[c]) / a.stddev[c];
-      const float tr = __fsub_rn(raw_at(a, ((img + (size_t)y0 * a.w + x1) * 3) + c), a.mean[c]) / a.stddev[c];
-      const float bl = __fsub_rn(raw_at(a, ((img + (size_t)y1 * a.w + x0) * 3) + c), a.mean[c]) / a.stddev[c];
-      const float br = __fsub_rn(raw_at(a, ((img + (size_t)y1 * a.w + x1) * 3) + c), a.mean[c]) / a.stddev[c];
+      const float tl = __fsub_rn(raw_at(a, ((img + (size_t)y0 * pitch + x0) * 3) + c), a.mean[c]) / a.stddev[c];
+      const float tr = __fsub_rn(raw_at(a, ((img + (size_t)y0 * pitch + x1) * 3) + c), a.mean[c]) / a.stddev[c];
+      const float bl = __fsub_rn(raw_at(a, ((img + (size_t)y1 * pitch + x0) * 3) + c), a.mean[c]) / a.stddev[c];
+      const float br = __fsub_rn(raw_at(a, ((img + (size_t)y1 * pitch + x1) * 3) + c), a.mean[c]) / a.stddev[c];
       const float top = __fadd_rn(tl, __fmul_rn(__fsub_rn(tr, tl), lx));
       const float bot = __fadd_rn(bl, __fmul_rn(__fsub_rn(br, bl), lx));
       v[c] = __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), ly));
@@ -103,6 +104,22 @@ __global__ __launch_bounds__(256) void k_preprocess_train(const PrepArgs a, cons
   }
   T* o = reinterpret_cast<T*>(a.out) + (((size_t)b * a.out_h + y) * a.out_w + x) * 3;
   o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_preprocess_train(const PrepArgs a, const edet_prep_image_t* __restrict__ per) {
+  train_pixel<T>(a, per, a.h, a.w, a.w, (size_t)blockIdx.z * a.h * a.w);
+}
+
+// The canvas batch: a.h x a.w is the canvas; image b is the top-left h x w of its slot, (h, w) = sizes[b] clamped into the
+// slot: every tap is clamped to [0, h - 1] x [0, w - 1], so nothing outside the image is read.  The output is written whole,
+// as in the dense batch.
+template <typename T>
+__global__ __launch_bounds__(256) void k_preprocess_train_canvas(const PrepArgs a, const edet_prep_image_t* __restrict__ per,
+                                                                const int32_t* __restrict__ sizes) {
+  const int b = blockIdx.z;
+  const int h = min(max(sizes[2 * b], 1), a.h), w = min(max(sizes[2 * b + 1], 1), a.w);
+  train_pixel<T>(a, per, h, w, a.w, (size_t)b * a.h * a.w);
 }
 
 // Boxes of one image per workgroup: normalised [ymin, xmin, ymax, xmax] -> [mirrored] -> pixels of the scaled image ->
@@ -186,15 +203,17 @@ extern "C" int edet_preprocess_infer(const void* raw_images, int raw_is_float, i
   return 0;
 }
 
-extern "C" int edet_preprocess_train(const void* raw_images, int raw_is_float, int batch, int height, int width,
-                                     int out_height, int out_width, const float* mean_rgb, const float* stddev_rgb,
-                                     const edet_prep_image_t* per_image_dev, void* out, const float* boxes_in,
-                                     const float* classes_in, const int* counts_in, int max_boxes, float* boxes_out,
-                                     float* classes_out, int* counts_out, int dtype, void* stream) {
-  EDET_CHECK(raw_images && out && mean_rgb && stddev_rgb && per_image_dev, "edet_preprocess_train: null");
-  EDET_CHECK(batch >= 1 && height >= 1 && width >= 1 && out_height >= 1 && out_width >= 1,
-             "edet_preprocess_train: bad sizes");
-  EDET_CHECK(dtype == EDET_F32 || dtype == EDET_BF16, "edet_preprocess_train: dtype %d", dtype);
+namespace {
+
+// what the two training entry points share: sizes_dev == NULL is the dense batch
+int preprocess_train(const char* name, const void* raw_images, int raw_is_float, int batch, int height, int width, int out_height,
+                     int out_width, const float* mean_rgb, const float* stddev_rgb, const int32_t* sizes_dev,
+                     const edet_prep_image_t* per_image_dev, void* out, const float* boxes_in, const float* classes_in,
+                     const int* counts_in, int max_boxes, float* boxes_out, float* classes_out, int* counts_out, int dtype,
+                     void* stream) {
+  EDET_CHECK(raw_images && out && mean_rgb && stddev_rgb && per_image_dev, "%s: null", name);
+  EDET_CHECK(batch >= 1 && height >= 1 && width >= 1 && out_height >= 1 && out_width >= 1, "%s: bad sizes", name);
+  EDET_CHECK(dtype == EDET_F32 || dtype == EDET_BF16, "%s: dtype %d", name, dtype);
   PrepArgs a;
   a.raw = raw_images; a.raw_is_float = raw_is_float;
   a.batch = batch; a.h = height; a.w = width; a.out_h = out_height; a.out_w = out_width;
@@ -202,14 +221,43 @@ extern "C" int edet_preprocess_train(const void* raw_images, int raw_is_float, i
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean_rgb[c]; a.stddev[c] = stddev_rgb[c]; }
   a.out = out;
   const dim3 grid(cdiv(out_width, 64), cdiv(out_height, 4), batch);
-  if (dtype == EDET_BF16) edet_launch(k_preprocess_train<bf16_t>, grid, dim3(256), 0, to_stream(stream), a, per_image_dev);
-  else edet_launch(k_preprocess_train<float>, grid, dim3(256), 0, to_stream(stream), a, per_image_dev);
-  if (max_boxes > 0) {
-    EDET_CHECK(boxes_in && classes_in && counts_in && boxes_out && classes_out && counts_out,
-               "edet_preprocess_train: null box arrays");
-    EDET_CHECK(max_boxes <= PREP_MAX_BOXES, "edet_preprocess_train: max_boxes = %d (<= %d)", max_boxes, PREP_MAX_BOXES);
-    edet_launch(k_preprocess_boxes, dim3(batch), dim3(256), 0, to_stream(stream), per_image_dev, boxes_in, classes_in, counts_in, max_boxes, out_height, out_width, boxes_out, classes_out, counts_out);
+  hipStream_t st = to_stream(stream);
+  if (sizes_dev) {
+    if (dtype == EDET_BF16) edet_launch(k_preprocess_train_canvas<bf16_t>, grid, dim3(256), 0, st, a, per_image_dev, sizes_dev);
+    else edet_launch(k_preprocess_train_canvas<float>, grid, dim3(256), 0, st, a, per_image_dev, sizes_dev);
+  } else {
+    if (dtype == EDET_BF16) edet_launch(k_preprocess_train<bf16_t>, grid, dim3(256), 0, st, a, per_image_dev);
+    else edet_launch(k_preprocess_train<float>, grid, dim3(256), 0, st, a, per_image_dev);
   }
-  EDET_LAUNCH_CHECK("edet_preprocess_train");
+  if (max_boxes > 0) {
+    EDET_CHECK(boxes_in && classes_in && counts_in && boxes_out && classes_out && counts_out, "%s: null box arrays", name);
+    EDET_CHECK(max_boxes <= PREP_MAX_BOXES, "%s: max_boxes = %d (<= %d)", name, max_boxes, PREP_MAX_BOXES);
+    edet_launch(k_preprocess_boxes, dim3(batch), dim3(256), 0, st, per_image_dev, boxes_in, classes_in, counts_in, max_boxes,
+                out_height, out_width, boxes_out, classes_out, counts_out);
+  }
+  EDET_LAUNCH_CHECK(name);
   return 0;
+}
+
+}  // namespace
+
+extern "C" int edet_preprocess_train(const void* raw_images, int raw_is_float, int batch, int height, int width,
+                                     int out_height, int out_width, const float* mean_rgb, const float* stddev_rgb,
+                                     const edet_prep_image_t* per_image_dev, void* out, const float* boxes_in,
+                                     const float* classes_in, const int* counts_in, int max_boxes, float* boxes_out,
+                                     float* classes_out, int* counts_out, int dtype, void* stream) {
+  return preprocess_train("edet_preprocess_train", raw_images, raw_is_float, batch, height, width, out_height, out_width, mean_rgb,
+                          stddev_rgb, nullptr, per_image_dev, out, boxes_in, classes_in, counts_in, max_boxes, boxes_out,
+                          classes_out, counts_out, dtype, stream);
+}
+
+extern "C" int edet_preprocess_train_canvas(const void* raw_images, int raw_is_float, int batch, int canvas_h, int canvas_w,
+                                            const int32_t* sizes_dev, int out_height, int out_width, const float* mean_rgb,
+                                            const float* stddev_rgb, const edet_prep_image_t* per_image_dev, void* out,
+                                            const float* boxes_in, const float* classes_in, const int* counts_in, int max_boxes,
+                                            float* boxes_out, float* classes_out, int* counts_out, int dtype, void* stream) {
+  EDET_CHECK(sizes_dev, "edet_preprocess_train_canvas: null sizes");
+  return preprocess_train("edet_preprocess_train_canvas", raw_images, raw_is_float, batch, canvas_h, canvas_w, out_height, out_width,
+                          mean_rgb, stddev_rgb, sizes_dev, per_image_dev, out, boxes_in, classes_in, counts_in, max_boxes, boxes_out,
+                          classes_out, counts_out, dtype, stream);
 }

@@ -32,17 +32,9 @@ using raug::clip_u8;
 using raug::gray_of;
 
 // ---- statistics: one workgroup per image --------------------------------------------------------------------------------
-__global__ __launch_bounds__(THREADS) void k_randaug_stats(const uint8_t* __restrict__ src, int n, const int32_t* __restrict__ ops,
-                                                          uint8_t* __restrict__ luts) {
-  __shared__ int hist[3 * 256];
-  __shared__ int lo_s[3], hi_s[3], step_s[3];
-  const int img = blockIdx.x;
-  const int op = ops[img];
-  if (op != OP_AUTOCONTRAST && op != OP_EQUALIZE) return;      // (uniform over the workgroup)
-  for (int i = threadIdx.x; i < 3 * 256; i += THREADS) hist[i] = 0;
-  __syncthreads();
-  const uint8_t* p = src + (size_t)img * n;
-  // bytes in front of the first 4-byte boundary, whole words, bytes behind the last one; channel of byte k = k % 3
+// the bytes [p, p + n) into the three histograms: bytes in front of the first 4-byte boundary, whole words, bytes behind the
+// last one; channel of byte k = k % 3 (p is the first byte of a pixel)
+__device__ __forceinline__ void hist_span(const uint8_t* __restrict__ p, int n, int* hist) {
   const int head = min((int)((4 - (reinterpret_cast<uintptr_t>(p) & 3)) & 3), n);
   const int words = (n - head) / 4;
   if ((int)threadIdx.x < head) atomicAdd(&hist[(threadIdx.x % 3) * 256 + p[threadIdx.x]], 1);
@@ -58,6 +50,16 @@ __global__ __launch_bounds__(THREADS) void k_randaug_stats(const uint8_t* __rest
   }
   const int tail = head + 4 * words;
   if ((int)threadIdx.x < n - tail) atomicAdd(&hist[((tail + threadIdx.x) % 3) * 256 + p[tail + threadIdx.x]], 1);
+}
+
+// One image of `rows` spans of n bytes each, pitch bytes apart (dense: one span, the whole image) -> its table.
+__device__ __forceinline__ void stats_image(const uint8_t* __restrict__ p, int rows, int n, size_t pitch, int op,
+                                            uint8_t* __restrict__ out) {
+  __shared__ int hist[3 * 256];
+  __shared__ int lo_s[3], hi_s[3], step_s[3];
+  for (int i = threadIdx.x; i < 3 * 256; i += THREADS) hist[i] = 0;
+  __syncthreads();
+  for (int y = 0; y < rows; ++y) hist_span(p + (size_t)y * pitch, n, hist);
   __syncthreads();
   if (threadIdx.x < 3) {      // one thread per channel: lowest / highest occupied bin, Equalize's step, the running sum
     int* h = hist + threadIdx.x * 256;
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(THREADS) void k_randaug_stats(const uint8_t* __rest
     }
     lo_s[threadIdx.x] = lo;
     hi_s[threadIdx.x] = hi;
-    step_s[threadIdx.x] = (n / 3 - h[hi]) / 255;      // (sum of the non-zero bins - the last of them) // 255
+    step_s[threadIdx.x] = (rows * (n / 3) - h[hi]) / 255;      // (sum of the non-zero bins - the last of them) // 255
     int run = 0;
     for (int i = 0; i < 256; ++i) {
       run += h[i];
@@ -78,7 +80,6 @@ __global__ __launch_bounds__(THREADS) void k_randaug_stats(const uint8_t* __rest
     }
   }
   __syncthreads();
-  uint8_t* out = luts + (size_t)img * 768;
   for (int i = threadIdx.x; i < 768; i += THREADS) {
     const int c = i >> 8, v = i & 255;
     int r = v;
@@ -97,9 +98,31 @@ __global__ __launch_bounds__(THREADS) void k_randaug_stats(const uint8_t* __rest
   }
 }
 
+__global__ __launch_bounds__(THREADS) void k_randaug_stats(const uint8_t* __restrict__ src, int n, const int32_t* __restrict__ ops,
+                                                          uint8_t* __restrict__ luts) {
+  const int img = blockIdx.x;
+  const int op = ops[img];
+  if (op != OP_AUTOCONTRAST && op != OP_EQUALIZE) return;      // (uniform over the workgroup)
+  stats_image(src + (size_t)img * n, 1, n, 0, op, luts + (size_t)img * 768);
+}
+
+// The canvas batch: the histograms count the h x w rectangle of the image's slot only, (h, w) = sizes[img] clamped into the
+// slot.  An image as wide as the canvas is one span, as in the dense batch; a narrower one is a span per row.
+__global__ __launch_bounds__(THREADS) void k_randaug_stats_canvas(const uint8_t* __restrict__ src, int ch, int cw,
+                                                                 const int32_t* __restrict__ sizes, const int32_t* __restrict__ ops,
+                                                                 uint8_t* __restrict__ luts) {
+  const int img = blockIdx.x;
+  const int op = ops[img];
+  if (op != OP_AUTOCONTRAST && op != OP_EQUALIZE) return;      // (uniform over the workgroup)
+  const int h = clampi(sizes[2 * img], 1, ch), w = clampi(sizes[2 * img + 1], 1, cw);
+  const uint8_t* p = src + (size_t)img * ch * cw * 3;
+  if (w == cw) stats_image(p, 1, h * w * 3, 0, op, luts + (size_t)img * 768);
+  else stats_image(p, h, w * 3, (size_t)cw * 3, op, luts + (size_t)img * 768);
+}
+
 // ---- one layer ----------------------------------------------------------------------------------------------------------
 struct Args {
-  int op, h, w, i0, i1, i2, i3;
+  int op, h, w, pitch, i0, i1, i2, i3;      // pitch: pixels from one row of the image to the next (dense: w)
   float a0, a1, a2, b0, b1, b2, f;
   const uint8_t* img;      // this image of src
   const uint8_t* lut;      // its 3 x 256 table
@@ -115,7 +138,7 @@ __device__ __forceinline__ Px geometric(const Args& a, int x, int y) {
   const float sx = roundf((a.a0 * fx + a.a1 * fy) + a.a2);
   const float sy = roundf((a.b0 * fx + a.b1 * fy) + a.b2);
   if (!(sx >= 0.f && sx <= (float)(a.w - 1) && sy >= 0.f && sy <= (float)(a.h - 1))) return Px{128, 128, 128};
-  return load_px(a.img + ((size_t)(int)sy * a.w + (int)sx) * 3);
+  return load_px(a.img + ((size_t)(int)sy * a.pitch + (int)sx) * 3);
 }
 
 // PIL's SMOOTH kernel on the interior, the original on the one-pixel border (autoaugment.py:323-349), then the blend
@@ -127,7 +150,7 @@ __device__ __forceinline__ Px sharpness(const Args& a, int x, int y, Px o) {
   for (int dy = -1; dy <= 1; ++dy) {
 #pragma unroll
     for (int dx = -1; dx <= 1; ++dx) {
-      const Px q = load_px(a.img + ((size_t)(y + dy) * a.w + (x + dx)) * 3);
+      const Px q = load_px(a.img + ((size_t)(y + dy) * a.pitch + (x + dx)) * 3);
       const float k = (dy == 0 && dx == 0) ? w5 : w1;
       sr = sr + k * (float)q.r;
       sg = sg + k * (float)q.g;
@@ -171,19 +194,20 @@ template <> __device__ __forceinline__ bf16_t out_of<bf16_t>(int v) { return f2b
 
 template <typename T> struct alignas(sizeof(T) * 4) Quad { T v[4]; };
 
-// blockIdx.y = the image (the operation is uniform over a workgroup).  P pixels per thread and step: 4 (12 bytes in, three
-// 4-element stores out) where H W is a multiple of 4 and both batches are 16-byte aligned, else 1 (byte by byte).
-template <typename T, int P>
-__global__ __launch_bounds__(THREADS) void k_randaug_apply(const uint8_t* __restrict__ src, T* __restrict__ dst, int h, int w,
-                                                          const int32_t* __restrict__ ops, const int32_t* __restrict__ iargs,
-                                                          const float* __restrict__ fargs, const uint8_t* __restrict__ luts) {
-  const int img = blockIdx.y;
+// One image: `in` / `out` are its first pixel, `pitch` its row pitch in pixels (dense: w, the pixels are consecutive; canvas:
+// the canvas width, and only the h x w rectangle is read and written).  P pixels per thread and step: 4 (12 bytes in, three
+// 4-element stores out) or 1 (byte by byte); with CANVAS, P = 4 needs w and pitch to be multiples of 4.
+template <typename T, int P, bool CANVAS>
+__device__ __forceinline__ void apply_image(const uint8_t* __restrict__ in, T* __restrict__ out, int h, int w, int pitch, int img,
+                                            const int32_t* __restrict__ ops, const int32_t* __restrict__ iargs,
+                                            const float* __restrict__ fargs, const uint8_t* __restrict__ luts) {
   const int npix = h * w;
   Args a;
   a.op = ops ? ops[img] : OP_IDENTITY;
   if (a.op < 0 || a.op > OP_IDENTITY) a.op = OP_IDENTITY;
   a.h = h;
   a.w = w;
+  a.pitch = pitch;
   a.i0 = a.i1 = a.i2 = a.i3 = 0;
   a.a0 = a.a1 = a.a2 = a.b0 = a.b1 = a.b2 = 0.f;
   a.f = 1.f;
@@ -202,24 +226,24 @@ __global__ __launch_bounds__(THREADS) void k_randaug_apply(const uint8_t* __rest
     a.i1 = clampi(a.i1, 0, w); a.i3 = clampi(a.i3, 0, w);
   }
   if (a.op == OP_CONTRAST) a.i0 = (int)fminf((float)npix / 256.0f, 255.f);
-  a.img = src + (size_t)img * npix * 3;
+  a.img = in;
   a.lut = luts + (size_t)img * 768;
-  T* out = dst + (size_t)img * npix * 3;
   const int step = gridDim.x * THREADS;
   for (int q = blockIdx.x * THREADS + threadIdx.x; q * P < npix; q += step) {
     const int p0 = q * P;
     int y = p0 / w, x = p0 - y * w;
     if constexpr (P == 4) {
-      uint32_t in[3];
+      const int q3 = CANVAS ? ((y * pitch + x) >> 2) * 3 : q * 3;      // the group's first dword
+      uint32_t in4[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) in[k] = reinterpret_cast<const uint32_t*>(a.img)[q * 3 + k];
+      for (int k = 0; k < 3; ++k) in4[k] = reinterpret_cast<const uint32_t*>(a.img)[q3 + k];
       int res[12];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         Px o;
-        o.r = (in[(3 * e) >> 2] >> (8 * ((3 * e) & 3))) & 255;
-        o.g = (in[(3 * e + 1) >> 2] >> (8 * ((3 * e + 1) & 3))) & 255;
-        o.b = (in[(3 * e + 2) >> 2] >> (8 * ((3 * e + 2) & 3))) & 255;
+        o.r = (in4[(3 * e) >> 2] >> (8 * ((3 * e) & 3))) & 255;
+        o.g = (in4[(3 * e + 1) >> 2] >> (8 * ((3 * e + 1) & 3))) & 255;
+        o.b = (in4[(3 * e + 2) >> 2] >> (8 * ((3 * e + 2) & 3))) & 255;
         const Px r = apply_px(a, x, y, o);
         res[3 * e] = r.r; res[3 * e + 1] = r.g; res[3 * e + 2] = r.b;
         if (++x == w) { x = 0; ++y; }
@@ -229,15 +253,43 @@ __global__ __launch_bounds__(THREADS) void k_randaug_apply(const uint8_t* __rest
         Quad<T> o4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o4.v[e] = out_of<T>(res[4 * k + e]);
-        reinterpret_cast<Quad<T>*>(out)[q * 3 + k] = o4;
+        reinterpret_cast<Quad<T>*>(out)[q3 + k] = o4;
       }
     } else {
-      const Px r = apply_px(a, x, y, load_px(a.img + (size_t)p0 * 3));
-      out[(size_t)p0 * 3] = out_of<T>(r.r);
-      out[(size_t)p0 * 3 + 1] = out_of<T>(r.g);
-      out[(size_t)p0 * 3 + 2] = out_of<T>(r.b);
+      const size_t o = CANVAS ? (size_t)(y * pitch + x) * 3 : (size_t)p0 * 3;
+      const Px r = apply_px(a, x, y, load_px(a.img + o));
+      out[o] = out_of<T>(r.r);
+      out[o + 1] = out_of<T>(r.g);
+      out[o + 2] = out_of<T>(r.b);
     }
   }
+}
+
+// blockIdx.y = the image (the operation is uniform over a workgroup).  P pixels per thread and step: 4 where H W is a
+// multiple of 4 and both batches are 16-byte aligned, else 1.
+template <typename T, int P>
+__global__ __launch_bounds__(THREADS) void k_randaug_apply(const uint8_t* __restrict__ src, T* __restrict__ dst, int h, int w,
+                                                          const int32_t* __restrict__ ops, const int32_t* __restrict__ iargs,
+                                                          const float* __restrict__ fargs, const uint8_t* __restrict__ luts) {
+  const int img = blockIdx.y;
+  const int npix = h * w;
+  apply_image<T, P, false>(src + (size_t)img * npix * 3, dst + (size_t)img * npix * 3, h, w, w, img, ops, iargs, fargs, luts);
+}
+
+// The canvas batch: image blockIdx.y is the top-left h x w of its ch x cw slot in src and in dst, (h, w) = sizes[img]
+// clamped into the slot; the rest of the dst slot is not written.  The grid is sized from the canvas.  vec_ok: cw is a
+// multiple of 4 and both batches are 16-byte aligned -- then the images whose own width is a multiple of 4 take the
+// four-pixel path (a choice per image, uniform over the workgroup).
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_randaug_apply_canvas(const uint8_t* __restrict__ src, T* __restrict__ dst, int ch,
+                                                                 int cw, const int32_t* __restrict__ sizes, int vec_ok,
+                                                                 const int32_t* __restrict__ ops, const int32_t* __restrict__ iargs,
+                                                                 const float* __restrict__ fargs, const uint8_t* __restrict__ luts) {
+  const int img = blockIdx.y;
+  const int h = clampi(sizes[2 * img], 1, ch), w = clampi(sizes[2 * img + 1], 1, cw);
+  const size_t slot = (size_t)img * ch * cw * 3;
+  if (vec_ok && w % 4 == 0) apply_image<T, 4, true>(src + slot, dst + slot, h, w, cw, img, ops, iargs, fargs, luts);
+  else apply_image<T, 1, true>(src + slot, dst + slot, h, w, cw, img, ops, iargs, fargs, luts);
 }
 
 template <typename T>
@@ -251,6 +303,18 @@ void launch_apply(const uint8_t* src, void* dst, int batch, int h, int w, const 
   const dim3 grid((unsigned)gx, (unsigned)batch);
   if (vec) edet_launch(k_randaug_apply<T, 4>, grid, dim3(THREADS), 0, st, src, (T*)dst, h, w, ops, iargs, fargs, luts);
   else edet_launch(k_randaug_apply<T, 1>, grid, dim3(THREADS), 0, st, src, (T*)dst, h, w, ops, iargs, fargs, luts);
+}
+
+template <typename T>
+void launch_apply_canvas(const uint8_t* src, void* dst, int batch, int ch, int cw, const int32_t* sizes, const int32_t* ops,
+                         const int32_t* iargs, const float* fargs, const uint8_t* luts, hipStream_t st) {
+  const int npix = ch * cw;
+  const bool vec = cw % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+  const int units = vec ? npix / 4 : npix;
+  int gx = (units + THREADS * 4 - 1) / (THREADS * 4);
+  if (gx > 256) gx = 256;
+  edet_launch(k_randaug_apply_canvas<T>, dim3((unsigned)gx, (unsigned)batch), dim3(THREADS), 0, st, src, (T*)dst, ch, cw, sizes,
+              (int)vec, ops, iargs, fargs, luts);
 }
 
 }  // namespace
@@ -279,5 +343,37 @@ extern "C" int edet_randaug_apply(const uint8_t* src, void* dst, int batch, int 
   else if (out_dtype == EDET_BF16) launch_apply<bf16_t>(src, dst, batch, height, width, ops, iargs, fargs, luts, st);
   else EDET_CHECK(false, "edet_randaug_apply: bad out_dtype %d", out_dtype);
   EDET_LAUNCH_CHECK("edet_randaug_apply");
+  return 0;
+}
+
+extern "C" int edet_randaug_stats_canvas(const uint8_t* src, int batch, int canvas_h, int canvas_w, const int32_t* sizes_dev,
+                                         const int32_t* ops, uint8_t* luts, void* stream) {
+  EDET_CHECK(src && sizes_dev && ops && luts, "edet_randaug_stats_canvas: null pointer");
+  EDET_CHECK(batch > 0 && canvas_h > 0 && canvas_w > 0, "edet_randaug_stats_canvas: batch %d, canvas %d x %d", batch, canvas_h,
+             canvas_w);
+  EDET_CHECK((int64_t)canvas_h * canvas_w * 3 < (int64_t)1 << 31, "edet_randaug_stats_canvas: canvas %d x %d too large", canvas_h,
+             canvas_w);
+  edet_launch(k_randaug_stats_canvas, dim3(batch), dim3(THREADS), 0, to_stream(stream), src, canvas_h, canvas_w, sizes_dev, ops,
+              luts);
+  EDET_LAUNCH_CHECK("edet_randaug_stats_canvas");
+  return 0;
+}
+
+extern "C" int edet_randaug_apply_canvas(const uint8_t* src, void* dst, int batch, int canvas_h, int canvas_w,
+                                         const int32_t* sizes_dev, const int32_t* ops, const int32_t* iargs, const float* fargs,
+                                         const uint8_t* luts, int out_dtype, void* stream) {
+  EDET_CHECK(src && dst && sizes_dev, "edet_randaug_apply_canvas: null pointer");
+  EDET_CHECK(!ops || (iargs && fargs && luts), "edet_randaug_apply_canvas: ops without iargs / fargs / luts");
+  EDET_CHECK((const void*)src != dst, "edet_randaug_apply_canvas: in place (the geometric operations and Sharpness read neighbours)");
+  EDET_CHECK(batch > 0 && batch <= 65535 && canvas_h > 0 && canvas_w > 0, "edet_randaug_apply_canvas: batch %d, canvas %d x %d",
+             batch, canvas_h, canvas_w);
+  EDET_CHECK((int64_t)canvas_h * canvas_w * 3 < (int64_t)1 << 31, "edet_randaug_apply_canvas: canvas %d x %d too large", canvas_h,
+             canvas_w);
+  hipStream_t st = to_stream(stream);
+  if (out_dtype == OUT_U8) launch_apply_canvas<uint8_t>(src, dst, batch, canvas_h, canvas_w, sizes_dev, ops, iargs, fargs, luts, st);
+  else if (out_dtype == EDET_F32) launch_apply_canvas<float>(src, dst, batch, canvas_h, canvas_w, sizes_dev, ops, iargs, fargs, luts, st);
+  else if (out_dtype == EDET_BF16) launch_apply_canvas<bf16_t>(src, dst, batch, canvas_h, canvas_w, sizes_dev, ops, iargs, fargs, luts, st);
+  else EDET_CHECK(false, "edet_randaug_apply_canvas: bad out_dtype %d", out_dtype);
+  EDET_LAUNCH_CHECK("edet_randaug_apply_canvas");
   return 0;
 }

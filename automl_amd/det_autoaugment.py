@@ -11,6 +11,10 @@ Mirror of the reference module's public names as far as they are built: the poli
 position of a sub-policy: the operation differs per image, chosen from device memory.  The numpy restatement the kernels are
 compared with bit for bit is tests/det_autoaug_ref.py.
 
+A canvas batch (``sizes=``, what ``jpeg.JpegDecoder.decode`` returns next to the images): image ``i`` is the top-left
+``sizes[i]`` of its slot and is distorted as that image alone would be -- its own height and width in every argument, box and
+statistic (the ``*_canvas`` entry points).  The draws do not depend on the sizes.  The kernels write inside the rectangles only.
+
 Not pinned by anything here, as for the classifier's RandAugment (automl_amd/autoaugment.py): TensorFlow Addons' rounding rule
 in the geometric image operations and float32 sine / cosine (numpy's, on the host); TensorFlow's random streams (the draws are
 numpy's); ``reduce_mean``'s summation order in Contrast for an image whose grey sum reaches 2^24 (more than 65,793 pixels) --
@@ -26,6 +30,7 @@ import torch
 
 from automl_amd import _lib
 from automl_amd import autoaugment as v2aa
+from automl_amd import utils
 from automl_amd._lib import call, ptr
 
 _MAX_LEVEL = 10.
@@ -233,13 +238,15 @@ def autoaug_args(draws, policy, h, w, magnitude=None):
   [L, B] (the reference's operation, NONE where nothing happens), ops int32 [L, B] / iargs int32 [L, B, 4] / fargs float32
   [L, B, 8] in edet_randaug_apply's layout, dargs float64 [L, B, 4] (BBox_Cutout: pad_fraction and its three draws).  An
   operation that is not applied and a layer past the end of a shorter sub-policy are the identity for image and boxes.
-  magnitude: the level of every operation of 'randaug'."""
+  magnitude: the level of every operation of 'randaug'.  h, w: two numbers, or arrays [batch] for a canvas batch: column i is
+  then what image i alone gets at its own size."""
   table = _table(policy)
   d = AutoAugDraws(*draws)
   sign = np.asarray(d.sign)
   if sign.ndim != 2:
     raise ValueError('draws must be arrays [num_layers, batch], got sign %s' % (sign.shape,))
   layers, b = sign.shape
+  hs, ws = np.broadcast_to(np.asarray(h), (b,)), np.broadcast_to(np.asarray(w), (b,))
   index = np.asarray(d.index)
   if table == 'randaug':
     if magnitude is None:
@@ -273,6 +280,7 @@ def autoaug_args(draws, policy, h, w, magnitude=None):
       idx = (k, i)
       pol[idx], ops[idx] = OP_ID[name], APPLY_ID[name]
       sg = float(sign[idx])
+      h, w = int(hs[i]), int(ws[i])
       if name == 'Rotate_BBox':
         fargs[idx][:6] = v2aa.rotate_coefficients(sg * arg[0], h, w)
       elif name == 'ShearX_BBox':
@@ -335,28 +343,39 @@ def unpack_args(buf, layout):
   return AutoAugArgs(**out)
 
 
-def apply_layers(src, out, boxes, boxes_out, counts, args, luts, scratch, stream):
+def apply_layers(src, out, boxes, boxes_out, counts, args, luts, scratch, stream, sizes=None):
   """The launches of `args.policy.shape[0]` layers on device tensors: src uint8 [B, H, W, 3] -> out uint8, boxes float32
   [B, M, 4] -> boxes_out (another buffer: the caller's boxes are not written), counts int32 [B].  args: AutoAugArgs of device
   tensors (the kernels write BBox_Cutout's rectangle into iargs and Contrast's apply id into ops); luts uint8 [B, 3, 256];
-  scratch: two uint8 buffers like src for the layers in between (the image kernel never runs in place)."""
+  scratch: two uint8 buffers like src for the layers in between (the image kernel never runs in place).  sizes: int32 [B, 2]
+  on the device for a canvas batch (args made from the same sizes): out and scratch are then written inside each image's
+  rectangle only."""
   b, h, w, m = int(src.shape[0]), int(src.shape[1]), int(src.shape[2]), int(boxes.shape[1])
   layers = int(args.policy.shape[0])
   cur, bcur = src, boxes
   for k in range(layers):
     dst = out if k == layers - 1 else scratch[k % 2]
-    call('edet_autoaug_boxes', ptr(bcur), ptr(boxes_out), ptr(counts), b, m, h, w, ptr(args.policy[k]), ptr(args.iargs[k]),
-         ptr(args.fargs[k]), ptr(args.dargs[k]), stream, nbytes=2 * bcur.numel() * 4)
-    call('edet_randaug_stats', ptr(cur), b, h, w, ptr(args.ops[k]), ptr(luts), stream, nbytes=cur.numel())
-    call('edet_autoaug_contrast_lut', ptr(cur), b, h, w, ptr(args.policy[k]), ptr(args.ops[k]), ptr(args.fargs[k]), ptr(luts),
-         stream, nbytes=cur.numel())
-    call('edet_randaug_apply', ptr(cur), ptr(dst), b, h, w, ptr(args.ops[k]), ptr(args.iargs[k]), ptr(args.fargs[k]), ptr(luts),
-         _lib.EDET_U8, stream, nbytes=2 * cur.numel())
+    if sizes is None:
+      call('edet_autoaug_boxes', ptr(bcur), ptr(boxes_out), ptr(counts), b, m, h, w, ptr(args.policy[k]), ptr(args.iargs[k]),
+           ptr(args.fargs[k]), ptr(args.dargs[k]), stream, nbytes=2 * bcur.numel() * 4)
+      call('edet_randaug_stats', ptr(cur), b, h, w, ptr(args.ops[k]), ptr(luts), stream, nbytes=cur.numel())
+      call('edet_autoaug_contrast_lut', ptr(cur), b, h, w, ptr(args.policy[k]), ptr(args.ops[k]), ptr(args.fargs[k]), ptr(luts),
+           stream, nbytes=cur.numel())
+      call('edet_randaug_apply', ptr(cur), ptr(dst), b, h, w, ptr(args.ops[k]), ptr(args.iargs[k]), ptr(args.fargs[k]), ptr(luts),
+           _lib.EDET_U8, stream, nbytes=2 * cur.numel())
+    else:
+      call('edet_autoaug_boxes_canvas', ptr(bcur), ptr(boxes_out), ptr(counts), b, m, ptr(sizes), ptr(args.policy[k]),
+           ptr(args.iargs[k]), ptr(args.fargs[k]), ptr(args.dargs[k]), stream, nbytes=2 * bcur.numel() * 4)
+      call('edet_randaug_stats_canvas', ptr(cur), b, h, w, ptr(sizes), ptr(args.ops[k]), ptr(luts), stream, nbytes=cur.numel())
+      call('edet_autoaug_contrast_lut_canvas', ptr(cur), b, h, w, ptr(sizes), ptr(args.policy[k]), ptr(args.ops[k]),
+           ptr(args.fargs[k]), ptr(luts), stream, nbytes=cur.numel())
+      call('edet_randaug_apply_canvas', ptr(cur), ptr(dst), b, h, w, ptr(sizes), ptr(args.ops[k]), ptr(args.iargs[k]),
+           ptr(args.fargs[k]), ptr(luts), _lib.EDET_U8, stream, nbytes=2 * cur.numel())
     cur, bcur = dst, boxes_out
   return out, boxes_out
 
 
-def _distort(images_u8, boxes, counts, policy, num_layers, magnitude, rng, draws):
+def _distort(images_u8, boxes, counts, policy, num_layers, magnitude, rng, draws, sizes=None):
   x = torch.from_numpy(images_u8) if isinstance(images_u8, np.ndarray) else images_u8
   if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3:
     raise ValueError('images must be uint8 [batch, height, width, 3], got %s %s' % (x.dtype, tuple(x.shape)))
@@ -364,6 +383,9 @@ def _distort(images_u8, boxes, counts, policy, num_layers, magnitude, rng, draws
   bx = torch.as_tensor(boxes, dtype=torch.float32)
   if bx.dim() != 3 or bx.shape[0] != b or bx.shape[2] != 4 or bx.shape[1] < 1:
     raise ValueError('boxes must be float32 [batch, max_boxes >= 1, 4], got %s' % (tuple(bx.shape),))
+  if sizes is not None:      # (checked before the generator moves)
+    sizes = utils.canvas_sizes(sizes, b, h, w)
+    h, w = sizes[:, 0], sizes[:, 1]
   x = x.to('cuda').contiguous()
   bx = bx.to(x.device).contiguous()
   cn = torch.as_tensor(counts).to(x.device).to(torch.int32).reshape(b).contiguous()
@@ -376,25 +398,29 @@ def _distort(images_u8, boxes, counts, policy, num_layers, magnitude, rng, draws
   if layout['policy'][1] != (layers, b):
     raise ValueError('draws are for %s, want [num_layers, batch] = %s' % (layout['policy'][1], (layers, b)))
   args = unpack_args(torch.from_numpy(host).to(x.device), layout)
-  out, boxes_out = torch.empty_like(x), torch.empty_like(bx)
+  out, boxes_out = (torch.empty_like(x) if sizes is None else torch.zeros_like(x)), torch.empty_like(bx)
   luts = torch.zeros((b, 3, 256), dtype=torch.uint8, device=x.device)
   scratch = [torch.empty_like(x) for _ in range(min(layers - 1, 2))]
-  return apply_layers(x, out, bx, boxes_out, cn, args, luts, scratch, torch.cuda.current_stream().cuda_stream)
+  return apply_layers(x, out, bx, boxes_out, cn, args, luts, scratch, torch.cuda.current_stream().cuda_stream,
+                      None if sizes is None else torch.from_numpy(sizes).to(x.device))
 
 
-def distort_image_with_autoaugment(images_u8, boxes, counts, augmentation_name, rng=None, draws=None):
+def distort_image_with_autoaugment(images_u8, boxes, counts, augmentation_name, rng=None, draws=None, sizes=None):
   """:1592-1629 for a batch on the device: images_u8 uint8 [B, H, W, 3], boxes float32 [B, M, 4] padded and normalised (ymin,
   xmin, ymax, xmax), counts [B] valid rows (numpy or torch) -> (images uint8, boxes) device tensors; rows at or past
-  counts[i] pass through.  draws: autoaug_draws' tuple, else drawn from `rng` (a numpy Generator; default: a fresh one)."""
+  counts[i] pass through.  draws: autoaug_draws' tuple, else drawn from `rng` (a numpy Generator; default: a fresh one).
+  sizes: [B, 2] (height, width) of each image on the canvas [H, W] -- host data (utils.canvas_sizes; a device tensor is copied
+  to the host, which waits for the device), checked before the generator moves; the images come back zero outside their
+  rectangles."""
   if augmentation_name == 'randaug':
     raise ValueError("Invalid augmentation_name: randaug ('randaug' is distort_image_with_randaugment's)")
-  return _distort(images_u8, boxes, counts, available_policy(augmentation_name), 0, None, rng, draws)
+  return _distort(images_u8, boxes, counts, available_policy(augmentation_name), 0, None, rng, draws, sizes)
 
 
-def distort_image_with_randaugment(images_u8, boxes, counts, num_layers, magnitude, rng=None, draws=None):
+def distort_image_with_randaugment(images_u8, boxes, counts, num_layers, magnitude, rng=None, draws=None, sizes=None):
   """:1632-1667 for a batch on the device; arguments and results as distort_image_with_autoaugment's."""
   if int(num_layers) < 0:
     raise ValueError('num_layers %r must be >= 0' % (num_layers,))
   for name in RANDAUG_OPS:
     level_to_arg(name, magnitude)      # raises for a magnitude no operation could take
-  return _distort(images_u8, boxes, counts, 'randaug', int(num_layers), float(magnitude), rng, draws)
+  return _distort(images_u8, boxes, counts, 'randaug', int(num_layers), float(magnitude), rng, draws, sizes)

@@ -39,7 +39,9 @@ def eval_config(config):
 def evaluate(model, batches, evaluator=None, eval_samples=None, max_batches=None):
   """model: an EfficientDetNet, or an EfficientDetNetTrain -- then its CURRENT variables are evaluated, not the EMA shadows.
   batches: an iterable of (raw_images uint8 [B, H, W, 3], boxes [B, M, 4] normalised, classes [B, M], counts [B], is_crowds
-  [B, M], areas [B, M], source_ids [B]); the batch size may change, a smaller last batch is evaluated.  evaluator: default
+  [B, M], areas [B, M], source_ids [B]); the batch size may change, a smaller last batch is evaluated.  raw_images may be the
+  pair (raw, sizes) of a canvas batch, as jpeg.JpegDecoder.decode returns it (sizes [B, 2] host data): every image is then
+  evaluated at its own size, and one input stage serves every batch on the same canvas.  evaluator: default
   EvaluationMetric(filename=config.val_json_file, label_map=config.label_map); it is NOT reset here.  eval_samples: stop
   after ceil(eval_samples / batch) batches, the batch size being the first batch's (eval.py:104-105); max_batches: a plain
   bound on the batches (COCOCallback's take(count)).
@@ -54,6 +56,7 @@ def evaluate(model, batches, evaluator=None, eval_samples=None, max_batches=None
   limit = max_batches
   for n, batch in enumerate(batches):
     raw, boxes, classes, counts, is_crowds, areas, source_ids = batch
+    raw, sizes = det_input.split_raw(raw)
     raw, boxes = torch.as_tensor(raw), torch.as_tensor(boxes)
     b, m = int(raw.shape[0]), int(boxes.shape[1])
     if n == 0 and eval_samples:
@@ -67,7 +70,7 @@ def evaluate(model, batches, evaluator=None, eval_samples=None, max_batches=None
     if inp is None:
       inp = stages[key] = det_input.DetectionEvalInput(config, model.anchors((h, w)), b, key[1], key[2], m, dtype=eng.tdtype,
                                                        device=eng.device)
-    images, labels = inp.run(raw, boxes, classes, counts, is_crowds, areas, source_ids, *inp.own_buffers())
+    images, labels = inp.run(raw, boxes, classes, counts, is_crowds, areas, source_ids, *inp.own_buffers(), sizes=sizes)
     cls_outputs, box_outputs = efficientdet_net.EfficientDetNet.__call__(model, images, False)      # no pre / post-processing
     if hasattr(model, 'train_step'):
       eng._cast_version = -1      # a training step that follows (perhaps the captured one) makes its compute copies again

@@ -84,18 +84,25 @@ class DetectionInputProcessor(object):
   first result is asked for.  The random draws come from `rng` (numpy Generator) or are handed in (`draws=`), which is
   how the tests feed the values the reference's fixtures were made with -- TensorFlow's RNG stream cannot be
   reproduced.  boxes [B, max_boxes, 4] normalised (ymin, xmin, ymax, xmax), classes [B, max_boxes] (or [.., 1]), counts
-  [B] valid rows per image (None: all rows)."""
+  [B] valid rows per image (None: all rows).
 
-  def __init__(self, images, output_size, boxes=None, classes=None, counts=None, rng=None, dtype=torch.float32):
+  sizes [B, 2] makes `images` a CANVAS batch, what jpeg.JpegDecoder.decode returns: image i is the top-left sizes[i] =
+  (height, width) of its slot and is processed as that image alone would be (edet_preprocess_train_canvas) -- the scale
+  factors come from its own size, so image_scale and image_scale_to_original differ per image.  Sizes are host data
+  (utils.canvas_sizes: a device tensor is copied to the host, which waits for the device) and are checked here, before any
+  draw."""
+
+  def __init__(self, images, output_size, boxes=None, classes=None, counts=None, rng=None, dtype=torch.float32, sizes=None):
     if images.dim() != 4 or images.shape[-1] != 3:
       raise ValueError('raw images must be [batch, height, width, 3], got %s' % (tuple(images.shape),))
     if dtype not in (torch.float32, torch.bfloat16):
       raise ValueError('dtype must be float32 or bfloat16')
     if images.dtype not in (torch.uint8, torch.float32):
       images = images.to(torch.float32)
+    self._batch, self._height, self._width = (int(v) for v in images.shape[:3])
+    self._sizes = None if sizes is None else utils.canvas_sizes(sizes, self._batch, self._height, self._width)
     self._raw = images.cuda().contiguous()
     self._output_size = utils.parse_image_size(output_size)
-    self._batch, self._height, self._width = (int(v) for v in self._raw.shape[:3])
     self._dtype = dtype
     self._rng = rng if rng is not None else np.random.default_rng()
     self._mean = self._std = None
@@ -123,6 +130,10 @@ class DetectionInputProcessor(object):
     self._mean = np.broadcast_to(np.asarray(mean_rgb, np.float32).reshape(-1), (3,)).copy()
     self._std = np.broadcast_to(np.asarray(stddev_rgb, np.float32).reshape(-1), (3,)).copy()
 
+  def _size(self, i):
+    """(height, width) of image i: its own on a canvas batch."""
+    return (self._height, self._width) if self._sizes is None else (int(self._sizes[i, 0]), int(self._sizes[i, 1]))
+
   def _uniform(self, draws, count):
     if draws is None:
       return self._rng.random((self._batch, count)).astype(np.float32)
@@ -141,15 +152,14 @@ class DetectionInputProcessor(object):
     u = self._uniform(draws, 3)
     for i in range(self._batch):
       self._image_scale[i], self._scaled[i], self._offset[i] = training_scale_factors(
-          u[i], scale_min, scale_max, target, self._output_size, self._height, self._width)
+          u[i], scale_min, scale_max, target, self._output_size, *self._size(i))
     self._scales_set = True
     self._result = None
 
   def set_scale_factors_to_output_size(self):
     """dataloader.py:113-124 (evaluation: the whole image into the top-left corner, no offset)."""
-    scale, scaled = output_size_scale_factors(self._output_size, self._height, self._width)
-    self._image_scale[:] = scale
-    self._scaled[:] = scaled
+    for i in range(self._batch):
+      self._image_scale[i], self._scaled[i] = output_size_scale_factors(self._output_size, *self._size(i))
     self._offset[:] = 0
     self._scales_set = True
     self._result = None
@@ -174,12 +184,16 @@ class DetectionInputProcessor(object):
       co = torch.empty_like(self._classes)
       cnt = torch.empty_like(self._counts)
     p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-    _lib.call('edet_preprocess_train', self._raw.data_ptr(), 1 if self._raw.dtype == torch.float32 else 0, b,
-              self._height, self._width, oh, ow, mean, std, per_dev.data_ptr(), out.data_ptr(), p(self._boxes),
-              p(self._classes), p(self._counts), m, p(bo), p(co), p(cnt),
-              _lib.EDET_BF16 if self._dtype == torch.bfloat16 else _lib.EDET_F32,
-              torch.cuda.current_stream().cuda_stream)
-    self._keep_alive = per_dev
+    sizes_dev = None if self._sizes is None else torch.from_numpy(self._sizes).to(self._raw.device)
+    tail = (oh, ow, mean, std, per_dev.data_ptr(), out.data_ptr(), p(self._boxes), p(self._classes), p(self._counts), m, p(bo),
+            p(co), p(cnt), _lib.EDET_BF16 if self._dtype == torch.bfloat16 else _lib.EDET_F32,
+            torch.cuda.current_stream().cuda_stream)
+    head = (self._raw.data_ptr(), 1 if self._raw.dtype == torch.float32 else 0, b, self._height, self._width)
+    if sizes_dev is None:
+      _lib.call('edet_preprocess_train', *head, *tail)
+    else:
+      _lib.call('edet_preprocess_train_canvas', *head, sizes_dev.data_ptr(), *tail)
+    self._keep_alive = (per_dev, sizes_dev)
     self._result = (out, bo, co, cnt)
     return self._result
 

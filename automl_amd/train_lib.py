@@ -461,7 +461,10 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
 
   def _raw_input(self, raw, boxes, training):
     """What train_step_raw and test_step_raw open with: the raw batch checked on the host -> (engine, the input stage of this
-    shape: det_input.DetectionInput / DetectionEvalInput, built when the shape, the dtype or the AutoAugment switch moved)."""
+    shape: det_input.DetectionInput / DetectionEvalInput, built when the shape, the dtype or the AutoAugment switch moved,
+    raw images, sizes checked or None).  raw: the images, or the pair (images, sizes) of a canvas batch -- the stage is then
+    keyed on the canvas and serves every batch on it."""
+    raw, sizes = det_input.split_raw(raw)
     raw = torch.as_tensor(raw)
     if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
       raise ValueError('raw images must be uint8 [batch, height, width, 3], got %s %s' % (raw.dtype, tuple(raw.shape)))
@@ -482,7 +485,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
       stage = det_input.DetectionInput if training else det_input.DetectionEvalInput
       cached = (key, stage(c, self.anchors((h, w)), b, rh, rw, m, dtype=eng.tdtype, device=eng.device, **extra))
       setattr(self, attr, cached)
-    return eng, cached[1]
+    return eng, cached[1], raw, cached[1].check_sizes(sizes)
 
   def train_step_raw(self, data, sync_loss=True, draws=None):
     """One training step from a raw batch: data = (raw_images uint8 [B, H, W, 3], boxes float32 [B, M, 4] normalised (ymin,
@@ -500,18 +503,24 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     The box-aware AutoAugment / RandAugment of aug/autoaugment.py (dataloader.py:312-319) runs between GridMask and the crop
     once set_autoaugment(policy) has switched it on ('randaug', 'v2', 'v3', 'test'; 'v0', 'v1' and the *_Only_BBoxes
     operations are not built); its draws then follow the others in the same generator, or come as the fourth field of
-    det_input.Draws (det_autoaugment.autoaug_draws).  The config key autoaugment_policy itself is still refused."""
+    det_input.Draws (det_autoaugment.autoaug_draws).  The config key autoaugment_policy itself is still refused.
+
+    A canvas batch: raw_images = (raw uint8 [B, Hc, Wc, 3], sizes int32 [B, 2]) as jpeg.JpegDecoder.decode returns it -- image
+    i is the top-left sizes[i] = (height, width) of its slot and goes through every launch at its own size, as the reference
+    processes it (dataloader.py:301-353; det_input.py "A canvas batch").  One stage serves every batch on the same canvas.
+    Sizes are host data: a numpy array or a CPU tensor; a device tensor is copied to the host once, and that copy waits for
+    the device.  They are checked before the generator moves; with sizes GridMask's gridblock draw is a stream of its own."""
     c = self.config
     if getattr(c, 'autoaugment_policy', None):
       raise ValueError('autoaugment_policy=%r is not built (the box-aware AutoAugment / RandAugment of aug/autoaugment.py, '
                        'dataloader.py:312-319); train_step_raw would have to ignore it -- the part that is built is switched '
                        'on with set_autoaugment(policy)' % (c.autoaugment_policy,))
     raw, boxes, classes, counts = data
-    eng, inp = self._raw_input(raw, boxes, training=True)
+    eng, inp, raw, sizes = self._raw_input(raw, boxes, training=True)
     if draws is None:
       if self._input_rng is None:
         self._input_rng = det_input.input_rng(self._seed)
-      draws = inp.draw(self._input_rng)
+      draws = inp.draw(self._input_rng, sizes)
     g = self._graph
     if self.use_graph and g is not None and g['engine'] is eng:
       images, labels = g['images'], g['labels']
@@ -519,7 +528,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
       images, labels = inp.own_buffers()
       if self.use_graph:      # they become the captured step's static buffers
         self._graph = self._new_graph_state(eng, images, labels)
-    inp.run(raw, boxes, classes, counts, draws, images, labels)
+    inp.run(raw, boxes, classes, counts, draws, images, labels, sizes=sizes)
     return self.train_step((images, labels), sync_loss=sync_loss)
 
   def train_step(self, data, sync_loss=True):
@@ -630,9 +639,10 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     (det_input.DetectionEvalInput: no draws, no GridMask, no AutoAugment) runs on the device in front of the pass, straight
     into the captured pass's static buffers.  -> (loss values, labels): labels also holds 'source_ids', 'image_scales' and
     'groundtruth_data', so a caller can go on to detections without a second input pass (the buffers are reused by the next
-    call)."""
+    call).  raw_images may be the pair (raw, sizes) of a canvas batch, as train_step_raw takes it: 'image_scales' and the
+    ground truth are then each image's own."""
     raw, boxes, classes, counts, is_crowds, areas, source_ids = data
-    eng, inp = self._raw_input(raw, boxes, training=False)
+    eng, inp, raw, sizes = self._raw_input(raw, boxes, training=False)
     if self.use_graph:
       g = self._eval_graph_state(eng, inp.own_buffers)
       images, labels = g['images'], g['labels']
@@ -641,7 +651,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
           labels[k] = torch.empty(shape, dtype=dt, device=eng.device)
     else:
       images, labels = inp.own_buffers()
-    inp.run(raw, boxes, classes, counts, is_crowds, areas, source_ids, images, labels)
+    inp.run(raw, boxes, classes, counts, is_crowds, areas, source_ids, images, labels, sizes=sizes)
     self._eval_pass(eng, images, labels)
     return (eng.eval_loss_values() if sync_loss else {}), labels
 

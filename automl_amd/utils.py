@@ -50,3 +50,22 @@ def unpack_rng_state(rng, words):
   v = [int(x) for x in np.asarray(words, dtype=np.uint64)]
   rng.bit_generator.state = {'bit_generator': 'PCG64', 'state': {'state': v[0] | (v[1] << 64), 'inc': v[2] | (v[3] << 64)},
                              'has_uint32': v[4], 'uinteger': v[5]}
+
+
+def canvas_sizes(sizes, batch, canvas_h, canvas_w):
+  """The (height, width) of every image of a canvas batch [batch, canvas_h, canvas_w, 3] -- image i is the top-left
+  sizes[i] of its slot, as jpeg.JpegDecoder.decode returns them -- checked -> int32 numpy [batch, 2].  Sizes are HOST data: a
+  numpy array, a list or a CPU tensor; a device tensor is copied to the host once, and that copy waits for the device.  A
+  wrong shape or a size outside [1, canvas] raises a ValueError that names the image."""
+  if hasattr(sizes, 'detach'):      # a torch tensor
+    sizes = sizes.detach().cpu().numpy()
+  s = np.asarray(sizes)
+  if s.shape != (int(batch), 2) or s.dtype.kind not in 'iu':
+    raise ValueError('sizes must be integers [batch, 2] = (height, width) per image, batch %d, got %s %s'
+                     % (batch, s.dtype, s.shape))
+  bad = np.flatnonzero((s[:, 0] < 1) | (s[:, 0] > int(canvas_h)) | (s[:, 1] < 1) | (s[:, 1] > int(canvas_w)))
+  if bad.size:
+    i = int(bad[0])
+    raise ValueError('image %d: size %d x %d is outside [1, canvas] of the %d x %d canvas'
+                     % (i, int(s[i, 0]), int(s[i, 1]), canvas_h, canvas_w))
+  return np.ascontiguousarray(s, dtype=np.int32)

@@ -510,6 +510,21 @@ int edet_mix_labels(const int32_t* labels, int batch, int num_classes, int heigh
 int edet_randaug_stats(const uint8_t* src, int batch, int height, int width, const int32_t* ops, uint8_t* luts, void* stream);
 int edet_randaug_apply(const uint8_t* src, void* dst, int batch, int height, int width, const int32_t* ops,
                        const int32_t* iargs, const float* fargs, const uint8_t* luts, int out_dtype, void* stream);
+/* The same two on a CANVAS batch: src (and dst, in its own element type) [batch][canvas_h][canvas_w][3]; image b is the
+ * top-left sizes_dev[b] = {height, width} of its slot (int32 [batch][2], DEVICE memory), its row pitch canvas_w.  Every
+ * height, width and pixel count above is then the image's own: the in-image test and the 128 fill of the geometric
+ * operations, Sharpness' border, Cutout's clamps, Contrast's H W / 256, Equalize's step; the histograms count the image's
+ * pixels only.  Image b inside its rectangle is what the dense call gives for that image alone, bit for bit.  The sizes
+ * are clamped in the kernel, height into [1, canvas_h] and width into [1, canvas_w], so no row can send an access outside
+ * its slot.  Nothing outside the rectangle is read; dst is written INSIDE the rectangle only, the rest of its slot is left as
+ * it was (nothing downstream reads it).  The grid is sized from the canvas.  The four-pixel path is chosen per image: where
+ * width % 4 == 0, canvas_w % 4 == 0 and src / dst are 16-byte aligned; the byte path otherwise.
+ * batch <= 65535, canvas_h * canvas_w * 3 < 2^31. */
+int edet_randaug_stats_canvas(const uint8_t* src, int batch, int canvas_h, int canvas_w, const int32_t* sizes_dev,
+                              const int32_t* ops, uint8_t* luts, void* stream);
+int edet_randaug_apply_canvas(const uint8_t* src, void* dst, int batch, int canvas_h, int canvas_w, const int32_t* sizes_dev,
+                              const int32_t* ops, const int32_t* iargs, const float* fargs, const uint8_t* luts, int out_dtype,
+                              void* stream);
 
 /* ---- crop, resize and flip of decoded images (efficientnetv2/preprocessing.py:22-70) ----
  * raw uint8 [batch][canvas_h][canvas_w][3]; image b occupies the top-left height x width of its canvas.  Per image:
@@ -686,6 +701,16 @@ int edet_preprocess_train(const void* raw_images, int raw_is_float, int batch, i
                           const edet_prep_image_t* per_image_dev, void* out, const float* boxes_in,
                           const float* classes_in, const int* counts_in, int max_boxes, float* boxes_out,
                           float* classes_out, int* counts_out, int dtype, void* stream);
+/* The same on a CANVAS batch: raw_images [batch][canvas_h][canvas_w][3]; image b is the top-left sizes_dev[b] = {height,
+ * width} of its slot (int32 [batch][2], DEVICE memory, clamped in the kernel into [1, canvas_h] x [1, canvas_w]), its row
+ * pitch canvas_w.  The resize ratio, the tap clamps and the mirrored tap width - 1 - x use the image's own size, so nothing
+ * outside the image is read; the per-image rows are the caller's, made from that size.  out is written whole, as above:
+ * image b is what the dense call gives for that image alone, bit for bit. */
+int edet_preprocess_train_canvas(const void* raw_images, int raw_is_float, int batch, int canvas_h, int canvas_w,
+                                 const int32_t* sizes_dev, int out_height, int out_width, const float* mean_rgb,
+                                 const float* stddev_rgb, const edet_prep_image_t* per_image_dev, void* out,
+                                 const float* boxes_in, const float* classes_in, const int* counts_in, int max_boxes,
+                                 float* boxes_out, float* classes_out, int* counts_out, int dtype, void* stream);
 
 /* ---- ground truth of an evaluation batch (dataloader.py:344-353, :389) ----------------------------------------------------
  * boxes [batch][max_boxes][4], classes [batch][max_boxes], kept_counts [batch]: what edet_preprocess_train leaves (the kept
@@ -725,6 +750,14 @@ typedef struct edet_gridmask_image { /* 48 bytes, one per image, read from DEVIC
 } edet_gridmask_image_t;
 int edet_gridmask(const uint8_t* src, uint8_t* dst, int batch, int height, int width,
                   const edet_gridmask_image_t* per_image_dev, void* stream);
+/* The same on a CANVAS batch: src, dst [batch][canvas_h][canvas_w][3]; image b is the top-left sizes_dev[b] = {height,
+ * width} of its slot (int32 [batch][2], DEVICE memory, clamped in the kernel into [1, canvas_h] x [1, canvas_w]), its row
+ * pitch canvas_w.  The crop corner (S - height) / 2, (S - width) / 2 is the image's own (S is per row already).  Nothing
+ * outside the rectangle is read and dst is written INSIDE it only: the rest of a dst slot is left as it was (nothing
+ * downstream reads it).  The grid is sized from the canvas; the dword path is chosen per image, where width % 4 == 0,
+ * canvas_w % 4 == 0 and src / dst are 16-byte aligned.  batch <= 65535, canvas_h * canvas_w * 3 < 2^31. */
+int edet_gridmask_canvas(const uint8_t* src, uint8_t* dst, int batch, int canvas_h, int canvas_w, const int32_t* sizes_dev,
+                         const edet_gridmask_image_t* per_image_dev, void* stream);
 
 /* ---- box-aware AutoAugment / RandAugment of the detector's input (efficientdet/aug/autoaugment.py) ----------------------
  * The image operations are edet_randaug_stats / edet_randaug_apply above; the two calls here make the boxes follow and write
@@ -752,6 +785,15 @@ int edet_autoaug_boxes(const float* boxes, float* boxes_out, const int32_t* coun
                        int width, const int32_t* policy, int32_t* iargs, const float* fargs, const double* dargs, void* stream);
 int edet_autoaug_contrast_lut(const uint8_t* src, int batch, int height, int width, const int32_t* policy, int32_t* ops,
                               const float* fargs, uint8_t* luts, void* stream);
+/* The same two on a CANVAS batch (edet_randaug_stats_canvas above): H and W of the box arithmetic, BBox_Cutout's rectangle
+ * and the divisor of Contrast's mean are sizes_dev[b] = {height, width} (int32 [batch][2], DEVICE memory).  The boxes are
+ * normalised, so edet_autoaug_boxes_canvas needs no canvas: it clamps a size into [1, 2^24 - 1], what the dense call accepts.
+ * edet_autoaug_contrast_lut_canvas clamps into [1, canvas_h] x [1, canvas_w] and sums the image's own pixels only. */
+int edet_autoaug_boxes_canvas(const float* boxes, float* boxes_out, const int32_t* counts, int batch, int max_boxes,
+                              const int32_t* sizes_dev, const int32_t* policy, int32_t* iargs, const float* fargs,
+                              const double* dargs, void* stream);
+int edet_autoaug_contrast_lut_canvas(const uint8_t* src, int batch, int canvas_h, int canvas_w, const int32_t* sizes_dev,
+                                     const int32_t* policy, int32_t* ops, const float* fargs, uint8_t* luts, void* stream);
 
 /* ---- COCO box AP / AR of an evaluator state (efficientdet/coco_metric.py; COCOeval for iouType 'bbox') ----------------------
  * The images of the state in ascending image id, padded: dets fp32 [n_images][max_dets][6] rows {x, y, width, height, score,
