@@ -6,6 +6,7 @@
 // :493-604 (_detection_loss), :486-491 (_reg_l2_loss), :675-683 (clip + apply), :176-199 (optimizer).
 #include "rowmap_impl.h"
 
+#include <cfloat>
 #include <type_traits>
 
 namespace {
@@ -16,7 +17,7 @@ static_assert(THREADS == ROW_THREADS, "the row map is laid out for this workgrou
 // logits [positions][ld], channel j = anchor * num_classes + class.
 // Per element (train_lib.py:357-406 with label_smoothing 0): u = +-x, 1 - p_t = sigmoid(u),
 // ce = softplus(u); loss = alpha_t * sigmoid(u)^gamma * softplus(u) / normalizer.  One exp, one rcp,
-// one log and one sqrt (gamma = 1.5) or exp2/log2 pair (general gamma) per logit; the anchor index is
+// one log and one sqrt (gamma = 1.5) or one pow (general gamma; pow(0, 0) = 1) per logit; the anchor index is
 // advanced incrementally along the 8-wide chunk, so there is one integer division per 16 bytes.
 // LS: label smoothing (tf2/train_lib.py:400-402): the cross entropy is taken against y*(1-ls) + ls/2 while alpha and the
 // modulating factor keep the hard label.  With u = -x for the positive class and x otherwise, ce_smoothed = softplus(u) -
@@ -566,6 +567,9 @@ inline void focal_dispatch(int dtype, bool g15, bool ls, F&& f) {
   (void)dtype_dispatch(dtype, by_flags);
 }
 
+// the hyper-parameters every focal entry point accepts: alpha in [0, 1], gamma finite and >= 0 (a NaN fails both)
+inline bool focal_args_ok(float alpha, float gamma) { return alpha >= 0.f && alpha <= 1.f && gamma >= 0.f && gamma <= FLT_MAX; }
+
 }  // namespace
 
 extern "C" int edet_focal_loss_smooth(const void* logits, int ld, const int32_t* cls_targets,
@@ -580,6 +584,8 @@ extern "C" int edet_focal_loss_smooth(const void* logits, int ld, const int32_t*
   EDET_CHECK(num_anchors >= 1 && positions >= 0, "edet_focal_loss: bad shape");
   EDET_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "edet_focal_loss: label_smoothing %g outside [0, 1]", (double)label_smoothing);
   EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_focal_loss: bad dtype %d", dtype);
+  EDET_CHECK(focal_args_ok(alpha, gamma), "edet_focal_loss: alpha %g outside [0, 1] or gamma %g negative or not finite", (double)alpha, (double)gamma);
+  if (positions == 0) return 0;      // nothing to add: sums, dbias and dlogits stay as they are
   const bool g15 = gamma == 1.5f;
   const float half_ls = 0.5f * label_smoothing;
   const int nch = num_anchors * num_classes;
@@ -614,8 +620,10 @@ extern "C" int edet_box_loss(const void* box_out, int ld, const float* box_targe
                              float grad_scale, const float* norm_scale_dev, void* dbox, float* dbias,
                              float* sums, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
   EDET_CHECK(box_out && box_targets && dbox && sums, "edet_box_loss: null pointer");
-  EDET_CHECK(ld % 8 == 0 && ld >= nch && ld <= 2048, "edet_box_loss: bad ld %d", ld);
+  EDET_CHECK(ld % 8 == 0 && nch >= 1 && ld >= nch && ld <= 2048 && positions >= 0, "edet_box_loss: bad ld %d", ld);
   EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_box_loss: bad dtype %d", dtype);
+  EDET_CHECK(delta > 0.f && delta <= FLT_MAX, "edet_box_loss: delta %g must be positive and finite", (double)delta);
+  if (positions == 0) return 0;      // nothing to add: sums, dbias and dbox stay as they are
   const LossGrid L = loss_grid(ld, positions, nch, BOX_GRID_CAP, workspace, workspace_bytes);
   if (dtype == EDET_BF16)
     edet_launch(k_box<bf16_t>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const bf16_t*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, grad_scale, norm_scale_dev, (bf16_t*)dbox, dbias, sums, L.part, L.m);
@@ -639,6 +647,8 @@ extern "C" int edet_focal_loss_eval(const void* logits, int ld, const int32_t* c
   EDET_CHECK(num_classes >= 1 && num_anchors >= 1 && positions >= 0, "edet_focal_loss_eval: bad shape");
   EDET_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "edet_focal_loss_eval: label_smoothing %g outside [0, 1]", (double)label_smoothing);
   EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_focal_loss_eval: bad dtype %d", dtype);
+  EDET_CHECK(focal_args_ok(alpha, gamma), "edet_focal_loss_eval: alpha %g outside [0, 1] or gamma %g negative or not finite", (double)alpha, (double)gamma);
+  if (positions == 0) return 0;
   const bool g15 = gamma == 1.5f;
   const float half_ls = 0.5f * label_smoothing;
   const LossGrid L = loss_grid(ld, positions, num_anchors * num_classes, focal_grid_cap(dtype, g15), workspace, workspace_bytes);
@@ -659,6 +669,8 @@ extern "C" int edet_box_loss_eval(const void* box_out, int ld, const float* box_
   EDET_CHECK(box_out && box_targets && sums, "edet_box_loss_eval: null pointer");
   EDET_CHECK(ld % 8 == 0 && nch >= 1 && ld >= nch && ld <= 2048 && positions >= 0, "edet_box_loss_eval: bad ld %d", ld);
   EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_box_loss_eval: bad dtype %d", dtype);
+  EDET_CHECK(delta > 0.f && delta <= FLT_MAX, "edet_box_loss_eval: delta %g must be positive and finite", (double)delta);
+  if (positions == 0) return 0;
   const LossGrid L = loss_grid(ld, positions, nch, BOX_GRID_CAP, workspace, workspace_bytes);
   if (dtype == EDET_BF16)
     edet_launch(k_box_eval<bf16_t>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const bf16_t*)box_out, ld, box_targets, positions, nch, delta, inv_normalizer, norm_scale_dev, sums, L.part, L.m);

@@ -396,7 +396,13 @@ int edet_fuse_weights_bwd(const float* w0, const float* w1, const float* w2, int
  * (sum(mean_num_positives) + 1, train_lib.py:517).
  * workspace: caller-owned device scratch for the per-workgroup partial rows (loss sum + bias gradient), added in a
  * fixed order -- the same loss and bias gradient on every run; (a few thousand rows of 1 + channels floats: 8 MiB
- * covers every EfficientDet head); NULL or too small: the kernel runs as ONE workgroup (slow, no atomics).  */
+ * covers every EfficientDet head); NULL or too small: the kernel runs as ONE workgroup (slow, no atomics).
+ * Refused (-1, nothing launched): alpha outside [0, 1], gamma negative or not finite (gamma == 1.5 has kernels of its own,
+ * every other value goes through pow; 0 is accepted: sigmoid^0 = 1 also where the sigmoid underflows to 0), label_smoothing
+ * outside [0, 1], delta <= 0 or not finite, ld no multiple of 8, below the channels or above 2048, no classes / anchors /
+ * channels, positions < 0.  positions == 0 is accepted and writes nothing.  Padding columns and the logits of ignored anchors
+ * (-2) / the box outputs of masked targets (+-0.0) are not read into the result: they may hold anything, NaN included; the
+ * padding columns of the gradient are written as zeros.  */
 int edet_focal_loss(const void* logits, int ld, const int32_t* cls_targets,
                     int64_t positions, int num_anchors, int num_classes,
                     float alpha, float gamma, float inv_normalizer, const float* norm_scale_dev,

@@ -171,10 +171,14 @@ TOWER_SD_CASE = ('efficientdet-d0', 'survival_prob=0.8', 128, 4)
 # scaling of its input: the round-4 red gate.  tests/test_train_step_conditioning.py now measures every case of this list.)
 CONV_AFTER_CASE = ('efficientdet-d0', 'conv_after_downsample=True', 128, 4)
 NO_RS_BN_CASE = ('efficientdet-d0', 'apply_bn_for_resampling=False', 128, 2)      # the resample convolutions without BatchNorm
+# the loss hyper-parameters away from their defaults, through the config and engine.py to the kernels: the general-gamma
+# instantiations of the focal kernels (k_focal_ls<float, false>), alpha, the Huber delta
+LOSS_HPARAMS_CASE = ('efficientdet-d0', 'gamma=2.0,alpha=0.4,delta=0.2,label_smoothing=0.1', 128, 2)
 
 
 TRAIN_STEP_CASES = CASES[:2] + [('efficientdet-d1', '', 192, 2), CASES[3], ('efficientdet-d7x', '', 384, 2), CASES[4],
-                                CASES[5], CASES[6], FREEZE_CASE, SMOOTH_CASE, TOWER_SD_CASE, CONV_AFTER_CASE, NO_RS_BN_CASE]
+                                CASES[5], CASES[6], FREEZE_CASE, SMOOTH_CASE, TOWER_SD_CASE, CONV_AFTER_CASE, NO_RS_BN_CASE,
+                                LOSS_HPARAMS_CASE]
 TRAIN_STEP_SEEDS = (5, 23, 29)        # variables, images, labels
 # Per-tensor gradient errors are taken relative to max(|g|_max of the tensor, GRAD_FLOOR * the largest |g| of the step).
 # 1e-3 (tests/test_oracle_conditioning.py uses the same): the tensors below it are the ones whose gradient is ZERO in exact
