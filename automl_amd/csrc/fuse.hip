@@ -33,6 +33,38 @@ struct FuseArgs {
   const float* wraw[3];
   float* wn_out;
   int method;
+  // the node's specialised loop (FUSE_*, a function of the node's shape and modes only); 0: the generic body
+  int fast;
+};
+
+// Node shapes with a specialised loop (scalar fusion weights): every input but the last is an identity, the last one the
+// exact 2x up-sample of a top-down node or the pooled input of a bottom-up node -- every BiFPN node of D0 .. D7x.
+// FUSE_ID_UP2_QUAD (backward only): the up-sampled input's gradient is wanted from this kernel, so a thread owns the 2x2
+// output pixels of one of ITS pixels.
+enum { FUSE_GENERIC = 0, FUSE_ID_UP2 = 1, FUSE_ID_ID_POOL = 2, FUSE_ID_POOL = 3, FUSE_ID_UP2_QUAD = 4 };
+// chunks per thread and trip of the specialised loops: all their loads are issued before the first is used.  Two chunks of
+// an {identity, up-sample} node are 4 (forward) to 8 (backward) 16-byte loads per lane; ONE chunk of a pooled node is
+// already 11 to 15 (nine taps), and two of them take the bf16 backward kernel from 230 to 256 VGPRs + 20 AGPRs (one wave
+// per SIMD instead of two; measured slower, as were one and four chunks for the up-sample node: LABNOTES.md)
+constexpr int FUSE_DEPTH_UP2 = 2, FUSE_DEPTH_POOL = 1;
+
+// 16 bytes (bf16) / 32 bytes (fp32) as loaded: the conversion to floats waits until every load of the trip is issued
+template <typename T> struct Raw8;
+template <> struct Raw8<bf16_t> {
+  uint4 v;
+  __device__ __forceinline__ void load(const bf16_t* p) { v = *reinterpret_cast<const uint4*>(p); }
+  __device__ __forceinline__ void get(float x[8]) const { unpack8(v, x); }
+};
+template <> struct Raw8<float> {
+  float4 a, b;
+  __device__ __forceinline__ void load(const float* p) {
+    a = *reinterpret_cast<const float4*>(p);
+    b = *reinterpret_cast<const float4*>(p + 4);
+  }
+  __device__ __forceinline__ void get(float x[8]) const {
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
+    x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+  }
 };
 
 // normalised fusion weights of one channel from the raw variables (efficientdet_keras.py:84-113): method 1 = 'sum' (ones),
@@ -137,6 +169,283 @@ __device__ __forceinline__ void sample_input(const FuseArgs& a, int i, const Vie
   }
 }
 
+// One trip of a specialised loop: UU chunks (q, q + qstride, ..) of a node with NIN - 1 identity inputs and a last input of
+// mode LAST.  Every load of the trip -- the inputs (the pooled one: nine taps at clamped addresses), dout and the old value
+// of an accumulated input gradient -- is issued first; the arithmetic that follows is the generic body's, operation by
+// operation and chunk by chunk, so outputs and the order of the sums in dw_acc are the same.
+template <typename T, bool BWD, int NIN, int LAST, int UU>
+__device__ __forceinline__ void fuse_fast_trip(const FuseArgs& a, T* __restrict__ out, const T* __restrict__ dout,
+                                               T* __restrict__ ds, unsigned char* __restrict__ pool_argmax,
+                                               const float (&wn)[3], ViewCoef (&k)[NIN], bool hoisted, uint32_t q,
+                                               uint32_t qstride, float (&dw_acc)[3]) {
+  constexpr int NID = NIN - 1, NTAP = LAST == EDET_RS_POOL ? 9 : 1;
+  const uint32_t unvec = (uint32_t)(a.c / 8), uow = (uint32_t)a.ow, uoh = (uint32_t)a.oh;
+  const edet_tview_t& vl = a.in[NID];
+  int c0[UU];
+  size_t opix[UU];
+  uint32_t inside[UU];                                 // pooled input: bit ky*3+kx set = the tap lies inside the image
+  Raw8<T> rid[UU][NID], rlast[UU][NTAP], rd[UU], rold[UU][NID];
+#pragma unroll
+  for (int u = 0; u < UU; ++u) {
+    const uint32_t qq = q + (uint32_t)u * qstride;
+    const uint32_t pix = qq / unvec;
+    c0[u] = (int)(qq - pix * unvec) * 8;
+    const uint32_t prow = pix / uow;
+    const int ox = (int)(pix - prow * uow);
+    const int n = (int)(prow / uoh);
+    const int oy = (int)(prow - (uint32_t)n * uoh);
+    opix[u] = (size_t)(n * a.oh + oy) * a.ow + ox;
+#pragma unroll
+    for (int i = 0; i < NID; ++i)
+      rid[u][i].load(reinterpret_cast<const T*>(a.in[i].data) + opix[u] * a.in[i].ld + c0[u]);
+    const T* base = reinterpret_cast<const T*>(vl.data);
+    inside[u] = 0;
+    if (LAST == EDET_RS_UP2) {
+      rlast[u][0].load(base + ((size_t)(n * vl.h + (oy >> 1)) * vl.w + (ox >> 1)) * vl.ld + c0[u]);
+    } else {
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        const int sy = oy * 2 - a.pad_t[NID] + ky;
+        const int cy = min(max(sy, 0), vl.h - 1);
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int sx = ox * 2 - a.pad_l[NID] + kx;
+          const int cx = min(max(sx, 0), vl.w - 1);
+          inside[u] |= (sy == cy && sx == cx) ? 1u << (ky * 3 + kx) : 0u;
+          rlast[u][NTAP == 9 ? ky * 3 + kx : 0].load(base + ((size_t)(n * vl.h + cy) * vl.w + cx) * vl.ld + c0[u]);
+        }
+      }
+    }
+    if (BWD) {
+      rd[u].load(dout + opix[u] * a.ldo + c0[u]);
+#pragma unroll
+      for (int i = 0; i < NID; ++i)
+        if (a.gin[i] && a.gbeta[i])
+          rold[u][i].load(reinterpret_cast<const T*>(a.gin[i]) + opix[u] * a.in[i].ld + c0[u]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < UU; ++u) {
+    if (!hoisted) {
+#pragma unroll
+      for (int i = 0; i < NIN; ++i) view_load_coef(a.in[i], c0[u], k[i]);
+    }
+    float s[8], xi[NIN][8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NID; ++i) {
+      rid[u][i].get(xi[i]);
+      affine8(a.in[i], k[i], xi[i]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] = fmaf(wn[i], xi[i][e], s[e]);
+    }
+    if (LAST == EDET_RS_UP2) {
+      rlast[u][0].get(xi[NID]);
+      affine8(vl, k[NID], xi[NID]);
+    } else {
+      // out-of-image taps: -inf after the load; the first maximum of the row-major scan wins ties, as in sample_input
+      int idx[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { xi[NID][e] = -INFINITY; idx[e] = 0; }
+#pragma unroll
+      for (int tap = 0; tap < NTAP; ++tap) {
+        float t[8];
+        rlast[u][tap].get(t);
+        affine8(vl, k[NID], t);
+        const bool in = (inside[u] >> tap) & 1u;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          t[e] = in ? t[e] : -INFINITY;
+          if (BWD) {
+            const bool gt = t[e] > xi[NID][e];
+            idx[e] = gt ? tap : idx[e];
+            xi[NID][e] = gt ? t[e] : xi[NID][e];
+          } else {
+            xi[NID][e] = fmaxf(xi[NID][e], t[e]);
+          }
+        }
+      }
+      if (BWD)
+        *reinterpret_cast<uint2*>(pool_argmax + opix[u] * a.c + c0[u]) =
+            make_uint2((uint32_t)idx[0] | ((uint32_t)idx[1] << 8) | ((uint32_t)idx[2] << 16) | ((uint32_t)idx[3] << 24),
+                       (uint32_t)idx[4] | ((uint32_t)idx[5] << 8) | ((uint32_t)idx[6] << 16) | ((uint32_t)idx[7] << 24));
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = fmaf(wn[NID], xi[NID][e], s[e]);
+    const size_t off = opix[u] * a.ldo + c0[u];
+    if (!BWD) {
+      if (a.act == EDET_ACT_SWISH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = swishf_(s[e]);
+      } else if (a.act > EDET_ACT_SWISH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = act_other_(a.act, s[e]);
+      }
+      store8<T>(out + off, s);
+    } else {
+      float d[8];
+      rd[u].get(d);
+      if (a.act == EDET_ACT_SWISH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d[e] *= swish_gradf_(s[e]);
+      } else if (a.act > EDET_ACT_SWISH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d[e] *= act_other_grad_(a.act, s[e]);
+      }
+      if (a.write_ds) store8<T>(ds + off, d);
+#pragma unroll
+      for (int i = 0; i < NID; ++i) {
+        if (a.gin[i]) {
+          // the product and the sum are rounded one after the other, as edet_fuse_bwd_input and the generic body do it
+          // (their load of the old value sits between the two; here it is in registers already and hipcc would contract)
+#pragma clang fp contract(off)
+          float g[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) g[e] = to_f<T>(from_f<T>(d[e]));
+#pragma unroll
+          for (int e = 0; e < 8; ++e) g[e] *= wn[i];
+          if (a.gbeta[i]) {
+            float old[8];
+            rold[u][i].get(old);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g[e] += old[e];
+          }
+          store8<T>(reinterpret_cast<T*>(a.gin[i]) + opix[u] * a.in[i].ld + c0[u], g);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NIN; ++i)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dw_acc[i] = fmaf(d[e], xi[i][e], dw_acc[i]);
+    }
+  }
+}
+
+// The grid-stride loop of one node shape: FUSE_DEPTH chunks per trip while the thread has that many left, then one at a
+// time -- the thread owns the chunks q0, q0 + qstride, .. of the generic loop and visits them in the same order.  The
+// views' scale and shift are loaded once when the thread's channel chunk is the same on every trip.
+template <typename T, bool BWD, int NIN, int LAST>
+__device__ __forceinline__ void fuse_fast_loop(const FuseArgs& a, T* __restrict__ out, const T* __restrict__ dout,
+                                               T* __restrict__ ds, unsigned char* __restrict__ pool_argmax,
+                                               const float (&wn)[3], uint32_t q0, uint32_t qstride, uint32_t total32,
+                                               float (&dw_acc)[3]) {
+  const uint32_t unvec = (uint32_t)(a.c / 8);
+  const bool hoisted = qstride % unvec == 0;
+  ViewCoef k[NIN];
+  if (hoisted) {
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) view_load_coef(a.in[i], (int)(q0 % unvec) * 8, k[i]);
+  }
+  constexpr int DEPTH = LAST == EDET_RS_POOL ? FUSE_DEPTH_POOL : FUSE_DEPTH_UP2;
+  uint32_t q = q0;
+  for (; q + (DEPTH - 1) * qstride < total32; q += DEPTH * qstride)
+    fuse_fast_trip<T, BWD, NIN, LAST, DEPTH>(a, out, dout, ds, pool_argmax, wn, k, hoisted, q, qstride, dw_acc);
+  for (; q < total32; q += qstride)
+    fuse_fast_trip<T, BWD, NIN, LAST, 1>(a, out, dout, ds, pool_argmax, wn, k, hoisted, q, qstride, dw_acc);
+}
+
+
+// Backward of a top-down node {identity, 2x up-sample} that also writes the up-sampled input's gradient: the grid-stride
+// loop runs over the chunks of the COARSE input, a thread takes the 2x2 output pixels above its pixel in row-major order
+// (four chunks of loads in flight) and adds their ds -- each rounded to the storage type first, as edet_fuse_bwd_input
+// reads them from the stored tensor, and in its order -- into gin[1].  ds itself is stored only when asked for.
+template <typename T>
+__device__ __forceinline__ void fuse_up2_quad_loop(const FuseArgs& a, const T* __restrict__ dout, T* __restrict__ ds,
+                                                   const float (&wn)[3], uint32_t q0, uint32_t qstride,
+                                                   float (&dw_acc)[3]) {
+  const edet_tview_t& vc = a.in[1];
+  const uint32_t unvec = (uint32_t)(a.c / 8), uw = (uint32_t)vc.w, uh = (uint32_t)vc.h;
+  const uint32_t total32 = (uint32_t)a.n * uh * uw * unvec;
+  const bool hoisted = qstride % unvec == 0;
+  ViewCoef k[2];
+  if (hoisted) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) view_load_coef(a.in[i], (int)(q0 % unvec) * 8, k[i]);
+  }
+  const bool old0 = a.gin[0] && a.gbeta[0], old1 = a.gbeta[1] != 0;
+  for (uint32_t q = q0; q < total32; q += qstride) {
+    const uint32_t pix = q / unvec;
+    const int c0 = (int)(q - pix * unvec) * 8;
+    const uint32_t prow = pix / uw;
+    const int sx = (int)(pix - prow * uw);
+    const int n = (int)(prow / uh);
+    const int sy = (int)(prow - (uint32_t)n * uh);
+    const size_t cpix = (size_t)(n * vc.h + sy) * vc.w + sx;
+    size_t opix[4];
+    Raw8<T> rc, rid[4], rd[4], rold0[4], rold1;
+    rc.load(reinterpret_cast<const T*>(vc.data) + cpix * vc.ld + c0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      opix[j] = (size_t)(n * a.oh + 2 * sy + (j >> 1)) * a.ow + 2 * sx + (j & 1);
+      rid[j].load(reinterpret_cast<const T*>(a.in[0].data) + opix[j] * a.in[0].ld + c0);
+      rd[j].load(dout + opix[j] * a.ldo + c0);
+      if (old0) rold0[j].load(reinterpret_cast<const T*>(a.gin[0]) + opix[j] * a.in[0].ld + c0);
+    }
+    if (old1) rold1.load(reinterpret_cast<const T*>(a.gin[1]) + cpix * vc.ld + c0);
+    if (!hoisted) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) view_load_coef(a.in[i], c0, k[i]);
+    }
+    float xc[8], gc[8];
+    rc.get(xc);
+    affine8(vc, k[1], xc);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gc[e] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float s[8], x0[8], d[8];
+      rid[j].get(x0);
+      affine8(a.in[0], k[0], x0);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] = fmaf(wn[1], xc[e], fmaf(wn[0], x0[e], 0.f));
+      rd[j].get(d);
+      if (a.act == EDET_ACT_SWISH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d[e] *= swish_gradf_(s[e]);
+      } else if (a.act > EDET_ACT_SWISH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d[e] *= act_other_grad_(a.act, s[e]);
+      }
+      if (a.write_ds) store8<T>(ds + opix[j] * a.ldo + c0, d);
+      float r[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) r[e] = to_f<T>(from_f<T>(d[e]));
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gc[e] += r[e];
+      if (a.gin[0]) {
+#pragma clang fp contract(off)      // (as in fuse_fast_trip)
+        float g[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] = r[e] * wn[0];
+        if (old0) {
+          float old[8];
+          rold0[j].get(old);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) g[e] += old[e];
+        }
+        store8<T>(reinterpret_cast<T*>(a.gin[0]) + opix[j] * a.in[0].ld + c0, g);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dw_acc[0] = fmaf(d[e], x0[e], dw_acc[0]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dw_acc[1] = fmaf(d[e], xc[e], dw_acc[1]);
+    }
+    {
+#pragma clang fp contract(off)        // (as in fuse_fast_trip)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gc[e] *= wn[1];
+      if (old1) {
+        float old[8];
+        rold1.get(old);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gc[e] += old[e];
+      }
+    }
+    store8<T>(reinterpret_cast<T*>(a.gin[1]) + cpix * vc.ld + c0, gc);
+  }
+}
+
 // PCDW (backward, one fusion weight per channel, dwn wanted): thread = (8-channel chunk, pixel slice) for the whole
 // kernel, so its dwn sums stay in registers; the slices are added through LDS in slice order and the workgroup's sums go
 // to its partial row (edet_reduce_partials adds the rows in order) or, for a single workgroup, into dwn -- no atomics,
@@ -177,6 +486,19 @@ __device__ __forceinline__ void fuse_body(const FuseArgs& a, T* __restrict__ out
     qstride = (uint32_t)(gridDim.x * slices * nvec);
   }
   const uint32_t total32 = (uint32_t)total, unvec = (uint32_t)nvec, uow = (uint32_t)a.ow, uoh = (uint32_t)a.oh;
+  // the node shapes with a loop of their own (kernel-uniform code from the host; inside this kernel, not a kernel of
+  // their own, for the reason given above): the generic loop below then has no trip left
+  if (!PCDW && a.fast != FUSE_GENERIC) {
+    if (BWD && a.fast == FUSE_ID_UP2_QUAD)
+      fuse_up2_quad_loop<T>(a, dout, ds, wn, q0, qstride, dw_acc);
+    else if (a.fast == FUSE_ID_UP2)
+      fuse_fast_loop<T, BWD, 2, EDET_RS_UP2>(a, out, dout, ds, pool_argmax, wn, q0, qstride, total32, dw_acc);
+    else if (a.fast == FUSE_ID_ID_POOL)
+      fuse_fast_loop<T, BWD, 3, EDET_RS_POOL>(a, out, dout, ds, pool_argmax, wn, q0, qstride, total32, dw_acc);
+    else
+      fuse_fast_loop<T, BWD, 2, EDET_RS_POOL>(a, out, dout, ds, pool_argmax, wn, q0, qstride, total32, dw_acc);
+    q0 = total32;
+  }
   for (uint32_t q = q0; q < total32; q += qstride) {
     uint32_t pix = q / unvec;
     const int c0 = (int)(q - pix * unvec) * 8;
@@ -367,7 +689,9 @@ struct FuseInArgs {
   int idx;
   int n, oh, ow, ldds;
   int beta;
+  int fast;     // FUSE_IN_*: scalar weight and an exact 2x up-sample, or a pool with recorded winners; 0: the generic branches
 };
+enum { FUSE_IN_GENERIC = 0, FUSE_IN_UP2 = 1, FUSE_IN_POOL_ARGMAX = 2 };
 
 template <typename T>
 __global__ __launch_bounds__(THREADS) void k_fuse_bwd_input(const FuseInArgs a, const T* __restrict__ ds,
@@ -389,6 +713,57 @@ __global__ __launch_bounds__(THREADS) void k_fuse_bwd_input(const FuseInArgs a, 
     float g[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) g[e] = 0.f;
+    const size_t goff = ((size_t)(n * v.h + sy) * v.w + sx) * v.ld + c0;
+    if (a.fast != FUSE_IN_GENERIC) {
+#pragma clang fp contract(off)        // (product, then sum with the old gradient: two roundings, as in the generic branches)
+      // the 2x2 destination pixels of an up-sampled pixel, or the (at most) 2x2 pool windows that hold this pixel: the four
+      // ds chunks, the windows' winner bytes and the old gradient are loaded together, from clamped addresses; what lies
+      // outside is masked in the sums, which run in the generic branches' order
+      const bool pool = a.fast == FUSE_IN_POOL_ARGMAX;
+      int oy[2], ox[2];
+      bool oky[2], okx[2];
+      if (pool) {
+        oy[0] = (sy + a.pad_t - 2 + 1) / 2; oy[1] = (sy + a.pad_t) / 2;
+        ox[0] = (sx + a.pad_l - 2 + 1) / 2; ox[1] = (sx + a.pad_l) / 2;
+        oky[0] = oy[0] < a.oh; oky[1] = oy[1] != oy[0] && oy[1] < a.oh;       // (oy[0], ox[0] >= 0: the division truncates)
+        okx[0] = ox[0] < a.ow; okx[1] = ox[1] != ox[0] && ox[1] < a.ow;
+      } else {
+        oy[0] = 2 * sy; oy[1] = 2 * sy + 1;
+        ox[0] = 2 * sx; ox[1] = 2 * sx + 1;
+        oky[0] = oky[1] = okx[0] = okx[1] = true;
+      }
+      Raw8<T> rt[4], rold;
+      uint2 am[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const size_t opix = (size_t)(n * a.oh + min(oy[j >> 1], a.oh - 1)) * a.ow + min(ox[j & 1], a.ow - 1);
+        rt[j].load(ds + opix * a.ldds + c0);
+        am[j] = pool ? *reinterpret_cast<const uint2*>(argmax + opix * v.c + c0) : make_uint2(0u, 0u);
+      }
+      if (a.beta) rold.load(gout + goff);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float t[8];
+        rt[j].get(t);
+        const bool ok = oky[j >> 1] && okx[j & 1];
+        const uint32_t tap = (uint32_t)((sy - (oy[j >> 1] * 2 - a.pad_t)) * 3 + (sx - (ox[j & 1] * 2 - a.pad_l)));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const uint32_t w = e < 4 ? am[j].x : am[j].y;
+          if (ok && (!pool || ((w >> (8 * (e & 3))) & 0xffu) == tap)) g[e] += t[e];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] *= wn;
+      if (a.beta) {
+        float old[8];
+        rold.get(old);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] += old[e];
+      }
+      store8<T>(gout + goff, g);
+      continue;
+    }
     if (a.mode == EDET_RS_IDENTITY) {
       load8<T>(ds + ((size_t)(n * a.oh + sy) * a.ow + sx) * a.ldds + c0, g);
     } else if (a.mode == EDET_RS_UP2) {
@@ -543,6 +918,15 @@ int fill_args(FuseArgs& a, const edet_tview_t* in0, const edet_tview_t* in1, con
   }
   a.n = in0->n; a.c = in0->c;
   EDET_CHECK(ldo % 8 == 0 && ldo >= a.c, "edet_fuse: bad ldo");
+  // the specialised loop of this node shape, if it has one: scalar weights, identities and then one 2x up-sample or one pool
+  a.fast = FUSE_GENERIC;
+  bool ids = wc == 1 && nin >= 2;
+  for (int i = 0; i + 1 < nin; ++i) ids = ids && modes[i] == EDET_RS_IDENTITY;
+  if (ids) {
+    const edet_tview_t* last = ins[nin - 1];
+    if (modes[nin - 1] == EDET_RS_UP2 && nin == 2 && oh == 2 * last->h && ow == 2 * last->w) a.fast = FUSE_ID_UP2;
+    else if (modes[nin - 1] == EDET_RS_POOL) a.fast = nin == 3 ? FUSE_ID_ID_POOL : FUSE_ID_POOL;
+  }
   return 0;
 }
 
@@ -599,18 +983,26 @@ extern "C" int edet_fuse_bwd_pre(const edet_tview_t* in0, const edet_tview_t* in
                                  int method, float* const* dwraw, int dtype, void* stream) {
   FuseArgs a;
   if (int rc = fill_args(a, in0, in1, in2, modes, nin, wn, wc, act, oh, ow, ldo)) return rc;
-  EDET_CHECK(dout && ds, "edet_fuse_bwd_pre: null pointer");
+  EDET_CHECK(dout && (ds || !write_ds), "edet_fuse_bwd_pre: null pointer");
   a.write_ds = write_ds;
   for (int i = 0; i < nin; ++i) {
     a.gin[i] = gin ? gin[i] : nullptr;
     a.gbeta[i] = (gin && gbeta) ? gbeta[i] : 0;
-    EDET_CHECK(!a.gin[i] || modes[i] == EDET_RS_IDENTITY, "edet_fuse_bwd_pre: gin[%d] given for a resampled input", i);
+    // (the 2x up-sampled input of a top-down node {identity, up-sample} with scalar weights: the quad loop writes its gradient)
+    EDET_CHECK(!a.gin[i] || modes[i] == EDET_RS_IDENTITY || (i == 1 && a.fast == FUSE_ID_UP2),
+               "edet_fuse_bwd_pre: gin[%d] given for a resampled input", i);
   }
+  const bool quad = a.fast == FUSE_ID_UP2 && a.gin[1];
+  if (quad) a.fast = FUSE_ID_UP2_QUAD;
+  // chunks of the grid-stride loop: the output's, or the coarse input's when a thread takes a 2x2 quad of output pixels
+  const int64_t items = quad ? (int64_t)a.n * a.in[1].h * a.in[1].w * (a.c / 8) : (int64_t)a.n * oh * ow * (a.c / 8);
+  // (the specialised backward loops record the pool winners; a node that recomputes them takes the generic body)
+  if (!pool_argmax && (a.fast == FUSE_ID_ID_POOL || a.fast == FUSE_ID_POOL)) a.fast = FUSE_GENERIC;
   const bool pcdw = wc > 1 && dwn;
   EDET_CHECK(!pcdw || a.c <= 8 * THREADS, "edet_fuse_bwd_pre: per-channel fusion weights need c <= %d", 8 * THREADS);
   const size_t lds = pcdw ? (size_t)(THREADS / (a.c / 8)) * nin * a.c * sizeof(float) : 0;
   EDET_CHECK((int64_t)a.n * oh * ow * (a.c / 8) < (1ll << 31), "edet_fuse_bwd_pre: tensor too large for the 32-bit index arithmetic");
-  int grid = ew_grid((int64_t)a.n * oh * ow * (a.c / 8), dtype == EDET_BF16 ? (pcdw ? reinterpret_cast<const void*>(&k_fuse_pc<bf16_t>) : reinterpret_cast<const void*>(&k_fuse<bf16_t, true>)) : nullptr, lds);
+  int grid = ew_grid(items, dtype == EDET_BF16 ? (pcdw ? reinterpret_cast<const void*>(&k_fuse_pc<bf16_t>) : reinterpret_cast<const void*>(&k_fuse<bf16_t, true>)) : nullptr, lds);
   // ordered partial rows through the workspace -- [grid][4] for scalar fusion weights, [grid][nin * c] for per-channel ones;
   // without a workspace that holds them ONE workgroup adds its sums into dwn (no atomics either way)
   const size_t row = pcdw ? (size_t)nin * a.c : 4;
@@ -667,6 +1059,8 @@ extern "C" int edet_fuse_bwd_input(const edet_tview_t* in, int mode, const float
   EDET_CHECK((int64_t)in->n * in->h * in->w * (in->c / 8) < (1ll << 31), "edet_fuse_bwd_input: tensor too large for the 32-bit index arithmetic");
   const int grid = ew_grid((int64_t)in->n * in->h * in->w * (in->c / 8), dtype == EDET_BF16 ? reinterpret_cast<const void*>(&k_fuse_bwd_input<bf16_t>) : nullptr);
   const unsigned char* am = mode == EDET_RS_POOL ? reinterpret_cast<const unsigned char*>(pool_argmax) : nullptr;
+  if (wc == 1 && mode == EDET_RS_UP2 && oh == 2 * in->h && ow == 2 * in->w) a.fast = FUSE_IN_UP2;
+  else if (wc == 1 && mode == EDET_RS_POOL && am) a.fast = FUSE_IN_POOL_ARGMAX;
   if (dtype == EDET_BF16) edet_launch(k_fuse_bwd_input<bf16_t>, grid, dim3(THREADS), 0, to_stream(stream), a, (const bf16_t*)ds, (bf16_t*)gout, am);
   else if (dtype == EDET_F32) edet_launch(k_fuse_bwd_input<float>, grid, dim3(THREADS), 0, to_stream(stream), a, (const float*)ds, (float*)gout, am);
   else EDET_CHECK(false, "edet_fuse_bwd_input: bad dtype %d", dtype);

@@ -124,7 +124,6 @@ class Engine(LayerEngine):
     for v in inputs:
       v.consumers += 1
     if self.training:
-      ds = self.buf(key + ':ds', (n, oh, ow, out.ld), self.tdtype)
       dwn = self.zbuf(key + ':dwn', (max(4, 3 * wc),))
       npool = sum(1 for m in modes if m == RS_POOL)
       amax = self.buf(key + ':amax', (npool, n, oh, ow, c), torch.uint8) if npool and self.pool_argmax else None
@@ -134,8 +133,13 @@ class Engine(LayerEngine):
         tv2 = [v.tview() for v in inputs]
         tvp2 = [ctypes.byref(t) for t in tv2] + [None] * (3 - nin)
         # identity inputs that need a gradient: written by the fusion kernel itself (no edet_fuse_bwd_input launch, no
-        # second read of ds); ds is stored only when a resampled input still has to read it
-        merged = [modes[i] == RS_IDENTITY and v.raw.needs_grad for i, v in enumerate(inputs)]
+        # second read of ds); so is the 2x up-sampled input of a top-down node {identity, up-sample} with scalar weights
+        # (a thread of the kernel then owns the 2x2 output pixels of one of its pixels); ds is stored only when another
+        # resampled input still has to read it
+        up2_merged = (wc == 1 and list(modes) == [RS_IDENTITY, RS_UP2] and
+                      oh == 2 * inputs[1].raw.h and ow == 2 * inputs[1].raw.w)
+        merged = [(modes[i] == RS_IDENTITY or (i == 1 and up2_merged)) and v.raw.needs_grad
+                  for i, v in enumerate(inputs)]
         gin = (ctypes.c_void_p * 3)()
         gbeta = (ctypes.c_int * 3)()
         for i, v in enumerate(inputs):
@@ -144,6 +148,8 @@ class Engine(LayerEngine):
             gbeta[i] = 1 if v.raw.grad_written else 0
             v.raw.grad_written = True
         write_ds = 1 if any(v.raw.needs_grad and not merged[i] for i, v in enumerate(inputs)) else 0
+        # (a node that stores no ds has no ds buffer: nothing stale under that key for whoever reads the buffers)
+        ds = self.buf(key + ':ds', (n, oh, ow, out.ld), self.tdtype) if write_ds else None
         wgrad_folded = wfold and bool(wnames) and method != 1
         dwraw = (ctypes.c_void_p * 3)(*([ptr(self.grad(w)) for w in wnames] + [None] * (3 - len(wnames)))) if wgrad_folded else None
         call('edet_fuse_bwd_pre', tvp2[0], tvp2[1], tvp2[2], marr, nin, ptr(wn), wc, act, ptr(out.grad), oh, ow,

@@ -359,7 +359,10 @@ int edet_fuse_fwd(const edet_tview_t* in0, const edet_tview_t* in1, const edet_t
 /* ds = dout * act'(s) (s recomputed) written to `ds`; dwn[i] += sum ds * x_i.
  * gin / gbeta (may be NULL): per input, the gradient buffer of an EDET_RS_IDENTITY input that this call writes itself
  * (gin[i] (+)= wn[i] * ds when gbeta[i]; exactly what edet_fuse_bwd_input gives) -- saves that launch and its read of
- * ds; write_ds = 0 when no other input needs the stored ds.
+ * ds; write_ds = 0 when no other input needs the stored ds (`ds` may then be NULL).  Also accepted: gin[1] of a node {EDET_RS_IDENTITY,
+ * EDET_RS_UP2} with wc == 1, oh == 2 h and ow == 2 w (the top-down nodes of a BiFPN): gin[1] (+)= wn[1] * (the sum of
+ * the 2x2 ds above each pixel, each rounded to the storage type, in row-major order) -- again edet_fuse_bwd_input's bits.
+ * gin of any other resampled input (a pool, another up-sampling ratio, per-channel weights) is an error.
  * workspace (may be NULL): caller-owned scratch for the per-workgroup partial sums of the scalar fusion weights
  * (16 bytes per workgroup: 64 KiB is enough; per-channel weights: nin * c floats per workgroup), added in a fixed order
  * -- the same dwn on every run; NULL or too small: the kernel runs as ONE workgroup that adds its sums into dwn itself
