@@ -296,3 +296,9 @@ template <typename F> inline bool dtype_dispatch(int dtype, F&& f) {
 
 static inline hipStream_t to_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// grid of a one-dimensional grid-stride kernel with 256-lane workgroups: one thread per item, at most `cap` workgroups (the
+// caps are the callers' own; rowmap_impl.h's ew_grid sizes by residency instead)
+static inline unsigned flat_grid(int64_t count, int64_t cap) {
+  const int64_t g = (count + 255) / 256;
+  return (unsigned)(g < cap ? g : cap);
+}

@@ -14,7 +14,7 @@
 // rows hold a crowd flag and an area next to a box of -1.
 //
 // The evaluation step's loss kernels (edet_focal_loss_eval, edet_box_loss_eval, edet_l2_loss) are instantiations of the
-// training kernels' bodies and live with them in loss_opt.hip: their sums have to come out of the same contracted arithmetic.
+// training kernels' bodies and live with them in det_loss.hip: their sums have to come out of the same contracted arithmetic.
 // This file is compiled with -ffp-contract=off (automl_amd/build.py), as the other restatements of the input pipeline are.
 #include "common.h"
 

@@ -1,4 +1,4 @@
-// The row x channel-vector thread map of the 256-lane elementwise / reduction kernels (bn.hip, se.hip, loss_opt.hip) and
+// The row x channel-vector thread map of the 256-lane elementwise / reduction kernels (bn.hip, se.hip, det_loss.hip) and
 // the grid rule of the grid-stride elementwise kernels (bn.hip, fuse.hip).  Everything sits in the unnamed namespace:
 // RowMap is a kernel parameter, so its name is part of those kernels' symbols.
 #pragma once

@@ -1,4 +1,4 @@
-// Stem: dense 3x3 stride-2 convolution with Cin = 3 (TF 'SAME'), plus parameter cast kernels.
+// Stem: dense 3x3 stride-2 convolution with Cin = 3 (TF 'SAME').
 //
 // Cin = 3 gives K = 27: too thin for the matrix cores and only ~3 % of the network's bytes, so
 // this is a direct VALU convolution: the input tile is staged in LDS (fp32), each thread owns one
@@ -519,48 +519,6 @@ __global__ __launch_bounds__(THREADS) void k_stem_bwd_weight(const StemArgs a) {
 }
 
 template <typename T>
-__global__ void k_cast(const float* __restrict__ src, T* __restrict__ dst, int64_t count) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
-       i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = from_f<T>(src[i]);
-}
-
-// dst[r][c] (ld_out, zero padded) = src[r][c]            (transpose == 0, dst rows = rows)
-// dst[c][r] (ld_out, zero padded) = src[r][c]            (transpose == 1, dst rows = cols)
-template <typename T>
-__global__ void k_cast_matrix(const float* __restrict__ src, T* __restrict__ dst, int rows, int cols,
-                              int ld_out, int transpose) {
-  const int drows = transpose ? cols : rows;
-  const int dcols = transpose ? rows : cols;
-  const int64_t total = (int64_t)drows * ld_out;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = (int)(i / ld_out), c = (int)(i - (int64_t)r * ld_out);
-    float v = 0.f;
-    if (c < dcols) v = transpose ? src[(size_t)c * cols + r] : src[(size_t)r * cols + c];
-    dst[i] = from_f<T>(v);
-  }
-}
-
-// every item of a cast plan in one launch: blockIdx.y = item, blockIdx.x strides over its elements
-template <typename T>
-__global__ void k_cast_batch(const edet_cast_item_t* __restrict__ items) {
-  const edet_cast_item_t it = items[blockIdx.y];
-  const float* src = it.src;
-  T* dst = reinterpret_cast<T*>(it.dst);
-  const int drows = it.transpose ? it.cols : it.rows;
-  const int dcols = it.transpose ? it.rows : it.cols;
-  const int64_t total = (int64_t)drows * it.ld_out;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = (int)(i / it.ld_out), c = (int)(i - (int64_t)r * it.ld_out);
-    float v = 0.f;
-    if (c < dcols) v = it.transpose ? src[(size_t)c * it.cols + r] : src[(size_t)r * it.cols + c];
-    dst[i] = from_f<T>(v);
-  }
-}
-
-template <typename T>
 int stem_launch(bool fwd, StemArgs& a, hipStream_t st) {
   if (!fwd && sizeof(T) == 2) {
     a.tiles_y = cdiv(a.oh, MROWS);
@@ -653,41 +611,4 @@ extern "C" int edet_stem_bwd_weight(const void* images, int n, int h, int w,
   if (dtype == EDET_BF16) return stem_launch<bf16_t>(false, a, to_stream(stream));
   if (dtype == EDET_F32) return stem_launch<float>(false, a, to_stream(stream));
   EDET_CHECK(false, "edet_stem_bwd_weight: bad dtype %d", dtype);
-}
-
-extern "C" int edet_cast(const float* src, void* dst, int64_t count, int dtype, void* stream) {
-  EDET_CHECK(src && dst, "edet_cast: null pointer");
-  if (count <= 0) return 0;
-  const int grid = (int)((count + 255) / 256 < 2048 ? (count + 255) / 256 : 2048);
-  if (dtype == EDET_BF16) edet_launch(k_cast<bf16_t>, grid, dim3(256), 0, to_stream(stream), src, (bf16_t*)dst, count);
-  else if (dtype == EDET_F32) edet_launch(k_cast<float>, grid, dim3(256), 0, to_stream(stream), src, (float*)dst, count);
-  else EDET_CHECK(false, "edet_cast: bad dtype %d", dtype);
-  EDET_LAUNCH_CHECK("edet_cast");
-  return 0;
-}
-
-extern "C" int edet_cast_matrix(const float* src, void* dst, int rows, int cols, int ld_out,
-                                int transpose, int dtype, void* stream) {
-  EDET_CHECK(src && dst, "edet_cast_matrix: null pointer");
-  EDET_CHECK(ld_out >= (transpose ? rows : cols), "edet_cast_matrix: ld_out too small");
-  const int64_t total = (int64_t)(transpose ? cols : rows) * ld_out;
-  const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  if (dtype == EDET_BF16)
-    edet_launch(k_cast_matrix<bf16_t>, grid, dim3(256), 0, to_stream(stream), src, (bf16_t*)dst, rows, cols, ld_out, transpose);
-  else if (dtype == EDET_F32)
-    edet_launch(k_cast_matrix<float>, grid, dim3(256), 0, to_stream(stream), src, (float*)dst, rows, cols, ld_out, transpose);
-  else EDET_CHECK(false, "edet_cast_matrix: bad dtype %d", dtype);
-  EDET_LAUNCH_CHECK("edet_cast_matrix");
-  return 0;
-}
-
-extern "C" int edet_cast_batch(const edet_cast_item_t* items_dev, int count, int max_blocks_per_item, int dtype,
-                               void* stream) {
-  EDET_CHECK(items_dev && count > 0 && max_blocks_per_item > 0, "edet_cast_batch: bad arguments");
-  const dim3 grid(max_blocks_per_item, count);
-  if (dtype == EDET_BF16) edet_launch(k_cast_batch<bf16_t>, grid, dim3(256), 0, to_stream(stream), items_dev);
-  else if (dtype == EDET_F32) edet_launch(k_cast_batch<float>, grid, dim3(256), 0, to_stream(stream), items_dev);
-  else EDET_CHECK(false, "edet_cast_batch: bad dtype %d", dtype);
-  EDET_LAUNCH_CHECK("edet_cast_batch");
-  return 0;
 }

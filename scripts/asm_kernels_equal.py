@@ -2,6 +2,7 @@
 """Compares two `hipcc --cuda-device-only -S` outputs of one source kernel by kernel.
 
 usage: asm_kernels_equal.py PARENT.s CHANGE.s [CHANGE2.s ...]
+       asm_kernels_equal.py PARENT.s [PARENT2.s ...] -- CHANGE.s [CHANGE2.s ...]
 
 The compiler emits the kernels of a file in the order in which the host code first names their instantiations, so a
 change that only reorders the host code's launch tables moves whole kernels in the assembly.  This script cuts both
@@ -13,6 +14,7 @@ the rest of the file are identical.
 
 Several CHANGE files: the parent source was split.  Their kernels are compared with the parent's as one set; the parts that
 exist once per file (what precedes the first kernel, what follows the last, the metadata frame) are then left out.
+Several PARENT files before a `--`: kernels moved between sources; both sides are compared as one set each.
 """
 import re
 import sys
@@ -51,22 +53,32 @@ def cut(path):
   return blocks
 
 
-def main():
-  per_file = ('HEAD', 'TAIL', 'META')
-  a, b = cut(sys.argv[1]), {}
-  for path in sys.argv[2:]:
+PER_FILE = ('HEAD', 'TAIL', 'META')
+
+
+def cut_all(paths, side):
+  blocks = {}
+  for path in paths:
     part = cut(path)
-    twice = sorted(k for k in part if k in b and k not in per_file)
-    assert not twice, 'in more than one change file: %s' % twice
-    b.update(part)
-  if len(sys.argv) > 3:
-    for k in per_file:
+    twice = sorted(k for k in part if k in blocks and k not in PER_FILE)
+    assert not twice, 'in more than one %s file: %s' % (side, twice)
+    blocks.update(part)
+  return blocks
+
+
+def main():
+  args = sys.argv[1:]
+  cutoff = args.index('--') if '--' in args else 1
+  parents, changes = args[:cutoff], [p for p in args[cutoff:] if p != '--']
+  a, b = cut_all(parents, 'parent'), cut_all(changes, 'change')
+  if len(args) > 2:
+    for k in PER_FILE:
       a.pop(k, None)
       b.pop(k, None)
   bad = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
-  kernels = [k for k in a if not k.startswith('meta:') and k not in per_file]
+  kernels = [k for k in a if not k.startswith('meta:') and k not in PER_FILE]
   same_order = [k for k in a] == [k for k in b]
-  print('%d kernels in %s, %d blocks differ%s' % (len(kernels), sys.argv[1], len(bad), '' if same_order else ' (emission order differs)'))
+  print('%d kernels in %s, %d blocks differ%s' % (len(kernels), ' + '.join(parents), len(bad), '' if same_order else ' (emission order differs)'))
   for k in bad[:10]:
     print('  differs:', k, '(parent only)' if k not in b else '(change only)' if k not in a else '')
   return 1 if bad else 0

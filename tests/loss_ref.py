@@ -1,4 +1,4 @@
-"""Float64 numpy reference of the detection losses (csrc/loss_opt.hip: focal_body, box_body), with an elementwise error bound
+"""Float64 numpy reference of the detection losses (csrc/det_loss.hip: focal_body, box_body), with an elementwise error bound
 derived from the kernels' arithmetic, and the comparator the device tests use (tests/test_gpu_detection_loss.py; the CPU
 tests of this file are in tests/test_loss_ref.py).
 

@@ -260,6 +260,45 @@ def test_softmax_xent_soft(dt, nc, b, smoothing):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('dt', gu.DTYPES, ids=lambda d: d[0])
+@pytest.mark.parametrize('entry', ['edet_softmax_xent', 'edet_softmax_xent_soft'])
+def test_softmax_xent_without_workspace(entry, dt):
+  """workspace = NULL against a workspace, sums starting at [0.5, 2, 3, 7].  Batch 1..4 is one workgroup either way: the
+  same bits everywhere.  Batch 9 is three workgroups with partial rows against ONE workgroup whose waves walk rows w, w + 4,
+  w + 8 and add into sums themselves: a row's arithmetic does not know the grid, so dlogits has the same bits and the counts
+  are equal; the loss is the same 9 non-negative terms and the 0.5 added in another order -- at most 10 additions each way,
+  each rounding by at most 2^-24 of a partial sum that is at most the total, so the two differ by at most 2 * 10 * 2^-24 *
+  total (24 taken for the second-order terms).  sums[3] is nobody's."""
+  name, edt, tdt = dt
+  nc, smoothing = 24, 0.1
+  for b in (1, 2, 3, 4, 9):
+    logits, labels, y = _soft_problem(name, tdt, b, nc, gu.seed_of('no_workspace', b))
+    ld = gu.to_dev(logits.view(b, 1, 1, nc), tdt)
+    lab, yd = labels.to(gu.DEV), y.to(gu.DEV).contiguous()
+    wsp = torch.empty(4096, dtype=torch.float32, device=gu.DEV)
+
+    def run(ws):
+      sums = torch.tensor([0.5, 2.0, 3.0, 7.0], dtype=torch.float32, device=gu.DEV)
+      dl = torch.full_like(ld, float('nan'))
+      tgt = (ptr(lab),) if entry == 'edet_softmax_xent' else (ptr(yd), yd.shape[1])
+      call(entry, ptr(ld), ld.shape[-1], *tgt, b, nc, smoothing, 1.0, ptr(dl), ptr(sums), ptr(ws),
+           ws.numel() * 4 if ws is not None else 0, edt, gu.stream())
+      torch.cuda.synchronize()
+      return sums.cpu(), dl
+    s_ws, d_ws = run(wsp)
+    s_no, d_no = run(None)
+    print('%s %s b=%d: sums %s (workspace) %s (none)' % (entry, name, b, s_ws.tolist(), s_no.tolist()))
+    assert torch.equal(d_ws.view(torch.uint8), d_no.view(torch.uint8)), b
+    assert torch.equal(s_ws[1:], s_no[1:]) and float(s_no[3]) == 7.0, (b, s_ws, s_no)
+    assert float(s_no[1]) >= 2.0 and float(s_no[2]) >= float(s_no[1]) + 1.0, (b, s_no)      # added into, top5 >= top1
+    assert float(s_no[0]) > 0.5, (b, s_no)
+    if b <= 4:
+      assert float(s_ws[0]) == float(s_no[0]), (b, s_ws, s_no)
+    else:
+      assert abs(float(s_ws[0]) - float(s_no[0])) <= 24 * 2.0 ** -24 * float(s_ws[0]), (b, s_ws, s_no)
+
+
+@pytest.mark.gpu
 def test_softmax_xent_soft_refuses_bad_arguments():
   x = torch.zeros(2, 8, device=gu.DEV)
   y = torch.zeros(2, 16, device=gu.DEV)

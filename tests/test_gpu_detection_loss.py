@@ -1,4 +1,4 @@
-"""The detection loss kernels (csrc/loss_opt.hip: edet_focal_loss, edet_focal_loss_smooth, edet_box_loss and their _eval twins)
+"""The detection loss kernels (csrc/det_loss.hip: edet_focal_loss, edet_focal_loss_smooth, edet_box_loss and their _eval twins)
 against the float64 closed form of tests/loss_ref.py, ELEMENT BY ELEMENT: every gradient within the bound loss_ref derives from
 the kernel's arithmetic for that element (no max-norm: the focal gradient spans many decades), the bias gradients and the loss
 sums against exactly rounded sums of the reference, the loss of single elements through one-element launches.  General gamma
