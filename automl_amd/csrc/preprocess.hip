@@ -5,6 +5,10 @@
 //                           :113-124, resize_and_crop_image :126-139 (tf.image.resize bilinear with half-pixel
 //                           centres, tf.image.pad_to_bounding_box) for a batch of equally sized raw images.
 //
+//   edet_preprocess_infer_canvas   the same for a CANVAS batch, every image at its own size and scale as
+//                           infer_lib.ServingDriver._preprocess :219-235 runs DetectionInputProcessor per image, and
+//                           optionally a second copy of the batch mirrored along the padded width (flip TTA).
+//
 //   edet_preprocess_train   dataloader.DetectionInputProcessor :144-200 as InputReader.process_example drives it in
 //                           training (:321-336): normalize_image, random_horizontal_flip (object_detection/
 //                           preprocessor.py:113-199), set_training_random_scale_factors :66-111 (the draws and the scale
@@ -13,8 +17,10 @@
 //
 // One thread per output pixel: the four taps of each channel are normalised ((v - mean) / stddev, as the reference
 // normalises before it resizes) and blended top row, bottom row, then vertically -- the operation order of TF's
-// resize_bilinear_op.cc.  Pixels outside the scaled image are zero.  HBM-bound: the raw batch is read once (each
-// tap from cache), the output written once.
+// resize_bilinear_op.cc.  Pixels outside the scaled image are zero.  The raw batch is read once (each tap from cache),
+// the output written once.  Measured (scripts/bench_infer.py, LABNOTES.md "Inference on a canvas"): the inference kernels
+// take the same time for bf16 and fp32 output, 0.9 and 1.6 TB/s, so the twelve IEEE divisions and the tap addressing per
+// pixel bound them, not the memory; a second, mirrored store of every pixel costs 6 %.
 #include <math.h>
 
 #include "common.h"
@@ -70,17 +76,20 @@ __global__ __launch_bounds__(256) void k_preprocess_infer(const PrepArgs a) {
   o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]);
 }
 
-// Training: output pixel (y, x) = pixel (y + offset_y, x + offset_x) of the image resized to [scaled_h, scaled_w]
-// (zero beyond it), the raw image mirrored left-right first when flip is set.  The raw image is h x w, its first pixel at
-// pixel index `img` of a.raw and its rows `pitch` pixels apart (dense: img = b h w, pitch = w).
-template <typename T>
-__device__ __forceinline__ void train_pixel(const PrepArgs& a, const edet_prep_image_t* __restrict__ per, int h, int w, int pitch,
-                                            size_t img) {
+// Output pixel (y, x) = pixel (y + offset_y, x + offset_x) of the image resized to [scaled_h, scaled_w] (zero beyond it), the raw
+// image mirrored left-right first when flip is set.  The raw image is h x w, its first pixel at pixel index `img` of a.raw and
+// its rows `pitch` pixels apart (dense: img = b h w, pitch = w).  per(b) gives the image's row: the training kernels read it
+// from the caller's array, the inference canvas kernel makes it (no flip, no offset: k_preprocess_infer's pixel, operation by
+// operation).  Every tap is clamped to [0, h - 1] x [0, w - 1], so nothing outside the image is read.  With `mirrored` the
+// pixel, computed once, is stored a second time at column out_w - 1 - x of the same row.
+template <typename T, typename Per>
+__device__ __forceinline__ void resize_pixel(const PrepArgs& a, const Per& per, int h, int w, int pitch, size_t img,
+                                             T* __restrict__ mirrored) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
   const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int b = blockIdx.z;
   if (x >= a.out_w || y >= a.out_h) return;
-  const edet_prep_image_t p = per[b];
+  const edet_prep_image_t p = per(b);
   const int Y = y + p.offset_y, X = x + p.offset_x;
   float v[3] = {0.f, 0.f, 0.f};
   if (X < p.scaled_w && Y < p.scaled_h) {
@@ -104,11 +113,21 @@ __device__ __forceinline__ void train_pixel(const PrepArgs& a, const edet_prep_i
   }
   T* o = reinterpret_cast<T*>(a.out) + (((size_t)b * a.out_h + y) * a.out_w + x) * 3;
   o[0] = from_f<T>(v[0]); o[1] = from_f<T>(v[1]); o[2] = from_f<T>(v[2]);
+  if (mirrored) {
+    T* m = mirrored + (((size_t)b * a.out_h + y) * a.out_w + (a.out_w - 1 - x)) * 3;
+    m[0] = from_f<T>(v[0]); m[1] = from_f<T>(v[1]); m[2] = from_f<T>(v[2]);
+  }
 }
+
+// the training kernels' per-image rows: the caller's array
+struct PerImageRows {
+  const edet_prep_image_t* __restrict__ rows;
+  __device__ __forceinline__ edet_prep_image_t operator()(int b) const { return rows[b]; }
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_preprocess_train(const PrepArgs a, const edet_prep_image_t* __restrict__ per) {
-  train_pixel<T>(a, per, a.h, a.w, a.w, (size_t)blockIdx.z * a.h * a.w);
+  resize_pixel<T>(a, PerImageRows{per}, a.h, a.w, a.w, (size_t)blockIdx.z * a.h * a.w, nullptr);
 }
 
 // The canvas batch: a.h x a.w is the canvas; image b is the top-left h x w of its slot, (h, w) = sizes[b] clamped into the
@@ -119,7 +138,26 @@ __global__ __launch_bounds__(256) void k_preprocess_train_canvas(const PrepArgs 
                                                                 const int32_t* __restrict__ sizes) {
   const int b = blockIdx.z;
   const int h = min(max(sizes[2 * b], 1), a.h), w = min(max(sizes[2 * b + 1], 1), a.w);
-  train_pixel<T>(a, per, h, w, a.w, (size_t)b * a.h * a.w);
+  resize_pixel<T>(a, PerImageRows{per}, h, w, a.w, (size_t)b * a.h * a.w, nullptr);
+}
+
+// Inference on a canvas batch: image b as above, resized to scaled[b] = (scaled_h, scaled_w) clamped into the output, into the
+// top-left corner.  `mirrored`, when not null, receives the batch mirrored along the PADDED width.  Both outputs are written
+// whole.  (The dense k_preprocess_infer keeps its own body: sharing this one changed its machine code and cost it 1 %.)
+struct InferRows {
+  const int32_t* __restrict__ scaled;
+  int out_h, out_w;
+  __device__ __forceinline__ edet_prep_image_t operator()(int b) const {
+    return edet_prep_image_t{0, min(max(scaled[2 * b], 1), out_h), min(max(scaled[2 * b + 1], 1), out_w), 0, 0};
+  }
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_preprocess_infer_canvas(const PrepArgs a, const int32_t* __restrict__ sizes,
+                                                                const int32_t* __restrict__ scaled, T* __restrict__ mirrored) {
+  const int b = blockIdx.z;
+  const int h = min(max(sizes[2 * b], 1), a.h), w = min(max(sizes[2 * b + 1], 1), a.w);
+  resize_pixel<T>(a, InferRows{scaled, a.out_h, a.out_w}, h, w, a.w, (size_t)b * a.h * a.w, mirrored);
 }
 
 // Boxes of one image per workgroup: normalised [ymin, xmin, ymax, xmax] -> [mirrored] -> pixels of the scaled image ->
@@ -200,6 +238,33 @@ extern "C" int edet_preprocess_infer(const void* raw_images, int raw_is_float, i
   if (dtype == EDET_BF16) edet_launch(k_preprocess_infer<bf16_t>, grid, dim3(256), 0, to_stream(stream), a);
   else edet_launch(k_preprocess_infer<float>, grid, dim3(256), 0, to_stream(stream), a);
   EDET_LAUNCH_CHECK("edet_preprocess_infer");
+  return 0;
+}
+
+extern "C" int edet_preprocess_infer_canvas(const void* raw_images, int raw_is_float, int batch, int canvas_h, int canvas_w,
+                                            const int32_t* sizes_dev, const int32_t* scaled_dev, int out_height, int out_width,
+                                            const float* mean_rgb, const float* stddev_rgb, void* out, void* out_mirrored,
+                                            int dtype, void* stream) {
+  EDET_CHECK(raw_images && out && mean_rgb && stddev_rgb && sizes_dev && scaled_dev, "edet_preprocess_infer_canvas: null");
+  EDET_CHECK(out_mirrored != out, "edet_preprocess_infer_canvas: out_mirrored is out");
+  EDET_CHECK(batch >= 1 && batch <= 65535 && canvas_h >= 1 && canvas_w >= 1 && out_height >= 1 && out_width >= 1,
+             "edet_preprocess_infer_canvas: bad sizes");
+  EDET_CHECK(dtype == EDET_F32 || dtype == EDET_BF16, "edet_preprocess_infer_canvas: dtype %d", dtype);
+  PrepArgs a;
+  a.raw = raw_images; a.raw_is_float = raw_is_float;
+  a.batch = batch; a.h = canvas_h; a.w = canvas_w; a.out_h = out_height; a.out_w = out_width;
+  a.scaled_h = a.scaled_w = 0;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean_rgb[c]; a.stddev[c] = stddev_rgb[c]; }
+  a.out = out;
+  const dim3 grid(cdiv(out_width, 64), cdiv(out_height, 4), batch);
+  hipStream_t st = to_stream(stream);
+  if (dtype == EDET_BF16)
+    edet_launch(k_preprocess_infer_canvas<bf16_t>, grid, dim3(256), 0, st, a, sizes_dev, scaled_dev,
+                reinterpret_cast<bf16_t*>(out_mirrored));
+  else
+    edet_launch(k_preprocess_infer_canvas<float>, grid, dim3(256), 0, st, a, sizes_dev, scaled_dev,
+                reinterpret_cast<float*>(out_mirrored));
+  EDET_LAUNCH_CHECK("edet_preprocess_infer_canvas");
   return 0;
 }
 

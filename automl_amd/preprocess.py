@@ -35,6 +35,53 @@ def preprocess_infer(raw_images, image_size, mean_rgb, stddev_rgb, dtype=torch.f
 F = np.float32
 
 
+def infer_canvas_factors(sizes, batch, canvas_h, canvas_w, image_size):
+  """The host half of preprocess_infer_canvas, no device touched: sizes checked (utils.canvas_sizes) -> (sizes int32 [B, 2],
+  scaled int32 [B, 2] = (scaled_h, scaled_w), image_scales float32 [B] = 1 / scale), each row output_size_scale_factors of
+  that image's own size.  An image whose scaled height or width would be 0 raises a ValueError that names it."""
+  sizes = utils.canvas_sizes(sizes, batch, canvas_h, canvas_w)
+  oh, ow = utils.parse_image_size(image_size)
+  scaled = np.zeros((batch, 2), np.int32)
+  scales = np.zeros(batch, np.float32)
+  for i in range(batch):
+    scale, scaled[i] = output_size_scale_factors((oh, ow), int(sizes[i, 0]), int(sizes[i, 1]))
+    if int(scaled[i].min()) < 1:
+      raise ValueError('image %d: %d x %d scaled into %d x %d is empty (%d x %d)'
+                       % (i, int(sizes[i, 0]), int(sizes[i, 1]), oh, ow, int(scaled[i, 0]), int(scaled[i, 1])))
+    scales[i] = F(1.0) / scale
+  return sizes, scaled, scales
+
+
+def preprocess_infer_canvas(raw, sizes, image_size, mean_rgb, stddev_rgb, dtype=torch.float32, mirrored=False):
+  """preprocess_infer for a CANVAS batch, what jpeg.JpegDecoder.decode and v2_preprocessing.pad_batch return: raw [B, Hc, Wc,
+  3] uint8 or float32, image i the top-left sizes[i] = (height, width) of its slot, processed as that image alone would be
+  (infer_lib.py:219-235: the input processor per image) -> (images [B, h, w, 3] `dtype` on the GPU, image_scales [B] float32
+  on the GPU), each image at its own scale.  mirrored=True -> (images, mirrored_images, image_scales): the second tensor is
+  torch.flip(images, dims=[2]), the batch mirrored along the padded width, written by the same launch.  Sizes are HOST data
+  (utils.canvas_sizes) and are checked, with the scaled sizes, before anything touches the device."""
+  if raw.dim() != 4 or raw.shape[-1] != 3:
+    raise ValueError('raw images must be [batch, height, width, 3], got %s' % (tuple(raw.shape),))
+  if dtype not in (torch.float32, torch.bfloat16):
+    raise ValueError('dtype must be float32 or bfloat16')
+  b, hc, wc = (int(v) for v in raw.shape[:3])
+  sizes, scaled, scales = infer_canvas_factors(sizes, b, hc, wc, image_size)
+  oh, ow = utils.parse_image_size(image_size)
+  if raw.dtype not in (torch.uint8, torch.float32):
+    raw = raw.to(torch.float32)
+  raw = raw.cuda().contiguous()
+  # one upload for all three host arrays: int32 [5 B] = sizes [B, 2], scaled [B, 2], the bits of image_scales [B]
+  per = torch.from_numpy(np.concatenate([sizes.reshape(-1), scaled.reshape(-1), scales.view(np.int32)])).to(raw.device)
+  out = torch.empty((b, oh, ow, 3), dtype=dtype, device=raw.device)
+  flipped = torch.empty_like(out) if mirrored else None
+  mean = (ctypes.c_float * 3)(*[float(v) for v in np.broadcast_to(np.asarray(mean_rgb, np.float32).reshape(-1), (3,))])
+  std = (ctypes.c_float * 3)(*[float(v) for v in np.broadcast_to(np.asarray(stddev_rgb, np.float32).reshape(-1), (3,))])
+  _lib.call('edet_preprocess_infer_canvas', raw.data_ptr(), 1 if raw.dtype == torch.float32 else 0, b, hc, wc, per.data_ptr(),
+            per.data_ptr() + 8 * b, oh, ow, mean, std, out.data_ptr(), None if flipped is None else flipped.data_ptr(),
+            _lib.EDET_BF16 if dtype == torch.bfloat16 else _lib.EDET_F32, torch.cuda.current_stream().cuda_stream)
+  image_scales = per[4 * b:].view(torch.float32)
+  return (out, flipped, image_scales) if mirrored else (out, image_scales)
+
+
 MAX_BOXES = 1024      # PREP_MAX_BOXES of csrc/preprocess.hip
 
 

@@ -690,6 +690,20 @@ int edet_label_anchors(const float* anchor_boxes, const int* level_anchors, int 
 int edet_preprocess_infer(const void* raw_images, int raw_is_float, int batch, int height, int width,
                           int out_height, int out_width, const float* mean_rgb, const float* stddev_rgb, void* out,
                           float* image_scale_to_original, int dtype, void* stream);
+/* The same on a CANVAS batch, every image at its own size (infer_lib.py:219-235 runs the input processor per image):
+ * raw_images [batch][canvas_h][canvas_w][3]; image b is the top-left sizes_dev[b] = {height, width} of its slot (int32
+ * [batch][2], DEVICE memory, clamped in the kernel into [1, canvas_h] x [1, canvas_w]), its row pitch canvas_w.  scaled_dev
+ * [batch][2] = {scaled_h, scaled_w} (int32, DEVICE memory, clamped into [1, out_height] x [1, out_width]): the size image b
+ * is resized to, the caller's set_scale_factors_to_output_size of that image's own size; the scales back to the raw images
+ * stay with the caller, who made them from the same values.  The resize ratio and the tap clamps use the image's own size, so
+ * nothing outside the image is read.  out is written whole, zeros included: image b is what edet_preprocess_infer gives for
+ * that image alone, bit for bit.  out_mirrored, when not NULL (and not out), receives the same batch mirrored along the
+ * PADDED width, out_mirrored[b][y][out_width - 1 - x] = out[b][y][x], every pixel computed once and stored twice: the
+ * second network input of flip test-time augmentation.  batch <= 65535.  */
+int edet_preprocess_infer_canvas(const void* raw_images, int raw_is_float, int batch, int canvas_h, int canvas_w,
+                                 const int32_t* sizes_dev, const int32_t* scaled_dev, int out_height, int out_width,
+                                 const float* mean_rgb, const float* stddev_rgb, void* out, void* out_mirrored, int dtype,
+                                 void* stream);
 
 
 /* ---- training image + box preprocessing --------------------------------
