@@ -82,6 +82,12 @@ class JpegImage(ctypes.Structure):
               ('first_block', ctypes.c_int32 * 3), ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class ExampleSpec(ctypes.Structure):
+  """edet_example_spec_t: one wanted key of edet_example_parse."""
+  _fields_ = [('key', ctypes.c_char_p), ('key_len', ctypes.c_int32), ('kind', ctypes.c_int32), ('capacity', ctypes.c_int32),
+              ('reserved', ctypes.c_int32)]
+
+
 NMS_HARD, NMS_GAUSSIAN, NMS_LINEAR = 0, 1, 2
 NMS_TF_V5, NMS_NUMPY = 0, 1
 NMS_PAD_INDEX0, NMS_PAD_ZERO, NMS_PAD_DUMMY = 0, 1, 2
@@ -224,6 +230,11 @@ SIGNATURES = {
                                  ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_int],
     'edet_jpeg_idct': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     'edet_jpeg_color': [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p],
+    'edet_crc32c': [c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)],
+    'edet_tfrecord_index': [c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, ctypes.c_size_t,
+                            ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],
+    'edet_example_parse': [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t), c_int, ctypes.POINTER(ExampleSpec), c_int,
+                           c_int, ctypes.POINTER(c_void_p), c_void_p, c_void_p],
 }
 
 _lib = None

@@ -14,7 +14,7 @@ Decoded: 8-bit Huffman streams of SOF0 / SOF1 in one interleaved scan, greyscale
 at 4:4:4, 4:2:2 or 4:2:0.  Refused with a reason, never approximated: progressive, arithmetic-coded, 12-bit, lossless and
 hierarchical files, CMYK / YCCK, 4:4:0, 4:1:1 and any other sampling, RGB-coded components, several scans, malformed or
 truncated streams.  Not built: EXIF orientation (TensorFlow ignores it too), PNG / GIF / BMP, decode_and_crop_jpeg,
-dct_method, fancy_upscaling=False, ratio, TFRecord / tf.Example parsing.
+dct_method, fancy_upscaling=False, ratio.  (TFRecord / tf.Example input is automl_amd/dataloader.py.)
 """
 import collections
 import ctypes
@@ -44,23 +44,36 @@ JpegInfo = collections.namedtuple('JpegInfo', 'height width components precision
                                               'quant_id comp_id jfif adobe_transform')
 
 
-def _bytes(contents, what='contents'):
+def _buffer(contents, what='contents'):
+  """-> (what to keep alive, address or bytes for a void* argument, length) of the bytes of a JPEG file WITHOUT copying them:
+  bytes go as they are, a contiguous bytearray, memoryview (such as a span inside a mapped TFRecord file) or uint8 vector by
+  its address.  Only a memoryview that is not contiguous is copied."""
+  if isinstance(contents, bytes):
+    return contents, contents, len(contents)
   if isinstance(contents, np.ndarray) and contents.dtype == np.uint8 and contents.ndim == 1:
-    return contents.tobytes()
-  if isinstance(contents, (bytes, bytearray, memoryview)):
-    return bytes(contents)
-  raise ValueError('%s must be the bytes of a JPEG file (bytes, bytearray, memoryview or a uint8 vector), got %s'
-                   % (what, type(contents).__name__))
+    a = np.ascontiguousarray(contents)
+  elif isinstance(contents, (bytearray, memoryview)):
+    view = memoryview(contents)
+    if not view.c_contiguous:
+      data = view.tobytes()
+      return data, data, len(data)
+    a = np.frombuffer(view.cast('B') if view.format != 'B' or view.ndim != 1 else view, np.uint8)
+  else:
+    raise ValueError('%s must be the bytes of a JPEG file (bytes, bytearray, memoryview or a uint8 vector), got %s'
+                     % (what, type(contents).__name__))
+  if a.size == 0:
+    return b'', b'', 0
+  return a, a.ctypes.data, int(a.size)
 
 
 def jpeg_info(contents):
   """What the file says in front of its first scan (edet_jpeg_info; host only, no device needed): a JpegInfo whose kind is
   'baseline', 'extended', 'progressive' or 'other'.  h_samp, v_samp, quant_id and comp_id are per component (at most four).
   A stream without a frame header and a scan raises ValueError."""
-  data = _bytes(contents)
+  _keep, data, size = _buffer(contents)
   out = _lib.JpegInfo()
   try:
-    call('edet_jpeg_info', data, len(data), ctypes.byref(out))
+    call('edet_jpeg_info', data, size, ctypes.byref(out))
   except _lib.EdetError as e:
     raise ValueError(str(e))
   k = min(int(out.components), 4)
@@ -79,11 +92,13 @@ def worst_blocks(canvas_h, canvas_w):
 
 def entropy_decode(datas, canvas_h, canvas_w, coef, images, qtables, status, threads=0):
   """edet_jpeg_entropy_decode on host arrays (numpy or CPU tensors): coef int16 [capacity], images uint8 [B * 80], qtables
-  uint16 [B, 4, 64], status int32 [B].  Blocks until the batch is decoded; needs no device."""
+  uint16 [B, 4, 64], status int32 [B].  Blocks until the batch is decoded; needs no device.  The streams are read where they
+  lie (_buffer): nothing is copied, so a memoryview into a mapped file goes to the workers as it is."""
   n = len(datas)
-  keep = [_bytes(d, 'contents[%d]' % i) for i, d in enumerate(datas)]
-  ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) for d in keep])
-  sizes = (ctypes.c_size_t * n)(*[len(d) for d in keep])
+  keep = [_buffer(d, 'contents[%d]' % i) for i, d in enumerate(datas)]      # alive until the call returns
+  ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) if isinstance(d, bytes) else d
+                                 for _, d, _ in keep])
+  sizes = (ctypes.c_size_t * n)(*[size for _, _, size in keep])
 
   def host(a):
     return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()

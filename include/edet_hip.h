@@ -956,6 +956,58 @@ int edet_jpeg_idct(const int16_t* coef, const edet_jpeg_image_t* images_dev, con
 int edet_jpeg_color(const uint8_t* planes, const edet_jpeg_image_t* images_dev, int batch, int canvas_h, int canvas_w,
                     size_t plane_capacity, uint8_t* raw, void* stream);
 
+/* ---- TFRecord input (dataloader.py:404-460 reads TFRecord shards of tf.train.Example; object_detection/
+ * tf_example_decoder.py:30-169 names the keys) -- HOST only, csrc/tfrecord_host.cpp: plain C++, no device call.  Every input
+ * is a (pointer, length) pair into the caller's memory, every output a caller-allocated array with a stated capacity; nothing
+ * is allocated for the caller, and a malformed input gives a status without a read outside its buffer.  The formats are
+ * read by their specifications (tensorflow/core/lib/io/record_writer.h, core/example/{example,feature}.proto); restated in
+ * tests/tfrecord_ref.py.
+ * edet_crc32c: CRC-32C (Castagnoli, reflected 0x82f63b78) of data[n] continuing from *crc (0 to begin); slicing by eight.
+ * edet_tfrecord_index: walks the framing of buf[nbytes] -- uint64 length (little-endian), uint32 masked CRC of those eight
+ * bytes, payload, uint32 masked CRC of the payload; mask(c) = ((c >> 15 | c << 17) + 0xa282ead8) -- and writes each payload's
+ * offset and length; verify = 0 skips both CRCs.  Returns an EDET_TFRECORD_* status (-1: a null pointer); *count = records
+ * written, *consumed = the offset of the record the status is about, which after EDET_TFRECORD_CAPACITY is where a second
+ * call (buf + consumed, nbytes - consumed) goes on, and nbytes after EDET_TFRECORD_OK.  The length is checked before anything
+ * is added to it. */
+#define EDET_TFRECORD_OK 0
+#define EDET_TFRECORD_TRUNCATED_HEADER 1   /* fewer than 12 bytes are left                                                   */
+#define EDET_TFRECORD_TRUNCATED_PAYLOAD 2  /* verify: the length's CRC matched, and the payload or its CRC ends behind the buffer */
+#define EDET_TFRECORD_LENGTH_CRC 3
+#define EDET_TFRECORD_DATA_CRC 4
+#define EDET_TFRECORD_LENGTH_RANGE 5       /* verify = 0: a length, checked by nobody, that runs past the buffer            */
+#define EDET_TFRECORD_CAPACITY 6           /* `capacity` records are written and another follows, its payload not yet checked */
+/* edet_example_parse: n serialized tf.train.Example messages on min(threads, 16, n) worker threads (threads <= 0: 16; never
+ * the machine's core count).  Example.features = 1; Features.feature = 1, map entries with key = 1 and value = 2; Feature =
+ * oneof bytes_list = 1, float_list = 2, int64_list = 3, each with a repeated value = 1.  spec[nspec] names the wanted keys;
+ * values[k] is where key k's values go: EDET_EXAMPLE_BYTES int64 [n][capacity][2] = (offset into the record, length) -- the
+ * bytes are not copied --, EDET_EXAMPLE_FLOAT float [n][capacity] (the stored bits), EDET_EXAMPLE_INT64 int64 [n][capacity];
+ * counts int32 [n][nspec] is the number of values, -1 for a key the record does not have.  Accepted: packed (wire type 2) and
+ * unpacked (5 / 0) repeated scalars, mixed too; unknown fields of any wire type, skipped (a group field by field up to its
+ * end tag, at most 32 deep); a repeated map key (the last entry wins); a Feature with no member set (count 0); a member set twice (merged), another member after it (the last
+ * wins).  Unwanted features are skipped unread.  status int32 [n] is an EDET_EXAMPLE_* per record; the values and counts of a
+ * record whose status is not 0 are unspecified.  The call itself fails (-1) only on its arguments. */
+#define EDET_EXAMPLE_BYTES 1
+#define EDET_EXAMPLE_FLOAT 2
+#define EDET_EXAMPLE_INT64 3
+#define EDET_EXAMPLE_OK 0
+#define EDET_EXAMPLE_VARINT 1      /* a varint of more than ten bytes, or cut off by the end of its message                  */
+#define EDET_EXAMPLE_LENGTH 2      /* a length, a fixed-width value or a packed float list that does not fit its message    */
+#define EDET_EXAMPLE_WIRE_TYPE 3   /* a known field with another wire type; an end-group tag that closes nothing; 6 and 7    */
+#define EDET_EXAMPLE_CAPACITY 4    /* a list longer than its spec's capacity                                                 */
+#define EDET_EXAMPLE_KIND 5        /* a wanted key whose Feature holds another kind of list                                  */
+typedef struct edet_example_spec { /* 24 bytes */
+  const char* key;                 /* not NUL-terminated: key_len bytes                                                      */
+  int32_t key_len;
+  int32_t kind;                    /* EDET_EXAMPLE_BYTES / FLOAT / INT64                                                     */
+  int32_t capacity;                /* values per record                                                                      */
+  int32_t reserved;
+} edet_example_spec_t;
+int edet_crc32c(const uint8_t* data, size_t n, uint32_t* crc);
+int edet_tfrecord_index(const uint8_t* buf, size_t nbytes, int verify, uint64_t* offsets, uint64_t* lengths,
+                        size_t capacity, size_t* count, size_t* consumed);
+int edet_example_parse(const uint8_t* const* records, const size_t* lengths, int n, const edet_example_spec_t* spec,
+                       int nspec, int threads, void* const* values, int32_t* counts, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
