@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libedet_hip.so')
 
 EDET_F32, EDET_BF16 = 0, 1
-EDET_U8 = 2      # out_dtype of edet_randaug_apply and edet_crop_resize only
+EDET_U8 = 2      # out_dtype of edet_randaug_apply, edet_crop_resize and edet_mosaic only
 ACT_NONE, ACT_SWISH, ACT_RELU, ACT_RELU6, ACT_HSWISH, ACT_MISH, ACT_SRELU = 0, 1, 2, 3, 4, 5, 6
 ACT_CODES = {'swish': ACT_SWISH, 'silu': ACT_SWISH, 'swish_native': ACT_SWISH, 'relu': ACT_RELU, 'relu6': ACT_RELU6,
              'hswish': ACT_HSWISH, 'mish': ACT_MISH, 'srelu': ACT_SRELU}
@@ -57,6 +57,12 @@ class CropImage(ctypes.Structure):
   """edet_crop_image_t: one row of edet_crop_resize's per-image array (v2_preprocessing.train_rows / eval_rows)."""
   _fields_ = [('height', ctypes.c_int32), ('width', ctypes.c_int32), ('crop_y', ctypes.c_int32), ('crop_x', ctypes.c_int32),
               ('crop_h', ctypes.c_int32), ('crop_w', ctypes.c_int32), ('flip', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class MosaicRow(ctypes.Structure):
+  """edet_mosaic_t: one row of edet_mosaic's per-mosaic array (mosaic.mosaic_rows)."""
+  _fields_ = [('index', ctypes.c_int32 * 4), ('x', ctypes.c_int32), ('y', ctypes.c_int32), ('height', ctypes.c_int32 * 4),
+              ('width', ctypes.c_int32 * 4), ('reserved', ctypes.c_int32 * 2)]
 
 
 class GridMaskImage(ctypes.Structure):
@@ -185,6 +191,9 @@ SIGNATURES = {
     'edet_randaug_apply_canvas': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p],
     'edet_crop_resize': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    'edet_mosaic': [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
+    'edet_mosaic_boxes': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                          c_void_p],
     'edet_zero': [c_void_p, ctypes.c_size_t, c_void_p],
     'edet_compact_rows': [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p],
     'edet_cast_to_f32': [c_void_p, c_void_p, c_int64, c_int, c_void_p],

@@ -10,8 +10,9 @@
 // The taps clamp at the CROP edges (the reference slices before it resizes) and the mirror is on the OUTPUT: output column x
 // is column out_w - 1 - x of the resized crop.  Every result is compared bit for bit with a numpy restatement
 // (tests/crop_ref.py on oracle/preprocess_oracle.resize_bilinear), so the arithmetic is part of the interface: this file is
-// compiled with -ffp-contract=off (automl_amd/build.py), and every product, sum and difference below is one rounded fp32
-// operation in the order of k_preprocess_infer (csrc/preprocess.hip): src = (o + 0.5) * (crop_n / out_n) - 0.5,
+// compiled with -ffp-contract=off (automl_amd/build.py), and every product, sum and difference of the tap body (resize_tap.h,
+// shared with csrc/mosaic.hip) is one rounded fp32 operation in the order of k_preprocess_infer (csrc/preprocess.hip):
+// src = (o + 0.5) * (crop_n / out_n) - 0.5,
 // lo = max(floor(src), 0), hi = min(ceil(src), crop_n - 1), t = src - floor(src); top row, bottom row, then vertical, each as
 // a + (b - a) * t.
 //
@@ -21,25 +22,15 @@
 // of a wave cover 256 consecutive pixels of that row, so a wave's stores are one contiguous stretch and its tap reads walk
 // two source rows in order.  A tap pixel is read as one 4-byte load (three bytes used) where the four bytes lie inside the
 // batch, which is everywhere but the batch's very last pixel.  No LDS, no atomics.
-#include "common.h"
+#include "resize_tap.h"
 
 namespace {
+
+using resize_tap::clampi;
 
 constexpr int THREADS = 256;      // 4 waves = 4 output rows of 256 pixels
 constexpr int RUN = 4;            // output pixels per thread
 constexpr int OUT_U8 = 2;         // EDET_U8
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// the three channel bytes of the pixel at byte offset `at` of the batch, in bits 0..23
-__device__ __forceinline__ uint32_t load_px(const uint8_t* __restrict__ raw, size_t at, size_t total) {
-  if (at + 4 <= total) {
-    uint32_t v;
-    __builtin_memcpy(&v, raw + at, 4);      // (no alignment promised: pixels are 3 bytes apart)
-    return v;
-  }
-  return (uint32_t)raw[at] | ((uint32_t)raw[at + 1] << 8) | ((uint32_t)raw[at + 2] << 16);
-}
 
 template <typename T> __device__ __forceinline__ T out_of(float v);
 // preprocessing.py:49-50: clip to [0, 255], then a truncating cast
@@ -47,8 +38,6 @@ template <> __device__ __forceinline__ uint8_t out_of<uint8_t>(float v) { return
 // preprocessing.py:153: (v - 128) / 128 (the division by a power of two is exact); bf16 rounds to nearest even
 template <> __device__ __forceinline__ float out_of<float>(float v) { return (v - 128.0f) / 128.0f; }
 template <> __device__ __forceinline__ bf16_t out_of<bf16_t>(float v) { return f2bf((v - 128.0f) / 128.0f); }
-
-template <typename T> struct alignas(sizeof(T) * 4) Quad { T v[4]; };
 
 // grid: x = stretches of 256 pixels of a row, y = groups of 4 rows, z = the image.  VEC: out_w % 4 == 0 and `out` 16-byte
 // aligned -> three vector stores per thread; else one store per value.
@@ -67,13 +56,10 @@ __global__ __launch_bounds__(THREADS) void k_crop_resize(const uint8_t* __restri
   const int ch = clampi(p.crop_h, 1, height - cy), cw = clampi(p.crop_w, 1, width - cx);
   const bool flip = p.flip != 0;
 
-  const float sy = ((float)y + 0.5f) * ((float)ch / (float)out_h) - 0.5f;
-  const float fy = floorf(sy);
-  const int ylo = max((int)fy, 0), yhi = min((int)ceilf(sy), ch - 1);
-  const float ly = sy - fy;
+  const resize_tap::Axis ty = resize_tap::axis_of(y, (float)ch / (float)out_h, ch);
   const size_t image = (size_t)b * canvas_h * canvas_w;
-  const size_t row_lo = (image + (size_t)(cy + ylo) * canvas_w + cx) * 3;
-  const size_t row_hi = (image + (size_t)(cy + yhi) * canvas_w + cx) * 3;
+  const size_t row_lo = (image + (size_t)(cy + ty.lo) * canvas_w + cx) * 3;
+  const size_t row_hi = (image + (size_t)(cy + ty.hi) * canvas_w + cx) * 3;
   const float xscale = (float)cw / (float)out_w;
 
   float v[RUN * 3];
@@ -81,36 +67,10 @@ __global__ __launch_bounds__(THREADS) void k_crop_resize(const uint8_t* __restri
   for (int e = 0; e < RUN; ++e) {
     const int x = min(x0 + e, out_w - 1);      // (a run that ends past the row repeats its last pixel and never stores it)
     const int xr = flip ? out_w - 1 - x : x;
-    const float sx = ((float)xr + 0.5f) * xscale - 0.5f;
-    const float fx = floorf(sx);
-    const int xlo = max((int)fx, 0), xhi = min((int)ceilf(sx), cw - 1);
-    const float lx = sx - fx;
-    const uint32_t tl = load_px(raw, row_lo + (size_t)xlo * 3, total), tr = load_px(raw, row_lo + (size_t)xhi * 3, total);
-    const uint32_t bl = load_px(raw, row_hi + (size_t)xlo * 3, total), br = load_px(raw, row_hi + (size_t)xhi * 3, total);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float ftl = (float)((tl >> (8 * c)) & 255), ftr = (float)((tr >> (8 * c)) & 255);
-      const float fbl = (float)((bl >> (8 * c)) & 255), fbr = (float)((br >> (8 * c)) & 255);
-      const float top = ftl + (ftr - ftl) * lx;
-      const float bot = fbl + (fbr - fbl) * lx;
-      v[e * 3 + c] = top + (bot - top) * ly;
-    }
+    resize_tap::pixel(raw, row_lo, row_hi, total, resize_tap::axis_of(xr, xscale, cw), ty.t, v + e * 3);
   }
   T* o = out + (((size_t)b * out_h + y) * out_w + x0) * 3;
-  if constexpr (VEC) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      Quad<T> q;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) q.v[e] = out_of<T>(v[4 * k + e]);
-      reinterpret_cast<Quad<T>*>(o)[k] = q;
-    }
-  } else {
-    const int n = min(RUN, out_w - x0) * 3;
-#pragma unroll
-    for (int k = 0; k < RUN * 3; ++k)
-      if (k < n) o[k] = out_of<T>(v[k]);
-  }
+  resize_tap::store_run<VEC>(o, v, min(RUN, out_w - x0), [](float f) { return out_of<T>(f); });
 }
 
 template <typename T>

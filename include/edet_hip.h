@@ -552,6 +552,37 @@ typedef struct edet_crop_image { /* 32 bytes, one per image, read from DEVICE me
 int edet_crop_resize(const uint8_t* raw, int batch, int canvas_h, int canvas_w, const edet_crop_image_t* per_image_dev,
                      void* out, int out_h, int out_w, int out_dtype, void* stream);
 
+/* ---- mosaic augmentation (efficientdet/aug/mosaic.py) ----
+ * raw uint8 [batch][canvas_h][canvas_w][3] as for edet_crop_resize; `groups` mosaics [groups][out_h][out_w][3] in one
+ * launch.  Mosaic g is made of four source images: with the divide points (x, y) of its row, image index[0] resized to
+ * x rows by y columns fills rows [0, x), columns [0, y); index[1], (out_h - x) by y, lies BELOW it (rows [x, out_h));
+ * index[2], x by (out_w - y), to its right (columns [y, out_w)); index[3] takes the rest (mosaic.py:115-128, :246-250).
+ * Every pixel is tf.image.resize of the WHOLE source image to its quadrant's size at the quadrant-local position, in
+ * edet_crop_resize's arithmetic (csrc/resize_tap.h), restated in tests/mosaic_ref.py and compared bit for bit.
+ * out_dtype EDET_F32 = the resized values as they are (what the reference returns), EDET_U8 = clip(v, 0, 255) truncated.
+ * Every field of per_mosaic_dev is clamped in the kernel: index into [0, batch - 1], height into [1, canvas_h], width
+ * into [1, canvas_w], x into [1, out_h - 1], y into [1, out_w - 1]: nothing outside a source image's rectangle is read.
+ * out_h, out_w >= 2, groups <= 65535, batch * canvas_h * canvas_w * 3 addressed as size_t, canvas_h * canvas_w * 3 < 2^31. */
+typedef struct edet_mosaic { /* 64 bytes, one per mosaic, read from DEVICE memory */
+  int32_t index[4];              /* source images: top-left, below it, right of it, the rest */
+  int32_t x, y;                  /* divide points: x splits the ROWS, y the COLUMNS (the reference's names) */
+  int32_t height[4], width[4];   /* valid extent of each source image inside its canvas */
+  int32_t reserved[2];
+} edet_mosaic_t;
+int edet_mosaic(const uint8_t* raw, int batch, int canvas_h, int canvas_w, const edet_mosaic_t* per_mosaic_dev, int groups,
+                void* out, int out_h, int out_w, int out_dtype, void* stream);
+/* The boxes of the same mosaics (this library's batch form; the reference's class scales pixel boxes on the host).
+ * boxes [batch][max_boxes][4] float normalised (ymin, xmin, ymax, xmax), classes [batch][max_boxes] float, counts [batch]
+ * valid rows per image (clamped into [0, max_boxes]).  boxes_out [groups][4 * max_boxes][4], classes_out
+ * [groups][4 * max_boxes], counts_out [groups]: the valid rows of source 0, then 1, 2, 3, in their order, the rest -1.
+ * For a quadrant at offset (oy, ox) of size (qh, qw), one rounded fp32 operation each:
+ *   ymin' = ((float)oy + ymin * (float)qh) / (float)out_h,  xmin' = ((float)ox + xmin * (float)qw) / (float)out_w,
+ * the maxima likewise; nothing is clipped.  index, x and y are clamped as in edet_mosaic; heights and widths are not
+ * read.  One thread per output row, no atomics.  max_boxes >= 1, groups * 4 * max_boxes < 2^31. */
+int edet_mosaic_boxes(const float* boxes, const float* classes, const int32_t* counts, int batch, int max_boxes,
+                      const edet_mosaic_t* per_mosaic_dev, int groups, int out_h, int out_w, float* boxes_out,
+                      float* classes_out, int32_t* counts_out, void* stream);
+
 /* ---- optimizer -----------------------------------------------------------------
  * train_lib.py:486-491 (L2), :675-682 (per-tensor clip_by_norm then
  * clip_by_global_norm), Keras SGD momentum, TFA MovingAverage (:176-199).
