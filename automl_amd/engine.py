@@ -600,6 +600,21 @@ class Engine(LayerEngine):
       all_reduce(self.grads_flat)
     self.optimizer_apply(ema_decay is not None, all_reduce is not None)
 
+  # the five values of loss_values / eval_loss_values, in the order loss_vector writes them
+  LOSS_KEYS = ('cls_loss', 'box_loss', 'det_loss', 'reg_l2_loss', 'loss')
+
+  def loss_vector(self, sums, out):
+    """LOSS_KEYS of a step on the device, for a caller that sums them over steps without reading them (train_lib's fit and
+    evaluate): sums = loss_sums or eval_sums [cls, box, L2, -] -> out float32 [5], formed in float32 with the roundings
+    loss_values makes on the host -- box_loss_weight * box rounded, then added to cls; det + L2 -- so a value read from
+    `out` is the float32 of the one loss_values reports.  Small torch launches on the current stream; nothing waits."""
+    torch.mul(sums[1:2], float(self.config.box_loss_weight), out=out[2:3])
+    out[2:3].add_(sums[0:1])
+    out[0:2].copy_(sums[0:2])
+    out[3:4].copy_(sums[2:3])
+    torch.add(out[2:3], sums[2:3], out=out[4:5])
+    return out
+
   def loss_values(self):
     s = self.loss_sums.detach().cpu().numpy()
     c = self.config

@@ -802,6 +802,14 @@ class LayerEngine(object):
       self.tape.append(bwd)
     return vg
 
+  def drop_rng_state(self):
+    """The state of the generator behind the stochastic-depth draws (uint8 numpy, 16 bytes: seed and offset), for a
+    training-state file; set_drop_rng_state puts it back, so the next refresh_drop_masks draws what it would have drawn."""
+    return self._rng.get_state().cpu().numpy().copy()
+
+  def set_drop_rng_state(self, state):
+    self._rng.set_state(torch.as_tensor(np.asarray(state, dtype=np.uint8)))
+
   def refresh_drop_masks(self):
     """New stochastic-depth draws: mask[n, :] = floor(p + u_n) / p, u_n ~ U[0,1) per image
     (utils.drop_connect, utils.py:329-344).  Device-side torch ops, outside any captured graph."""

@@ -5,10 +5,18 @@ training BatchNorm, focal + Huber detection loss (:493-604), L2 on kernels (:486
 clip_by_norm then clip_by_global_norm (:675-682, on the LOCAL gradient), gradient all-reduce SUM
 across data-parallel replicas (implicit in optimizer.apply_gradients, :683), SGD momentum and the
 TFA MovingAverage EMA (:176-199).  LR schedules restate :37-173.
+
+``EfficientDetNetTrain.fit`` / ``.evaluate`` are the loop of ``tf.keras.Model.fit`` as tf2/train.py:283-290 calls it, over
+``train_step_raw`` / ``test_step_raw`` without a wait for the device per step; ``ModelCheckpoint`` and ``get_callbacks``
+mirror :293-325; ``save_train_state`` / ``restore_train_state`` write and read, next to a checkpoint, everything else a
+next step reads, so that an interrupted run continues bit for bit.  The entry point is automl_amd/train.py.
 """
+import collections.abc
+import json
 import math
 import os
 
+import numpy as np
 import torch
 
 from automl_amd import _lib
@@ -181,6 +189,13 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     self._det_eval_input = None
     self._eval_graphs = {}
     self.autoaugment = None      # set_autoaugment: the box-aware AutoAugment / RandAugment in front of train_step_raw's crop
+    # restore_train_state into a model without an engine: applied by _ensure_engine
+    self._pending_state = None
+    self._pending_drop_rng = {}
+    # fit / evaluate: float32 [5] device sums of Engine.LOSS_KEYS over the steps, and the vector a step's values are formed in
+    self._loss_acc = {}
+    self.fit_input = None        # the iterator fit is reading from (ModelCheckpoint saves its state)
+    self.stop_training = False
 
   def set_autoaugment(self, policy):
     """Switches the box-aware AutoAugment / RandAugment of aug/autoaugment.py (dataloader.py:312-319) on for train_step_raw:
@@ -378,10 +393,21 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     g['steps'] += 1
 
   def _ensure_engine(self, batch, height, width):
+    known = (batch, height, width) in self._engines
     eng = super()._ensure_engine(batch, height, width)
     expr = getattr(self.config, 'var_freeze_expr', None) or None
     if eng.arena.frozen_expr != expr:
       eng.arena.set_frozen(expr)         # tf2/train_lib.py:478-491: out of L2, gradients and updates (None: un-freeze)
+    # what restore_train_state left for a model that had no engine yet: the optimizer state goes into the arena the first
+    # engine brings, a stochastic-depth generator state into the engine of its shape when that one is made
+    if self._pending_state is not None:
+      state, self._pending_state = self._pending_state, None
+      check_arena_length(state, eng.arena)
+      self.set_optimizer_state(state)
+    if not known:
+      rng_state = self._pending_drop_rng.pop(_shape_key(batch, height, width), None)
+      if rng_state is not None:
+        eng.set_drop_rng_state(rng_state)
     return eng
 
   def _positives_momentum(self):
@@ -655,6 +681,167 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     self._eval_pass(eng, images, labels)
     return (eng.eval_loss_values() if sync_loss else {}), labels
 
+  # ---- fit / evaluate: the loop of tf.keras.Model.fit as tf2/train.py:283-290 calls it ----------------------------------
+  def _accumulate(self, name, sums, first):
+    """acc[name] (+)= Engine.LOSS_KEYS of the step whose sums lie in `sums`, on the current stream: Engine.loss_vector, then ONE
+    in-place add into the accumulator, in step order.  first: the accumulator starts at zero.  Nothing is read."""
+    if name not in self._loss_acc:
+      dev = sums.device
+      self._loss_acc[name] = (torch.zeros(5, dtype=torch.float32, device=dev), torch.zeros(5, dtype=torch.float32, device=dev))
+    acc, vec = self._loss_acc[name]
+    if first:
+      acc.zero_()
+    acc.add_(self.engine.loss_vector(sums, vec))
+    return acc
+
+  def _read_losses(self, acc):
+    """The one place fit and evaluate read loss values from the device (it waits for the stream) -> float32 numpy [5]."""
+    return acc.detach().cpu().numpy()
+
+  def _mean_losses(self, acc, steps, prefix=''):
+    """Keras' Mean: total / count, both float32, the total summed on the device in step order."""
+    mean = self._read_losses(acc) / np.float32(steps)
+    return {prefix + k: float(mean[i]) for i, k in enumerate(engine_lib.Engine.LOSS_KEYS)}
+
+  def evaluate(self, x, steps=None):
+    """tf.keras.Model.evaluate over test_step: x = an iterable of the raw batches test_step_raw takes; -> the means of its five
+    values over `steps` batches (all of them for None), accumulated on the device and read ONCE, at the end.  Like test_step
+    it moves nothing of the training state."""
+    acc, n = None, 0
+    for batch in x:
+      if steps is not None and n >= steps:
+        break
+      self.test_step_raw(batch, sync_loss=False)
+      acc = self._accumulate('evaluate', self.engine.eval_sums, n == 0)
+      n += 1
+    if not n:
+      raise ValueError('evaluate: the data holds no batch')
+    return self._mean_losses(acc, n)
+
+  def fit(self, x, epochs=1, steps_per_epoch=None, initial_epoch=0, callbacks=None, validation_data=None, validation_steps=None,
+          verbose=1):
+    """tf.keras.Model.fit for the detector.  x: an iterator of raw batches as dataloader.InputReader(...)(params, batch_size,
+    canvas=...) yields them; every batch goes to train_step_raw(batch, sync_loss=False).  An epoch is steps_per_epoch batches,
+    or the iterator's end for None; the iterator is NOT restarted between epochs (the reader repeats on its own), and fit
+    ends early when it runs dry.  -> History: .history = {name: [value per epoch]}, .epoch = the epoch numbers.
+
+    The loop does not wait for the device per step.  After a step its loss values are added, on the step's stream, into a
+    float32 device accumulator (_accumulate); the epoch's logs are accumulator / steps in float32 -- Keras' Mean with the sum
+    in step order -- for loss, cls_loss, box_loss, det_loss, reg_l2_loss, plus learning_rate of the last step.  The waits
+    are the reader's arena event, the one read at the end of an epoch, a batch-level callback that ACCESSES a device value of
+    its logs (LazyLogs: the running means of the epoch), and a checkpoint.
+
+    validation_data: an iterable of test_step_raw's batches that can be iterated once per epoch (a list, or
+    RepeatableReader(reader)); every epoch ends with evaluate(validation_data, steps=validation_steps), whose values enter
+    the logs under 'val_' + name.  callbacks: objects with any of set_model, on_train_begin, on_train_end(logs),
+    on_epoch_begin(epoch, logs), on_epoch_end(epoch, logs), on_train_batch_end(step, logs); a callback that sets
+    model.stop_training ends the run after the epoch."""
+    if self.use_dist:
+      raise ValueError('data-parallel fit is not built: the replicas would each average their own losses and write the same '
+                       'checkpoint; drive train_step_raw per replica by hand')
+    callbacks = list(callbacks or [])
+
+    def call(name, *args):
+      for cb in callbacks:
+        fn = getattr(cb, name, None)
+        if fn is not None:
+          fn(*args)
+    batch_level = [cb.on_train_batch_end for cb in callbacks if getattr(cb, 'on_train_batch_end', None) is not None]
+    history = History()
+    self.fit_input, self.stop_training = x, False
+    it = iter(x)
+    call('set_model', self)
+    call('on_train_begin', None)
+    logs = {}
+    for epoch in range(int(initial_epoch), int(epochs)):
+      call('on_epoch_begin', epoch, None)
+      acc, steps, lr = None, 0, None
+      while steps_per_epoch is None or steps < steps_per_epoch:
+        try:
+          batch = next(it)
+        except StopIteration:
+          break
+        lr = self.train_step_raw(batch, sync_loss=False)['learning_rate']
+        acc = self._accumulate('fit', self.engine.loss_sums, steps == 0)
+        steps += 1
+        if batch_level:
+          blogs = LazyLogs({'learning_rate': lr, 'step': self.iterations}, engine_lib.Engine.LOSS_KEYS,
+                           lambda acc=acc, steps=steps: self._mean_losses(acc, steps))
+          for fn in batch_level:
+            fn(steps - 1, blogs)
+      if not steps:
+        break      # the data ran dry at an epoch's border
+      logs = self._mean_losses(acc, steps)
+      logs['learning_rate'] = lr
+      if validation_data is not None:
+        logs.update({'val_' + k: v for k, v in self.evaluate(validation_data, steps=validation_steps or None).items()})
+      call('on_epoch_end', epoch, logs)
+      history.append(epoch, logs)
+      if verbose:
+        print('Epoch %d/%d: %d steps - %s' % (epoch + 1, epochs, steps, ' - '.join(
+            '%s: %.4g' % (k, v) for k, v in logs.items() if isinstance(v, (int, float)) and not k.startswith('AP_/'))), flush=True)
+      if self.stop_training or (steps_per_epoch is not None and steps < steps_per_epoch):
+        break
+    call('on_train_end', logs)
+    return history
+
+
+class History(object):
+  """What fit returns (tf.keras.callbacks.History): .history = {name: [one value per epoch]}, .epoch = [epoch numbers]."""
+
+  def __init__(self):
+    self.history, self.epoch = {}, []
+
+  def append(self, epoch, logs):
+    self.epoch.append(epoch)
+    for k, v in logs.items():
+      self.history.setdefault(k, []).append(v)
+
+
+class LazyLogs(collections.abc.Mapping):
+  """The logs of a batch-level callback: `host` values (learning_rate, step) are plain; the values under `device_keys` are
+  read -- read() -> {key: value}, one wait for the device, at most once per batch -- only when one of them is ACCESSED.
+  Asking for the keys, for membership or for a host value reads nothing."""
+
+  def __init__(self, host, device_keys, read):
+    self._host, self._device_keys, self._read, self._values = dict(host), tuple(device_keys), read, None
+
+  def __getitem__(self, key):
+    if key in self._host:
+      return self._host[key]
+    if key not in self._device_keys:
+      raise KeyError(key)
+    if self._values is None:
+      self._values = self._read()
+    return self._values[key]
+
+  def __iter__(self):
+    yield from self._device_keys
+    yield from self._host
+
+  def __len__(self):
+    return len(self._device_keys) + len(self._host)
+
+  def __contains__(self, key):
+    return key in self._host or key in self._device_keys
+
+
+class RepeatableReader(object):
+  """An evaluation reader (dataloader.DeviceReader: one pass, then it has ended) as data that can be iterated again and again,
+  which fit's validation_data and COCOCallback need once per epoch: every iter() puts the reader back to the state it was
+  wrapped in and hands it out."""
+
+  def __init__(self, reader):
+    self.reader = reader
+    self._initial = reader.get_state()
+
+  def __iter__(self):
+    self.reader.set_state(self._initial)
+    return iter(self.reader)
+
+  def close(self):
+    self.reader.close()
+
 
 class COCOCallback(object):
   """tf2/train_lib.py:202-250: COCO AP of the model on a test set every `update_freq` epochs.  test_batches: an iterable of
@@ -689,3 +876,173 @@ class COCOCallback(object):
         logs.update(eval_results)
       return eval_results
     return None
+
+
+# ---- the training-state file: everything a next step reads that util_keras.save_ckpt does not hold ---------------------------
+TRAIN_STATE_SUFFIX = '.train_state.npz'
+TRAIN_STATE_FORMAT = 1
+_SLOT_KEYS = ('velocity', 'ema', 'adam_v', 'rms')
+
+
+def train_state_path(ckpt_prefix):
+  return ckpt_prefix + TRAIN_STATE_SUFFIX
+
+
+def _shape_key(batch, height, width):
+  return '%dx%dx%d' % (batch, height, width)
+
+
+def arena_length(model):
+  """Elements of the model's flat variable arena (layer_engine.ParamArena: the trainable variables in creation order, each
+  padded to a multiple of four), from the variable list alone -- no device."""
+  from automl_amd import util_keras
+  return sum(((int(np.prod(shape)) if shape else 1) + 3) // 4 * 4 for _, shape, trainable in util_keras.model_variables(model) if trainable)
+
+
+def check_arena_length(state, arena):
+  if int(np.asarray(state['velocity']).size) != int(arena.velocity.numel()):
+    raise ValueError('the training state is another model\'s: its arena holds %d elements, this model\'s %d'
+                     % (np.asarray(state['velocity']).size, arena.velocity.numel()))
+
+
+def _model_identity(model):
+  from automl_amd import util_keras
+  return {'num_variables': len(util_keras.model_variables(model)), 'arena_length': arena_length(model),
+          'optimizer': str(getattr(model.config, 'optimizer', 'sgd')).lower()}
+
+
+def save_train_state(model, path, reader=None):
+  """Writes <ckpt prefix>.train_state.npz next to a checkpoint: get_optimizer_state() in full (velocity, ema, the second slot
+  under its key, iterations, moving_normalizer, input_rng_state), the stochastic-depth generator's state of every engine the
+  model holds (by batch x height x width), and reader.get_state() -- with the variables, the shadows and the BatchNorm
+  statistics of the checkpoint, everything the next step reads.  Arrays are npz members; everything else is ONE JSON member,
+  'meta' (uint8).  No pickle.  Reading the slots waits for the device."""
+  state = model.get_optimizer_state()
+  arrays, meta = {}, {'format': TRAIN_STATE_FORMAT}
+  meta.update(_model_identity(model))
+  for k, v in state.items():
+    if k in _SLOT_KEYS or k == 'input_rng_state':
+      arrays[k] = np.asarray(v)
+    elif k == 'iterations':
+      meta[k] = int(v)
+    elif k == 'moving_normalizer':
+      meta[k] = float(v)
+    else:
+      raise ValueError('save_train_state: the optimizer state has a key this file has no place for: %r' % (k,))
+  for (b, h, w), eng in getattr(model, '_engines', {}).items():
+    arrays['drop_rng.' + _shape_key(b, h, w)] = np.asarray(eng.drop_rng_state(), np.uint8)
+  for key, v in getattr(model, '_pending_drop_rng', {}).items():      # restored, and its engine not made since
+    arrays.setdefault('drop_rng.' + key, np.asarray(v, np.uint8))
+  meta['reader'] = None if reader is None else reader.get_state()
+  arrays['meta'] = np.frombuffer(json.dumps(meta).encode('utf-8'), np.uint8)
+  tmp = path + '.tmp'
+  with open(tmp, 'wb') as f:
+    np.savez(f, **arrays)
+  os.replace(tmp, path)
+  return path
+
+
+def load_train_state(path):
+  """-> (meta dict, {member: array}) of a training-state file; allow_pickle=False."""
+  with np.load(path, allow_pickle=False) as z:
+    arrays = {k: z[k] for k in z.files}
+  meta = json.loads(arrays.pop('meta').tobytes().decode('utf-8'))
+  if meta.get('format') != TRAIN_STATE_FORMAT:
+    raise ValueError('%s: training-state format %r, this code reads %d' % (path, meta.get('format'), TRAIN_STATE_FORMAT))
+  return meta, arrays
+
+
+def restore_train_state(model, path, reader=None):
+  """Puts a save_train_state file back into `model` (and the reader's part into `reader`).  A file from another model is
+  refused with the difference named: the variable count, the arena length or the optimizer.  A model without an engine keeps
+  the state until its first engine is made (as set_weights / set_ema_weights do); model.iterations is set at once, so the
+  caller can form initial_epoch from it.  -> the meta dict."""
+  meta, arrays = load_train_state(path)
+  mine = _model_identity(model)
+  what = {'num_variables': 'variables', 'arena_length': 'arena elements', 'optimizer': 'as optimizer'}
+  diff = ['%s %s, this model %s' % (meta.get(k), what[k], mine[k]) for k in ('num_variables', 'arena_length', 'optimizer')
+          if meta.get(k) != mine[k]]
+  if diff:
+    raise ValueError('%s is the training state of another model: the file has %s' % (path, '; '.join(diff)))
+  state = {k: arrays[k] for k in _SLOT_KEYS + ('input_rng_state',) if k in arrays}
+  state['iterations'] = int(meta['iterations'])
+  if 'moving_normalizer' in meta:
+    state['moving_normalizer'] = float(meta['moving_normalizer'])
+  drop = {k[len('drop_rng.'):]: v for k, v in arrays.items() if k.startswith('drop_rng.')}
+  if reader is not None:
+    if meta.get('reader') is None:
+      raise ValueError('%s holds no reader state' % (path,))
+    reader.set_state(meta['reader'])
+  if model.engine is None:
+    model._pending_state, model._pending_drop_rng = state, drop
+    model.iterations = state['iterations']
+  else:
+    check_arena_length(state, model.engine.arena)
+    model.set_optimizer_state(state)
+    model._pending_drop_rng = {}
+    for (b, h, w), eng in model._engines.items():
+      if _shape_key(b, h, w) in drop:
+        eng.set_drop_rng_state(drop.pop(_shape_key(b, h, w)))
+    model._pending_drop_rng = drop
+  return meta
+
+
+# ---- callbacks (tf2/train_lib.py:293-325) ------------------------------------------------------------------------------------
+class ModelCheckpoint(object):
+  """tf.keras.callbacks.ModelCheckpoint(save_weights_only=True) / tfa AverageModelCheckpoint(update_weights=False) as
+  get_callbacks uses them: save_freq='epoch' saves at every epoch's end, an integer every that many batches.  The file is
+  util_keras.save_ckpt(model, filepath.format(epoch=epoch + 1), ema=bool(moving_average_decay), global_step=iterations) --
+  the name-based layout, plain variables and /ExponentialMovingAverage shadows in one checkpoint -- and next to it the
+  training-state file with the state of the iterator fit reads from.  Saving waits for the device."""
+
+  def __init__(self, filepath, save_freq='epoch', verbose=0):
+    if save_freq != 'epoch' and (not isinstance(save_freq, int) or save_freq < 1):
+      raise ValueError("save_freq must be 'epoch' or a positive number of batches, got %r" % (save_freq,))
+    self.filepath, self.save_freq, self.verbose = filepath, save_freq, verbose
+    self.model = None
+    self._epoch = self._batches = 0
+    # a batch-level callback only where batches are counted: fit builds batch logs only for callbacks that have one
+    self.on_train_batch_end = None if save_freq == 'epoch' else self._count_batch
+
+  def set_model(self, model):
+    self.model = model
+
+  def _count_batch(self, step, logs=None):
+    self._batches += 1
+    if self._batches % self.save_freq == 0:
+      self.save(self._epoch)
+
+  def on_epoch_begin(self, epoch, logs=None):
+    self._epoch = epoch
+
+  def on_epoch_end(self, epoch, logs=None):
+    if self.save_freq == 'epoch':
+      self.save(epoch)
+
+  def save(self, epoch):
+    from automl_amd import util_keras
+    model = self.model
+    prefix = self.filepath.format(epoch=epoch + 1)
+    os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+    util_keras.save_ckpt(model, prefix, ema=bool(model.config.moving_average_decay), global_step=model.iterations)
+    reader = model.fit_input if hasattr(model.fit_input, 'get_state') else None
+    save_train_state(model, train_state_path(prefix), reader)
+    if self.verbose:
+      print('Epoch %d: saving model to %s' % (epoch + 1, prefix), flush=True)
+    return prefix
+
+
+def get_callbacks(params, val_dataset=None):
+  """tf2/train_lib.py:293-325: the checkpoint callback -- <model_dir>/emackpt-{epoch:d} with moving_average_decay,
+  <model_dir>/ckpt-{epoch:d} without, the reference's names -- and COCOCallback(val_dataset, map_freq) when both are given.
+  TensorBoard is left out; sample_image (DisplayCallback: the visualisation is not built) raises."""
+  if params.get('sample_image', None):
+    raise ValueError('sample_image=%r: DisplayCallback is not built (it needs the visualisation of '
+                     'visualize/vis_utils.py, tf2/train_lib.py:253-290)' % (params['sample_image'],))
+  name = 'emackpt-{epoch:d}' if params['moving_average_decay'] else 'ckpt-{epoch:d}'
+  ckpt = ModelCheckpoint(os.path.join(params['model_dir'], name), save_freq=params.get('save_freq', 'epoch'),
+                         verbose=params.get('verbose', 0))
+  callbacks = [ckpt]
+  if params.get('map_freq', None) and val_dataset is not None and params.get('strategy', None) != 'tpu':
+    callbacks.append(COCOCallback(val_dataset, params['map_freq']))
+  return callbacks
