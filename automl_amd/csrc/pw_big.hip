@@ -3,7 +3,7 @@
 // The 1x1 convolutions of the late EfficientNet stages (40x40 and 20x20 feature maps, 80..1152 channels
 // on one side and 480..1152 on the other; D7x: up to 3840) have 100-600 FLOP per byte of the streamed
 // operand: they are the only layers of this network where the matrix cores, not the HBM stream, set the
-// pace, and the wave-private streaming kernels of pw_stream.hip (one MFMA tile per wave, weights resident
+// pace, and the wave-private streaming kernels of pw_stream_*.hip (one MFMA tile per wave, weights resident
 // in LDS) do not fit them.  These kernels are classic workgroup-tiled GEMMs, with the producer's BatchNorm /
 // swish / SE gate (forward) or the BatchNorm backward (gradients) applied between the global load and the
 // LDS store of the streamed operand:

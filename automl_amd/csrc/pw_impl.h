@@ -5,7 +5,7 @@
 #pragma once
 #include "common.h"
 
-// ---- wave-private streaming kernels, weights resident in LDS (pw_stream.hip)
+// ---- wave-private streaming kernels, weights resident in LDS (pw_stream_fwd / _dgrad / _wgrad / _fused.hip)
 int pws_try_fwd(const edet_tview_t* in, const void* wt, int ldw, const float* bias, void* out, int cout,
                 int ldo, float* stat_partials, int* nparts_out, hipStream_t st);
 int pws_try_dgrad(const edet_gview_t* dy, const void* w, int ldw, const edet_tview_t* in,

@@ -1,7 +1,7 @@
 // One-pass TILED backward of a pointwise (1x1) convolution on gfx950: data gradient AND weight gradient from a single
 // read of (dz, y, x).
 //
-// The wave-private one-pass kernel of pw_stream.hip (k_pw_bwd_fused) keeps the whole dW block of a wave in registers,
+// The wave-private one-pass kernel of pw_stream_fused.hip (k_pw_bwd_fused) keeps the whole dW block of a wave in registers,
 // which limits it to the expand / project layers of the large maps (dW <= ~45 tiles of 16 x 16) and makes it own every
 // register of a compute unit.  The layers it cannot take -- the 58 64 -> 64 layers of the BiFPN and the class / box
 // towers, the 40x40 / 20x20 backbone projections (K up to 1152 channels against N <= 128) -- ran the two tiled kernels
@@ -70,7 +70,7 @@ __device__ __forceinline__ uint4 keep_first(uint4 v, int nvalid) {
 
 // MFMA fragment "8 consecutive rows (row0 ..) of one channel" of a row-major bf16 tile through the LDS transpose read:
 // in a 16-lane group lane i addresses 4 consecutive channels (8 bytes) of row row0 + i / 4 -- together a [4 rows][16
-// channels] block starting at channel col0 -- and receives the 4 rows of channel col0 + i (pw_stream.hip, r03m).
+// channels] block starting at channel col0 -- and receives the 4 rows of channel col0 + i (pw_stream_impl.h, r03m).
 __device__ __forceinline__ bf16x8 column_frag_tr(const unsigned char* tile, int stride, int row0, int col0, int fi) {
   const unsigned char* p = tile + (row0 + (fi >> 2)) * stride + (col0 + (fi & 3) * 4) * 2;
   typedef __attribute__((address_space(3))) bf16x4v_t* lds_ptr_t;

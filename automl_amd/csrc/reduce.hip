@@ -1,5 +1,5 @@
 // The partial-sum reduction service: "dst += the sum of my P partial rows", the last stage of every kernel that hands its
-// workgroups' sums over through a workspace instead of atomics (pw_gemm, pw_big, pw_stream, pw_tile_bwd, dwconv, dw_march,
+// workgroups' sums over through a workspace instead of atomics (pw_gemm, pw_big, pw_stream_*, pw_tile_bwd, dwconv, dw_march,
 // stem, fuse, det_loss, softmax_xent): at once (k_reduce_partials) or recorded per stream and batched (k_reduce_batch, edet_reduce_defer).
 #include <map>
 #include <vector>

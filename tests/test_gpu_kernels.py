@@ -1,5 +1,6 @@
 """-m gpu: every HIP kernel, called through the C ABI, against the CPU oracle's ops (+ autograd)."""
 import ctypes
+import re
 import sys
 
 import numpy as np
@@ -454,6 +455,128 @@ def test_pw_bwd_weight(dt, shape, mode, use_ws, pw_impl, ws_mib=16):
        ws_mib * 1024 * 1024 if use_ws else 0, edt, gu.stream())
   torch.cuda.synchronize()
   gu.check(dw, want, name, 'pw_bwd_weight %s %s' % (shape, mode), rtol=2e-2 if name == 'bf16' else 1e-3)
+
+
+# ------------------------------------------------------------------------------------ streaming kernels: host decisions
+def pws_host_decision(monkeypatch, op, cin, cout, gbn=False, act=ACT_NONE, flag=False, env=(), nhw=(2, 9, 7)):
+  """One bf16 call of `op` with the launch log on: (the pws:: instantiations that ran, nparts_out or None).
+  act != none: the view also carries BatchNorm coefficients; flag: EDET_EPI_Y_IS_CONV_OF_INPUT; env: selectors."""
+  _, edt, tdt = gu.DTYPES[1]
+  n, h, w = nhw
+  rng = np.random.default_rng(gu.seed_of(('pws host', op, cin, cout)))
+  xd = gu.to_dev(gu.rnd(rng, (n, h, w, cin), tdt), tdt)
+  sc = sh = None
+  if act != ACT_NONE:
+    sc = gu.fdev(torch.from_numpy((1 + 0.3 * rng.standard_normal(cin)).astype(np.float32)))
+    sh = gu.fdev(torch.from_numpy((0.3 * rng.standard_normal(cin)).astype(np.float32)))
+  tv = gu.tview(xd, cin, sc, sh, None, act)
+  npart = NP(-1)
+  with monkeypatch.context() as mp:
+    mp.setenv('EDET_PW_IMPL', 'stream')
+    for k, v in env:
+      mp.setenv(k, v)
+    _lib.launch_log_start()
+    try:
+      if op == 'fwd':
+        ldk, ldo = gu.pad8(cin), gu.pad8(cout)
+        wt = gu.to_dev(gu.rnd(rng, (1, 1, cout, cin), tdt, 1.0 / np.sqrt(cin)), tdt)
+        out = torch.zeros(n, h, w, ldo, dtype=tdt, device=gu.DEV)
+        parts = partial_buf(cout)
+        call('edet_pw_fwd', ctypes.byref(tv), ptr(wt), ldk, None, ptr(out), cout, ldo, ptr(parts), ctypes.byref(npart),
+             edt, gu.stream())
+      else:
+        dz, y, ga, gb, gcc, _ = make_grad_view(rng, n, h, w, cout, tdt, gbn)
+        gv = gu.gview(gu.to_dev(dz, tdt), cout, gu.to_dev(y, tdt) if gbn else None, ga, gb, gcc)
+        wd = gu.to_dev(gu.rnd(rng, (1, 1, cin, cout), tdt, 1.0 / np.sqrt(cout)), tdt)
+        gout = torch.zeros(n, h, w, gu.pad8(cin), dtype=tdt, device=gu.DEV)
+        epi = BwdEpi(ptr(gout), 0, None, None, None, None, _lib.EPI_Y_IS_CONV_OF_INPUT if flag else 0)
+        dwd = torch.zeros(cin, cout, dtype=torch.float32, device=gu.DEV)
+        wsp = torch.empty(1024 * 1024, dtype=torch.float32, device=gu.DEV)
+        if op == 'dgrad':
+          call('edet_pw_bwd_data', ctypes.byref(gv), ptr(wd), gu.pad8(cout), ctypes.byref(tv), ctypes.byref(epi),
+               ctypes.byref(npart), edt, gu.stream())
+        elif op == 'wgrad':
+          call('edet_pw_bwd_weight', ctypes.byref(tv), ctypes.byref(gv), ptr(dwd), ptr(wsp), wsp.numel() * 4, edt, gu.stream())
+          npart = NP(-1)
+        else:
+          assert op == 'bwd'
+          call('edet_pw_bwd', ctypes.byref(gv), ptr(wd), gu.pad8(cout), ctypes.byref(tv), ctypes.byref(epi),
+               ctypes.byref(npart), ptr(dwd), ptr(wsp), wsp.numel() * 4, edt, gu.stream())
+      torch.cuda.synchronize()
+    finally:
+      log = _lib.launch_log_stop()
+  ran = tuple(sorted(m.group(0) for m in (re.search(r'pws::k_\w+(?:<[^()]*>)?', k) for k in log) if m))
+  return ran, (None if op == 'wgrad' else npart.value)
+
+
+RELU = (('act', ACT_RELU),)
+GBN = (('gbn', True),)
+NOY_FLAG = (('gbn', True), ('flag', True))
+NOY_OFF = NOY_FLAG + (('env', (('EDET_PW_NOY', '0'),)),)
+CLASS_B = (('env', (('EDET_PWS_FUSED_MINROWS', '0'), ('EDET_PWT', '0'))),)
+ROWS_4800 = (('nhw', (3, 40, 40)),)
+FWD, DGRAD, WGRAD, FUSED = 'pws::k_pw_fwd<%s>', 'pws::k_pw_dgrad<8, %s>', 'pws::k_pw_wgrad<%s>', 'pws::k_pw_bwd_fused<%s>'
+FUSED_NOY = ('pws::k_noy_apply', FUSED % '%s, true, 2, 9, true, 1, true, true')
+FUSED_A, FUSED_44, FUSED_39 = (FUSED % s for s in ('12, 4, %s, 2, 9, false, 1, true, true', '4, 8, %s, 4, 4, false, 1, false, false',
+                                                   '%s, 3, 9, false, 3, false, false'))
+# ((entry point, cin, cout, options of pws_host_decision), (instantiations, nparts_out)), recorded with the library built from
+# the single pw_stream.hip this family came from.  Two images of 9 x 7 (126 rows: ragged tiles that straddle the images),
+# ROWS_4800: three of 40 x 40, where the workgroup count is more than one.
+PWS_PINNED = [
+    (('fwd', 16, 24, ()), ((FWD % '4, true, false',), 1)), (('fwd', 16, 24, RELU), ((FWD % '8, false, true',), 1)),
+    (('fwd', 80, 24, ()), ((FWD % '6, true, false',), 1)), (('fwd', 80, 24, RELU), ((FWD % '8, false, true',), 1)),
+    # 24 -> 24: the 6-pass EXACT plan is 55,296 bytes of LDS, over the 53 KB the guarded 5-pass plan fits in
+    (('fwd', 24, 24, ()), ((FWD % '8, false, false',), 1)), (('fwd', 24, 24, RELU), ((FWD % '8, false, true',), 1)),
+    (('fwd', 32, 24, ()), ((FWD % '6, true, false',), 1)), (('fwd', 32, 24, RELU), ((FWD % '8, false, true',), 1)),
+    (('fwd', 144, 24, ()), ((FWD % '11, true, false',), 1)), (('fwd', 144, 24, RELU), ((FWD % '16, false, true',), 1)),
+    (('fwd', 192, 24, ()), ((FWD % '16, true, false',), 1)), (('fwd', 192, 24, RELU), ((FWD % '16, false, true',), 1)),
+    (('fwd', 96, 24, ()), ((FWD % '7, true, false',), 1)), (('fwd', 128, 256, ()), ((FWD % '8, true, false',), 1)),
+    (('fwd', 16, 1152, ()), ((FWD % '8, false, false',), 1)),
+    (('fwd', 16, 24, ROWS_4800), ((FWD % '4, true, false',), 3)), (('fwd', 144, 24, ROWS_4800), ((FWD % '11, true, false',), 10)),
+    (('fwd', 32, 16, RELU + ROWS_4800), ((FWD % '8, false, true',), 4)),
+    (('dgrad', 24, 40, ()), ((DGRAD % 'false, false',), 1)), (('dgrad', 24, 40, GBN), ((DGRAD % 'true, false',), 1)),
+    (('dgrad', 24, 40, RELU), ((DGRAD % 'false, true',), 1)), (('dgrad', 24, 40, RELU + GBN), ((DGRAD % 'true, true',), 1)),
+    (('dgrad', 24, 40, ROWS_4800), ((DGRAD % 'false, false',), 10)), (('dgrad', 24, 40, GBN + ROWS_4800), ((DGRAD % 'true, false',), 10)),
+    # N >= K: the gradient is the 64-wide operand (UG)
+    (('wgrad', 24, 40, ()), ((WGRAD % 'true, false, false',), None)), (('wgrad', 24, 40, GBN), ((WGRAD % 'true, true, false',), None)),
+    (('wgrad', 24, 40, RELU), ((WGRAD % 'true, false, true',), None)), (('wgrad', 24, 40, RELU + GBN), ((WGRAD % 'true, true, true',), None)),
+    (('wgrad', 40, 24, ()), ((WGRAD % 'false, false, false',), None)), (('wgrad', 40, 24, GBN), ((WGRAD % 'false, true, false',), None)),
+    (('wgrad', 40, 24, RELU), ((WGRAD % 'false, false, true',), None)), (('wgrad', 40, 24, RELU + GBN), ((WGRAD % 'false, true, true',), None)),
+    (('wgrad', 24, 40, ROWS_4800), ((WGRAD % 'true, false, false',), None)), (('wgrad', 144, 24, ROWS_4800), ((WGRAD % 'false, false, false',), None)),
+    # class A: NOY with either pair of load passes, the form that reads y by selector / without the flag, no BatchNorm backward
+    (('bwd', 16, 96, NOY_FLAG), ((FUSED_NOY[0], FUSED_NOY[1] % '13, 2'), 1)), (('bwd', 24, 144, NOY_FLAG), ((FUSED_NOY[0], FUSED_NOY[1] % '22, 4'), 1)),
+    (('bwd', 16, 96, NOY_OFF), ((FUSED_A % 'true',), 1)), (('bwd', 24, 144, NOY_OFF), ((FUSED_A % 'true',), 1)),
+    (('bwd', 16, 96, GBN), ((FUSED_A % 'true',), 1)), (('bwd', 24, 144, GBN), ((FUSED_A % 'true',), 1)),
+    (('bwd', 16, 96, ()), ((FUSED_A % 'false',), 1)), (('bwd', 24, 144, ()), ((FUSED_A % 'false',), 1)),
+    (('bwd', 16, 96, NOY_FLAG + ROWS_4800), ((FUSED_NOY[0], FUSED_NOY[1] % '13, 2'), 10)), (('bwd', 24, 144, GBN + ROWS_4800), ((FUSED_A % 'true',), 19)),
+    # class B.  64 -> 64 is outside it (KO < 2 R): the two streaming kernels
+    (('bwd', 32, 16, CLASS_B), ((FUSED_44 % 'false',), 1)), (('bwd', 32, 16, CLASS_B + GBN), ((FUSED_44 % 'true',), 1)),
+    (('bwd', 64, 64, CLASS_B), ((DGRAD % 'false, false', WGRAD % 'true, false, false'), 1)),
+    (('bwd', 64, 64, CLASS_B + GBN), ((DGRAD % 'true, false', WGRAD % 'true, true, false'), 1)),
+    (('bwd', 96, 24, CLASS_B), ((FUSED_39 % '2, 7, false',), 1)), (('bwd', 96, 24, CLASS_B + GBN), ((FUSED_39 % '2, 7, true',), 1)),
+    (('bwd', 144, 24, CLASS_B), ((FUSED_39 % '2, 11, false',), 1)), (('bwd', 144, 24, CLASS_B + GBN), ((FUSED_39 % '2, 11, true',), 1)),
+    (('bwd', 144, 40, CLASS_B), ((FUSED_39 % '3, 11, false',), 1)), (('bwd', 144, 40, CLASS_B + GBN), ((FUSED_39 % '3, 11, true',), 1)),
+    (('bwd', 32, 16, CLASS_B + ROWS_4800), ((FUSED_44 % 'false',), 5)), (('bwd', 144, 24, CLASS_B + GBN + ROWS_4800), ((FUSED_39 % '2, 11, true',), 19)),
+    # below EDET_PWS_FUSED_MINROWS: the two streaming kernels
+    (('bwd', 32, 16, ROWS_4800), ((DGRAD % 'false, false', WGRAD % 'false, false, false'), 5)),
+]
+
+
+def test_pws_host_decisions(monkeypatch):
+  """The instantiation each pws_try_* routine (pw_stream_fwd / _dgrad / _wgrad / _fused.hip) chooses and the partial count
+  it reports, by demangled name: the assembly comparison that accompanies a change of those files does not see the host
+  side.  EDET_PW_IMPL=stream keeps the dispatch's own routing rules out of it.  Every instantiation of the four families
+  appears in PWS_PINNED except k_pw_fwd<16, false, false>, which no shape reaches: above 128 input channels a super-tile
+  takes 11 or 16 load passes (3 or 2 rows per pass, one 32-row tile), both of them EXACT pass counts, so the EXACT plan is
+  the guarded plan and `l2 != 0 && nwc2 == a.NWC` in pws_try_fwd always holds; relu / relu6 / hswish views take
+  k_pw_fwd<16, false, true>."""
+  bad = []
+  for (op, cin, cout, opts), want in PWS_PINNED:
+    got = pws_host_decision(monkeypatch, op, cin, cout, **dict(opts))
+    print(((op, cin, cout, opts), got))
+    if got != want:
+      bad.append(((op, cin, cout, opts), got, want))
+  assert not bad, bad
 
 
 # ------------------------------------------------------------------------------------ partial-sum reductions, exactly
