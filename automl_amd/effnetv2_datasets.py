@@ -1,0 +1,280 @@
+"""efficientnetv2/datasets.py on MI355X, as far as it can exist here: the ImageNet TFRecord reader (:72-448), the dataset
+training configurations (:646-729) and ``build_dataset_input`` -> the batches TrainableModel.train_step / test_step take.
+
+  reader = ImageNetInput(True, '/data/imagenet', seed=1)(256, canvas=(512, 512))
+  for batch in reader:            # ((raw uint8 [B, Hc, Wc, 3] on the device, sizes int32 [B, 2]), labels int32 [B])
+    model.train_step(batch)       # TrainableModel(image_size=...): crop, resize, flip, RandAugment, mixing on the device
+
+Pinned to the reference: the split table (``ImageNetInput.cfg``, :78-91), split = 'train' / 'eval' by is_training (:140), the
+files sorted(glob(data_dir / files))[slice] with Python's own slicing (:342-344: 'train' of fewer than 21 files is empty, and an
+empty list raises), the two keys of a record -- 'image/encoded' (bytes) and 'image/class/label' (int64), class id = label - 1
+(:309-320) -- and drop_remainder=True in both modes (:406-407).
+
+This project's definition (tf.data's 128 K-element shuffle and non-deterministic interleave are pinned nowhere): the order is
+dataloader.RecordOrder's -- training: the file list permuted per epoch by a generator seeded by `seed`, round-robin over at
+most 16 open files, a 64-record shuffle buffer, repeating; evaluation, and debug=True: file order, one pass (no permutation, no
+shuffle, no repeat).  shard=(n, i) keeps files[i::n] of the sliced list (:352).
+get_state() / set_state() of a reader resume the same stream.
+
+The structure is dataloader.InputReader's: ONE background thread reads, verifies and parses up to `depth` batches ahead
+(tfrecord.parse_examples with a two-entry spec); the reader's jpeg.JpegDecoder and every HIP call stay on the consumer's thread,
+and the image bytes go to the Huffman workers as memoryviews into the mapped files.  Worker threads are 1 .. 16, never the
+machine's core count.  The labels stay on the host: train_step range-checks host labels before any launch.
+
+Deliberate differences.  (1) A missing label (the reference's default -1), label 0 or a label above num_classes becomes an
+all-zero one-hot row in the reference, which then trains on it; here such a record raises tfrecord.TFRecordError naming the
+file, the record number and its byte offset, as the detector's reader does for a malformed record.  (2) The reference
+decodes, crops and augments inside its input pipeline at the stage's image size; here the reader delivers decoded canvases
+and TrainableModel does the rest on the device, so ONE reader serves every progressive stage (image_size / image_dtype of
+build_dataset_input are accepted and unused).  (3) ImagenetFt names the tfds data set 'imagenettfds' in the reference; here
+the fine-tuning recipe reads the ImageNet TFRecords, the only reader that is built.
+
+What the decoder refuses passes through unchanged: ImageNet holds a few CMYK JPEGs and a PNG, and jpeg.JpegDecoder's statuses
+and ``fallback=`` (a callable from the bytes to uint8 [h, w, 3]) apply as they are; without a fallback the error names the
+file and the record.  An image larger than the canvas is the decoder's TOO_LARGE and goes the same way -- full-size ImageNet
+has images of several thousand pixels a side, so a run either sizes the canvas for them, hands them to `fallback`, or waits
+for the follow-up this points at: a decode that writes only a window of the image (tf.image.decode_and_crop_jpeg,
+preprocessing.py:142), which is not built.
+
+Not built, raising ValueError('... is not built: ...'): every tfds-backed configuration (cifar10, cifar100, flowers,
+tfflowers, cars, imagenettfds: tensorflow_datasets is not available and its on-disk format is not read), imagenet21k (its
+multiclass labels need the sigmoid loss, which train_step does not have), and the null input of data_dir None / '' / 'null'
+(black images with all-zero label rows, :305-307: train_step's labels are class ids or one-hot rows, an all-zero row is
+neither).  cache, transpose_image and file_buffer_size_m have no counterpart."""
+import collections
+import copy
+import glob
+import os
+import re
+
+import numpy as np
+
+from automl_amd import dataloader
+from automl_amd import hparams_config
+from automl_amd import tfrecord
+
+Config = hparams_config.Config
+
+SPEC = (('image/encoded', 'bytes', 1), ('image/class/label', 'int64', 1))
+
+HostBatch = collections.namedtuple('HostBatch', 'index images labels state')
+
+# datasets.py:78-91; a slice is [start, stop] so that the table stays plain data (config.yaml)
+IMAGENET_CFG = dict(
+    data_dir=None, num_classes=1000, multiclass=False, tfds_split=None,
+    splits=dict(train=dict(num_images=1256144, files='train*', slice=[20, None]),
+                minival=dict(num_images=25021, files='train*', slice=[0, 20]),
+                eval=dict(num_images=50000, files='val*', slice=[0, None]),
+                trainval=dict(num_images=1281167, files='train*', slice=[0, None])))
+
+_TFDS = 'it is read through tensorflow_datasets, which is not available, and its on-disk format is not read'
+UNBUILT_DATASETS = {
+    'imagenet21k': 'its labels are multiclass (several classes per image) and need the sigmoid loss, which train_step does '
+                   'not have (datasets.py:451-503)',
+    'imagenettfds': _TFDS, 'cifar10': _TFDS, 'cifar100': _TFDS, 'flowers': _TFDS, 'tfflowers': _TFDS, 'cars': _TFDS,
+}
+# the dataset training configurations (datasets.py:646-760) -> the data set each of them names
+_UNBUILT_CONFIGS = {'imagenet21k': 'imagenet21k', 'cifar10ft': 'cifar10', 'cifar100ft': 'cifar100', 'flowersft': 'flowers',
+                    'tfflowersft': 'tfflowers', 'carsft': 'cars'}
+
+# datasets.py:646-663
+IMAGENET_TRAIN_CFG = dict(
+    data=dict(ds_name='imagenet', multiclass=False),
+    train=dict(epochs=350, lr_base=0.016, lr_warmup_epoch=5, lr_sched='exponential', label_smoothing=0.1),
+    eval=dict(batch_size=8))
+# datasets.py:699-727 (fine-tuning: less regularisation); ds_name: the module's docstring, difference (3)
+IMAGENETFT_TRAIN_CFG = dict(
+    model=dict(dropout_rate=0.000001, survival_prob=0.8),
+    train=dict(batch_size=512, stages=0, epochs=15, optimizer='rmsprop', lr_sched='constant', lr_base=0.0005,
+               lr_warmup_epoch=1, ema_decay=0.9996, weight_decay=1e-5, label_smoothing=0.1, min_steps=10000, isize=1.0),
+    data=dict(ds_name='imagenet', augname='ft', mixup_alpha=0, cutmix_alpha=0))
+
+
+def _not_built(name, reason):
+  return ValueError('dataset %r is not built: %s' % (name, reason))
+
+
+def get_dataset_class(ds_name):
+  """datasets.py:631-641; 'imagenet' (and the fine-tuning configuration's name 'imagenetft') -> ImageNetInput."""
+  name = str(ds_name).lower()
+  if name in ('imagenet', 'imagenetft'):
+    return ImageNetInput
+  if name in UNBUILT_DATASETS:
+    raise _not_built(ds_name, UNBUILT_DATASETS[name])
+  raise ValueError('unknown dataset %r (datasets.py:631-641 has imagenet, imagenet21k, imagenettfds, cifar10, cifar100, '
+                   'flowers, tfflowers, cars)' % (ds_name,))
+
+
+def get_dataset_config(name):
+  """datasets.py:764-768: the training configuration 'imagenet' or 'imagenetft' with the data set's own table merged into
+  its data section -> a Config with data / train / eval ('imagenet') or model / train / data ('imagenetft')."""
+  key = str(name).lower()
+  if key in _UNBUILT_CONFIGS:
+    raise _not_built(name, UNBUILT_DATASETS[_UNBUILT_CONFIGS[key]])
+  if key == 'imagenet':
+    cfg = Config(copy.deepcopy(IMAGENET_TRAIN_CFG))
+  elif key == 'imagenetft':
+    cfg = Config(copy.deepcopy(IMAGENETFT_TRAIN_CFG))      # (the class's own table: nothing of ImageNet's is inherited)
+  else:
+    raise ValueError('ds:%s not registered: imagenet, imagenetft (built); %s (not built)' % (key, ', '.join(_UNBUILT_CONFIGS)))
+  cfg.data.update(get_dataset_class(cfg.data.ds_name).cfg)
+  return cfg
+
+
+def build_dataset_input(is_training, image_size, image_dtype, data_dir, split, ds_cfg, seed=None, debug=False):
+  """datasets.py:23-45 -> an ImageNetInput on ds_cfg (the data section of a configuration: ds_name, num_classes, splits).
+  image_size and image_dtype are accepted and unused: crop, resize, augmentation and the cast are TrainableModel's."""
+  del image_size, image_dtype
+  ds_cfg = ds_cfg.as_dict() if hasattr(ds_cfg, 'as_dict') else dict(ds_cfg)
+  return get_dataset_class(ds_cfg.get('ds_name', 'imagenet'))(is_training, data_dir, split, debug=debug, seed=seed, cfg=ds_cfg)
+
+
+class _Producer(dataloader._Producer):
+  """The host half for classification records: dataloader._Producer's order, open files and thread body with the two-key
+  parse in place of the detection decoder."""
+
+  def __init__(self, files, batch, shuffle, seed, num_classes, threads, verify):      # pylint: disable=super-init-not-called
+    self.files, self.batch = files, int(batch)
+    self.drop_remainder, self.num_classes = True, int(num_classes)
+    self.threads, self.verify = threads, verify
+    self.open = collections.OrderedDict()
+    self.views = {}
+    self.order = dataloader.RecordOrder(len(files), self._has, shuffle, seed, repeat=shuffle)
+
+  def _error(self, pair, what, status=None):
+    f, r = pair
+    return tfrecord.TFRecordError('%s: %s' % (self._where(f, r), what), self.files[f], r, self._file(f).offset(r), status)
+
+  def _assemble(self, index):
+    views = [self._view(f, r) for f, r in index]
+    parsed = tfrecord.parse_examples(views, SPEC, self.threads)
+    images, labels = [], np.zeros(len(index), np.int32)
+    for i, pair in enumerate(index):
+      status = int(parsed.status[i])
+      if status != tfrecord.E_OK:
+        raise self._error(pair, 'not a tf.train.Example that can be read: %s (status %d)' % (tfrecord.PARSING[status], status), status)
+      if parsed.counts['image/encoded'][i] < 1:
+        raise self._error(pair, "no 'image/encoded' feature")
+      if parsed.counts['image/class/label'][i] < 1:
+        raise self._error(pair, "no 'image/class/label' feature (the reference's default -1 would train on an all-zero label row)")
+      label = int(parsed.values['image/class/label'][i, 0])
+      if not 1 <= label <= self.num_classes:
+        raise self._error(pair, "'image/class/label' %d outside 1 .. %d (0 is the background; the reference would train on an "
+                          'all-zero label row)' % (label, self.num_classes))
+      labels[i] = label - 1      # datasets.py:317-320
+      offset, length = (int(v) for v in parsed.values['image/encoded'][i, 0])
+      images.append(views[i][offset:offset + length])
+    return HostBatch(index, images, labels, self.order.get_state())
+
+
+class DeviceReader(object):
+  """Iterator over ((raw, sizes), labels): dataloader.HostReader's batches through the reader's own jpeg.JpegDecoder."""
+
+  def __init__(self, host, canvas, depth, threads, fallback):
+    self._host, self._canvas = host, (int(canvas[0]), int(canvas[1]))
+    self._depth, self._threads, self._fallback = depth, threads, fallback
+    self._decoder = None
+    self.files = host.files
+
+  def __iter__(self):
+    return self
+
+  def __next__(self):
+    hb = next(self._host)
+    if self._decoder is None:
+      from automl_amd import jpeg
+      threads = None if self._threads is None else min(int(self._threads), len(hb.images))
+      self._decoder = jpeg.JpegDecoder(len(hb.images), self._canvas[0], self._canvas[1], depth=self._depth, threads=threads)
+    try:
+      raw, sizes = self._decoder.decode(hb.images, fallback=self._fallback)
+    except ValueError as e:
+      raise ValueError(name_refused(str(e), hb.index, self.files))
+    return (raw, sizes), hb.labels
+
+  def get_state(self):
+    return self._host.get_state()
+
+  def set_state(self, state):
+    self._host.set_state(state)
+
+  def close(self):
+    self._host.close()
+
+
+def name_refused(message, index, files):
+  """The decoder's message about contents[i] of a batch with that record named: '<file> record <r>: <message>'."""
+  m = re.search(r'contents\[(\d+)\]', message)
+  if m is None or int(m.group(1)) >= len(index):
+    return '%s; the batch holds %s' % (message, ['%s record %d' % (files[f], r) for f, r in index])
+  f, r = index[int(m.group(1))]
+  return '%s record %d: %s' % (files[f], r, message)
+
+
+class ImageNetInput(object):
+  """datasets.py:72-448.  reader(batch_size, canvas=(Hc, Wc), ...) -- also input_obj(batch_size, ...) -- returns the iterator
+  of ((raw, sizes), labels); host_reader(batch_size, ...) the host half alone (HostBatch: index, images, labels; no device).
+  seed: the generator behind the training order (None: numpy's entropy).  cfg: the data section to use instead of the class
+  table (num_classes, splits.<split>.num_images / files / slice), as build_dataset_input passes it."""
+  cfg = Config(copy.deepcopy(IMAGENET_CFG))
+
+  def __init__(self, is_training, data_dir, split=None, debug=False, seed=None, cfg=None):
+    if data_dir is None or data_dir in ('', 'null'):
+      raise ValueError("data_dir=%r: the null input is not built: the reference then feeds black images with all-zero label "
+                       "rows (datasets.py:305-307, :338-340), and train_step's labels are class ids or one-hot rows -- an "
+                       'all-zero row is neither' % (data_dir,))
+    self.is_training, self.data_dir, self.debug, self.seed = bool(is_training), str(data_dir), bool(debug), seed
+    self.split = split or ('train' if is_training else 'eval')      # datasets.py:140
+    table = self.cfg.as_dict()
+    if cfg is not None:
+      given = cfg.as_dict() if hasattr(cfg, 'as_dict') else cfg
+      table = Config(table)
+      table.update({k: v for k, v in given.items() if k in ('num_classes', 'splits')})
+      table = table.as_dict()
+    if self.split not in table['splits']:
+      raise ValueError('split %r: one of %s' % (self.split, ', '.join(table['splits'])))
+    self.num_classes = int(table['num_classes'])
+    self.split_info = table['splits'][self.split]
+    if not self.split_info.get('files'):
+      raise ValueError('split %r of this data configuration names no files' % (self.split,))
+
+  @property
+  def num_images(self):
+    return self.split_info['num_images']
+
+  def files(self, shard=None):
+    """sorted(glob(data_dir / files))[slice] (datasets.py:342-344), files[i::n] of them for shard=(n, i) (:352)."""
+    pattern = os.path.join(self.data_dir, self.split_info['files'])
+    found = sorted(glob.glob(pattern))
+    if not found:
+      raise ValueError('%r matches no file (split %r)' % (pattern, self.split))
+    start, stop = self.split_info.get('slice') or (None, None)
+    files = found[slice(start, stop)]
+    if not files:
+      raise ValueError('split %r keeps files[%s:%s] of %r, and only %d match: none is left' % (
+          self.split, '' if start is None else start, '' if stop is None else stop, pattern, len(found)))
+    if shard is not None:
+      n, i = int(shard[0]), int(shard[1])
+      if n < 1 or not 0 <= i < n:
+        raise ValueError('shard=(%d, %d): (number of shards, index below it)' % (n, i))
+      if i >= len(files):
+        raise ValueError('shard %d of %d gets none of the %d files of split %r' % (i, n, len(files), self.split))
+      files = files[i::n]
+    return files
+
+  def host_reader(self, batch_size, shard=None, depth=2, threads=None, verify=True):
+    batch = int(batch_size)
+    if batch < 1:
+      raise ValueError('batch_size %d < 1' % batch)
+    if threads is not None and not 1 <= int(threads) <= tfrecord.MAX_THREADS:
+      raise ValueError('threads %d outside 1 .. %d' % (threads, tfrecord.MAX_THREADS))
+    producer = _Producer(self.files(shard), batch, self.is_training and not self.debug, self.seed, self.num_classes, threads,
+                         verify)
+    producer.open_first()
+    return dataloader.HostReader(producer, depth, False)
+
+  def reader(self, batch_size, canvas=None, shard=None, depth=2, threads=None, fallback=None, verify=True):
+    if canvas is None or len(canvas) != 2:
+      raise ValueError('canvas=(Hc, Wc) is needed: the slot every decoded image is written into (jpeg.JpegDecoder)')
+    return DeviceReader(self.host_reader(batch_size, shard, depth, threads, verify), canvas, depth, threads, fallback)
+
+  __call__ = reader

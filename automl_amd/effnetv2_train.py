@@ -43,17 +43,30 @@ cutmix, each part with itself in reverse order as ``mixing`` does (``mix_split``
 seeded by the model's seed whose state travels with the optimizer state.  Mixing float labels on the device is not built
 (a ``ValueError``).
 
+``TrainableModel.fit`` / ``.evaluate`` are the loop of ``tf.keras.Model.fit`` as ``main_tf2.py:235-295`` calls it, over
+``train_step`` / ``test_step`` without a wait for the device per step: the step's ``cls_sums`` are added on the device into a
+float32 accumulator that is read once per epoch, and ``metrics_from_sums`` is the one place the four metrics are formed, for a
+step and for an epoch.  ``fit(stages=...)`` applies the progressive stage of every epoch through ``set_stage``.
+``save_train_state`` / ``restore_train_state`` write and read, next to a checkpoint, everything else a next step reads (both
+slots, the shadows, the iteration count, the four generators, the current stage, the reader's position), so that an
+interrupted run continues bit for bit; ``ModelCheckpoint`` is ``train_lib``'s callback writing this trainer's two files.  The
+reader is automl_amd/effnetv2_datasets.py, the entry point automl_amd/effnetv2_main.py.
+
 Single GPU.  Not built, and raising or absent rather than ignored: data-parallel classifier training, ``conv_dropout``,
 AutoAugment v0 and ``ra_aa``, the legacy ``effnetv1_*`` preprocessing, the TF1 trainer's EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
 reference's TF2 trainer, keeps none).
 """
+import json
 import math
+import os
 
 import numpy as np
 import torch
 
 from automl_amd import autoaugment
 from automl_amd import effnetv2_model
+from automl_amd import train_lib
+from automl_amd import util_keras
 from automl_amd import utils
 from automl_amd import v2_preprocessing
 from automl_amd.layer_engine import LayerEngine, Update, capture_graph
@@ -156,12 +169,19 @@ def progressive_stages(model_name, epochs, stages=None, ibase=None, sched=None):
   ram = data.get('ram')
   ram = 15 if ram is None else ram
   mixup, cutmix = float(data.get('mixup_alpha') or 0.0), float(data.get('cutmix_alpha') or 0.0)
+  return stage_list(train_size, epochs, total, sched, IBASE if ibase is None else ibase, ram, mixup, cutmix)
+
+
+def stage_list(train_size, epochs, total, sched, ibase, ram, mixup, cutmix):
+  """main_tf2.py:256-275 on plain values (progressive_stages reads them from a named model's recipe, effnetv2_main from the
+  assembled configuration): `total` stages over `epochs` epochs up to train_size; a falsy ibase = train_size / 2 (:258)."""
+  total = int(total or 0)
   if total < 0:
-    raise ValueError('stages %r must be >= 0' % (stages,))
+    raise ValueError('stages %r must be >= 0' % (total,))
   if not total:
     return [dict(start_epoch=0, end_epoch=int(epochs), image_size=train_size, ra_magnitude=float(ram), mixup_alpha=mixup,
                  cutmix_alpha=cutmix)]
-  ibase = (IBASE if ibase is None else ibase) or (train_size / 2)
+  ibase = ibase or (train_size / 2)
   ram_list = np.linspace(5, ram, total) if sched else [ram] * total
   mixup_list = np.linspace(0, mixup, total) if sched else [mixup] * total
   cutmix_list = np.linspace(0, cutmix, total) if sched else [cutmix] * total
@@ -226,6 +246,27 @@ def draw_mix(rng, batch, h, w, mixup_alpha, cutmix_alpha):
 
 _pack_rng_state, _unpack_rng_state = utils.pack_rng_state, utils.unpack_rng_state
 
+METRIC_KEYS = ('loss', 'reg_l2_loss', 'acc_top1', 'acc_top5')
+
+
+def metrics_from_sums(sums, steps, batch, dtype=np.float32, prefix=''):
+  """The one place the four metrics are formed from sums laid out as V2Engine.cls_sums (mean loss, top-1 rows, top-5 rows,
+  L2 loss), added up over `steps` steps of `batch` images: loss = (A[0] + A[3]) / n, reg_l2_loss = A[3] / n, acc_top1 = A[1] /
+  (n B), acc_top5 = A[2] / (n B) -- Keras' Mean and TopKCategoricalAccuracy over equal batches.  dtype: the arithmetic's;
+  float32 for the epoch logs of fit and evaluate, float64 for the single step's values of train_step / test_step."""
+  a = np.asarray(sums).astype(dtype)
+  n, rows = dtype(steps), dtype(steps) * dtype(batch)
+  return {prefix + 'loss': float((a[0] + a[3]) / n), prefix + 'reg_l2_loss': float(a[3] / n),
+          prefix + 'acc_top1': float(a[1] / rows), prefix + 'acc_top5': float(a[2] / rows)}
+
+
+def stage_of_epoch(stages, epoch):
+  """The entry of a progressive_stages list whose [start_epoch, end_epoch) holds `epoch`; None when none does."""
+  for stage in stages:
+    if stage['start_epoch'] <= epoch < stage['end_epoch']:
+      return stage
+  return None
+
 
 class TrainableModel(effnetv2_model.EffNetV2Model):
   """EffNetV2Model plus the reference's train_step / test_step (main_tf2.py:62-117).
@@ -286,6 +327,10 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.transformations = 'crop|flip' if transformations is None else str(transformations)
     self._crop_rng = v2_preprocessing.crop_rng(self._seed)
     self._crop_forced = None
+    # fit / evaluate: float32 [4] device sums of cls_sums over the steps, by name
+    self._sums_acc = {}
+    self.fit_input = None        # the iterator fit is reading from (ModelCheckpoint saves its state)
+    self.stop_training = False
 
   @staticmethod
   def _check_size(size):
@@ -432,9 +477,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     return eng, dev_images, labels.to(device=eng.device, dtype=torch.float32 if soft else torch.int32).contiguous()
 
   def _metrics(self, eng, lr=None):
-    s = eng.cls_sums.detach().cpu().numpy()
-    out = {'loss': float(s[0]) + float(s[3]), 'reg_l2_loss': float(s[3]), 'acc_top1': float(s[1]) / eng.batch,
-           'acc_top5': float(s[2]) / eng.batch}
+    out = metrics_from_sums(eng.cls_sums.detach().cpu().numpy(), 1, eng.batch, np.float64)
     if lr is not None:
       out['gradient_norm'] = float(eng.gnorm.item())
       out['learning_rate'] = lr
@@ -526,8 +569,9 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       return {'learning_rate': lr}
     return self._metrics(eng, lr)
 
-  def test_step(self, data):
-    """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117).  Never mixes and never augments; both
+  def test_step(self, data, sync_loss=True):
+    """forward(training=False) + loss + metrics, no update (main_tf2.py:105-117; sync_loss=False skips the read-back and
+    returns {}).  Never mixes and never augments; both
     label kinds; with augname set, uint8 images are normalised (x - 128) / 128 on the way in.  With image_size set, uint8
     images are decoded images on a canvas (train_step's input): preprocess_for_eval's centre crop and resize to
     eval_image_size or image_size (v2_preprocessing.eval_rows), never flipped, then normalised."""
@@ -545,7 +589,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     eng.softmax_loss(labels, self.label_smoothing)
     # the compiled loss's regularisation term; the gradient arena of the last train_step stays as it is
     eng.l2_loss_eval(self.weight_decay)
-    return self._metrics(eng)
+    return self._metrics(eng) if sync_loss else {}
 
   # ---- state ---------------------------------------------------------------------------------------------------------
   def get_optimizer_state(self):
@@ -584,3 +628,217 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       _unpack_rng_state(self._ra_rng, state['randaug_rng_state'])
     if self.image_size is not None and 'crop_rng_state' in state:
       _unpack_rng_state(self._crop_rng, state['crop_rng_state'])
+
+  # ---- fit / evaluate: the loop of tf.keras.Model.fit as main_tf2.py:235-295 calls it -----------------------------------
+  def current_stage(self):
+    """What set_stage sets, as the model has it now: image_size, ra_magnitude, mixup_alpha, cutmix_alpha."""
+    return {'image_size': self.image_size, 'ra_magnitude': float(self.ra_magnitude), 'mixup_alpha': self.mixup_alpha,
+            'cutmix_alpha': self.cutmix_alpha}
+
+  def _in_stage(self, stage):
+    keys = ('image_size', 'mixup_alpha', 'cutmix_alpha') + (('ra_magnitude',) if self.augname is not None else ())
+    mine = self.current_stage()
+    return all(float(stage[k]) == float(mine[k]) for k in keys)
+
+  def _accumulate(self, name, first):
+    """acc[name] (+)= the last step's cls_sums, on the step's stream: ONE in-place add, in step order.  first: the
+    accumulator starts at zero.  Nothing is read."""
+    sums = self.engine.cls_sums
+    acc = self._sums_acc.get(name)
+    if acc is None or acc.device != sums.device:
+      acc = self._sums_acc[name] = torch.zeros(4, dtype=torch.float32, device=sums.device)
+    if first:
+      acc.zero_()
+    acc.add_(sums)
+    return acc
+
+  def _epoch_metrics(self, acc, steps, batch, prefix=''):
+    """The one place fit and evaluate read values from the device (it waits for the stream)."""
+    return metrics_from_sums(acc.detach().cpu().numpy(), steps, batch, np.float32, prefix)
+
+  def evaluate(self, x, steps=None):
+    """tf.keras.Model.evaluate over test_step: x = an iterable of test_step's batches -> {'loss', 'reg_l2_loss', 'acc_top1',
+    'acc_top5'} over `steps` batches (all of them for None): cls_sums added up on the device in step order, float32, and read
+    ONCE, at the end (metrics_from_sums).  Like test_step it moves nothing of the training state."""
+    acc, n, batch = None, 0, None
+    for data in x:
+      if steps is not None and n >= steps:
+        break
+      self.test_step(data, sync_loss=False)
+      if batch is None:
+        batch = self.engine.batch
+      elif batch != self.engine.batch:
+        raise ValueError('evaluate: a batch of %d after batches of %d (the metrics are means over equal batches)' % (self.engine.batch, batch))
+      acc = self._accumulate('evaluate', n == 0)
+      n += 1
+    if not n:
+      raise ValueError('evaluate: the data holds no batch')
+    return self._epoch_metrics(acc, n, batch)
+
+  def fit(self, x, epochs=1, steps_per_epoch=None, initial_epoch=0, callbacks=None, validation_data=None, validation_steps=None,
+          verbose=1, stages=None):
+    """tf.keras.Model.fit for the classifier.  x: an iterator of train_step's batches, as effnetv2_datasets.ImageNetInput(...)(
+    batch_size, canvas=...) yields them; every batch goes to train_step(batch, sync_loss=False).  An epoch is steps_per_epoch
+    batches, or the iterator's end for None; the iterator is NOT restarted between epochs (the reader repeats on its own), and
+    fit ends early when it runs dry.  -> train_lib.History.
+
+    stages: a list as progressive_stages returns it.  At the start of every epoch the stage whose [start_epoch, end_epoch)
+    holds the epoch is applied through set_stage, when it differs from what the model has (current_stage) -- one fit and one
+    reader for the whole staged run, where the reference calls fit once per stage (main_tf2.py:256-284); an initial_epoch
+    inside a stage picks that stage.
+
+    The loop does not wait for the device per step.  After a step its cls_sums are added, on the step's stream, into a
+    float32 device accumulator; the epoch's logs are metrics_from_sums of it, plus learning_rate of the last step.  The waits
+    are the reader's arena event, the one read at the end of an epoch, a batch-level callback that ACCESSES a device value of
+    its logs (train_lib.LazyLogs: the running values of the epoch), and a checkpoint.  With mixing on, the metrics are those
+    of the mixed batch, as in train_step.
+
+    validation_data: an iterable of test_step's batches that can be iterated once per epoch (a list, or
+    train_lib.RepeatableReader(reader)); every epoch ends with evaluate(validation_data, steps=validation_steps), whose
+    values enter the logs under 'val_' + name.  callbacks: train_lib.fit's protocol -- objects with any of set_model,
+    on_train_begin, on_train_end(logs), on_epoch_begin(epoch, logs), on_epoch_end(epoch, logs), on_train_batch_end(step,
+    logs); a callback that sets model.stop_training ends the run after the epoch."""
+    callbacks = list(callbacks or [])
+
+    def call(name, *args):
+      for cb in callbacks:
+        fn = getattr(cb, name, None)
+        if fn is not None:
+          fn(*args)
+    batch_level = [cb.on_train_batch_end for cb in callbacks if getattr(cb, 'on_train_batch_end', None) is not None]
+    history = train_lib.History()
+    self.fit_input, self.stop_training = x, False
+    it = iter(x)
+    call('set_model', self)
+    call('on_train_begin', None)
+    logs = {}
+    for epoch in range(int(initial_epoch), int(epochs)):
+      if stages:
+        stage = stage_of_epoch(stages, epoch)
+        if stage is not None and not self._in_stage(stage):
+          self.set_stage(stage)
+      call('on_epoch_begin', epoch, None)
+      acc, steps, lr, batch = None, 0, None, None
+      while steps_per_epoch is None or steps < steps_per_epoch:
+        try:
+          data = next(it)
+        except StopIteration:
+          break
+        lr = self.train_step(data, sync_loss=False)['learning_rate']
+        if batch is None:
+          batch = self.engine.batch
+        elif batch != self.engine.batch:
+          raise ValueError('fit: a batch of %d after batches of %d (the metrics are means over equal batches)' % (self.engine.batch, batch))
+        acc = self._accumulate('fit', steps == 0)
+        steps += 1
+        if batch_level:
+          blogs = train_lib.LazyLogs({'learning_rate': lr, 'step': self.iterations}, METRIC_KEYS,
+                                     lambda acc=acc, steps=steps, batch=batch: self._epoch_metrics(acc, steps, batch))
+          for fn in batch_level:
+            fn(steps - 1, blogs)
+      if not steps:
+        break      # the data ran dry at an epoch's border
+      logs = self._epoch_metrics(acc, steps, batch)
+      logs['learning_rate'] = lr
+      if validation_data is not None:
+        logs.update({'val_' + k: v for k, v in self.evaluate(validation_data, steps=validation_steps or None).items()})
+      call('on_epoch_end', epoch, logs)
+      history.append(epoch, logs)
+      if verbose:
+        print('Epoch %d/%d: %d steps - %s' % (epoch + 1, epochs, steps, ' - '.join(
+            '%s: %.4g' % (k, v) for k, v in logs.items() if isinstance(v, (int, float)))), flush=True)
+      if self.stop_training or (steps_per_epoch is not None and steps < steps_per_epoch):
+        break
+    call('on_train_end', logs)
+    return history
+
+
+# ---- the training-state file: everything a next step reads that util_keras.save_ckpt does not hold ---------------------------
+_ARRAY_KEYS = ('velocity', 'ema', 'adam_v', 'rms', 'rng_state', 'mix_rng_state', 'randaug_rng_state', 'crop_rng_state')
+TRAIN_STATE_KIND = 'effnetv2'
+
+
+def _model_identity(model):
+  return {'num_variables': len(util_keras.model_variables(model)), 'arena_length': train_lib.arena_length(model),
+          'optimizer': model.optimizer}
+
+
+def save_train_state(model, path, reader=None):
+  """Writes <ckpt prefix>.train_state.npz next to a checkpoint, in train_lib.save_train_state's conventions: get_optimizer_state()
+  in full (both slots, the shadows, iterations, rng_state, mix_rng_state, randaug_rng_state, crop_rng_state), the model's
+  current stage (image size, RandAugment magnitude, the two alphas) and reader.get_state() -- with the variables and the
+  BatchNorm statistics of the checkpoint, everything the next step reads.  Arrays are npz members; everything else is ONE
+  JSON member, 'meta' (uint8).  No pickle; written to a temporary name and renamed.  A model without an engine that holds a
+  restored state writes that state.  Reading the slots waits for the device."""
+  if model.engine is None and model._pending_state is not None:
+    state = dict(model._pending_state)
+  else:
+    state = model.get_optimizer_state()
+  arrays, meta = {}, {'format': train_lib.TRAIN_STATE_FORMAT, 'kind': TRAIN_STATE_KIND}
+  meta.update(_model_identity(model))
+  for k, v in state.items():
+    if k in _ARRAY_KEYS:
+      arrays[k] = np.asarray(v)
+    elif k == 'iterations':
+      meta[k] = int(v)
+    else:
+      raise ValueError('save_train_state: the optimizer state has a key this file has no place for: %r' % (k,))
+  meta['stage'] = model.current_stage()
+  meta['reader'] = None if reader is None else reader.get_state()
+  arrays['meta'] = np.frombuffer(json.dumps(meta).encode('utf-8'), np.uint8)
+  tmp = path + '.tmp'
+  with open(tmp, 'wb') as f:
+    np.savez(f, **arrays)
+  os.replace(tmp, path)
+  return path
+
+
+def restore_train_state(model, path, reader=None):
+  """Puts a save_train_state file back into `model` (and the reader's part into `reader`).  A file from another model is
+  refused with the difference named: the variable count, the arena length or the optimizer.  The stage goes in at once
+  (set_image_size / set_randaug / set_mix_alphas, where the model has them); a model without an engine keeps the rest until
+  its first engine is made, and model.iterations is set at once, so the caller can form initial_epoch from it.  -> the meta
+  dict."""
+  meta, arrays = train_lib.load_train_state(path)
+  if meta.get('kind') != TRAIN_STATE_KIND:
+    raise ValueError('%s is not a classifier training state (kind %r, this code reads %r)' % (path, meta.get('kind'), TRAIN_STATE_KIND))
+  mine = _model_identity(model)
+  what = {'num_variables': 'variables', 'arena_length': 'arena elements', 'optimizer': 'as optimizer'}
+  diff = ['%s %s, this model %s' % (meta.get(k), what[k], mine[k]) for k in ('num_variables', 'arena_length', 'optimizer')
+          if meta.get(k) != mine[k]]
+  if diff:
+    raise ValueError('%s is the training state of another model: the file has %s' % (path, '; '.join(diff)))
+  if reader is not None:
+    if meta.get('reader') is None:
+      raise ValueError('%s holds no reader state' % (path,))
+    reader.set_state(meta['reader'])
+  stage = meta.get('stage') or {}
+  if model.image_size is not None and stage.get('image_size') is not None:
+    model.set_image_size(stage['image_size'])
+  if model.augname is not None and 'ra_magnitude' in stage:
+    model.set_randaug(stage['ra_magnitude'])
+  if 'mixup_alpha' in stage:
+    model.set_mix_alphas(stage['mixup_alpha'], stage['cutmix_alpha'])
+  state = {k: arrays[k] for k in _ARRAY_KEYS if k in arrays}
+  state['iterations'] = int(meta['iterations'])
+  if model.engine is not None:
+    train_lib.check_arena_length(state, model.engine.arena)
+  model.set_optimizer_state(state)
+  return meta
+
+
+class ModelCheckpoint(train_lib.ModelCheckpoint):
+  """train_lib.ModelCheckpoint for this trainer: the same callback (save_freq 'epoch' or a number of batches), whose file is
+  util_keras.save_ckpt(model, filepath.format(epoch=epoch + 1), ema=bool(model.ema_decay), global_step=model.iterations) with
+  this module's training-state file next to it.  Saving waits for the device."""
+
+  def save(self, epoch):
+    model = self.model
+    prefix = self.filepath.format(epoch=epoch + 1)
+    os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+    util_keras.save_ckpt(model, prefix, ema=bool(model.ema_decay), global_step=model.iterations)
+    reader = model.fit_input if hasattr(model.fit_input, 'get_state') else None
+    save_train_state(model, train_lib.train_state_path(prefix), reader)
+    if self.verbose:
+      print('Epoch %d: saving model to %s' % (epoch + 1, prefix), flush=True)
+    return prefix
