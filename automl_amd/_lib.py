@@ -239,6 +239,10 @@ SIGNATURES = {
                                  ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_int],
     'edet_jpeg_idct': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     'edet_jpeg_color': [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p],
+    'edet_jpeg_entropy_decode_scaled': [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t), c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_int],
+    'edet_jpeg_idct_scaled': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
+    'edet_jpeg_color_scaled': [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p],
     'edet_crc32c': [c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)],
     'edet_tfrecord_index': [c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, ctypes.c_size_t,
                             ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],

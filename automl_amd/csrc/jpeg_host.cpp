@@ -1,7 +1,9 @@
 // The host stage of the JPEG decoder (include/edet_hip.h, "baseline JPEG decode"): the marker walk and the Huffman decode of
 // SOF0 / SOF1 streams into int16 coefficients.  Plain C++17 -- no device call and no device header, so the same file builds
 // with a host compiler alone (tests/c_host/jpeg_host_check.cpp runs it under the address and undefined-behaviour sanitizers).
-// Everything behind it -- dequantisation, inverse DCT, upsampling, colour -- is csrc/jpeg.hip.
+// Everything behind it -- dequantisation, inverse DCT, upsampling, colour -- is csrc/jpeg.hip, and csrc/jpeg_scaled.hip for the
+// reduced sizes: edet_jpeg_entropy_decode_scaled differs from edet_jpeg_entropy_decode only in the headers -- a denominator per
+// image, the output size in the descriptor -- and shares everything else with it (entropy_decode below).
 //
 // The statuses, the order in which a file is refused and every stored coefficient are those of tests/jpeg_ref.py (walk,
 // check_frame, parse), statement for statement.  Every read of the input goes through a length check, every table index is
@@ -128,8 +130,16 @@ int walk(const uint8_t* d, size_t n, Parsed& P) {
   }
 }
 
-// jpeg_ref.check_frame
-int check_frame(const edet_jpeg_info_t& f, int canvas_h, int canvas_w) {
+// the smallest denominator in {1, 2, 4, 8} not above max_denom whose output ceil(height / d) x ceil(width / d) fits the
+// canvas, or `forced` if that is not 0; 0: nothing fits
+int choose_denom(int height, int width, int canvas_h, int canvas_w, int max_denom, int forced) {
+  for (int d = forced ? forced : 1; d <= (forced ? forced : max_denom); d *= 2)
+    if ((height + d - 1) / d <= canvas_h && (width + d - 1) / d <= canvas_w) return d;
+  return 0;
+}
+
+// jpeg_ref.check_frame; *denom: the denominator the image is decoded at (choose_denom)
+int check_frame(const edet_jpeg_info_t& f, int canvas_h, int canvas_w, int max_denom, int forced, int* denom) {
   if (f.kind == EDET_JPEG_KIND_PROGRESSIVE) return EDET_JPEG_PROGRESSIVE;
   if (f.kind == EDET_JPEG_KIND_OTHER)
     return (f.sof == 0xC9 || f.sof == 0xCA || f.sof == 0xCB || f.sof == 0xCD || f.sof == 0xCE || f.sof == 0xCF)
@@ -147,8 +157,8 @@ int check_frame(const edet_jpeg_info_t& f, int canvas_h, int canvas_w) {
     return EDET_JPEG_MALFORMED;
   }
   if (f.height < 1 || f.width < 1) return EDET_JPEG_MALFORMED;
-  if (f.height > canvas_h || f.width > canvas_w) return EDET_JPEG_TOO_LARGE;
-  return 0;
+  *denom = choose_denom(f.height, f.width, canvas_h, canvas_w, max_denom, forced);
+  return *denom ? 0 : EDET_JPEG_TOO_LARGE;
 }
 
 // the scan header against the frame (jpeg_ref.parse up to the tables): the Huffman table ids per component
@@ -362,13 +372,26 @@ extern "C" int edet_jpeg_info(const uint8_t* data, size_t n, edet_jpeg_info_t* o
   return 0;
 }
 
-extern "C" int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h,
-                                        int canvas_w, int16_t* coef_host, size_t coef_capacity,
-                                        edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status,
-                                        int threads) {
+namespace {
+
+// Both entry points: the headers, then the scans.  max_denom 1 and denoms NULL is the full-size decode; `scaled` says
+// whether the descriptor carries the denominator (the full-size entry point keeps writing 0 there).
+int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
+                   int max_denom, const int32_t* denoms, bool scaled, int16_t* coef_host, size_t coef_capacity,
+                   edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status, int threads) {
   if (!datas || !sizes || !coef_host || !images_host || !qtables_host || !status || batch < 1) {
-    edet_set_error("edet_jpeg_entropy_decode: null pointer or batch %d < 1", batch);
+    edet_set_error("%s: null pointer or batch %d < 1", who, batch);
     return -1;
+  }
+  if (max_denom != 1 && max_denom != 2 && max_denom != 4 && max_denom != 8) {
+    edet_set_error("%s: max_denom %d is not 1, 2, 4 or 8", who, max_denom);
+    return -1;
+  }
+  for (int b = 0; denoms && b < batch; ++b) {
+    if (denoms[b] != 1 && denoms[b] != 2 && denoms[b] != 4 && denoms[b] != 8) {
+      edet_set_error("%s: denoms[%d] = %d is not 1, 2, 4 or 8", who, b, (int)denoms[b]);
+      return -1;
+    }
   }
   if (threads <= 0) threads = batch < MAX_THREADS ? batch : MAX_THREADS;
   if (threads > MAX_THREADS) threads = MAX_THREADS;
@@ -388,12 +411,14 @@ extern "C" int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_
     memset(&im, 0, sizeof(im));
     memset(qtables_host + (size_t)b * 256, 0, 256 * sizeof(uint16_t));
     int st = walk(datas[b], sizes[b], J.P);
-    if (!st) st = check_frame(J.P.info, canvas_h, canvas_w);
+    int denom = 1;
+    if (!st) st = check_frame(J.P.info, canvas_h, canvas_w, max_denom, denoms ? (int)denoms[b] : 0, &denom);
     if (!st) st = check_scan(J.P, J.td, J.ta);
     if (!st) {
       const edet_jpeg_info_t& f = J.P.info;
-      im.height = f.height;
-      im.width = f.width;
+      im.height = (f.height + denom - 1) / denom;      // the output size; the block grids below are the file's
+      im.width = (f.width + denom - 1) / denom;
+      im.reserved = scaled ? denom : 0;
       im.components = f.components;
       im.h_max = f.components == 3 ? f.h_samp[0] : 1;
       im.v_max = f.components == 3 ? f.v_samp[0] : 1;
@@ -453,4 +478,22 @@ extern "C" int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_
     for (auto& t : pool) t.join();
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h,
+                                        int canvas_w, int16_t* coef_host, size_t coef_capacity,
+                                        edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status,
+                                        int threads) {
+  return entropy_decode("edet_jpeg_entropy_decode", datas, sizes, batch, canvas_h, canvas_w, 1, nullptr, false, coef_host,
+                        coef_capacity, images_host, qtables_host, status, threads);
+}
+
+extern "C" int edet_jpeg_entropy_decode_scaled(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h,
+                                               int canvas_w, int max_denom, const int32_t* denoms, int16_t* coef_host,
+                                               size_t coef_capacity, edet_jpeg_image_t* images_host,
+                                               uint16_t* qtables_host, int32_t* status, int threads) {
+  return entropy_decode("edet_jpeg_entropy_decode_scaled", datas, sizes, batch, canvas_h, canvas_w, max_denom, denoms, true,
+                        coef_host, coef_capacity, images_host, qtables_host, status, threads);
 }

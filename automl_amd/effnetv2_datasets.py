@@ -31,10 +31,16 @@ the fine-tuning recipe reads the ImageNet TFRecords, the only reader that is bui
 
 What the decoder refuses passes through unchanged: ImageNet holds a few CMYK JPEGs and a PNG, and jpeg.JpegDecoder's statuses
 and ``fallback=`` (a callable from the bytes to uint8 [h, w, 3]) apply as they are; without a fallback the error names the
-file and the record.  An image larger than the canvas is the decoder's TOO_LARGE and goes the same way -- full-size ImageNet
-has images of several thousand pixels a side, so a run either sizes the canvas for them, hands them to `fallback`, or waits
-for the follow-up this points at: a decode that writes only a window of the image (tf.image.decode_and_crop_jpeg,
-preprocessing.py:142), which is not built.
+file and the record.  An image larger than the canvas is the decoder's TOO_LARGE and goes the same way with max_ratio=1, the
+default.  Full-size ImageNet has images of several thousand pixels a side: reader(..., max_ratio=8) decodes such an image at
+the smallest tf.io.decode_jpeg ratio (2, 4 or 8: libjpeg's reduced-size decode, jpeg.choose_ratio) whose output fits the
+canvas, and `sizes` are then the output sizes, so nothing behind the decoder changes.  The ratio is a function of the file's
+header and the canvas alone: the order of the records and get_state() / set_state() are what they are without it.
+Deliberate difference (4): the reference decodes every image at full size and crops and resizes from that; with a ratio, the
+crop and the bicubic / bilinear resize start from libjpeg's reduced image, for the images larger than the canvas only.  An
+image that is still too large at max_ratio, or a batch whose files have more 8x8 blocks than the decoder's coefficient arena
+(jpeg.JpegDecoder's coef_blocks), is TOO_LARGE as before.  A window decode (tf.image.decode_and_crop_jpeg,
+preprocessing.py:142) is not built: the crop is drawn inside the model's step, not in the reader.
 
 Not built, raising ValueError('... is not built: ...'): every tfds-backed configuration (cifar10, cifar100, flowers,
 tfflowers, cars, imagenettfds: tensorflow_datasets is not available and its on-disk format is not read), imagenet21k (its
@@ -170,9 +176,9 @@ class _Producer(dataloader._Producer):
 class DeviceReader(object):
   """Iterator over ((raw, sizes), labels): dataloader.HostReader's batches through the reader's own jpeg.JpegDecoder."""
 
-  def __init__(self, host, canvas, depth, threads, fallback):
+  def __init__(self, host, canvas, depth, threads, fallback, max_ratio=1):
     self._host, self._canvas = host, (int(canvas[0]), int(canvas[1]))
-    self._depth, self._threads, self._fallback = depth, threads, fallback
+    self._depth, self._threads, self._fallback, self._max_ratio = depth, threads, fallback, max_ratio
     self._decoder = None
     self.files = host.files
 
@@ -184,7 +190,9 @@ class DeviceReader(object):
     if self._decoder is None:
       from automl_amd import jpeg
       threads = None if self._threads is None else min(int(self._threads), len(hb.images))
-      self._decoder = jpeg.JpegDecoder(len(hb.images), self._canvas[0], self._canvas[1], depth=self._depth, threads=threads)
+      ratio = {} if self._max_ratio == 1 else {'max_ratio': self._max_ratio}      # (1: the decoder as it is built without it)
+      self._decoder = jpeg.JpegDecoder(len(hb.images), self._canvas[0], self._canvas[1], depth=self._depth, threads=threads,
+                                       **ratio)
     try:
       raw, sizes = self._decoder.decode(hb.images, fallback=self._fallback)
     except ValueError as e:
@@ -272,9 +280,12 @@ class ImageNetInput(object):
     producer.open_first()
     return dataloader.HostReader(producer, depth, False)
 
-  def reader(self, batch_size, canvas=None, shard=None, depth=2, threads=None, fallback=None, verify=True):
+  def reader(self, batch_size, canvas=None, shard=None, depth=2, threads=None, fallback=None, verify=True, max_ratio=1):
     if canvas is None or len(canvas) != 2:
       raise ValueError('canvas=(Hc, Wc) is needed: the slot every decoded image is written into (jpeg.JpegDecoder)')
-    return DeviceReader(self.host_reader(batch_size, shard, depth, threads, verify), canvas, depth, threads, fallback)
+    if max_ratio not in (1, 2, 4, 8):
+      raise ValueError('max_ratio=%r: 1, 2, 4 or 8 (jpeg.JpegDecoder)' % (max_ratio,))
+    return DeviceReader(self.host_reader(batch_size, shard, depth, threads, verify), canvas, depth, threads, fallback,
+                        max_ratio)
 
   __call__ = reader

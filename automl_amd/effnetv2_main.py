@@ -6,7 +6,8 @@
 
 The flags of efficientnetv2/cflags.py that mean something here keep their names: ``--model_name``, ``--dataset_cfg``,
 ``--hparam_str``, ``--data_dir``, ``--model_dir``, ``--mode``.  ``--canvas=HxW`` (the slot the reader's JPEG decoder writes
-every image into), ``--dtype`` (default: bf16 with runtime.mixed_precision, else f32) and ``--seed`` (the model's, its input
+every image into), ``--jpeg_max_ratio`` (1, 2, 4 or 8: an image larger than the canvas is decoded at the smallest
+tf.io.decode_jpeg ratio that fits it; default 1, full size only), ``--dtype`` (default: bf16 with runtime.mixed_precision, else f32) and ``--seed`` (the model's, its input
 draws' and the reader's) are this project's own.
 
 The configuration is assembled as :121-125 does: ``base_config()`` -- hparams.base_config's train / eval / data / runtime
@@ -101,6 +102,9 @@ def define_flags():
   ap.add_argument('--mode', default='train', choices=['train', 'traineval', 'eval'], help='train, traineval or eval.')
   boolean('export_to_tpu', 'refused: there is no TPU path')
   ap.add_argument('--canvas', type=_canvas, default=(512, 512), help='HxW of the slot every decoded image is written into')
+  ap.add_argument('--jpeg_max_ratio', type=int, default=1, choices=[1, 2, 4, 8],
+                  help='the largest ratio (tf.io.decode_jpeg) the reader may decode an image at so that it fits --canvas; 1: '
+                       'full size only, a larger image is refused; 8 is recommended for full-size ImageNet')
   ap.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help='storage dtype of the activations')
   ap.add_argument('--seed', type=int, default=0, help='seed of the model, its input draws and the reader')
   return ap
@@ -216,7 +220,7 @@ def get_dataset(flags, config, plan, is_training):
   split = plan['train_split'] if is_training else plan['eval_split']
   batch = config.train.batch_size if is_training else config.eval.batch_size
   ds = effnetv2_datasets.build_dataset_input(is_training, None, None, flags.data_dir, split, config.data, seed=flags.seed)
-  return ds(batch, canvas=flags.canvas)
+  return ds(batch, canvas=flags.canvas, max_ratio=flags.jpeg_max_ratio)
 
 
 class _WithoutHead(object):

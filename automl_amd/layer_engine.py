@@ -16,6 +16,7 @@ Reference structure followed: efficientdet/backbone/efficientnet_model.py:360-41
 import collections
 import contextlib
 import ctypes
+import gc
 import re
 import math
 
@@ -269,13 +270,24 @@ def capture_graph(arena, body, pool=None):
   """body() captured into a new hipGraph.  thread_local: other threads of the process (the RCCL watchdog) may touch the
   HIP runtime meanwhile.  The capture pass runs the body's host bookkeeping once WITHOUT executing anything, so the
   arena's counters are put back where they were (also when the capture raises); ParamArena.count_step accounts for every
-  replay."""
+  replay.
+  The cyclic garbage collector stays out of the capture.  torch.cuda.graph collected on entry up to torch 2.8 and does so now
+  only with TORCH_CUDAGRAPH_GC set, so a dead cycle that owns device objects -- a model that was dropped with its captured
+  graphs, events and pinned buffers, as a test or a driver that builds a second model leaves behind -- could be finalised by
+  an automatic collection in the middle of the body: releasing a graph and its pool, or recording the event behind a pinned
+  buffer, while a stream of this thread is capturing is an error raised inside a destructor, which ends the process.  So what
+  is dead is collected before the capture begins, and automatic collection is off until it has ended."""
   counters = (arena.version, arena.step_count)
   graph = torch.cuda.CUDAGraph()
+  gc.collect()
+  collecting = gc.isenabled()
+  gc.disable()
   try:
     with torch.cuda.graph(graph, pool=pool, capture_error_mode='thread_local'):
       body()
   finally:
+    if collecting:
+      gc.enable()
     arena.version, arena.step_count = counters
   return graph
 

@@ -951,7 +951,7 @@ typedef struct edet_jpeg_image { /* 80 bytes, one per image: written by the host
   int32_t first_block[3];        /* per component: where its blocks start in BOTH arenas, in blocks: coefficient element
                                     64 first_block, plane byte 64 first_block.  The components of an image are adjacent.  */
   int32_t total_blocks;          /* of the image: the sum of blocks_w blocks_h                                             */
-  int32_t reserved;
+  int32_t reserved;              /* 0; edet_jpeg_entropy_decode_scaled: the denominator 1, 2, 4 or 8 (height, width: the output) */
 } edet_jpeg_image_t;
 /* edet_jpeg_info (host): walks the markers of `data` up to the first SOS.  Fails (-1) on a stream without SOI, with a bad
  * segment length, with two frame headers, or that ends before SOS; every read is bounds-checked.
@@ -986,6 +986,44 @@ int edet_jpeg_idct(const int16_t* coef, const edet_jpeg_image_t* images_dev, con
                    int max_blocks, uint8_t* planes, size_t plane_capacity, void* stream);
 int edet_jpeg_color(const uint8_t* planes, const edet_jpeg_image_t* images_dev, int batch, int canvas_h, int canvas_w,
                     size_t plane_capacity, uint8_t* raw, void* stream);
+
+/* ---- JPEG decode at reduced size (tf.io.decode_jpeg's `ratio`; libjpeg's scale_denom 2, 4, 8: jdmaster.c, jidctred.c,
+ * jdsample.c) ----------------------------------------------------------------------------------------------------------------
+ * The same split and the same arenas as above, through three entry points of their own (csrc/jpeg_host.cpp, csrc/
+ * jpeg_scaled.hip); the full-size ones above are untouched.  With denom in {1, 2, 4, 8} and m = 8 / denom the output is
+ * ceil(height / denom) x ceil(width / denom), and a block of component c is inverse-transformed to s_c x s_c samples:
+ * s_c = m, except the chroma of a 4:2:0 file at m < 8, which is 2 m and then needs no upsampling.  Restated in
+ * tests/jpeg_scaled_ref.py, which is compared with Pillow's draft mode (libjpeg-turbo) byte for byte.
+ * edet_jpeg_entropy_decode_scaled (host, blocks until done): edet_jpeg_entropy_decode with a denominator per image.  denoms
+ * NULL: each image gets the smallest of 1, 2, 4, 8 not above max_denom (itself 1, 2, 4 or 8) whose output fits the canvas;
+ * none fits: EDET_JPEG_TOO_LARGE.  denoms int32 [batch]: each image gets denoms[b] (max_denom does not bound it), and an
+ * output that does not fit is EDET_JPEG_TOO_LARGE.  The descriptor's height and width are the OUTPUT size and its `reserved`
+ * field is the denominator (edet_jpeg_entropy_decode writes 0, which the kernels below read as 1); block grids, first_block,
+ * total_blocks, the quantisation tables and every coefficient are the full-size stage's: 64 int16 per block whatever the
+ * denominator, so coef_capacity bounds the blocks of the FILES, not of the outputs.  The call fails (-1) on a null pointer,
+ * batch < 1, a max_denom or a denoms[b] outside {1, 2, 4, 8}; nothing is written then.
+ * edet_jpeg_idct_scaled (device, one launch): edet_jpeg_idct's arguments.  The plane of component c is uint8 [blocks_h s_c]
+ * [blocks_w s_c] at byte 64 first_block[c] -- it starts where the full-size plane would and is never longer.  Per block,
+ * coefficient x table entry first, then by s_c -- 8: edet_jpeg_idct's transform.  4 (jpeg_idct_4x4): a pass reads entries 0-3
+ * and 5-7; t0 = v0 << 14, t2 = 15137 v2 - 6270 v6, t10 = t0 + t2, t12 = t0 - t2, a = -1730 v7 + 11893 v5 - 17799 v3 + 8697 v1,
+ * b = -4176 v7 - 4926 v5 + 7373 v3 + 20995 v1, outputs (t10 + b, t12 + a, t12 - a, t10 - b), each (x + (1 << (n - 1))) >> n
+ * with n = 12 behind the columns (all but column 4) and 19 behind rows 0-3.  2 (jpeg_idct_2x2): entries 0, 1, 3, 5, 7;
+ * t10 = v0 << 15, t0 = -5906 v7 + 6967 v5 - 10426 v3 + 29692 v1, outputs (t10 + t0, t10 - t0), n = 13, then 20.  1: (c0 q0 + 4)
+ * >> 3.  Then + 128, clamped to 0 .. 255.  Sums, products and left shifts wrap at 32 bits, right shifts are arithmetic.  A
+ * descriptor that fails edet_jpeg_idct's check, whose `reserved` is none of 0, 1, 2, 4, 8, or whose output does not lie inside
+ * its reduced planes is treated as refused before anything is read or written.  Alignment as for edet_jpeg_idct.
+ * edet_jpeg_color_scaled (device, one launch): edet_jpeg_color's arguments and contract -- the whole canvas is written, zero
+ * outside height x width, zero for a refused descriptor.  Chroma is upsampled by (h_max s_0 / s_1, v_max s_0 / s_1) = (1, 1),
+ * (2, 1) or (2, 2).  Where that is not (1, 1), edet_jpeg_color's h2v1 / h2v2 formulas apply only if m > 1 AND the component
+ * has more than two real columns, ceil(width / 2) of the output; otherwise (jdsample.c) every sample is repeated twice in its
+ * row, and every row twice for (2, 2).  Colour conversion as in edet_jpeg_color. */
+int edet_jpeg_entropy_decode_scaled(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
+                                    int max_denom, const int32_t* denoms, int16_t* coef_host, size_t coef_capacity,
+                                    edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status, int threads);
+int edet_jpeg_idct_scaled(const int16_t* coef, const edet_jpeg_image_t* images_dev, const uint16_t* qtables_dev, int batch,
+                          int max_blocks, uint8_t* planes, size_t plane_capacity, void* stream);
+int edet_jpeg_color_scaled(const uint8_t* planes, const edet_jpeg_image_t* images_dev, int batch, int canvas_h, int canvas_w,
+                           size_t plane_capacity, uint8_t* raw, void* stream);
 
 /* ---- TFRecord input (dataloader.py:404-460 reads TFRecord shards of tf.train.Example; object_detection/
  * tf_example_decoder.py:30-169 names the keys) -- HOST only, csrc/tfrecord_host.cpp: plain C++, no device call.  Every input

@@ -10,7 +10,11 @@ tiles (16 KB), so its Huffman stage is far shorter than a photograph's --, one J
                  stage of the next: wall clock per batch with one synchronisation at the end -> images per second;
   pillow         where Pillow is importable: Image.open(...).convert('RGB') of the same bytes on a pool of as many worker
                  threads (its decoder releases the interpreter lock), the independent baseline -> images per second.
-No ratio is asserted: the numbers are the result."""
+`--ratio` 2, 4 or 8 decodes every image at that tf.io.decode_jpeg ratio into a canvas of the reduced size, through the three
+*_scaled entry points (csrc/jpeg_scaled.hip); `--max_ratio` alone (with --ratio 1) runs full-size images through the same
+entry points.  With both at 1, the default, the full-size entry points are measured as before.  The host stage and the copy
+move the file's coefficients whatever the ratio; only the two kernels shrink.
+No ratio between two timings is asserted: the numbers are the result."""
 import argparse
 import io
 import json
@@ -60,16 +64,34 @@ def main(args):
     h, w = rgb.shape[:2]
   b = args.batch
   datas = [data] * b
+  ratio, max_ratio = args.ratio, max(args.ratio, args.max_ratio)
+  scaled = max_ratio > 1
+  ratios = [ratio] * b if scaled else None
   out = {'batch': b, 'height': h, 'width': w, 'file': os.path.basename(args.file) if args.file else 'big_480x640_420',
-         'file_bytes': len(data), 'reps': args.reps}
-  dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2)
+         'file_bytes': len(data), 'reps': args.reps, 'ratio': ratio, 'max_ratio': max_ratio,
+         'entry_points': 'scaled' if scaled else 'full size'}
+  file_blocks = jpeg.worst_blocks(h, w)
+  h, w = jpeg.scaled_size(h, w, ratio)      # the canvas: the output, exactly
+  out['canvas'] = [h, w]
+  if scaled:
+    dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2, max_ratio=max_ratio, coef_blocks=b * file_blocks)
+  else:
+    dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2)
   slot = dec._slots[0]
+  idct, color = ('edet_jpeg_idct_scaled', 'edet_jpeg_color_scaled') if scaled else ('edet_jpeg_idct', 'edet_jpeg_color')
+
+  def host_stage(threads):
+    if scaled:
+      jpeg.entropy_decode_scaled(datas, h, w, max_ratio, ratios, slot.coef_host, slot.images_host, slot.qtables_host,
+                                 slot.status, threads)
+    else:
+      jpeg.entropy_decode(datas, h, w, slot.coef_host, slot.images_host, slot.qtables_host, slot.status, threads)
   out['host_ms'] = {}
   for threads in (1, 4, 16):
     times = []
     for _ in range(args.reps + 1):
       t0 = time.perf_counter()
-      jpeg.entropy_decode(datas, h, w, slot.coef_host, slot.images_host, slot.qtables_host, slot.status, threads)
+      host_stage(threads)
       times.append((time.perf_counter() - t0) * 1e3)
     out['host_ms'][str(threads)] = dict(stats(times[1:]), images_per_s=round(b / (float(np.median(times[1:])) * 1e-3), 1))
   desc = jpeg.descriptors(slot.images_host, b)
@@ -77,6 +99,7 @@ def main(args):
   used = max(d.first_block[0] + d.total_blocks for d in desc)
   most = max(d.total_blocks for d in desc)
   out['coefficient_bytes'] = used * 128
+  out['blocks_per_image'] = most
 
   def copy():
     slot.coef[:used * 64].copy_(slot.coef_host[:used * 64], non_blocking=True)
@@ -88,20 +111,21 @@ def main(args):
   torch.cuda.synchronize()
   out['copy_ms'] = events(copy, 1, args.reps)
   out['copy_GBps'] = round(used * 128 / (out['copy_ms']['median_ms'] * 1e-3) / 1e9, 1)
-  out['idct_ms'] = events(lambda: call('edet_jpeg_idct', ptr(slot.coef), ptr(slot.images), ptr(slot.qtables), b, most,
+  out['idct_ms'] = events(lambda: call(idct, ptr(slot.coef), ptr(slot.images), ptr(slot.qtables), b, most,
                                        ptr(slot.planes), dec.blocks * 64, st), args.launches, args.reps)
-  out['color_ms'] = events(lambda: call('edet_jpeg_color', ptr(slot.planes), ptr(slot.images), b, h, w, dec.blocks * 64,
+  out['color_ms'] = events(lambda: call(color, ptr(slot.planes), ptr(slot.images), b, h, w, dec.blocks * 64,
                                         ptr(raw), st), args.launches, args.reps)
-  assert rgb is None or np.array_equal(raw[b - 1].cpu().numpy(), rgb), 'the decoded batch differs from the fixture'
+  out['idct_ns_per_block'] = round(out['idct_ms']['median_ms'] * 1e6 / (b * most), 3)
+  assert rgb is None or ratio > 1 or np.array_equal(raw[b - 1].cpu().numpy(), rgb), 'the decoded batch differs from the fixture'
   sizes = np.zeros((b, 2), np.int32)
   for _ in range(2):
-    dec.decode(datas, out=raw, sizes_out=sizes)
+    dec.decode(datas, out=raw, sizes_out=sizes, ratios=ratios)
   torch.cuda.synchronize()
   times = []
   for _ in range(args.reps):
     t0 = time.perf_counter()
     for _ in range(args.batches):
-      dec.decode(datas, out=raw, sizes_out=sizes)
+      dec.decode(datas, out=raw, sizes_out=sizes, ratios=ratios)
     torch.cuda.synchronize()
     times.append((time.perf_counter() - t0) * 1e3 / args.batches)
   out['end_to_end'] = dict(stats(times), threads=args.threads, depth=2, batches_per_rep=args.batches,
@@ -112,14 +136,18 @@ def main(args):
     out['pillow'] = None
   else:
     def one(d):
-      return np.asarray(Image.open(io.BytesIO(d)).convert('RGB'))
+      im = Image.open(io.BytesIO(d))
+      if ratio > 1:
+        im.draft('RGB', (im.size[0] // ratio, im.size[1] // ratio))      # libjpeg's scale_denom
+      return np.asarray(im.convert('RGB'))
     with ThreadPoolExecutor(max_workers=args.threads) as pool:
       times = []
       for _ in range(args.reps + 1):
         t0 = time.perf_counter()
         done = list(pool.map(one, datas))
         times.append((time.perf_counter() - t0) * 1e3)
-    assert np.array_equal(done[0], raw[0].cpu().numpy()), 'Pillow and the decoder differ'
+    # (draft mode does not reach a ratio larger than the image's smaller side: then the sizes differ and nothing is compared)
+    assert done[0].shape != tuple(raw[0].shape) or np.array_equal(done[0], raw[0].cpu().numpy()), 'Pillow and the decoder differ'
     out['pillow'] = dict(stats(times[1:]), threads=args.threads,
                          images_per_s=round(b / (float(np.median(times[1:])) * 1e-3), 1))
   print(json.dumps(out))
@@ -128,6 +156,9 @@ def main(args):
 if __name__ == '__main__':
   ap = argparse.ArgumentParser()
   ap.add_argument('--file', default='')
+  ap.add_argument('--ratio', type=int, default=1, choices=[1, 2, 4, 8], help='decode every image at this ratio')
+  ap.add_argument('--max_ratio', type=int, default=1, choices=[1, 2, 4, 8],
+                  help="the decoder's max_ratio; above 1 the *_scaled entry points run, also for --ratio 1")
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--threads', type=int, default=16)
   ap.add_argument('--reps', type=int, default=7)
