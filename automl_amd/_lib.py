@@ -178,6 +178,8 @@ SIGNATURES = {
                           c_float, c_float, c_float, c_void_p],
     'edet_opt_rmsprop_ema': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                              c_float, c_float, c_float, c_void_p],
+    'edet_opt_lion_ema': [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                          c_float, c_float, c_float, c_void_p],
     'edet_softmax_xent': [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                           ctypes.c_size_t, c_int, c_void_p],
     'edet_dropout_cast': [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],

@@ -82,9 +82,9 @@ struct edet_net {
   std::vector<Var> vars;                 // the variable table, in the Python arena's creation order
   std::map<std::string, int64_t> var_index;
   bool has_vars = false;
-  int optimizer = -1;                    // property "optimizer": 0 sgd, 1 adam; -1 = a plan without it
+  int optimizer = -1;                    // property "optimizer": 0 sgd, 1 adam, 2 lion; -1 = a plan without it
   int64_t iterations = 0;
-  double beta1 = 0.0, beta2 = 0.0;       // Adam plans
+  double beta1 = 0.0, beta2 = 0.0;       // Adam plans (Lion's constants are arguments of the recorded update launch)
   edet_allreduce_fn allreduce = nullptr;
   void* allreduce_ctx = nullptr;
 };
@@ -425,6 +425,7 @@ extern "C" int edet_train_step(edet_net_t* net, float learning_rate, float ema_d
     const double alpha = (double)learning_rate * sqrt(1.0 - pow(net->beta2, t)) / (1.0 - pow(net->beta1, t));
     h[0] = (float)alpha;
   }
+  // (SGD and Lion -- optimizer 0 and 2 -- take the schedule's rate as it is: Lion has no bias correction)
   const hipError_t e = hipMemcpyAsync((char*)net->bufs[it->second.buf] + it->second.off, h, sizeof(h), hipMemcpyHostToDevice,
                                       reinterpret_cast<hipStream_t>(stream));
   EDET_CHECK(e == hipSuccess, "edet_train_step: hipMemcpyAsync: %s", hipGetErrorString(e));

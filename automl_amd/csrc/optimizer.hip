@@ -206,6 +206,39 @@ struct RmspropRule {
   }
 };
 
+// Lion (lion/lion_tf2.py:60-74, _resource_apply_dense): c = m b1 + g (1 - b1); w -= lr (sign(c) + w wd), with the OLD m;
+// m = m b2 + g (1 - b2).  One slot.  Every product and sum is one rounded float32 operation in the order the reference
+// writes them -- nothing contracts into an FMA here, the EMA tail included -- so the result equals a numpy float32
+// restatement bit for bit (tests/lion_ref.py).  sign(+-0) = 0 and sign(NaN) = NaN: a diverged run stays visible.
+// This file is compiled with the default contraction, and HIP's __fmul_rn / __fadd_rn / __fsub_rn are plain operators that
+// contract like any other (the compiler fused them here when they were tried): the three helpers below are those operators
+// under `fp contract(off)`, which the default mode (fast-honor-pragmas) keeps out of every FMA after inlining.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
+struct LionRule {
+  static constexpr int SLOTS = 1;
+  float b1, b2, wd;
+  __device__ __forceinline__ void operator()(float g, float& m, float&, float& w, float& em, float lr, float decay,
+                                             bool has_ema) const {
+    const float c = add_rn(mul_rn(m, b1), mul_rn(g, sub_rn(1.f, b1)));
+    const float s = c > 0.f ? 1.f : (c < 0.f ? -1.f : (c == 0.f ? 0.f : c));
+    w = sub_rn(w, mul_rn(lr, add_rn(s, mul_rn(w, wd))));
+    m = add_rn(mul_rn(m, b2), mul_rn(g, sub_rn(1.f, b2)));
+    if (has_ema) em = sub_rn(em, mul_rn(sub_rn(1.f, decay), sub_rn(em, w)));
+  }
+};
+
 template <typename Rule>
 __device__ __forceinline__ void update_walk(Rule rule, float* params, const float* grads, float* slot_a, float* slot_b,
                                             float* ema, const int64_t* seg_off, const float* seg_factor,
@@ -275,6 +308,12 @@ __global__ __launch_bounds__(THREADS, 8) void k_rmsprop_ema(float* params, const
   update_walk(RmspropRule{rho, momentum, eps}, params, grads, ms, mom, ema, seg_off, seg_factor, seg_flags, hyper);
 }
 
+__global__ __launch_bounds__(THREADS, 8) void k_lion_ema(float* params, const float* grads, float* m, float* ema,
+                                                     const int64_t* seg_off, const float* seg_factor,
+                                                     const int32_t* seg_flags, const float* hyper, float b1, float b2, float wd) {
+  update_walk(LionRule{b1, b2, wd}, params, grads, m, nullptr, ema, seg_off, seg_factor, seg_flags, hyper);
+}
+
 }  // namespace
 
 extern "C" int edet_l2_loss(const float* params, const int64_t* seg_offsets, const int32_t* seg_flags, int nseg,
@@ -338,5 +377,15 @@ extern "C" int edet_opt_rmsprop_ema(float* params, const float* grads, float* ms
   edet_launch(k_rmsprop_ema, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, grads, ms, mom, ema, seg_offsets,
               seg_factor, seg_flags, hyper_dev, rho, momentum, epsilon);
   EDET_LAUNCH_CHECK("edet_opt_rmsprop_ema");
+  return 0;
+}
+
+extern "C" int edet_opt_lion_ema(float* params, const float* grads, float* m, float* ema,
+                                 const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
+                                 const float* hyper_dev, float beta1, float beta2, float wd, void* stream) {
+  EDET_CHECK(params && grads && m && seg_offsets && hyper_dev && nseg > 0, "edet_opt_lion_ema: bad arguments");
+  edet_launch(k_lion_ema, dim3(nseg, OPT_SPLIT), dim3(THREADS), 0, to_stream(stream), params, grads, m, ema, seg_offsets,
+              seg_factor, seg_flags, hyper_dev, beta1, beta2, wd);
+  EDET_LAUNCH_CHECK("edet_opt_lion_ema");
   return 0;
 }

@@ -204,7 +204,7 @@ bool parse_optimizer(PlanFile* pf, std::string* err) {
   };
   const int64_t optimizer = prop("optimizer", -1);
   pf->iterations = prop("iterations", 0);
-  PLAN_CHECK(optimizer >= -1 && optimizer <= 1 && pf->iterations >= 0, "bad optimizer properties");
+  PLAN_CHECK(optimizer >= -1 && optimizer <= 2 && pf->iterations >= 0, "bad optimizer properties");
   pf->optimizer = (int)optimizer;
   if (pf->optimizer == 1) {
     PLAN_CHECK(find_name(*pf, "adam_beta1_bits", true) && find_name(*pf, "adam_beta2_bits", true),
@@ -213,6 +213,18 @@ bool parse_optimizer(PlanFile* pf, std::string* err) {
     memcpy(&pf->beta1, &b1, 8);
     memcpy(&pf->beta2, &b2, 8);
     PLAN_CHECK(pf->beta1 >= 0.0 && pf->beta1 < 1.0 && pf->beta2 >= 0.0 && pf->beta2 < 1.0, "bad Adam betas");
+  }
+  if (pf->optimizer == 2) {
+    // Lion: the constants are arguments of the recorded update launch; the properties say what the plan was recorded with
+    PLAN_CHECK(find_name(*pf, "lion_beta1_bits", true) && find_name(*pf, "lion_beta2_bits", true) &&
+                   find_name(*pf, "lion_wd_bits", true),
+               "a Lion plan without its beta and wd properties");
+    const int64_t b1 = prop("lion_beta1_bits", 0), b2 = prop("lion_beta2_bits", 0), wd = prop("lion_wd_bits", 0);
+    memcpy(&pf->beta1, &b1, 8);
+    memcpy(&pf->beta2, &b2, 8);
+    memcpy(&pf->lion_wd, &wd, 8);
+    PLAN_CHECK(pf->beta1 >= 0.0 && pf->beta1 < 1.0 && pf->beta2 >= 0.0 && pf->beta2 < 1.0 && pf->lion_wd >= 0.0,
+               "bad Lion constants");
   }
   return true;
 }

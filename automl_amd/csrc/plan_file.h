@@ -97,9 +97,10 @@ struct PlanFile {
   std::vector<Program> programs;
   bool has_vars = false;
   std::vector<Var> vars;
-  int optimizer = -1;                         // property "optimizer": 0 sgd, 1 adam; -1 = a plan without it
+  int optimizer = -1;                         // property "optimizer": 0 sgd, 1 adam, 2 lion; -1 = a plan without it
   int64_t iterations = 0;
-  double beta1 = 0.0, beta2 = 0.0;            // Adam plans
+  double beta1 = 0.0, beta2 = 0.0;            // Adam and Lion plans
+  double lion_wd = 0.0;                       // Lion plans
 };
 
 struct StateRecord {

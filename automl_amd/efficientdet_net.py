@@ -38,6 +38,7 @@ class EfficientDetNet(object):
     self._engines = {}
 
   MAX_ENGINES = 2      # activation buffers of that many (batch, image size) shapes stay allocated
+  _lion = None         # optimizer='lion': {'beta_2':, 'wd':} for the engines (train_lib.EfficientDetNetTrain.set_lion)
 
   def _ensure_engine(self, batch, height, width):
     """The executor for this batch / image shape.  Buffers are per shape (static shapes); the variables, the
@@ -50,7 +51,7 @@ class EfficientDetNet(object):
       arena = self.engine.arena if self.engine is not None else None
       e = engine_lib.Engine(self.config, batch, (height, width), dtype=self._dtype, device=self._device,
                             seed=self._seed, params=self._init_params, stochastic_depth=self._stochastic_depth,
-                            arena=arena)
+                            arena=arena, **({'lion': self._lion} if self._lion else {}))
       if self._init_ema and arena is None:
         e.arena.set_ema_params(self._init_ema)      # shadows restored before the model was built (util_keras.restore_ckpt)
         self._init_ema = None

@@ -107,6 +107,9 @@ def define_flags():
                        'full size only, a larger image is refused; 8 is recommended for full-size ImageNet')
   ap.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help='storage dtype of the activations')
   ap.add_argument('--seed', type=int, default=0, help='seed of the model, its input draws and the reader')
+  ap.add_argument('--lion_beta2', type=float, default=None, help='train.optimizer=lion: beta_2 (default 0.99)')
+  ap.add_argument('--lion_wd', type=float, default=None,
+                  help='train.optimizer=lion: the decoupled weight decay wd (default 0), on every variable')
   return ap
 
 
@@ -207,12 +210,16 @@ def build_model(flags, config, plan):
       warmup_epochs=train.lr_warmup_epoch, decay_factor=train.lr_decay_factor, lr_decay_type=train.lr_sched,
       total_steps=plan['total_steps'], minimal_lr=plan['scaled_lr_min'])
   dtype = flags.dtype or ('bf16' if config.runtime.mixed_precision else 'f32')
+  lion = {k: v for k, v in (('lion_beta2', getattr(flags, 'lion_beta2', None)), ('lion_wd', getattr(flags, 'lion_wd', None)))
+          if v is not None}
+  if lion and str(train.optimizer).lower() != 'lion':
+    raise ValueError('--lion_beta2 / --lion_wd need train.optimizer=lion, this run has %r' % (train.optimizer,))
   return effnetv2_train.TrainableModel(
       config.model.model_name, config.model.as_dict(), weight_decay=train.weight_decay, optimizer=train.optimizer,
       learning_rate=learning_rate, label_smoothing=train.label_smoothing, dtype=dtype, seed=flags.seed,
       mixup_alpha=data.mixup_alpha, cutmix_alpha=data.cutmix_alpha, augname=data.augname,
       ra_num_layers=data.ra_num_layers, ra_magnitude=15 if data.ram is None else data.ram, image_size=plan['train_size'],
-      eval_image_size=plan['eval_size'])
+      eval_image_size=plan['eval_size'], **lion)
 
 
 def get_dataset(flags, config, plan, is_training):

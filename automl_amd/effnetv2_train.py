@@ -69,14 +69,21 @@ from automl_amd import train_lib
 from automl_amd import util_keras
 from automl_amd import utils
 from automl_amd import v2_preprocessing
-from automl_amd.layer_engine import LayerEngine, Update, capture_graph
+from automl_amd.layer_engine import LION_BETA2, LION_WD, LayerEngine, Update, capture_graph, lion_options
 
-OPTIMIZERS = ('rmsprop', 'momentum', 'sgd', 'adam')
+OPTIMIZERS = ('rmsprop', 'momentum', 'sgd', 'adam', 'lion')
 
 
-def build_update(optimizer, momentum):
+def build_update(optimizer, momentum, lion_beta2=LION_BETA2, lion_wd=LION_WD):
   """build_tf2_optimizer (main_tf2.py:36-59) as the engine's update description: 'rmsprop' (rho 0.9, momentum, epsilon
-  0.001), 'momentum' / 'sgd' (Keras SGD; the trainer passes momentum 0 for 'sgd'), 'adam' (tf.keras.optimizers.Adam(learning_rate) defaults)."""
+  0.001), 'momentum' / 'sgd' (Keras SGD; the trainer passes momentum 0 for 'sgd'), 'adam' (tf.keras.optimizers.Adam(learning_rate) defaults);
+  and 'lion' (lion/lion_tf2.py's Lion, what a user of the reference passes to Keras in the optimizer's place: beta_1 = momentum,
+  beta_2, decoupled decay wd)."""
+  if optimizer == 'lion':
+    beta_2, wd = lion_options({'beta_2': lion_beta2, 'wd': lion_wd})
+    if not 0.0 <= momentum < 1.0:
+      raise ValueError('lion: beta_1 (momentum) %r outside [0, 1)' % (momentum,))
+    return Update('lion', momentum, beta_2, wd=wd)
   if optimizer == 'rmsprop':
     return Update('rmsprop', momentum, epsilon=0.001, rho=0.9)
   if optimizer == 'adam':
@@ -274,7 +281,8 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   learning_rate: a float or a callable of the iteration count (WarmupLearningRateSchedule).  use_graph: capture the step
   at its second call for a batch shape and replay it afterwards; False = every launch eager (the tests compare both).
   check_device_labels: also range-check labels that arrive as device tensors (one synchronisation per step).
-  ``momentum`` is build_tf2_optimizer's (0.9), used by 'rmsprop' and 'momentum'.
+  ``momentum`` is build_tf2_optimizer's (0.9), used by 'rmsprop' and 'momentum'; optimizer='lion' takes it as beta_1, with
+  ``lion_beta2`` and ``lion_wd`` (lion_tf2.Lion's beta_2 and wd; the decay reaches every variable, as the reference's does).
   mixup_alpha / cutmix_alpha: the Beta parameters of datasets.py:244-301 (0 = off, the default: the step is then exactly
   the unmixed one); a named model's own pair is mix_alphas(model_name).
   augname: None (the default: nothing changes) or 'randaug' -- RandAugment of ra_num_layers layers at ra_magnitude on the
@@ -289,7 +297,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   def __init__(self, model_name='efficientnetv2-s', model_config=None, name=None, weight_decay=0.0, optimizer='rmsprop',
                learning_rate=0.016, label_smoothing=0.0, ema_decay=None, momentum=0.9, use_graph=True, check_device_labels=False,
                mixup_alpha=0.0, cutmix_alpha=0.0, augname=None, ra_num_layers=2, ra_magnitude=15, image_size=None,
-               eval_image_size=None, transformations='crop|flip', **kwargs):
+               eval_image_size=None, transformations='crop|flip', lion_beta2=LION_BETA2, lion_wd=LION_WD, **kwargs):
     super().__init__(model_name=model_name, model_config=model_config, include_top=True, name=name or model_name, **kwargs)
     optimizer = str(optimizer).lower()
     if optimizer not in OPTIMIZERS:
@@ -303,7 +311,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.weight_decay = float(weight_decay)
     self.optimizer = optimizer
     self.momentum = 0.0 if optimizer == 'sgd' else float(momentum)
-    self.update = build_update(optimizer, self.momentum)      # what every executor of this model is built with
+    self.update = build_update(optimizer, self.momentum, lion_beta2, lion_wd)      # what every executor of this model is built with
     self.learning_rate = learning_rate
     self.label_smoothing = float(label_smoothing)
     self.ema_decay = None if not ema_decay else float(ema_decay)
@@ -763,6 +771,11 @@ def _model_identity(model):
           'optimizer': model.optimizer}
 
 
+def _lion_identity(model):
+  """The two Lion scalars the state file carries besides the optimizer's name; None for the other optimizers."""
+  return train_lib.lion_identity(model.update)
+
+
 def save_train_state(model, path, reader=None):
   """Writes <ckpt prefix>.train_state.npz next to a checkpoint, in train_lib.save_train_state's conventions: get_optimizer_state()
   in full (both slots, the shadows, iterations, rng_state, mix_rng_state, randaug_rng_state, crop_rng_state), the model's
@@ -776,6 +789,8 @@ def save_train_state(model, path, reader=None):
     state = model.get_optimizer_state()
   arrays, meta = {}, {'format': train_lib.TRAIN_STATE_FORMAT, 'kind': TRAIN_STATE_KIND}
   meta.update(_model_identity(model))
+  if _lion_identity(model) is not None:
+    meta['lion'] = _lion_identity(model)
   for k, v in state.items():
     if k in _ARRAY_KEYS:
       arrays[k] = np.asarray(v)
@@ -806,6 +821,8 @@ def restore_train_state(model, path, reader=None):
   what = {'num_variables': 'variables', 'arena_length': 'arena elements', 'optimizer': 'as optimizer'}
   diff = ['%s %s, this model %s' % (meta.get(k), what[k], mine[k]) for k in ('num_variables', 'arena_length', 'optimizer')
           if meta.get(k) != mine[k]]
+  if not diff:
+    diff = train_lib.lion_difference(meta.get('lion'), _lion_identity(model))
   if diff:
     raise ValueError('%s is the training state of another model: the file has %s' % (path, '; '.join(diff)))
   if reader is not None:

@@ -14,23 +14,31 @@ import torch
 from automl_amd import _lib
 from automl_amd import netspec as netspec_lib
 from automl_amd._lib import ACT_NONE, ACT_SWISH, EDET_BF16, RS_IDENTITY, RS_POOL, RS_UP2, call, ptr
-from automl_amd.layer_engine import BN, LayerEngine, ParamArena, Raw, Update, View, capture_graph  # noqa: F401
+from automl_amd.layer_engine import BN, LayerEngine, ParamArena, Raw, Update, View, capture_graph, lion_options  # noqa: F401
 
 
 class Engine(LayerEngine):
   """Builds buffers for (config, batch, image size, dtype) and runs forward / backward / update."""
 
   def __init__(self, config, batch_size, image_size=None, dtype='bf16', device='cuda:0', seed=0,
-               params=None, spec=None, stochastic_depth=True, arena=None):
+               params=None, spec=None, stochastic_depth=True, arena=None, lion=None):
     self.config = config
     # optimizer = 'adam' (train_lib.py:183-186: beta_1 = momentum, Keras defaults for what the reference does not set),
-    # anything else Keras SGD
+    # 'lion' (lion/lion_tf2.py's Lion in the optimizer's place: beta_1 = momentum by the same convention; beta_2 and wd are
+    # no configuration keys and come in `lion`, a dict, with the reference's defaults), anything else Keras SGD
     momentum = float(config.momentum)
-    adam = str(config.optimizer).lower() == 'adam'
+    kind = str(config.optimizer).lower()
+    adam = kind == 'adam'
+    if kind == 'lion':
+      beta_2, wd = lion_options(lion)
+      update = Update('lion', momentum, beta_2, wd=wd)
+    elif lion:
+      raise ValueError('lion options %r with optimizer=%r' % (lion, config.optimizer))
+    else:
+      update = Update('adam', momentum, self.ADAM_BETA2, self.ADAM_EPSILON) if adam else Update('sgd', momentum)
     super().__init__(spec if spec is not None else netspec_lib.NetSpec(config), batch_size,
                      image_size if image_size is not None else config.image_size, dtype=dtype, device=device, seed=seed,
-                     params=params, arena=arena, stochastic_depth=stochastic_depth,
-                     update=Update('adam', momentum, self.ADAM_BETA2, self.ADAM_EPSILON) if adam else Update('sgd', momentum))
+                     params=params, arena=arena, stochastic_depth=stochastic_depth, update=update)
     if adam:
       self.arena.second_moment()
     self._side = None

@@ -292,9 +292,28 @@ def capture_graph(arena, body, pool=None):
   return graph
 
 
-# What an engine's update step runs: kind = 'sgd' (Keras SGD; momentum), 'adam' (momentum = beta_1, beta2, epsilon) or
-# 'rmsprop' (rho, momentum, epsilon).  Scalars a kind does not use stay None.
-Update = collections.namedtuple('Update', 'kind momentum beta2 epsilon rho', defaults=(None, None, None))
+# What an engine's update step runs: kind = 'sgd' (Keras SGD; momentum), 'adam' (momentum = beta_1, beta2, epsilon),
+# 'rmsprop' (rho, momentum, epsilon) or 'lion' (momentum = beta_1, beta2 = beta_2, wd).  Scalars a kind does not use stay None.
+Update = collections.namedtuple('Update', 'kind momentum beta2 epsilon rho wd', defaults=(None, None, None, None))
+LION_BETA2, LION_WD = 0.99, 0.0       # lion/lion_tf2.py:23-28
+
+
+def lion_options(options, beta_2=LION_BETA2, wd=LION_WD):
+  """The two Lion scalars that are no configuration keys, checked: `options` (a dict with 'beta_2' and / or 'wd', or None) over
+  the given current values -> (beta_2, wd)."""
+  options = dict(options or {})
+  unknown = sorted(set(options) - {'beta_2', 'wd'})
+  if unknown:
+    raise ValueError('lion: unknown option %s (beta_2 and wd are what there is)' % ', '.join(unknown))
+  if options.get('beta_2') is not None:
+    beta_2 = float(options['beta_2'])
+  if options.get('wd') is not None:
+    wd = float(options['wd'])
+  if not 0.0 <= beta_2 < 1.0:
+    raise ValueError('lion: beta_2 %r outside [0, 1)' % (beta_2,))
+  if not wd >= 0.0:
+    raise ValueError('lion: wd %r must be >= 0' % (wd,))
+  return beta_2, wd
 
 
 class Branch(object):
@@ -1069,6 +1088,10 @@ class LayerEngine(object):
     elif u.kind == 'rmsprop':
       call('edet_opt_rmsprop_ema', *head, ptr(self.arena.second_moment()), ptr(self.velocity), *tail, u.rho,
            float(u.momentum), u.epsilon, self.stream)
+    elif u.kind == 'lion':
+      # one slot (the velocity arena holds m); the rate is the schedule's, uncorrected (set_hyper)
+      call('edet_opt_lion_ema', *head, ptr(self.velocity), *tail, float(u.momentum), float(u.beta2), float(u.wd or 0.0),
+           self.stream)
     else:
       raise ValueError('unknown optimizer %r' % (u.kind,))
     self.arena.count_step()

@@ -33,8 +33,10 @@ File layout (little endian), version 1:
     the ELEMENT offset / count inside its fp32 arena -- trainable variables in 'params' (and, at the same offset, in the
     slots 'ema', 'velocity' and, for Adam, 'adam_v'), BatchNorm moving statistics in 'bn_state'.  It follows the last
     program, in front of the padding, where a reader that knows nothing of it never looks; the properties 'optimizer'
-    (0 sgd, 1 adam), 'iterations' (optimizer steps behind the state the plan starts from) and, for Adam, 'adam_beta1_bits' /
-    'adam_beta2_bits' / 'adam_epsilon_bits' (the doubles' bit patterns) go with it.
+    (0 sgd, 1 adam, 2 lion), 'iterations' (optimizer steps behind the state the plan starts from) and, for Adam,
+    'adam_beta1_bits' / 'adam_beta2_bits' / 'adam_epsilon_bits' (the doubles' bit patterns), for Lion 'lion_beta1_bits' /
+    'lion_beta2_bits' / 'lion_wd_bits' in the same convention, go with it (optimizer_props).  Lion keeps its one slot in
+    'velocity', as SGD does: a Lion plan has no 'adam_v' and its state files no slot 3.
   initial contents, 256-byte aligned, at the offsets the buffer table names.
 
 State files (edet_net_save_state / edet_net_load_state, read_state / write_state below), little endian, version 1:
@@ -514,6 +516,34 @@ def read_summary(path):
   return out
 
 
+OPTIMIZER_IDS = {'sgd': 0, 'adam': 1, 'lion': 2}      # property 'optimizer'
+
+
+def double_bits(v):
+  return struct.unpack('<Q', struct.pack('<d', float(v)))[0]
+
+
+def bits_double(bits):
+  return struct.unpack('<d', struct.pack('<Q', int(bits) & 0xffffffffffffffff))[0]
+
+
+def optimizer_props(update, iterations):
+  """The properties a plan carries of its update step (layer_engine.Update): the optimizer's id, the iteration count and the
+  optimizer's constants as the bit patterns of doubles.  Pure Python."""
+  if update.kind not in OPTIMIZER_IDS:
+    raise ValueError('plans record the sgd, adam and lion updates, not %r' % (update.kind,))
+  props = {'optimizer': OPTIMIZER_IDS[update.kind], 'iterations': int(iterations)}
+  if update.kind == 'adam':
+    constants = (('adam_beta1_bits', update.momentum), ('adam_beta2_bits', update.beta2), ('adam_epsilon_bits', update.epsilon))
+  elif update.kind == 'lion':
+    constants = (('lion_beta1_bits', update.momentum), ('lion_beta2_bits', update.beta2), ('lion_wd_bits', update.wd or 0.0))
+  else:
+    constants = ()
+  for key, v in constants:
+    props[key] = double_bits(v)
+  return props
+
+
 def write_state(path, variables, ema=None, momentum=None, adam_v=None, iterations=0):
   """Writes a state file (the format edet_net_save_state writes and edet_net_load_state reads): name -> fp32 array in the
   reference layout per slot -- the variables' values, the EMA shadows, the momentum slots (Adam: first moments), Adam's
@@ -736,11 +766,7 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
   else:
     rec.snapshot_initial_state(persistent, max_init_bytes, without=inputs)
   rec.variables = [(name, shape, tr, off, n) for name, (off, n, shape, tr) in eng.arena.offsets.items()]
-  rec.props.update({'optimizer': 1 if eng.adam else 0, 'iterations': int(eng.arena.step_count)})
-  if eng.adam:
-    for key, v in (('adam_beta1_bits', eng.update.momentum), ('adam_beta2_bits', eng.update.beta2),
-                   ('adam_epsilon_bits', eng.update.epsilon)):
-      rec.props[key] = struct.unpack('<Q', struct.pack('<d', v))[0]
+  rec.props.update(optimizer_props(eng.update, eng.arena.step_count))
   expected = {}
   # every program re-makes the compute copies of the variables (and, in inference, the BatchNorm vectors): a replayed step
   # follows other replayed steps, whose updates the host-side version counter of this engine has not seen

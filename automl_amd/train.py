@@ -74,7 +74,18 @@ def define_flags():
   boolean('profile', 'refused: use rocprofv3 on the process instead')
   ap.add_argument('--canvas', type=_canvas, default=(640, 640), help='HxW of the slot every decoded image is written into')
   ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'], help='storage dtype of the activations')
+  ap.add_argument('--lion_beta2', type=float, default=None, help='--hparams=optimizer=lion: beta_2 (default 0.99)')
+  ap.add_argument('--lion_wd', type=float, default=None,
+                  help='--hparams=optimizer=lion: the decoupled weight decay wd (default 0), on every variable')
   return ap
+
+
+def lion_of(flags, config):
+  """--lion_beta2 / --lion_wd -> EfficientDetNetTrain's `lion` keyword; refused for another optimizer."""
+  lion = {k: v for k, v in (('beta_2', flags.lion_beta2), ('wd', flags.lion_wd)) if v is not None}
+  if lion and str(config.optimizer).lower() != 'lion':
+    raise ValueError('--lion_beta2 / --lion_wd need --hparams=optimizer=lion, this run has %r' % (config.optimizer,))
+  return lion or None
 
 
 def parse_flags(argv):
@@ -161,7 +172,7 @@ def main(argv=None):
   steps_per_epoch = config.steps_per_epoch
   model = train_lib.EfficientDetNetTrain(config=config, dtype=flags.dtype, seed=flags.tf_random_seed or 0,
                                          steps_per_epoch=steps_per_epoch, global_batch_size=flags.batch_size,
-                                         use_graph=not flags.debug)
+                                         use_graph=not flags.debug, lion=lion_of(flags, config))
   latest = tf_checkpoint.latest_checkpoint(flags.model_dir) if os.path.isdir(flags.model_dir) else None
 
   if flags.mode == 'eval':

@@ -24,6 +24,7 @@ from automl_amd import det_autoaugment
 from automl_amd import det_input
 from automl_amd import efficientdet_net
 from automl_amd import engine as engine_lib
+from automl_amd import layer_engine
 from automl_amd import utils
 
 
@@ -143,14 +144,18 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
   """
 
   def __init__(self, *args, steps_per_epoch=1000, global_batch_size=None, process_group=None,
-               use_dist=False, use_graph=False, sync_bn=False, overlap_grad_reduce=None, **kwargs):
+               use_dist=False, use_graph=False, sync_bn=False, overlap_grad_reduce=None, lion=None, **kwargs):
     """use_graph: capture the whole step (forward, loss, backward, L2/clip, update: ~1600 kernel launches)
     into a hipGraph at the second call for a given batch shape and replay it afterwards; inputs are
     copied into static device buffers (input_buffers() exposes them for in-place filling), learning
     rate / EMA decay / loss normalizer travel through a small device vector.  With data parallelism the
-    gradient all-reduce stays an eager RCCL call between two captured halves."""
+    gradient all-reduce stays an eager RCCL call between two captured halves.
+    lion: with config.optimizer = 'lion', dict(beta_2=0.99, wd=0.0) -- lion_tf2.Lion's two arguments that are no
+    configuration keys (see set_lion)."""
     super().__init__(*args, **kwargs)
     self._check_training_options(self.config)
+    if lion is not None:
+      self.set_lion(**lion)
     # sync_bn: cross-replica BatchNorm statistics (the reference's --strategy=gpus / tpu BatchNorm classes,
     # utils.py:166-266): two small all-reduces per BatchNorm layer and step, eager launches only.
     self.sync_bn = sync_bn
@@ -207,6 +212,33 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     self.autoaugment = policy
     self._det_input = None
 
+  def set_lion(self, beta_2=None, wd=None):
+    """Lion's beta_2 and decoupled weight decay wd (lion/lion_tf2.py:23-28: 0.99 and 0; beta_1 is config.momentum, as for
+    Adam); None keeps a value.  wd reaches every variable the optimizer is given, BatchNorm scales and biases included, as the
+    reference's does.  The scalars are arguments of the update launch an engine records, so once an engine exists they are
+    fixed: build a new model for other values."""
+    if str(getattr(self.config, 'optimizer', 'sgd')).lower() != 'lion':
+      raise ValueError('set_lion needs config.optimizer = lion, this model has %r' % (self.config.optimizer,))
+    if self.engine is not None:
+      raise ValueError('set_lion after the first engine was made: beta_2 and wd are arguments of the update it launches '
+                       '(and of a step it has captured); set them before the first step, or build a new model')
+    current = self._lion or {}
+    beta_2, wd = layer_engine.lion_options({'beta_2': beta_2, 'wd': wd}, current.get('beta_2', layer_engine.LION_BETA2),
+                                           current.get('wd', layer_engine.LION_WD))
+    self._lion = {'beta_2': beta_2, 'wd': wd}
+
+  @property
+  def update(self):
+    """The update description of this model's engines (layer_engine.Update), from the configuration alone: no device."""
+    c = self.config
+    kind, momentum = str(getattr(c, 'optimizer', 'sgd')).lower(), float(c.momentum)
+    if kind == 'lion':
+      beta_2, wd = layer_engine.lion_options(self._lion)
+      return layer_engine.Update('lion', momentum, beta_2, wd=wd)
+    if kind == 'adam':
+      return layer_engine.Update('adam', momentum, layer_engine.LayerEngine.ADAM_BETA2, layer_engine.LayerEngine.ADAM_EPSILON)
+    return layer_engine.Update('sgd', momentum)
+
   def get_optimizer_state(self):
     """Optimizer slots, iteration count and -- with positives_momentum > 0 -- the moving loss normalizer.  (The reference
     creates that variable inside the loss call, train_lib.py:521-527, untracked by its checkpoints: a resumed reference
@@ -246,8 +278,9 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     unsupported = []
     if getattr(c, 'iou_loss_type', None):
       unsupported.append('iou_loss_type=%r (BoxIouLoss, train_lib.py:440-466)' % c.iou_loss_type)
-    if str(getattr(c, 'optimizer', 'sgd')).lower() not in ('sgd', 'adam'):
-      unsupported.append("optimizer=%r (the reference has 'sgd' and 'adam', train_lib.py:180-188)" % c.optimizer)
+    if str(getattr(c, 'optimizer', 'sgd')).lower() not in ('sgd', 'adam', 'lion'):
+      unsupported.append("optimizer=%r (the reference has 'sgd' and 'adam', train_lib.py:180-188; 'lion' is lion/lion_tf2.py's)"
+                         % c.optimizer)
     if unsupported:
       raise ValueError('training options that are not built: ' + '; '.join(unsupported))
 
@@ -911,6 +944,20 @@ def _model_identity(model):
           'optimizer': str(getattr(model.config, 'optimizer', 'sgd')).lower()}
 
 
+def lion_identity(update):
+  """What a training-state file carries of a Lion update besides the optimizer's name (beta_1 is the momentum both trainers
+  already have): {'beta_2':, 'wd':}; None for every other kind."""
+  return {'beta_2': float(update.beta2), 'wd': float(update.wd or 0.0)} if update.kind == 'lion' else None
+
+
+def lion_difference(theirs, mine):
+  """The differences between a file's 'lion' entry and this model's, worded for restore_train_state's refusal."""
+  if mine is None:
+    return []
+  theirs = theirs or {}
+  return ['lion %s %r, this model %r' % (k, theirs.get(k), mine[k]) for k in ('beta_2', 'wd') if theirs.get(k) != mine[k]]
+
+
 def save_train_state(model, path, reader=None):
   """Writes <ckpt prefix>.train_state.npz next to a checkpoint: get_optimizer_state() in full (velocity, ema, the second slot
   under its key, iterations, moving_normalizer, input_rng_state), the stochastic-depth generator's state of every engine the
@@ -920,6 +967,8 @@ def save_train_state(model, path, reader=None):
   state = model.get_optimizer_state()
   arrays, meta = {}, {'format': TRAIN_STATE_FORMAT}
   meta.update(_model_identity(model))
+  if meta['optimizer'] == 'lion':
+    meta['lion'] = lion_identity(model.update)
   for k, v in state.items():
     if k in _SLOT_KEYS or k == 'input_rng_state':
       arrays[k] = np.asarray(v)
@@ -962,6 +1011,8 @@ def restore_train_state(model, path, reader=None):
   what = {'num_variables': 'variables', 'arena_length': 'arena elements', 'optimizer': 'as optimizer'}
   diff = ['%s %s, this model %s' % (meta.get(k), what[k], mine[k]) for k in ('num_variables', 'arena_length', 'optimizer')
           if meta.get(k) != mine[k]]
+  if not diff and mine['optimizer'] == 'lion':
+    diff = lion_difference(meta.get('lion'), lion_identity(model.update))
   if diff:
     raise ValueError('%s is the training state of another model: the file has %s' % (path, '; '.join(diff)))
   state = {k: arrays[k] for k in _SLOT_KEYS + ('input_rng_state',) if k in arrays}

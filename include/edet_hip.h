@@ -627,6 +627,14 @@ int edet_opt_adam_ema(float* params, const float* grads, float* m, float* v, flo
 int edet_opt_rmsprop_ema(float* params, const float* grads, float* ms, float* mom, float* ema,
                          const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
                          const float* hyper_dev, float rho, float momentum, float epsilon, void* stream);
+/* Lion (lion/lion_tf2.py:60-74, _resource_apply_dense; defaults beta_1 0.9, beta_2 0.99, wd 0): c = m*beta1 + g*(1 - beta1);
+ * w -= lr*(sign(c) + w*wd), from the OLD m; m = m*beta2 + g*(1 - beta2).  m = the one slot arena (the SGD velocity's);
+ * hyper_dev[0] = the step's learning rate as the schedule gives it (no bias correction), hyper_dev[1] = EMA decay; clip factors,
+ * frozen segments and the optional EMA shadow as above.  Every product and sum is one rounded float32 operation (no FMA, the
+ * EMA tail included), sign(0) = 0, sign(NaN) = NaN: tests/lion_ref.py restates it in numpy bit for bit. */
+int edet_opt_lion_ema(float* params, const float* grads, float* m, float* ema,
+                      const int64_t* seg_offsets, const float* seg_factor, const int32_t* seg_flags, int nseg,
+                      const float* hyper_dev, float beta1, float beta2, float wd, void* stream);
 
 /* ---- step plumbing (round 6): the few operations of a step that are not layers, so that EVERY launch of a step goes
  * through this ABI and a step can be recorded and replayed without the Python interpreter (include/edet_net.h).

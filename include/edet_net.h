@@ -77,7 +77,10 @@ int edet_detect(edet_net_t* net, void* stream);
 
 /* One training step over "images" and the target buffers (EfficientDetNetTrain.train_step: forward with batch
  * statistics, focal + Huber loss, backward, L2, per-tensor and global-norm clip, [gradient exchange], the update + EMA).
- * The optimizer is the plan's (property "optimizer": 0 = SGD with momentum, 1 = Adam; train_lib.py:176-199).
+ * The optimizer is the plan's (property "optimizer": 0 = SGD with momentum, 1 = Adam; train_lib.py:176-199; 2 = Lion,
+ * lion/lion_tf2.py, with the properties "lion_beta1_bits" / "lion_beta2_bits" / "lion_wd_bits": the doubles' bit patterns
+ * of the constants the recorded update launch carries.  Lion has no bias correction: learning_rate reaches its update
+ * kernel as it is, as for SGD).
  * learning_rate / ema_decay are this step's RAW values of the schedule (train_lib.py:37-173, :193-197; ema_decay 0 = the
  * plan was recorded without a moving average).  Adam plans: the runtime forms tf.keras Adam's bias-corrected rate itself,
  * alpha = learning_rate * sqrt(1 - beta2^t) / (1 - beta1^t) with t = iterations + 1, in double arithmetic, rounded to
@@ -90,8 +93,8 @@ int edet_train_step(edet_net_t* net, float learning_rate, float ema_decay, void*
  * The plan's variable table: one entry per variable of the model, in the creation order of the Python host's arena, under
  * the reference's names ("class_net/class-predict/bias", "efficientnet-b0/stem/conv2d/kernel", ...), shapes in the
  * reference's layouts.  Values are fp32.  A trainable variable has the slots VALUE, EMA (the moving-average shadow),
- * MOMENTUM (SGD: the momentum accumulator; Adam: the first moment) and -- in Adam plans only -- ADAM_V (the second
- * moment); a BatchNorm moving statistic has VALUE only.  Every function refuses a plan recorded without the table.  */
+ * MOMENTUM (SGD: the momentum accumulator; Adam: the first moment; Lion: its one slot m) and -- in Adam plans only, so
+ * refused for SGD and Lion -- ADAM_V (the second moment); a BatchNorm moving statistic has VALUE only.  Every function refuses a plan recorded without the table.  */
 enum { EDET_SLOT_VALUE = 0, EDET_SLOT_EMA = 1, EDET_SLOT_MOMENTUM = 2, EDET_SLOT_ADAM_V = 3 };
 typedef struct {
   const char* name;      /* owned by the network, valid until edet_destroy */
