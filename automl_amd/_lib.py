@@ -88,6 +88,14 @@ class JpegImage(ctypes.Structure):
               ('first_block', ctypes.c_int32 * 3), ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class JpegWindow(ctypes.Structure):
+  """edet_jpeg_window_t: one row of the window decode's second per-image array (edet_jpeg_entropy_decode_window)."""
+  _fields_ = [('y', ctypes.c_int32), ('x', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
+              ('image_h', ctypes.c_int32), ('image_w', ctypes.c_int32), ('mcu_x0', ctypes.c_int32),
+              ('mcu_y0', ctypes.c_int32), ('mcus_w', ctypes.c_int32), ('mcus_h', ctypes.c_int32),
+              ('reserved', ctypes.c_int32 * 2)]
+
+
 class ExampleSpec(ctypes.Structure):
   """edet_example_spec_t: one wanted key of edet_example_parse."""
   _fields_ = [('key', ctypes.c_char_p), ('key_len', ctypes.c_int32), ('kind', ctypes.c_int32), ('capacity', ctypes.c_int32),
@@ -245,6 +253,10 @@ SIGNATURES = {
                                         c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_int],
     'edet_jpeg_idct_scaled': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p],
     'edet_jpeg_color_scaled': [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p],
+    'edet_jpeg_entropy_decode_window': [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t), c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int],
+    'edet_jpeg_color_window': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p],
     'edet_crc32c': [c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)],
     'edet_tfrecord_index': [c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, ctypes.c_size_t,
                             ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],

@@ -283,9 +283,17 @@ struct Bits {
   }
 };
 
-// the scan of one image -> coefficients; 0 or EDET_JPEG_MALFORMED
+// the kept MCUs of an image, in MCUs of its full grid: all of them, or what a window needs (kept_grid)
+struct Kept {
+  int x0, y0, w, h;      // first column and row, columns and rows kept
+  int full_w, full_h;    // the file's MCU grid
+};
+
+// The scan of one image -> coefficients; 0 or EDET_JPEG_MALFORMED.  im's block grids are those of the KEPT MCUs (the whole
+// grid for the full-size and scaled entry points): a block outside them is parsed, since the DC predictors must advance, and
+// not stored, and the scan is read no further than the last kept MCU row.
 int decode_scan(const uint8_t* d, size_t n, const Parsed& P, const int td[3], const int ta[3], const edet_jpeg_image_t& im,
-                int16_t* coef) {
+                const Kept& K, int16_t* coef) {
   const int nc = im.components;
   std::vector<Huff> tables(2 * (size_t)nc);
   for (int c = 0; c < nc; ++c) {
@@ -294,7 +302,8 @@ int decode_scan(const uint8_t* d, size_t n, const Parsed& P, const int td[3], co
   }
   memset(coef + (size_t)64 * im.first_block[0], 0, sizeof(int16_t) * 64 * (size_t)im.total_blocks);
   const int hs[3] = {im.h_max, 1, 1}, vs[3] = {im.v_max, 1, 1};
-  const int mcus_w = im.blocks_w[0] / hs[0], mcus_h = im.blocks_h[0] / vs[0];
+  const int mcus_w = K.full_w, mcus_h = K.y0 + K.h;      // (<= K.full_h: nothing behind the last kept row is read)
+  int16_t skipped[64];      // where a block outside the kept grid goes
   uint32_t pred[3] = {0, 0, 0};
   Bits bits(d, n, P.scan);
   const int ri = P.info.restart_interval;
@@ -317,13 +326,15 @@ int decode_scan(const uint8_t* d, size_t n, const Parsed& P, const int td[3], co
         todo = ri;
       }
       --todo;
+      const bool kept = my >= K.y0 && mx >= K.x0 && mx < K.x0 + K.w;
       for (int c = 0; c < nc; ++c) {
         const Huff& dc = tables[2 * c];
         const Huff& ac = tables[2 * c + 1];
         for (int yy = 0; yy < vs[c]; ++yy) {
           for (int xx = 0; xx < hs[c]; ++xx) {
-            const size_t at = (size_t)im.first_block[c] + (size_t)(my * vs[c] + yy) * im.blocks_w[c] + (mx * hs[c] + xx);
-            int16_t* blk = coef + 64 * at;
+            const size_t at = (size_t)im.first_block[c] + (size_t)((my - K.y0) * vs[c] + yy) * im.blocks_w[c] +
+                              ((mx - K.x0) * hs[c] + xx);
+            int16_t* blk = kept ? coef + 64 * at : skipped;
             bool ok = true;
             int s = bits.symbol(dc);
             if (s < 0) return EDET_JPEG_MALFORMED;
@@ -374,11 +385,45 @@ extern "C" int edet_jpeg_info(const uint8_t* data, size_t n, edet_jpeg_info_t* o
 
 namespace {
 
-// Both entry points: the headers, then the scans.  max_denom 1 and denoms NULL is the full-size decode; `scaled` says
+// The side of component c's blocks after the inverse transform at 8 / denom = m (jpeg_scaled.hip, sample_size)
+int sample_size(int h_max, int v_max, int m, int c) { return (c > 0 && h_max == 2 && v_max == 2 && m < 8) ? 2 * m : m; }
+
+// The kept grid of a window (include/edet_hip.h, "JPEG decode of a crop window"): the smallest rectangle of whole MCUs that
+// holds the samples every component needs for output pixels [y, y + h) x [x, x + w) of an out_h x out_w output.
+void kept_grid(int components, int h_max, int v_max, int denom, int out_h, int out_w, const int32_t win[4], Kept& K) {
+  const int m = 8 / denom, s0 = sample_size(h_max, v_max, m, 0);
+  int lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {-1, -1};      // MCU columns, MCU rows
+  for (int c = 0; c < components; ++c) {
+    const int s = sample_size(h_max, v_max, m, c);
+    for (int a = 0; a < 2; ++a) {      // 0: along x, 1: along y
+      const int samp = a == 0 ? h_max : v_max;
+      const int u = c == 0 ? 1 : samp * s0 / s;      // the up-sampling that is left, 1 or 2
+      const int per_mcu = c == 0 ? samp : 1;         // blocks of the component in an MCU
+      const int first = a == 0 ? win[1] : win[0], last = first + (a == 0 ? win[3] : win[2]) - 1;
+      const int real = ((a == 0 ? out_w : out_h) + u - 1) / u;
+      int from = first, to = last;
+      if (u == 2) {
+        from = (first >> 1) - 1 > 0 ? (first >> 1) - 1 : 0;
+        to = (last >> 1) + 1 < real - 1 ? (last >> 1) + 1 : real - 1;
+      }
+      from = from / s / per_mcu;
+      to = to / s / per_mcu;
+      if (from < lo[a]) lo[a] = from;
+      if (to > hi[a]) hi[a] = to;
+    }
+  }
+  K.x0 = lo[0];
+  K.w = hi[0] - lo[0] + 1;
+  K.y0 = lo[1];
+  K.h = hi[1] - lo[1] + 1;
+}
+
+// All entry points: the headers, then the scans.  windows / wins NULL: the whole grid of every image is kept.  max_denom 1 and denoms NULL is the full-size decode; `scaled` says
 // whether the descriptor carries the denominator (the full-size entry point keeps writing 0 there).
 int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
-                   int max_denom, const int32_t* denoms, bool scaled, int16_t* coef_host, size_t coef_capacity,
-                   edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status, int threads) {
+                   int max_denom, const int32_t* denoms, bool scaled, const int32_t* windows, edet_jpeg_window_t* wins,
+                   int16_t* coef_host, size_t coef_capacity, edet_jpeg_image_t* images_host, uint16_t* qtables_host,
+                   int32_t* status, int threads) {
   if (!datas || !sizes || !coef_host || !images_host || !qtables_host || !status || batch < 1) {
     edet_set_error("%s: null pointer or batch %d < 1", who, batch);
     return -1;
@@ -400,6 +445,7 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
   struct Job {
     Parsed P;
     int td[3], ta[3];
+    Kept K;
   };
   std::vector<Job> jobs((size_t)batch);
   // the headers, one image after the other: the place of an image in the arena depends on the images in front of it
@@ -412,8 +458,20 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
     memset(qtables_host + (size_t)b * 256, 0, 256 * sizeof(uint16_t));
     int st = walk(datas[b], sizes[b], J.P);
     int denom = 1;
-    if (!st) st = check_frame(J.P.info, canvas_h, canvas_w, max_denom, denoms ? (int)denoms[b] : 0, &denom);
+    if (windows) {      // the window has to fit the canvas, not the image; its coordinates are those of ONE denominator
+      memset(&wins[b], 0, sizeof(wins[b]));
+      if (!st) st = check_frame(J.P.info, INT32_MAX, INT32_MAX, max_denom, denoms ? (int)denoms[b] : 1, &denom);
+    } else if (!st) {
+      st = check_frame(J.P.info, canvas_h, canvas_w, max_denom, denoms ? (int)denoms[b] : 0, &denom);
+    }
     if (!st) st = check_scan(J.P, J.td, J.ta);
+    if (!st && windows) {
+      const edet_jpeg_info_t& f = J.P.info;
+      const int32_t* w = windows + 4 * (size_t)b;
+      const int out_h = (f.height + denom - 1) / denom, out_w = (f.width + denom - 1) / denom;
+      if (w[0] < 0 || w[1] < 0 || w[2] < 1 || w[3] < 1 || w[2] > out_h - w[0] || w[3] > out_w - w[1]) st = EDET_JPEG_WINDOW;
+      else if (w[2] > canvas_h || w[3] > canvas_w) st = EDET_JPEG_TOO_LARGE;
+    }
     if (!st) {
       const edet_jpeg_info_t& f = J.P.info;
       im.height = (f.height + denom - 1) / denom;      // the output size; the block grids below are the file's
@@ -423,10 +481,31 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
       im.h_max = f.components == 3 ? f.h_samp[0] : 1;
       im.v_max = f.components == 3 ? f.v_samp[0] : 1;
       const int mw = (f.width + 8 * im.h_max - 1) / (8 * im.h_max), mh = (f.height + 8 * im.v_max - 1) / (8 * im.v_max);
+      Kept& K = J.K;
+      K.x0 = K.y0 = 0;
+      K.w = K.full_w = mw;
+      K.h = K.full_h = mh;
+      edet_jpeg_window_t win;
+      memset(&win, 0, sizeof(win));
+      if (windows) {
+        // The image descriptor describes the kept MCUs as an image of their own -- their block grids, and for height and
+        // width their output pixels inside the image -- so edet_jpeg_idct_scaled runs on it as it is.
+        const int32_t* w = windows + 4 * (size_t)b;
+        kept_grid(f.components, im.h_max, im.v_max, denom, im.height, im.width, w, K);
+        const int m = 8 / denom;
+        const int px = im.h_max * sample_size(im.h_max, im.v_max, m, 0), py = im.v_max * sample_size(im.h_max, im.v_max, m, 0);
+        win.y = w[0]; win.x = w[1]; win.h = w[2]; win.w = w[3];
+        win.image_h = im.height; win.image_w = im.width;
+        win.mcu_x0 = K.x0; win.mcu_y0 = K.y0; win.mcus_w = K.w; win.mcus_h = K.h;
+        const int right = (K.x0 + K.w) * px < im.width ? (K.x0 + K.w) * px : im.width;
+        const int bottom = (K.y0 + K.h) * py < im.height ? (K.y0 + K.h) * py : im.height;
+        im.width = right - K.x0 * px;
+        im.height = bottom - K.y0 * py;
+      }
       size_t total = 0;
       for (int c = 0; c < f.components; ++c) {
-        im.blocks_w[c] = c == 0 ? mw * im.h_max : mw;
-        im.blocks_h[c] = c == 0 ? mh * im.v_max : mh;
+        im.blocks_w[c] = c == 0 ? K.w * im.h_max : K.w;
+        im.blocks_h[c] = c == 0 ? K.h * im.v_max : K.h;
         im.quant_id[c] = f.quant_id[c];
         total += (size_t)im.blocks_w[c] * (size_t)im.blocks_h[c];      // <= 3 * 8192 * 8192
       }
@@ -441,6 +520,7 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
         im.total_blocks = (int32_t)total;
         next_block += total;
         memcpy(qtables_host + (size_t)b * 256, J.P.qt, sizeof(J.P.qt));
+        if (windows) wins[b] = win;
       }
     }
     if (st) {
@@ -459,9 +539,10 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
       edet_jpeg_image_t& im = images_host[b];
       if (im.status) continue;
       const Job& J = jobs[(size_t)b];
-      const int st = decode_scan(datas[b], sizes[b], J.P, J.td, J.ta, im, coef_host);
+      const int st = decode_scan(datas[b], sizes[b], J.P, J.td, J.ta, im, J.K, coef_host);
       if (st) {
         memset(&im, 0, sizeof(im));
+        if (windows) memset(&wins[b], 0, sizeof(wins[b]));
         memset(qtables_host + (size_t)b * 256, 0, 256 * sizeof(uint16_t));
         im.status = st;
         status[b] = st;
@@ -486,8 +567,8 @@ extern "C" int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_
                                         int canvas_w, int16_t* coef_host, size_t coef_capacity,
                                         edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status,
                                         int threads) {
-  return entropy_decode("edet_jpeg_entropy_decode", datas, sizes, batch, canvas_h, canvas_w, 1, nullptr, false, coef_host,
-                        coef_capacity, images_host, qtables_host, status, threads);
+  return entropy_decode("edet_jpeg_entropy_decode", datas, sizes, batch, canvas_h, canvas_w, 1, nullptr, false, nullptr,
+                        nullptr, coef_host, coef_capacity, images_host, qtables_host, status, threads);
 }
 
 extern "C" int edet_jpeg_entropy_decode_scaled(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h,
@@ -495,5 +576,18 @@ extern "C" int edet_jpeg_entropy_decode_scaled(const uint8_t* const* datas, cons
                                                size_t coef_capacity, edet_jpeg_image_t* images_host,
                                                uint16_t* qtables_host, int32_t* status, int threads) {
   return entropy_decode("edet_jpeg_entropy_decode_scaled", datas, sizes, batch, canvas_h, canvas_w, max_denom, denoms, true,
-                        coef_host, coef_capacity, images_host, qtables_host, status, threads);
+                        nullptr, nullptr, coef_host, coef_capacity, images_host, qtables_host, status, threads);
+}
+
+extern "C" int edet_jpeg_entropy_decode_window(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h,
+                                               int canvas_w, int max_denom, const int32_t* denoms, const int32_t* windows,
+                                               int16_t* coef_host, size_t coef_capacity, edet_jpeg_image_t* images_host,
+                                               edet_jpeg_window_t* windows_host, uint16_t* qtables_host, int32_t* status,
+                                               int threads) {
+  if (!windows || !windows_host) {
+    edet_set_error("edet_jpeg_entropy_decode_window: null windows");
+    return -1;
+  }
+  return entropy_decode("edet_jpeg_entropy_decode_window", datas, sizes, batch, canvas_h, canvas_w, max_denom, denoms, true,
+                        windows, windows_host, coef_host, coef_capacity, images_host, qtables_host, status, threads);
 }

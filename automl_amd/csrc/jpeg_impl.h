@@ -1,5 +1,6 @@
 // What the two device stages of the JPEG decoder share (jpeg.hip: full size; jpeg_scaled.hip: libjpeg's reduced sizes): the
-// descriptor check, jidctint.c's one-dimensional pass, jdsample.c's fancy upsampling and the small integer helpers.
+// descriptor check, jidctint.c's one-dimensional pass, jdsample.c's fancy upsampling and the small integer helpers; and what
+// the reduced sizes share with the window decode (jpeg_window.hip): the denominator, the sample sizes and their check.
 #pragma once
 #include "common.h"
 
@@ -83,6 +84,79 @@ __device__ __forceinline__ void chroma4(const uint8_t* __restrict__ p, int pw, i
     out[1] = i0 == n - 1 ? col[1] : (3 * col[1] + col[2] + 2) >> 2;
     out[2] = (3 * col[2] + col[1] + 1) >> 2;
     out[3] = i0 + 1 == n - 1 ? col[2] : (3 * col[2] + col[3] + 2) >> 2;
+  }
+}
+
+// 8 / denominator, or 0 for a descriptor whose `reserved` is none of 0, 1, 2, 4, 8
+__device__ __forceinline__ int scaled_m(const edet_jpeg_image_t& d) {
+  const int r = d.reserved;
+  return (r == 0 || r == 1) ? 8 : r == 2 ? 4 : r == 4 ? 2 : r == 8 ? 1 : 0;
+}
+
+// The side of component c's blocks after the inverse transform (jdmaster.c): m, and 2 m for the chroma of a 4:2:0 file below
+// full size, which then lies at the output's resolution.
+__device__ __forceinline__ int sample_size(const edet_jpeg_image_t& d, int m, int c) {
+  return (c > 0 && d.h_max == 2 && d.v_max == 2 && m < 8) ? 2 * m : m;
+}
+
+// image_ok, the denominator, and the real samples of every component inside its REDUCED plane: d.height x d.width is the
+// output size, the chroma's real samples are half of it (rounded up) in each direction that is still subsampled.
+__device__ __forceinline__ bool scaled_ok(const edet_jpeg_image_t& d, int64_t cap_blocks) {
+  const int m = scaled_m(d);
+  if (m == 0 || !image_ok(d, cap_blocks)) return false;
+  const int s0 = sample_size(d, m, 0);
+  for (int c = 0; c < d.components; ++c) {
+    const int s = sample_size(d, m, c);
+    const int fh = c == 0 ? 1 : d.h_max * s0 / s, fv = c == 0 ? 1 : d.v_max * s0 / s;
+    if ((d.width + fh - 1) / fh > d.blocks_w[c] * s || (d.height + fv - 1) / fv > d.blocks_h[c] * s) return false;
+  }
+  return true;
+}
+
+// chroma4 for a thread whose four pixels x0 .. x0 + 3 start at ANY column of the image, read from the kept planes of a window
+// decode (jpeg_window.hip): sample (row, column) of the component lies at (row - oy, column - ox) of plane p, whose rows hold
+// pw samples.  n, rows, y and x0 are the IMAGE's, so the edge rules are those of the whole image.  A column that only a
+// pixel outside the window would read is clamped into the plane's row; its result is not used.
+template <int T>
+__device__ __forceinline__ int fancy1(const int col[4], int i0, int n, bool v2) {
+  constexpr int e = T >> 1;      // pixel x0 + j, T = j + (x0 & 1): chroma column i0 + e is col[1 + e]
+  const int i = i0 + e, cur = col[1 + e];
+  if (T & 1) {
+    const int next = col[e < 2 ? 2 + e : 3];
+    return v2 ? (i == n - 1 ? (4 * cur + 7) >> 4 : (3 * cur + next + 7) >> 4) : (i == n - 1 ? cur : (3 * cur + next + 2) >> 2);
+  }
+  const int prev = col[e];
+  return v2 ? (i == 0 ? (4 * cur + 8) >> 4 : (3 * cur + prev + 8) >> 4) : (i == 0 ? cur : (3 * cur + prev + 1) >> 2);
+}
+
+__device__ __forceinline__ void chroma4_window(const uint8_t* __restrict__ p, int pw, int ox, int oy, int n, int rows, bool v2,
+                                               int y, int x0, int out[4]) {
+  const int i0 = x0 >> 1;
+  int col[4];
+  int near = y, far = y;
+  if (v2) {
+    near = y >> 1;
+    far = (y & 1) ? near + 1 : near - 1;
+    far = min(max(far, 0), rows - 1);
+  }
+  near -= oy;
+  far -= oy;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = min(max(min(max(i0 - 1 + k, 0), n - 1) - ox, 0), pw - 1);
+    const int a = p[(size_t)near * pw + i];
+    col[k] = v2 ? 3 * a + (int)p[(size_t)far * pw + i] : a;
+  }
+  if (x0 & 1) {
+    out[0] = fancy1<1>(col, i0, n, v2);
+    out[1] = fancy1<2>(col, i0, n, v2);
+    out[2] = fancy1<3>(col, i0, n, v2);
+    out[3] = fancy1<4>(col, i0, n, v2);
+  } else {
+    out[0] = fancy1<0>(col, i0, n, v2);
+    out[1] = fancy1<1>(col, i0, n, v2);
+    out[2] = fancy1<2>(col, i0, n, v2);
+    out[3] = fancy1<3>(col, i0, n, v2);
   }
 }
 

@@ -15,6 +15,8 @@
 //
 // k_jpeg_color_scaled: k_jpeg_color's contract on planes of stride blocks_w s.  Four samples of a row are loaded as one word
 // only where the stride is a multiple of four, else byte by byte (and only the bytes inside the image).
+// scaled_m, sample_size and scaled_ok -- the denominator, the sample sizes and the descriptor check -- are jpeg_impl.h's,
+// shared with jpeg_window.hip.
 #include "common.h"
 #include "jpeg_impl.h"
 
@@ -25,32 +27,6 @@ using namespace jpeg_impl;
 constexpr int IDCT_THREADS = 256;
 constexpr int IDCT_BLOCKS = IDCT_THREADS / 8;
 constexpr int COLOR_THREADS = 256;
-
-// 8 / denominator, or 0 for a descriptor whose `reserved` is none of 0, 1, 2, 4, 8
-__device__ __forceinline__ int scaled_m(const edet_jpeg_image_t& d) {
-  const int r = d.reserved;
-  return (r == 0 || r == 1) ? 8 : r == 2 ? 4 : r == 4 ? 2 : r == 8 ? 1 : 0;
-}
-
-// The side of component c's blocks after the inverse transform (jdmaster.c): m, and 2 m for the chroma of a 4:2:0 file below
-// full size, which then lies at the output's resolution.
-__device__ __forceinline__ int sample_size(const edet_jpeg_image_t& d, int m, int c) {
-  return (c > 0 && d.h_max == 2 && d.v_max == 2 && m < 8) ? 2 * m : m;
-}
-
-// image_ok, the denominator, and the real samples of every component inside its REDUCED plane: d.height x d.width is the
-// output size, the chroma's real samples are half of it (rounded up) in each direction that is still subsampled.
-__device__ __forceinline__ bool scaled_ok(const edet_jpeg_image_t& d, int64_t cap_blocks) {
-  const int m = scaled_m(d);
-  if (m == 0 || !image_ok(d, cap_blocks)) return false;
-  const int s0 = sample_size(d, m, 0);
-  for (int c = 0; c < d.components; ++c) {
-    const int s = sample_size(d, m, c);
-    const int fh = c == 0 ? 1 : d.h_max * s0 / s, fv = c == 0 ? 1 : d.v_max * s0 / s;
-    if ((d.width + fh - 1) / fh > d.blocks_w[c] * s || (d.height + fv - 1) / fv > d.blocks_h[c] * s) return false;
-  }
-  return true;
-}
 
 // jidctred.c jpeg_idct_4x4, one pass: x[0 .. 3] and x[5 .. 7] in, x[0 .. 3] out; descale by n (12, then 19)
 __device__ __forceinline__ void idct4_1d(uint32_t x[8], int n) {

@@ -39,8 +39,21 @@ header and the canvas alone: the order of the records and get_state() / set_stat
 Deliberate difference (4): the reference decodes every image at full size and crops and resizes from that; with a ratio, the
 crop and the bicubic / bilinear resize start from libjpeg's reduced image, for the images larger than the canvas only.  An
 image that is still too large at max_ratio, or a batch whose files have more 8x8 blocks than the decoder's coefficient arena
-(jpeg.JpegDecoder's coef_blocks), is TOO_LARGE as before.  A window decode (tf.image.decode_and_crop_jpeg,
-preprocessing.py:142) is not built: the crop is drawn inside the model's step, not in the reader.
+(jpeg.JpegDecoder's coef_blocks), is TOO_LARGE as before.
+
+Window decode (tf.image.decode_and_crop_jpeg, preprocess_legacy.py:53-68): reader(..., decode_crop=True), training only.  The
+background thread reads each image's size from its header and draws ONE crop window per image with
+v2_preprocessing.sample_distorted_bounding_box at train_rows' defaults; the decoder stores, copies and transforms only the
+blocks that window needs (jpeg.JpegDecoder(windowed=True)), and the batches are ((raw, sizes), labels) as before with each
+window at the top-left of its slot and `sizes` the window sizes.  The model is then built with transformations='flip': its
+step takes the whole "image" and only draws the flip.  The windows come from a generator of their own, a PCG64 stream derived
+from the reader's seed, whose state travels with get_state() / set_state() under the key 'window_rng' -- present only with
+decode_crop, and a state with or without it given to a reader that is the other way round raises.  An image whose header
+cannot be read gets no draw and is left to the decoder's status and `fallback`; a stream that goes to `fallback` comes back
+whole.  With max_ratio > 1 each image is decoded at the smallest ratio at which the window's covering output window fits the
+canvas (jpeg.choose_window_ratio); one that fits at no ratio is the decoder's TOO_LARGE.  Deliberate difference (5): the
+reference decodes the window at full size whatever its size; and the order of the draws is this project's, as for the crop in
+the step.  Without decode_crop nothing changes, the reader's state and the order of its records included.
 
 Not built, raising ValueError('... is not built: ...'): every tfds-backed configuration (cifar10, cifar100, flowers,
 tfflowers, cars, imagenettfds: tensorflow_datasets is not available and its on-disk format is not read), imagenet21k (its
@@ -63,7 +76,10 @@ Config = hparams_config.Config
 
 SPEC = (('image/encoded', 'bytes', 1), ('image/class/label', 'int64', 1))
 
-HostBatch = collections.namedtuple('HostBatch', 'index images labels state')
+# windows / image_sizes (decode_crop only): int32 [B, 4] = (y, x, h, w) in full-size pixels and int32 [B, 2] from the headers;
+# an image whose header cannot be read has zeros in both
+HostBatch = collections.namedtuple('HostBatch', 'index images labels state windows image_sizes', defaults=(None, None))
+WINDOW_KEY = 'window_rng'
 
 # datasets.py:78-91; a slice is [start, stop] so that the table stays plain data (config.yaml)
 IMAGENET_CFG = dict(
@@ -135,17 +151,54 @@ def build_dataset_input(is_training, image_size, image_dtype, data_dir, split, d
   return get_dataset_class(ds_cfg.get('ds_name', 'imagenet'))(is_training, data_dir, split, debug=debug, seed=seed, cfg=ds_cfg)
 
 
+def window_rng(seed):
+  """The generator behind the crop windows of reader(decode_crop=True): a PCG64 stream of its own, derived from the reader's
+  seed (None: numpy's entropy)."""
+  return np.random.Generator(np.random.PCG64(np.random.SeedSequence(seed, spawn_key=(0x77696E646F77,))))
+
+
+class _Order(object):
+  """dataloader.RecordOrder with the window generator's state next to its own: what the producer and HostReader know as the
+  order.  rng None (no decode_crop): RecordOrder's state as it is."""
+
+  def __init__(self, order, rng):
+    self.order, self.rng = order, rng
+
+  def next(self):
+    return self.order.next()
+
+  @property
+  def finished(self):
+    return self.order.finished
+
+  def get_state(self):
+    state = self.order.get_state()
+    if self.rng is not None:
+      state[WINDOW_KEY] = copy.deepcopy(self.rng.bit_generator.state)
+    return state
+
+  def set_state(self, state):
+    if (WINDOW_KEY in state) != (self.rng is not None):
+      raise ValueError('this state has %s key %r and the reader was made with%s decode_crop: a state resumes a reader made the '
+                       'same way' % (('the', WINDOW_KEY, 'out') if WINDOW_KEY in state else ('no', WINDOW_KEY, '')))
+    state = dict(state)
+    if self.rng is not None:
+      self.rng.bit_generator.state = copy.deepcopy(state.pop(WINDOW_KEY))
+    self.order.set_state(state)
+
+
 class _Producer(dataloader._Producer):
   """The host half for classification records: dataloader._Producer's order, open files and thread body with the two-key
   parse in place of the detection decoder."""
 
-  def __init__(self, files, batch, shuffle, seed, num_classes, threads, verify):      # pylint: disable=super-init-not-called
+  def __init__(self, files, batch, shuffle, seed, num_classes, threads, verify, decode_crop=False):      # pylint: disable=super-init-not-called
     self.files, self.batch = files, int(batch)
     self.drop_remainder, self.num_classes = True, int(num_classes)
     self.threads, self.verify = threads, verify
     self.open = collections.OrderedDict()
     self.views = {}
-    self.order = dataloader.RecordOrder(len(files), self._has, shuffle, seed, repeat=shuffle)
+    self.order = _Order(dataloader.RecordOrder(len(files), self._has, shuffle, seed, repeat=shuffle),
+                        window_rng(seed) if decode_crop else None)
 
   def _error(self, pair, what, status=None):
     f, r = pair
@@ -170,14 +223,24 @@ class _Producer(dataloader._Producer):
       labels[i] = label - 1      # datasets.py:317-320
       offset, length = (int(v) for v in parsed.values['image/encoded'][i, 0])
       images.append(views[i][offset:offset + length])
-    return HostBatch(index, images, labels, self.order.get_state())
+    if self.order.rng is None:
+      return HostBatch(index, images, labels, self.order.get_state())
+    from automl_amd import jpeg, v2_preprocessing
+    sizes = jpeg.jpeg_sizes(images)
+    windows = np.zeros((len(index), 4), np.int32)
+    for i, (h, w) in enumerate(sizes):
+      if h >= 1 and w >= 1:      # (else: no draw; the decoder says what is wrong with the stream)
+        windows[i] = v2_preprocessing.sample_distorted_bounding_box(self.order.rng, int(h), int(w))
+      else:
+        sizes[i] = 0
+    return HostBatch(index, images, labels, self.order.get_state(), windows, sizes)
 
 
 class DeviceReader(object):
   """Iterator over ((raw, sizes), labels): dataloader.HostReader's batches through the reader's own jpeg.JpegDecoder."""
 
-  def __init__(self, host, canvas, depth, threads, fallback, max_ratio=1):
-    self._host, self._canvas = host, (int(canvas[0]), int(canvas[1]))
+  def __init__(self, host, canvas, depth, threads, fallback, max_ratio=1, decode_crop=False):
+    self._host, self._canvas, self._decode_crop = host, (int(canvas[0]), int(canvas[1])), bool(decode_crop)
     self._depth, self._threads, self._fallback, self._max_ratio = depth, threads, fallback, max_ratio
     self._decoder = None
     self.files = host.files
@@ -191,13 +254,38 @@ class DeviceReader(object):
       from automl_amd import jpeg
       threads = None if self._threads is None else min(int(self._threads), len(hb.images))
       ratio = {} if self._max_ratio == 1 else {'max_ratio': self._max_ratio}      # (1: the decoder as it is built without it)
+      if self._decode_crop:
+        ratio['windowed'] = True
       self._decoder = jpeg.JpegDecoder(len(hb.images), self._canvas[0], self._canvas[1], depth=self._depth, threads=threads,
                                        **ratio)
     try:
-      raw, sizes = self._decoder.decode(hb.images, fallback=self._fallback)
+      if self._decode_crop:
+        ratios, windows = self._output_windows(hb)
+        raw, sizes = self._decoder.decode(hb.images, fallback=self._fallback, windows=windows,
+                                          ratios=None if self._max_ratio == 1 else ratios)
+      else:
+        raw, sizes = self._decoder.decode(hb.images, fallback=self._fallback)
     except ValueError as e:
       raise ValueError(name_refused(str(e), hb.index, self.files))
     return (raw, sizes), hb.labels
+
+  def _output_windows(self, hb):
+    """The ratio of every image and its window in the output at that ratio (jpeg.choose_window_ratio).  A window that fits
+    the canvas at no ratio goes to the decoder at max_ratio, which calls it TOO_LARGE; an image without a readable header goes
+    with a one-pixel window, and the decoder gives the stream's own status."""
+    from automl_amd import jpeg
+    ratios, windows = [], np.zeros((len(hb.images), 4), np.int32)
+    for i, (window, (h, w)) in enumerate(zip(hb.windows, hb.image_sizes)):
+      if h < 1:
+        ratios.append(1)
+        windows[i] = (0, 0, 1, 1)
+        continue
+      got = jpeg.choose_window_ratio(window, int(h), int(w), self._canvas[0], self._canvas[1], self._max_ratio)
+      if got is None:
+        got = self._max_ratio, jpeg.covering_window(window, self._max_ratio)
+      ratios.append(got[0])
+      windows[i] = got[1]
+    return ratios, windows
 
   def get_state(self):
     return self._host.get_state()
@@ -269,23 +357,26 @@ class ImageNetInput(object):
       files = files[i::n]
     return files
 
-  def host_reader(self, batch_size, shard=None, depth=2, threads=None, verify=True):
+  def host_reader(self, batch_size, shard=None, depth=2, threads=None, verify=True, decode_crop=False):
     batch = int(batch_size)
     if batch < 1:
       raise ValueError('batch_size %d < 1' % batch)
     if threads is not None and not 1 <= int(threads) <= tfrecord.MAX_THREADS:
       raise ValueError('threads %d outside 1 .. %d' % (threads, tfrecord.MAX_THREADS))
+    if decode_crop and not self.is_training:
+      raise ValueError('decode_crop is for training: evaluation takes the whole image or its centre crop (eval_rows)')
     producer = _Producer(self.files(shard), batch, self.is_training and not self.debug, self.seed, self.num_classes, threads,
-                         verify)
+                         verify, bool(decode_crop))
     producer.open_first()
     return dataloader.HostReader(producer, depth, False)
 
-  def reader(self, batch_size, canvas=None, shard=None, depth=2, threads=None, fallback=None, verify=True, max_ratio=1):
+  def reader(self, batch_size, canvas=None, shard=None, depth=2, threads=None, fallback=None, verify=True, max_ratio=1,
+             decode_crop=False):
     if canvas is None or len(canvas) != 2:
       raise ValueError('canvas=(Hc, Wc) is needed: the slot every decoded image is written into (jpeg.JpegDecoder)')
     if max_ratio not in (1, 2, 4, 8):
       raise ValueError('max_ratio=%r: 1, 2, 4 or 8 (jpeg.JpegDecoder)' % (max_ratio,))
-    return DeviceReader(self.host_reader(batch_size, shard, depth, threads, verify), canvas, depth, threads, fallback,
-                        max_ratio)
+    return DeviceReader(self.host_reader(batch_size, shard, depth, threads, verify, decode_crop), canvas, depth, threads,
+                        fallback, max_ratio, decode_crop)
 
   __call__ = reader

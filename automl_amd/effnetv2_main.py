@@ -7,7 +7,8 @@
 The flags of efficientnetv2/cflags.py that mean something here keep their names: ``--model_name``, ``--dataset_cfg``,
 ``--hparam_str``, ``--data_dir``, ``--model_dir``, ``--mode``.  ``--canvas=HxW`` (the slot the reader's JPEG decoder writes
 every image into), ``--jpeg_max_ratio`` (1, 2, 4 or 8: an image larger than the canvas is decoded at the smallest
-tf.io.decode_jpeg ratio that fits it; default 1, full size only), ``--dtype`` (default: bf16 with runtime.mixed_precision, else f32) and ``--seed`` (the model's, its input
+tf.io.decode_jpeg ratio that fits it; default 1, full size only), ``--decode_crop`` (the training crop is drawn in the reader and only that window of each JPEG is
+decoded; the model then only flips), ``--dtype`` (default: bf16 with runtime.mixed_precision, else f32) and ``--seed`` (the model's, its input
 draws' and the reader's) are this project's own.
 
 The configuration is assembled as :121-125 does: ``base_config()`` -- hparams.base_config's train / eval / data / runtime
@@ -105,6 +106,9 @@ def define_flags():
   ap.add_argument('--jpeg_max_ratio', type=int, default=1, choices=[1, 2, 4, 8],
                   help='the largest ratio (tf.io.decode_jpeg) the reader may decode an image at so that it fits --canvas; 1: '
                        'full size only, a larger image is refused; 8 is recommended for full-size ImageNet')
+  ap.add_argument('--decode_crop', action='store_true',
+                  help="draw the training crop in the reader and decode only that window of each JPEG "
+                       "(tf.image.decode_and_crop_jpeg); the model is then built with transformations='flip'")
   ap.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help='storage dtype of the activations')
   ap.add_argument('--seed', type=int, default=0, help='seed of the model, its input draws and the reader')
   ap.add_argument('--lion_beta2', type=float, default=None, help='train.optimizer=lion: beta_2 (default 0.99)')
@@ -214,12 +218,14 @@ def build_model(flags, config, plan):
           if v is not None}
   if lion and str(train.optimizer).lower() != 'lion':
     raise ValueError('--lion_beta2 / --lion_wd need train.optimizer=lion, this run has %r' % (train.optimizer,))
+  # --decode_crop: the reader has cropped already (get_dataset), the step takes the whole "image" and draws the flip
+  crop = {'transformations': 'flip'} if getattr(flags, 'decode_crop', False) else {}
   return effnetv2_train.TrainableModel(
       config.model.model_name, config.model.as_dict(), weight_decay=train.weight_decay, optimizer=train.optimizer,
       learning_rate=learning_rate, label_smoothing=train.label_smoothing, dtype=dtype, seed=flags.seed,
       mixup_alpha=data.mixup_alpha, cutmix_alpha=data.cutmix_alpha, augname=data.augname,
       ra_num_layers=data.ra_num_layers, ra_magnitude=15 if data.ram is None else data.ram, image_size=plan['train_size'],
-      eval_image_size=plan['eval_size'], **lion)
+      eval_image_size=plan['eval_size'], **lion, **crop)
 
 
 def get_dataset(flags, config, plan, is_training):
@@ -227,7 +233,8 @@ def get_dataset(flags, config, plan, is_training):
   split = plan['train_split'] if is_training else plan['eval_split']
   batch = config.train.batch_size if is_training else config.eval.batch_size
   ds = effnetv2_datasets.build_dataset_input(is_training, None, None, flags.data_dir, split, config.data, seed=flags.seed)
-  return ds(batch, canvas=flags.canvas, max_ratio=flags.jpeg_max_ratio)
+  crop = {'decode_crop': True} if is_training and getattr(flags, 'decode_crop', False) else {}
+  return ds(batch, canvas=flags.canvas, max_ratio=flags.jpeg_max_ratio, **crop)
 
 
 class _WithoutHead(object):

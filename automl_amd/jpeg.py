@@ -13,8 +13,8 @@ is what tf.io.decode_jpeg's defaults and Pillow use; tests/jpeg_ref.py restates 
 Decoded: 8-bit Huffman streams of SOF0 / SOF1 in one interleaved scan, greyscale (replicated to three channels) or YCbCr
 at 4:4:4, 4:2:2 or 4:2:0.  Refused with a reason, never approximated: progressive, arithmetic-coded, 12-bit, lossless and
 hierarchical files, CMYK / YCCK, 4:4:0, 4:1:1 and any other sampling, RGB-coded components, several scans, malformed or
-truncated streams.  Not built: EXIF orientation (TensorFlow ignores it too), PNG / GIF / BMP, decode_and_crop_jpeg,
-dct_method, fancy_upscaling=False.  (TFRecord / tf.Example input is automl_amd/dataloader.py.)
+truncated streams.  Not built: EXIF orientation (TensorFlow ignores it too), PNG / GIF / BMP, dct_method,
+fancy_upscaling=False.  (TFRecord / tf.Example input is automl_amd/dataloader.py.)
 
 Reduced size: tf.io.decode_jpeg's `ratio` 2, 4 and 8 is libjpeg's scale_denom -- a block is inverse-transformed straight to
 4x4, 2x2 or 1x1 samples (jidctred.c), so the image comes out ceil(height / ratio) x ceil(width / ratio) at a fraction of the
@@ -22,6 +22,13 @@ device work (csrc/jpeg_scaled.hip: edet_jpeg_idct_scaled, edet_jpeg_color_scaled
 compared with Pillow's draft mode).  JpegDecoder(max_ratio=8) picks per image the smallest ratio whose output fits the canvas
 (choose_ratio), so a file of several thousand pixels a side lands in a 512 x 512 canvas instead of being TOO_LARGE; the Huffman
 stage and the coefficient copy still see the whole file.  max_ratio=1, the default, is the full-size decoder unchanged.
+
+Crop window: tf.image.decode_and_crop_jpeg's crop_window = (y, x, h, w), in the coordinates of the output image at the ratio it
+is decoded at.  The host stage stores only the blocks the window needs -- the kept grid, a rectangle of whole MCUs
+(window_grid) -- and stops reading behind its last MCU row, so the coefficient copy, the inverse DCT and the colour stage
+(csrc/jpeg_window.hip: edet_jpeg_color_window) all work on the kept area alone.  The result is the full decode's
+[y:y + h, x:x + w] byte for byte (tests/jpeg_window_ref.py).  JpegDecoder(windowed=True).decode(windows=...) takes one window
+per image; decode_and_crop_jpeg is the one-file form.
 """
 import collections
 import ctypes
@@ -43,9 +50,12 @@ REASONS = {
     MALFORMED: 'a malformed or truncated stream',
     UNSUPPORTED: 'a lossless or hierarchical frame, several or non-interleaved scans, or RGB-coded components',
 }
+WINDOW = 9
+REASONS[WINDOW] = 'a crop window outside the image, or with a side below 1'
 KINDS = ('baseline', 'extended', 'progressive', 'other')
 MAX_THREADS = 16
 IMAGE_BYTES = ctypes.sizeof(_lib.JpegImage)      # 80
+WINDOW_BYTES = ctypes.sizeof(_lib.JpegWindow)    # 48
 
 JpegInfo = collections.namedtuple('JpegInfo', 'height width components precision kind restart_interval sof h_samp v_samp '
                                               'quant_id comp_id jfif adobe_transform')
@@ -120,43 +130,171 @@ def worst_blocks(canvas_h, canvas_w):
   return max(3 * bh * bw, 4 * bh * mw, 6 * mh * mw)
 
 
+def _sample_sizes(components, h_max, v_max, ratio):
+  """Per component the side of a block after the inverse transform at `ratio`: 8 / ratio, twice that for the chroma of a
+  4:2:0 file below full size."""
+  m = 8 // ratio
+  return [2 * m if c > 0 and (h_max, v_max) == (2, 2) and m < 8 else m for c in range(components)]
+
+
+def window_grid(info, window, ratio=1):
+  """The kept grid of `window` = (y, x, h, w), in output pixels of jpeg_info's `info` decoded at `ratio`: ((mcu_y0, mcu_x0,
+  mcus_h, mcus_w), blocks) -- the smallest rectangle of whole MCUs that holds the samples every component needs (include/
+  edet_hip.h, "JPEG decode of a crop window"), and the 8x8 blocks it has, which is the descriptor's total_blocks.  A window
+  outside the output image or with a side below 1 raises ValueError."""
+  if ratio not in RATIOS:
+    raise ValueError('ratio=%r: 1, 2, 4 or 8' % (ratio,))
+  y, x, h, w = [int(v) for v in window]
+  out_h, out_w = scaled_size(info.height, info.width, ratio)
+  if y < 0 or x < 0 or h < 1 or w < 1 or y + h > out_h or x + w > out_w:
+    raise ValueError('crop window (y=%d, x=%d, h=%d, w=%d) is not inside the %d x %d image with sides of at least 1'
+                     % (y, x, h, w, out_h, out_w))
+  nc = 3 if info.components == 3 else 1
+  h_max, v_max = (info.h_samp[0], info.v_samp[0]) if nc == 3 else (1, 1)
+  sizes = _sample_sizes(nc, h_max, v_max, ratio)
+  lo, hi = [None, None], [None, None]      # MCU rows, MCU columns
+  for c in range(nc):
+    for axis, (first, size, whole, samp) in enumerate(((y, h, out_h, v_max), (x, w, out_w, h_max))):
+      u = 1 if c == 0 else samp * sizes[0] // sizes[c]
+      per_mcu = samp if c == 0 else 1
+      a, b = first, first + size - 1
+      if u == 2:
+        a, b = max(0, (a >> 1) - 1), min((whole + 1) // 2 - 1, (b >> 1) + 1)
+      a, b = a // sizes[c] // per_mcu, b // sizes[c] // per_mcu
+      lo[axis] = a if lo[axis] is None else min(lo[axis], a)
+      hi[axis] = b if hi[axis] is None else max(hi[axis], b)
+  mh, mw = hi[0] - lo[0] + 1, hi[1] - lo[1] + 1
+  per = h_max * v_max + 2 if nc == 3 else 1
+  return (lo[0], lo[1], mh, mw), per * mh * mw
+
+
+def worst_window_blocks(canvas_h, canvas_w, max_ratio=1):
+  """The most 8x8 blocks the kept grid of one window that fits the canvas can have, whatever the image around it, for any
+  supported sampling and any ratio up to max_ratio.  Along an axis a span of L output pixels touches at most (L + P - 2) // P + 1
+  MCUs of P output pixels; chroma that is still up-sampled by two needs up to three pixels more on either side (the guard of
+  the fancy formulas).  (The blocks kept grow with the square of the ratio, as the files' do: the default, max_ratio=1, is what
+  JpegDecoder multiplies by coef_blocks' rule.)"""
+  if max_ratio not in RATIOS:
+    raise ValueError('max_ratio=%r: 1, 2, 4 or 8' % (max_ratio,))
+
+  def mcus(length, p, guard):
+    return (length + (6 if guard else 0) + p - 2) // p + 1
+  most = 0
+  for ratio in RATIOS:
+    if ratio > max_ratio:
+      break
+    s = 8 // ratio
+    c444 = 3 * mcus(canvas_h, s, False) * mcus(canvas_w, s, False)
+    c422 = 4 * mcus(canvas_h, s, False) * mcus(canvas_w, 2 * s, True)
+    c420 = 6 * mcus(canvas_h, 2 * s, ratio == 1) * mcus(canvas_w, 2 * s, ratio == 1)
+    most = max(most, c444, c422, c420)
+  return most
+
+
+def covering_window(window_full, ratio):
+  """The window of the output at `ratio` that covers the full-size window (y, x, h, w): y' = y // ratio, h' = ceil((y + h) /
+  ratio) - y', x alike."""
+  y, x, h, w = [int(v) for v in window_full]
+  y2, x2 = y // ratio, x // ratio
+  return y2, x2, (y + h + ratio - 1) // ratio - y2, (x + w + ratio - 1) // ratio - x2
+
+
+def choose_window_ratio(window_full, height, width, canvas_h, canvas_w, max_ratio=8):
+  """For a window (y, x, h, w) in FULL-SIZE pixels of a height x width file: (ratio, window) with the smallest ratio of 1, 2, 4,
+  8 not above max_ratio at which the covering output window -- y' = y // r, h' = ceil((y + h) / r) - y', x alike -- fits the
+  canvas, or None if none does."""
+  if max_ratio not in RATIOS:
+    raise ValueError('max_ratio=%r: 1, 2, 4 or 8' % (max_ratio,))
+  y, x, h, w = [int(v) for v in window_full]
+  if y < 0 or x < 0 or h < 1 or w < 1 or y + h > height or x + w > width:
+    raise ValueError('crop window (y=%d, x=%d, h=%d, w=%d) is not inside the %d x %d image with sides of at least 1'
+                     % (y, x, h, w, height, width))
+  for r in RATIOS:
+    if r <= max_ratio:
+      out = covering_window((y, x, h, w), r)
+      if out[2] <= canvas_h and out[3] <= canvas_w:
+        return r, out
+  return None
+
+
+def jpeg_sizes(contents):
+  """(height, width) of every file from its headers (edet_jpeg_info; host only): int32 [B, 2], 0, 0 where the header cannot
+  be read."""
+  out = np.zeros((len(contents), 2), np.int32)
+  for i, c in enumerate(contents):
+    try:
+      info = jpeg_info(c)
+      out[i] = (info.height, info.width)
+    except ValueError:
+      pass
+  return out
+
+
+def _streams(datas):
+  """-> (count, what to keep alive, the void* array, the size_t array) of a batch of streams, read where they lie."""
+  n = len(datas)
+  keep = [_buffer(d, 'contents[%d]' % i) for i, d in enumerate(datas)]
+  ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) if isinstance(d, bytes) else d
+                                 for _, d, _ in keep])
+  return n, keep, ptrs, (ctypes.c_size_t * n)(*[size for _, _, size in keep])
+
+
+def _host(a):
+  return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def _forced(ratios, n):
+  """One ratio per image as an int32 array, or None."""
+  if ratios is None:
+    return None
+  if len(ratios) != n:
+    raise ValueError('%d ratios for %d files' % (len(ratios), n))
+  return (ctypes.c_int32 * n)(*[int(r) for r in ratios])
+
+
 def entropy_decode(datas, canvas_h, canvas_w, coef, images, qtables, status, threads=0):
   """edet_jpeg_entropy_decode on host arrays (numpy or CPU tensors): coef int16 [capacity], images uint8 [B * 80], qtables
   uint16 [B, 4, 64], status int32 [B].  Blocks until the batch is decoded; needs no device.  The streams are read where they
   lie (_buffer): nothing is copied, so a memoryview into a mapped file goes to the workers as it is."""
-  n = len(datas)
-  keep = [_buffer(d, 'contents[%d]' % i) for i, d in enumerate(datas)]      # alive until the call returns
-  ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) if isinstance(d, bytes) else d
-                                 for _, d, _ in keep])
-  sizes = (ctypes.c_size_t * n)(*[size for _, _, size in keep])
-
-  def host(a):
-    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+  n, _keep, ptrs, sizes = _streams(datas)      # (_keep: alive until the call returns)
   capacity = int(coef.size if isinstance(coef, np.ndarray) else coef.numel())
-  call('edet_jpeg_entropy_decode', ptrs, sizes, n, int(canvas_h), int(canvas_w), host(coef), capacity, host(images),
-       host(qtables), host(status), int(threads))
+  call('edet_jpeg_entropy_decode', ptrs, sizes, n, int(canvas_h), int(canvas_w), _host(coef), capacity, _host(images),
+       _host(qtables), _host(status), int(threads))
 
 
 def entropy_decode_scaled(datas, canvas_h, canvas_w, max_ratio, ratios, coef, images, qtables, status, threads=0):
   """edet_jpeg_entropy_decode_scaled on host arrays, as entropy_decode: ratios None (each image gets choose_ratio's answer)
   or one forced ratio per image.  The descriptors' height / width are the output sizes, `reserved` the ratio."""
-  n = len(datas)
-  keep = [_buffer(d, 'contents[%d]' % i) for i, d in enumerate(datas)]      # alive until the call returns
-  ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) if isinstance(d, bytes) else d
-                                 for _, d, _ in keep])
-  sizes = (ctypes.c_size_t * n)(*[size for _, _, size in keep])
-  forced = None
-  if ratios is not None:
-    if len(ratios) != n:
-      raise ValueError('%d ratios for %d files' % (len(ratios), n))
-    forced = (ctypes.c_int32 * n)(*[int(r) for r in ratios])
-
-  def host(a):
-    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+  n, _keep, ptrs, sizes = _streams(datas)      # (_keep: alive until the call returns)
+  forced = _forced(ratios, n)
   capacity = int(coef.size if isinstance(coef, np.ndarray) else coef.numel())
   call('edet_jpeg_entropy_decode_scaled', ptrs, sizes, n, int(canvas_h), int(canvas_w), int(max_ratio),
-       None if forced is None else ctypes.addressof(forced), host(coef), capacity, host(images), host(qtables), host(status),
+       None if forced is None else ctypes.addressof(forced), _host(coef), capacity, _host(images), _host(qtables), _host(status),
        int(threads))
+
+
+def entropy_decode_window(datas, canvas_h, canvas_w, max_ratio, ratios, windows, coef, images, wins, qtables, status,
+                          threads=0):
+  """edet_jpeg_entropy_decode_window on host arrays, as entropy_decode_scaled: windows int [B, 4] = (y, x, h, w) in output
+  pixels, ratios None (every image at ratio 1) or one per image; wins uint8 [B * 48] receives the window descriptors.  The
+  image descriptors describe the kept grids."""
+  n, _keep, ptrs, sizes = _streams(datas)      # (_keep: alive until the call returns)
+  forced = _forced(ratios, n)
+  win = None
+  if windows is not None:
+    win = np.ascontiguousarray(np.asarray(windows, np.int64).astype(np.int32))
+    if win.shape != (n, 4):
+      raise ValueError('windows must be [%d, 4] = (y, x, h, w) per file, got %s' % (n, list(win.shape)))
+  capacity = int(coef.size if isinstance(coef, np.ndarray) else coef.numel())
+  call('edet_jpeg_entropy_decode_window', ptrs, sizes, n, int(canvas_h), int(canvas_w), int(max_ratio),
+       None if forced is None else ctypes.addressof(forced), None if win is None else win.ctypes.data, _host(coef), capacity,
+       _host(images), _host(wins), _host(qtables), _host(status), int(threads))
+
+
+def window_descriptors(wins, batch):
+  """The per-image window array as a list of _lib.JpegWindow (copies)."""
+  raw = wins.tobytes() if isinstance(wins, np.ndarray) else wins.numpy().tobytes()
+  return [_lib.JpegWindow.from_buffer_copy(raw, i * WINDOW_BYTES) for i in range(batch)]
 
 
 def descriptors(images, batch):
@@ -169,7 +307,10 @@ class _Slot(object):
   """One set of arenas: pinned host memory the host stage writes, its device copy, the plane scratch, and the event behind
   the copies."""
 
-  def __init__(self, batch, blocks, device):
+  def __init__(self, batch, blocks, device, windowed=False):
+    if windowed:
+      self.windows_host = torch.zeros(batch * WINDOW_BYTES, dtype=torch.uint8).pin_memory()
+      self.windows = torch.zeros(batch * WINDOW_BYTES, dtype=torch.uint8, device=device)
     self.coef_host = torch.empty(blocks * 64, dtype=torch.int16).pin_memory()
     self.images_host = torch.zeros(batch * IMAGE_BYTES, dtype=torch.uint8).pin_memory()
     self.qtables_host = torch.zeros((batch, 4, 64), dtype=torch.int16).pin_memory()      # uint16 bits
@@ -192,9 +333,14 @@ class JpegDecoder(object):
   (the three *_scaled entry points; max_ratio=1 calls the full-size ones and allocates what it always did).  The coefficients
   of a file do not shrink with the ratio, so the arenas then hold coef_blocks 8x8 blocks per batch: by default four times the
   full-size worst case, batch * worst_blocks(canvas), at most max_ratio ** 2 times it (every image at the largest size that
-  still fits).  A batch whose files together have more blocks runs out of arena: the image that no longer fits is TOO_LARGE."""
+  still fits).  A batch whose files together have more blocks runs out of arena: the image that no longer fits is TOO_LARGE.
 
-  def __init__(self, batch, canvas_h, canvas_w, device='cuda:0', threads=None, depth=2, max_ratio=1, coef_blocks=None):
+  windowed=True: decode(windows=...) is allowed, and the arenas are sized for windows -- worst_window_blocks(canvas) in the
+  place of worst_blocks(canvas), under the same rule for max_ratio and coef_blocks: a window that fits the canvas can lie in
+  an image of any size, and keeps at most that many blocks at full size."""
+
+  def __init__(self, batch, canvas_h, canvas_w, device='cuda:0', threads=None, depth=2, max_ratio=1, coef_blocks=None,
+               windowed=False):
     batch, canvas_h, canvas_w, depth = int(batch), int(canvas_h), int(canvas_w), int(depth)
     if max_ratio not in RATIOS:
       raise ValueError('max_ratio=%r: 1, 2, 4 or 8' % (max_ratio,))
@@ -209,7 +355,8 @@ class JpegDecoder(object):
     threads = int(threads)
     if threads < 1 or threads > MAX_THREADS:
       raise ValueError('threads %d outside 1 .. %d' % (threads, MAX_THREADS))
-    full = batch * worst_blocks(canvas_h, canvas_w)
+    self.windowed = bool(windowed)
+    full = batch * (worst_window_blocks if self.windowed else worst_blocks)(canvas_h, canvas_w)
     most = max_ratio ** 2 * full
     if coef_blocks is None:
       coef_blocks = min(4, max_ratio ** 2) * full
@@ -227,10 +374,11 @@ class JpegDecoder(object):
                            'edet_jpeg_color): there is no CPU fall-back')
     _lib.load()
     self.batch, self.canvas_h, self.canvas_w, self.threads, self.depth = batch, canvas_h, canvas_w, threads, depth
-    self._slots = [_Slot(batch, self.blocks, self.device) for _ in range(depth)]
+    self._slots = [_Slot(batch, self.blocks, self.device, self.windowed) for _ in range(depth)]
     self._next = 0
 
-  def decode(self, contents, out=None, sizes_out=None, fallback=None, stream=None, ratios=None, ratios_out=None):
+  def decode(self, contents, out=None, sizes_out=None, fallback=None, stream=None, ratios=None, ratios_out=None,
+             windows=None):
     """contents: `batch` JPEG files as bytes -> (raw uint8 [B, Hc, Wc, 3] on the device, sizes int32 [B, 2] = (height,
     width) on the host): exactly pad_batch(decoded images, (Hc, Wc)).  out / sizes_out: where to write them (out a
     contiguous device tensor; every byte of it is written, so it needs no clearing).  A refused stream raises ValueError
@@ -241,7 +389,13 @@ class JpegDecoder(object):
     `depth` sets, so the host stage of one batch overlaps the device stage of the batch before.
     With max_ratio > 1 the sizes are the OUTPUT sizes.  ratios: one ratio per image (1, 2, 4 or 8, none above max_ratio) to use
     instead of the chosen one; an output that does not fit the canvas is TOO_LARGE.  ratios_out: a numpy int32 [B] array that
-    receives the ratio each image was decoded at (1 for an image that went to `fallback`)."""
+    receives the ratio each image was decoded at (1 for an image that went to `fallback`).
+    windows (a decoder built with windowed=True): int [B, 4] = (y, x, h, w) per image, in the coordinates of the image's
+    OUTPUT at its ratio -- ratios[i], or 1 throughout when max_ratio is 1; with max_ratio > 1 ratios must be given, since a
+    window belongs to one ratio.  Each canvas holds its window at the top-left, zero elsewhere, and sizes its (h, w).  A window
+    outside its image is refused like a stream (status WINDOW); so is one larger than the canvas (TOO_LARGE), while the image
+    around it may be of any size.  A stream that goes to `fallback` comes back WHOLE, uncropped, with the fallback image's
+    size.  windows=None calls the entry points it always did."""
     if len(contents) != self.batch:
       raise ValueError('%d files for a decoder of batch %d' % (len(contents), self.batch))
     b, hc, wc = self.batch, self.canvas_h, self.canvas_w
@@ -261,12 +415,24 @@ class JpegDecoder(object):
     if ratios_out is not None and not (isinstance(ratios_out, np.ndarray) and ratios_out.dtype == np.int32 and
                                        ratios_out.shape == (b,)):
       raise ValueError('ratios_out must be a numpy int32 [%d] array' % b)
-    scaled = self.max_ratio > 1
+    if windows is not None:
+      if not self.windowed:
+        raise ValueError('windows= needs a decoder built with windowed=True')
+      if ratios is None and self.max_ratio > 1:
+        raise ValueError('windows= with max_ratio=%d needs ratios=: a window is in the coordinates of one ratio' % self.max_ratio)
+      windows = np.asarray(windows)
+      if windows.shape != (b, 4) or windows.dtype.kind not in 'iu':
+        raise ValueError('windows must be int [%d, 4] = (y, x, h, w) per file' % b)
+    scaled = self.max_ratio > 1 or windows is not None
     slot = self._slots[self._next]
     self._next = (self._next + 1) % self.depth
     if slot.copied is not None:
       slot.copied.synchronize()      # the device has read this set's pinned arenas
-    if scaled:
+    if windows is not None:
+      entropy_decode_window(contents, hc, wc, self.max_ratio, ratios, windows, slot.coef_host, slot.images_host,
+                            slot.windows_host, slot.qtables_host, slot.status, self.threads)
+      wdesc = window_descriptors(slot.windows_host, b)
+    elif scaled:
       entropy_decode_scaled(contents, hc, wc, self.max_ratio, ratios, slot.coef_host, slot.images_host, slot.qtables_host,
                             slot.status, self.threads)
     else:
@@ -278,7 +444,7 @@ class JpegDecoder(object):
     for i, d in enumerate(desc):
       if d.status:
         if fallback is None:
-          why = self._reason(contents[i], d.status, None if ratios is None else ratios[i])
+          why = self._reason(contents[i], d.status, None if ratios is None else ratios[i], windows is not None)
           raise ValueError('contents[%d] is not decoded: %s (status %d)' % (i, why, d.status))
         img = fallback(contents[i])
         img = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
@@ -288,7 +454,7 @@ class JpegDecoder(object):
         filled[i] = img
         sizes_out[i] = (img.shape[0], img.shape[1])
       else:
-        sizes_out[i] = (d.height, d.width)
+        sizes_out[i] = (wdesc[i].h, wdesc[i].w) if windows is not None else (d.height, d.width)
     used = max([d.first_block[0] + d.total_blocks for d in desc if not d.status] or [0])
     most = max([d.total_blocks for d in desc] or [0])
     st = torch.cuda.current_stream(self.device) if stream is None else stream
@@ -299,21 +465,30 @@ class JpegDecoder(object):
         slot.coef[:used * 64].copy_(slot.coef_host[:used * 64], non_blocking=True)
       slot.images.copy_(slot.images_host, non_blocking=True)
       slot.qtables.copy_(slot.qtables_host, non_blocking=True)
+      if windows is not None:
+        slot.windows.copy_(slot.windows_host, non_blocking=True)
       slot.copied = torch.cuda.Event()
       slot.copied.record(st)
       raw = st.cuda_stream
       call('edet_jpeg_idct_scaled' if scaled else 'edet_jpeg_idct', ptr(slot.coef), ptr(slot.images), ptr(slot.qtables), b,
            most, ptr(slot.planes), self.blocks * 64, raw)
-      call('edet_jpeg_color_scaled' if scaled else 'edet_jpeg_color', ptr(slot.planes), ptr(slot.images), b, hc, wc,
-           self.blocks * 64, ptr(out), raw)
+      if windows is not None:
+        call('edet_jpeg_color_window', ptr(slot.planes), ptr(slot.images), ptr(slot.windows), b, hc, wc, self.blocks * 64,
+             ptr(out), raw)
+      else:
+        call('edet_jpeg_color_scaled' if scaled else 'edet_jpeg_color', ptr(slot.planes), ptr(slot.images), b, hc, wc,
+             self.blocks * 64, ptr(out), raw)
       slot.done = torch.cuda.Event()
       slot.done.record(st)
       for i, img in filled.items():
         out[i, :img.shape[0], :img.shape[1]].copy_(img, non_blocking=True)
     return out, sizes_out
 
-  def _reason(self, content, status, forced=None):
+  def _reason(self, content, status, forced=None, windowed=False):
     """REASONS[status]; for TOO_LARGE with max_ratio > 1 it says which of the two limits the image met."""
+    if windowed and status == TOO_LARGE:
+      return ('a crop window larger than the %d x %d canvas, or no room left in the coefficient arena of coef_blocks=%d blocks'
+              % (self.canvas_h, self.canvas_w, self.blocks))
     if status != TOO_LARGE or self.max_ratio == 1:
       return REASONS.get(int(status), '?')
     try:
@@ -349,4 +524,26 @@ def decode_jpeg(contents, channels=3, ratio=1):
     h, w = scaled_size(info.height, info.width, ratio)
     raw, _ = JpegDecoder(1, h, w, depth=1, max_ratio=ratio, coef_blocks=worst_blocks(info.height, info.width)).decode(
         [contents], ratios=[ratio])
+  return raw[0]
+
+
+def decode_and_crop_jpeg(contents, crop_window, channels=3, ratio=1):
+  """tf.image.decode_and_crop_jpeg(contents, crop_window, channels, ratio) with its defaults otherwise -> uint8 [h, w, 3] on
+  the device: decode_jpeg(contents, channels, ratio)[y:y + h, x:x + w] byte for byte, of which only the blocks the window needs
+  are copied to the device and transformed.  crop_window = (y, x, h, w) in pixels of the output at `ratio`; one that does not
+  lie inside it, or has a side below 1, raises ValueError, as does a stream that is not decoded."""
+  if channels not in (0, 3):
+    raise ValueError('channels=%r: 0 or 3 (a greyscale file is replicated to three channels)' % (channels,))
+  if ratio not in RATIOS:
+    raise ValueError('ratio=%r: 1, 2, 4 or 8' % (ratio,))
+  window = np.asarray(crop_window)
+  if window.shape != (4,) or window.dtype.kind not in 'iu':
+    raise ValueError('crop_window must be four integers (y, x, h, w), got %r' % (crop_window,))
+  info = jpeg_info(contents)
+  if info.height < 1 or info.width < 1:
+    raise ValueError('contents is not decoded: %s (status %d)' % (REASONS[MALFORMED], MALFORMED))
+  blocks = window_grid(info, window, ratio)[1]      # (raises for a window outside the image)
+  h, w = int(window[2]), int(window[3])
+  raw, _ = JpegDecoder(1, h, w, depth=1, max_ratio=ratio, coef_blocks=blocks, windowed=True).decode(
+      [contents], windows=window[None], ratios=[ratio])
   return raw[0]

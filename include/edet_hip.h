@@ -1033,6 +1033,59 @@ int edet_jpeg_idct_scaled(const int16_t* coef, const edet_jpeg_image_t* images_d
 int edet_jpeg_color_scaled(const uint8_t* planes, const edet_jpeg_image_t* images_dev, int batch, int canvas_h, int canvas_w,
                            size_t plane_capacity, uint8_t* raw, void* stream);
 
+/* ---- JPEG decode of a crop window (tf.image.decode_and_crop_jpeg's crop_window = [crop_y, crop_x, crop_height, crop_width];
+ * efficientnetv2/preprocess_legacy.py:53-68, 112-125) ------------------------------------------------------------------------
+ * The window of an image is, byte for byte, rows y .. y + h - 1 and columns x .. x + w - 1 of what the entry points above
+ * decode at the same denominator (1: edet_jpeg_idct / edet_jpeg_color; 2, 4, 8: the *_scaled pair), written at the top-left of
+ * the image's canvas slot; nothing is redefined.  The window is in the coordinates of the OUTPUT image, ceil(height / denom) x
+ * ceil(width / denom), as in TensorFlow's jpeg_mem, and must lie inside it with h >= 1 and w >= 1.  Only the blocks the window
+ * needs are stored, copied and inverse-transformed (csrc/jpeg_host.cpp, csrc/jpeg_window.hip; restated in
+ * tests/jpeg_window_ref.py).
+ * The kept grid.  Component c is inverse-transformed to s_c x s_c samples per block (above) and then up-sampled by u_x, u_y in
+ * {1, 2} (edet_jpeg_color_scaled: luma 1; chroma h_max s_0 / s_c, v_max s_0 / s_c); C_c = ceil(image_w / u_x) and R_c =
+ * ceil(image_h / u_y) are its real sample columns and rows.  The samples the window needs along x are [x, x + w - 1] for
+ * u_x = 1 and [max(0, (x >> 1) - 1), min(C_c - 1, ((x + w - 1) >> 1) + 1)] for u_x = 2 -- what the fancy formulas read, and
+ * used where libjpeg replicates as well; along y alike with R_c.  Blocks are samples / s_c, and the kept grid is the smallest
+ * rectangle of whole MCUs (mcu_x0, mcu_y0, mcus_w, mcus_h) that holds these blocks of every component.  A window that is the
+ * whole image keeps the whole grid. */
+#define EDET_JPEG_WINDOW 9        /* a window outside the output image, or with a side below 1                              */
+typedef struct edet_jpeg_window { /* 48 bytes, one per image: written by edet_jpeg_entropy_decode_window, read from DEVICE memory */
+  int32_t y, x, h, w;            /* the window, in output pixels; all fields 0 for an image whose status is not 0           */
+  int32_t image_h, image_w;      /* the output size of the WHOLE image: the edge rules of the up-sampling use these         */
+  int32_t mcu_x0, mcu_y0;        /* the first kept MCU column and row of the file's MCU grid                                */
+  int32_t mcus_w, mcus_h;        /* kept MCU columns and rows                                                               */
+  int32_t reserved[2];           /* 0                                                                                       */
+} edet_jpeg_window_t;
+/* edet_jpeg_entropy_decode_window (host, blocks until done): edet_jpeg_entropy_decode_scaled's arguments, windows int32
+ * [batch][4] = (y, x, h, w) and windows_host [batch], which it writes.  denoms NULL: every image is decoded at denominator 1
+ * (a window is in the coordinates of one denominator, so none is chosen); otherwise denoms[b].  The image descriptor
+ * describes the KEPT grid as an image of its own, so that edet_jpeg_idct_scaled runs on it unchanged: blocks_w / blocks_h
+ * are the kept blocks per component, first_block / total_blocks count kept blocks only, `reserved` is the denominator, and
+ * height / width are the output pixels the kept MCUs cover inside the image.  Coefficients are stored densely per component,
+ * in raster order over the kept grid.  Blocks outside it are parsed -- the DC predictors must advance -- and not stored, and
+ * parsing STOPS behind the last kept MCU row: damage behind that point is not reported (libjpeg, which reads a file row by
+ * row, would never read it either), so a stream that the whole-image entry points call EDET_JPEG_MALFORMED can decode here.
+ * Statuses, in this order behind the frame and scan checks: a window outside the output image or with a side below 1 is
+ * EDET_JPEG_WINDOW; a window higher or wider than the canvas is EDET_JPEG_TOO_LARGE (the IMAGE may exceed the canvas); an
+ * arena that runs out is EDET_JPEG_TOO_LARGE.  The call fails (-1) for what edet_jpeg_entropy_decode_scaled fails for and for
+ * null windows or windows_host.  Threads as above.
+ * The inverse DCT of a windowed batch is edet_jpeg_idct_scaled on these descriptors.
+ * edet_jpeg_color_window (device, one launch whatever the mix of samplings, denominators and windows):
+ * edet_jpeg_color_scaled's contract with an origin.  Canvas pixel (r, q) of the slot, r < h and q < w, is image pixel
+ * (y + r, x + q); sample (i, j) of component c lies at row i - mcu_y0 v_c s_c, column j - mcu_x0 h_c s_c of its kept plane
+ * (h_c, v_c: the component's blocks per MCU).  The first-column, last-column and row-clamp rules of the up-sampling, and the
+ * "more than two real columns" rule, use image_h and image_w, not the kept region.  The whole canvas is written: zero outside
+ * h x w, zero for a refused descriptor and for a pair of descriptors that the host stage could not have written -- the image
+ * descriptor must pass edet_jpeg_color_scaled's check against plane_capacity, and the window descriptor must name a window
+ * inside image_h x image_w and the canvas whose needed samples all lie inside the kept planes -- checked before anything is
+ * indexed.  windows_dev 4-byte aligned in DEVICE memory; the rest as edet_jpeg_color_scaled. */
+int edet_jpeg_entropy_decode_window(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
+                                    int max_denom, const int32_t* denoms, const int32_t* windows, int16_t* coef_host,
+                                    size_t coef_capacity, edet_jpeg_image_t* images_host, edet_jpeg_window_t* windows_host,
+                                    uint16_t* qtables_host, int32_t* status, int threads);
+int edet_jpeg_color_window(const uint8_t* planes, const edet_jpeg_image_t* images_dev, const edet_jpeg_window_t* windows_dev,
+                           int batch, int canvas_h, int canvas_w, size_t plane_capacity, uint8_t* raw, void* stream);
+
 /* ---- TFRecord input (dataloader.py:404-460 reads TFRecord shards of tf.train.Example; object_detection/
  * tf_example_decoder.py:30-169 names the keys) -- HOST only, csrc/tfrecord_host.cpp: plain C++, no device call.  Every input
  * is a (pointer, length) pair into the caller's memory, every output a caller-allocated array with a stated capacity; nothing

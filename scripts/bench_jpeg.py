@@ -14,6 +14,11 @@ tiles (16 KB), so its Huffman stage is far shorter than a photograph's --, one J
 *_scaled entry points (csrc/jpeg_scaled.hip); `--max_ratio` alone (with --ratio 1) runs full-size images through the same
 entry points.  With both at 1, the default, the full-size entry points are measured as before.  The host stage and the copy
 move the file's coefficients whatever the ratio; only the two kernels shrink.
+`--window` decodes a crop window of every image through edet_jpeg_entropy_decode_window, edet_jpeg_idct_scaled on the kept
+grids and edet_jpeg_color_window (csrc/jpeg_window.hip): `--window` or `--window sampled` draws one window per image with
+v2_preprocessing.sample_distorted_bounding_box from a fixed seed (at --ratio above 1: its covering output window),
+`--window whole` takes the whole image through the same path.  The canvas stays the whole output's size.  window_area is the
+mean share of the output's pixels the windows cover, kept_blocks the mean share of the file's blocks stored and copied.
 No ratio between two timings is asserted: the numbers are the result."""
 import argparse
 import io
@@ -65,15 +70,27 @@ def main(args):
   b = args.batch
   datas = [data] * b
   ratio, max_ratio = args.ratio, max(args.ratio, args.max_ratio)
-  scaled = max_ratio > 1
-  ratios = [ratio] * b if scaled else None
+  scaled = max_ratio > 1 or bool(args.window)
+  ratios = [ratio] * b if max_ratio > 1 else None
   out = {'batch': b, 'height': h, 'width': w, 'file': os.path.basename(args.file) if args.file else 'big_480x640_420',
          'file_bytes': len(data), 'reps': args.reps, 'ratio': ratio, 'max_ratio': max_ratio,
          'entry_points': 'scaled' if scaled else 'full size'}
   file_blocks = jpeg.worst_blocks(h, w)
   h, w = jpeg.scaled_size(h, w, ratio)      # the canvas: the output, exactly
   out['canvas'] = [h, w]
-  if scaled:
+  windows = None
+  if args.window:
+    from automl_amd import v2_preprocessing
+    rng = np.random.default_rng(args.window_seed)
+    full = [v2_preprocessing.sample_distorted_bounding_box(rng, out['height'], out['width']) if args.window == 'sampled'
+            else (0, 0, out['height'], out['width']) for _ in range(b)]
+    windows = np.array([jpeg.covering_window(win, ratio) for win in full], np.int32)
+    out['entry_points'] = 'window'
+    out['window'] = args.window
+    out['window_area'] = round(float(np.mean(windows[:, 2] * windows[:, 3])) / (h * w), 4)
+    dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2, max_ratio=max_ratio, windowed=True,
+                           coef_blocks=min(b * file_blocks, max_ratio ** 2 * b * jpeg.worst_window_blocks(h, w)))
+  elif scaled:
     dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2, max_ratio=max_ratio, coef_blocks=b * file_blocks)
   else:
     dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2)
@@ -81,7 +98,10 @@ def main(args):
   idct, color = ('edet_jpeg_idct_scaled', 'edet_jpeg_color_scaled') if scaled else ('edet_jpeg_idct', 'edet_jpeg_color')
 
   def host_stage(threads):
-    if scaled:
+    if windows is not None:
+      jpeg.entropy_decode_window(datas, h, w, max_ratio, ratios, windows, slot.coef_host, slot.images_host, slot.windows_host,
+                                 slot.qtables_host, slot.status, threads)
+    elif scaled:
       jpeg.entropy_decode_scaled(datas, h, w, max_ratio, ratios, slot.coef_host, slot.images_host, slot.qtables_host,
                                  slot.status, threads)
     else:
@@ -100,11 +120,15 @@ def main(args):
   most = max(d.total_blocks for d in desc)
   out['coefficient_bytes'] = used * 128
   out['blocks_per_image'] = most
+  if windows is not None:
+    out['kept_blocks'] = round(used / float(b * jpeg.window_grid(jpeg.jpeg_info(data), (0, 0, h, w), ratio)[1]), 4)
 
   def copy():
     slot.coef[:used * 64].copy_(slot.coef_host[:used * 64], non_blocking=True)
     slot.images.copy_(slot.images_host, non_blocking=True)
     slot.qtables.copy_(slot.qtables_host, non_blocking=True)
+    if windows is not None:
+      slot.windows.copy_(slot.windows_host, non_blocking=True)
   raw = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dec.device)
   st = torch.cuda.current_stream().cuda_stream
   copy()
@@ -113,19 +137,29 @@ def main(args):
   out['copy_GBps'] = round(used * 128 / (out['copy_ms']['median_ms'] * 1e-3) / 1e9, 1)
   out['idct_ms'] = events(lambda: call(idct, ptr(slot.coef), ptr(slot.images), ptr(slot.qtables), b, most,
                                        ptr(slot.planes), dec.blocks * 64, st), args.launches, args.reps)
-  out['color_ms'] = events(lambda: call(color, ptr(slot.planes), ptr(slot.images), b, h, w, dec.blocks * 64,
-                                        ptr(raw), st), args.launches, args.reps)
+  if windows is not None:
+    out['color_ms'] = events(lambda: call('edet_jpeg_color_window', ptr(slot.planes), ptr(slot.images), ptr(slot.windows), b, h,
+                                          w, dec.blocks * 64, ptr(raw), st), args.launches, args.reps)
+  else:
+    out['color_ms'] = events(lambda: call(color, ptr(slot.planes), ptr(slot.images), b, h, w, dec.blocks * 64,
+                                          ptr(raw), st), args.launches, args.reps)
   out['idct_ns_per_block'] = round(out['idct_ms']['median_ms'] * 1e6 / (b * most), 3)
-  assert rgb is None or ratio > 1 or np.array_equal(raw[b - 1].cpu().numpy(), rgb), 'the decoded batch differs from the fixture'
+  if windows is not None and rgb is not None and ratio == 1:
+    y, x, wh, ww = windows[b - 1]
+    want = np.zeros_like(rgb)
+    want[:wh, :ww] = rgb[y:y + wh, x:x + ww]
+    assert np.array_equal(raw[b - 1].cpu().numpy(), want), 'the decoded window differs from the fixture'
+  assert windows is not None or rgb is None or ratio > 1 or np.array_equal(raw[b - 1].cpu().numpy(), rgb), \
+      'the decoded batch differs from the fixture'
   sizes = np.zeros((b, 2), np.int32)
   for _ in range(2):
-    dec.decode(datas, out=raw, sizes_out=sizes, ratios=ratios)
+    dec.decode(datas, out=raw, sizes_out=sizes, ratios=ratios, windows=windows)
   torch.cuda.synchronize()
   times = []
   for _ in range(args.reps):
     t0 = time.perf_counter()
     for _ in range(args.batches):
-      dec.decode(datas, out=raw, sizes_out=sizes, ratios=ratios)
+      dec.decode(datas, out=raw, sizes_out=sizes, ratios=ratios, windows=windows)
     torch.cuda.synchronize()
     times.append((time.perf_counter() - t0) * 1e3 / args.batches)
   out['end_to_end'] = dict(stats(times), threads=args.threads, depth=2, batches_per_rep=args.batches,
@@ -147,7 +181,7 @@ def main(args):
         done = list(pool.map(one, datas))
         times.append((time.perf_counter() - t0) * 1e3)
     # (draft mode does not reach a ratio larger than the image's smaller side: then the sizes differ and nothing is compared)
-    assert done[0].shape != tuple(raw[0].shape) or np.array_equal(done[0], raw[0].cpu().numpy()), 'Pillow and the decoder differ'
+    assert windows is not None or done[0].shape != tuple(raw[0].shape) or np.array_equal(done[0], raw[0].cpu().numpy()), 'Pillow and the decoder differ'
     out['pillow'] = dict(stats(times[1:]), threads=args.threads,
                          images_per_s=round(b / (float(np.median(times[1:])) * 1e-3), 1))
   print(json.dumps(out))
@@ -159,6 +193,9 @@ if __name__ == '__main__':
   ap.add_argument('--ratio', type=int, default=1, choices=[1, 2, 4, 8], help='decode every image at this ratio')
   ap.add_argument('--max_ratio', type=int, default=1, choices=[1, 2, 4, 8],
                   help="the decoder's max_ratio; above 1 the *_scaled entry points run, also for --ratio 1")
+  ap.add_argument('--window', nargs='?', const='sampled', default='', choices=['sampled', 'whole'],
+                  help='decode a crop window of every image: sampled (sample_distorted_bounding_box, the default) or whole')
+  ap.add_argument('--window_seed', type=int, default=0)
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--threads', type=int, default=16)
   ap.add_argument('--reps', type=int, default=7)

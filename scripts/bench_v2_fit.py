@@ -17,6 +17,9 @@ is not importable the file goes in whole and the canvas is widened to hold it, w
 
   --mode hand_reader   the same hand loop fed by the reader (this tree): what the decode costs the step without fit.
 
+`--decode_crop` (modes fit and hand_reader): the reader draws the crop and decodes only that window of each file
+(reader(decode_crop=True)), and the model is built with transformations='flip', as effnetv2_main --decode_crop does.
+
 Prints one JSON line: images/s as the median of the rounds with the spread (max - min) beside it.  The comparison -- three
 processes of each mode, alternating -- is the caller's; no ratio is asserted here."""
 import argparse
@@ -75,7 +78,12 @@ def main(args):
          'jpeg_bytes': len(data), 'image_size': args.image_size, 'dtype': 'bf16', 'rounds': args.rounds, 'steps_per_round': args.steps,
          'root': os.path.relpath(os.path.abspath(args.root), ROOT)}
   net = effnetv2_train.TrainableModel(args.model, learning_rate=0.016, weight_decay=1e-5, label_smoothing=0.1, dtype='bf16', seed=0,
-                                      use_graph=True, image_size=args.image_size)
+                                      use_graph=True, image_size=args.image_size,
+                                      **({'transformations': 'flip'} if args.decode_crop else {}))
+  crop = {'decode_crop': True} if args.decode_crop else {}
+  out['decode_crop'] = bool(args.decode_crop)
+  if args.decode_crop and args.mode == 'hand':
+    sys.exit('--decode_crop needs the reader: --mode fit or hand_reader')
   rng = np.random.default_rng(args.seed)
   labels = rng.integers(0, CLASSES, n)
 
@@ -110,7 +118,7 @@ def main(args):
           w.write(tfrecord.encode_example({'image/encoded': data, 'image/class/label': [int(labels[i]) + 1]}))
     inp = effnetv2_datasets.ImageNetInput(True, tmp, 'trainval', seed=args.seed)
     if args.mode == 'hand_reader':
-      reader = inp(b, canvas=(canvas, canvas), depth=2, threads=args.threads)
+      reader = inp(b, canvas=(canvas, canvas), depth=2, threads=args.threads, **crop)
       for _ in range(3):      # eager, capture, replay
         net.train_step(next(reader), sync_loss=False)
       torch.cuda.synchronize()
@@ -127,7 +135,7 @@ def main(args):
       print(json.dumps(out))
       return
     # ---- the reader alone: the host half, then reader + decoder
-    host, rates = inp.host_reader(b, depth=2, threads=args.threads), []
+    host, rates = inp.host_reader(b, depth=2, threads=args.threads, **crop), []
     for _ in range(args.rounds + 1):
       t0 = time.perf_counter()
       for _ in range(args.steps):
@@ -135,7 +143,7 @@ def main(args):
       rates.append(args.steps * b / (time.perf_counter() - t0))
     host.close()
     out['host_records_per_s'] = stats(rates[1:])
-    reader, rates = inp(b, canvas=(canvas, canvas), depth=2, threads=args.threads), []
+    reader, rates = inp(b, canvas=(canvas, canvas), depth=2, threads=args.threads, **crop), []
     for _ in range(args.rounds + 1):
       t0 = time.perf_counter()
       for _ in range(args.steps):
@@ -145,7 +153,7 @@ def main(args):
     reader.close()
     out['reader_images_per_s'] = stats(rates[1:])
     # ---- fit over the reader
-    reader = inp(b, canvas=(canvas, canvas), depth=2, threads=args.threads)
+    reader = inp(b, canvas=(canvas, canvas), depth=2, threads=args.threads, **crop)
     net.fit(reader, epochs=1, steps_per_epoch=3, verbose=0)      # eager, capture, replay
     timer = EpochTimer()
     history = net.fit(reader, epochs=args.rounds + 1, steps_per_epoch=args.steps, callbacks=[timer], verbose=0)
@@ -171,4 +179,5 @@ if __name__ == '__main__':
   ap.add_argument('--rounds', type=int, default=5)
   ap.add_argument('--steps', type=int, default=8)
   ap.add_argument('--seed', type=int, default=0)
+  ap.add_argument('--decode_crop', action='store_true', help='the reader draws the crop and decodes only that window')
   main(ap.parse_args())
