@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libedet_hip.so')
 
 EDET_F32, EDET_BF16 = 0, 1
-EDET_U8 = 2      # out_dtype of edet_randaug_apply, edet_crop_resize and edet_mosaic only
+EDET_U8 = 2      # out_dtype of edet_randaug_apply(_norm), edet_crop_resize(_bicubic) and edet_mosaic only
 ACT_NONE, ACT_SWISH, ACT_RELU, ACT_RELU6, ACT_HSWISH, ACT_MISH, ACT_SRELU = 0, 1, 2, 3, 4, 5, 6
 ACT_CODES = {'swish': ACT_SWISH, 'silu': ACT_SWISH, 'swish_native': ACT_SWISH, 'relu': ACT_RELU, 'relu6': ACT_RELU6,
              'hswish': ACT_HSWISH, 'mish': ACT_MISH, 'srelu': ACT_SRELU}
@@ -197,10 +197,14 @@ SIGNATURES = {
     'edet_mix_labels': [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     'edet_randaug_stats': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     'edet_randaug_apply': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    'edet_randaug_apply_norm': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                ctypes.POINTER(c_float), c_void_p],
     'edet_randaug_stats_canvas': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     'edet_randaug_apply_canvas': [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_void_p],
     'edet_crop_resize': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    'edet_crop_resize_bicubic': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_float),
+                                 c_void_p],
     'edet_mosaic': [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p],
     'edet_mosaic_boxes': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                           c_void_p],

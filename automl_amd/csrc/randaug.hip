@@ -192,15 +192,29 @@ template <> __device__ __forceinline__ uint8_t out_of<uint8_t>(int v) { return (
 template <> __device__ __forceinline__ float out_of<float>(int v) { return (float)(v - 128) * (1.0f / 128.0f); }
 template <> __device__ __forceinline__ bf16_t out_of<bf16_t>(int v) { return f2bf((float)(v - 128) * (1.0f / 128.0f)); }
 
+// the conversion of one channel value into the destination's element: the fixed one above, or the legacy pipeline's
+// (v - mean[c]) / std[c] (preprocess_legacy.py:239-243) -- two rounded fp32 operations with an IEEE division, bf16 the one
+// final rounding of that value; uint8 is the value itself either way
+template <typename T> struct FixedOut {
+  __device__ __forceinline__ T operator()(int v, int) const { return out_of<T>(v); }
+};
+template <typename T> struct NormOut {
+  float mean[3], std[3];
+  __device__ __forceinline__ T operator()(int v, int c) const {
+    if constexpr (sizeof(T) == 1) return (T)v;
+    else return from_f<T>(((float)v - mean[c]) / std[c]);
+  }
+};
+
 template <typename T> struct alignas(sizeof(T) * 4) Quad { T v[4]; };
 
 // One image: `in` / `out` are its first pixel, `pitch` its row pitch in pixels (dense: w, the pixels are consecutive; canvas:
 // the canvas width, and only the h x w rectangle is read and written).  P pixels per thread and step: 4 (12 bytes in, three
 // 4-element stores out) or 1 (byte by byte); with CANVAS, P = 4 needs w and pitch to be multiples of 4.
-template <typename T, int P, bool CANVAS>
+template <typename T, int P, bool CANVAS, typename O = FixedOut<T>>
 __device__ __forceinline__ void apply_image(const uint8_t* __restrict__ in, T* __restrict__ out, int h, int w, int pitch, int img,
                                             const int32_t* __restrict__ ops, const int32_t* __restrict__ iargs,
-                                            const float* __restrict__ fargs, const uint8_t* __restrict__ luts) {
+                                            const float* __restrict__ fargs, const uint8_t* __restrict__ luts, const O conv = O()) {
   const int npix = h * w;
   Args a;
   a.op = ops ? ops[img] : OP_IDENTITY;
@@ -252,15 +266,15 @@ __device__ __forceinline__ void apply_image(const uint8_t* __restrict__ in, T* _
       for (int k = 0; k < 3; ++k) {
         Quad<T> o4;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o4.v[e] = out_of<T>(res[4 * k + e]);
+        for (int e = 0; e < 4; ++e) o4.v[e] = conv(res[4 * k + e], (4 * k + e) % 3);
         reinterpret_cast<Quad<T>*>(out)[q3 + k] = o4;
       }
     } else {
       const size_t o = CANVAS ? (size_t)(y * pitch + x) * 3 : (size_t)p0 * 3;
       const Px r = apply_px(a, x, y, load_px(a.img + o));
-      out[o] = out_of<T>(r.r);
-      out[o + 1] = out_of<T>(r.g);
-      out[o + 2] = out_of<T>(r.b);
+      out[o] = conv(r.r, 0);
+      out[o + 1] = conv(r.g, 1);
+      out[o + 2] = conv(r.b, 2);
     }
   }
 }
@@ -274,6 +288,17 @@ __global__ __launch_bounds__(THREADS) void k_randaug_apply(const uint8_t* __rest
   const int img = blockIdx.y;
   const int npix = h * w;
   apply_image<T, P, false>(src + (size_t)img * npix * 3, dst + (size_t)img * npix * 3, h, w, w, img, ops, iargs, fargs, luts);
+}
+
+// the same layer with the legacy normalisation in the last conversion (edet_randaug_apply_norm)
+template <typename T, int P>
+__global__ __launch_bounds__(THREADS) void k_randaug_apply_norm(const uint8_t* __restrict__ src, T* __restrict__ dst, int h, int w,
+                                                               const int32_t* __restrict__ ops, const int32_t* __restrict__ iargs,
+                                                               const float* __restrict__ fargs, const uint8_t* __restrict__ luts,
+                                                               NormOut<T> conv) {
+  const int img = blockIdx.y;
+  const int npix = h * w;
+  apply_image<T, P, false>(src + (size_t)img * npix * 3, dst + (size_t)img * npix * 3, h, w, w, img, ops, iargs, fargs, luts, conv);
 }
 
 // The canvas batch: image blockIdx.y is the top-left h x w of its ch x cw slot in src and in dst, (h, w) = sizes[img]
@@ -303,6 +328,24 @@ void launch_apply(const uint8_t* src, void* dst, int batch, int h, int w, const 
   const dim3 grid((unsigned)gx, (unsigned)batch);
   if (vec) edet_launch(k_randaug_apply<T, 4>, grid, dim3(THREADS), 0, st, src, (T*)dst, h, w, ops, iargs, fargs, luts);
   else edet_launch(k_randaug_apply<T, 1>, grid, dim3(THREADS), 0, st, src, (T*)dst, h, w, ops, iargs, fargs, luts);
+}
+
+template <typename T>
+void launch_apply_norm(const uint8_t* src, void* dst, int batch, int h, int w, const int32_t* ops, const int32_t* iargs,
+                       const float* fargs, const uint8_t* luts, const float* mean_std, hipStream_t st) {
+  NormOut<T> conv;
+  for (int c = 0; c < 3; ++c) {
+    conv.mean[c] = mean_std[c];
+    conv.std[c] = mean_std[3 + c];
+  }
+  const int npix = h * w;
+  const bool vec = npix % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+  const int units = vec ? npix / 4 : npix;
+  int gx = (units + THREADS * 4 - 1) / (THREADS * 4);      // launch_apply's grid
+  if (gx > 256) gx = 256;
+  const dim3 grid((unsigned)gx, (unsigned)batch);
+  if (vec) edet_launch(k_randaug_apply_norm<T, 4>, grid, dim3(THREADS), 0, st, src, (T*)dst, h, w, ops, iargs, fargs, luts, conv);
+  else edet_launch(k_randaug_apply_norm<T, 1>, grid, dim3(THREADS), 0, st, src, (T*)dst, h, w, ops, iargs, fargs, luts, conv);
 }
 
 template <typename T>
@@ -343,6 +386,27 @@ extern "C" int edet_randaug_apply(const uint8_t* src, void* dst, int batch, int 
   else if (out_dtype == EDET_BF16) launch_apply<bf16_t>(src, dst, batch, height, width, ops, iargs, fargs, luts, st);
   else EDET_CHECK(false, "edet_randaug_apply: bad out_dtype %d", out_dtype);
   EDET_LAUNCH_CHECK("edet_randaug_apply");
+  return 0;
+}
+
+extern "C" int edet_randaug_apply_norm(const uint8_t* src, void* dst, int batch, int height, int width, const int32_t* ops,
+                                       const int32_t* iargs, const float* fargs, const uint8_t* luts, int out_dtype,
+                                       const float* mean_std, void* stream) {
+  EDET_CHECK(src && dst && mean_std, "edet_randaug_apply_norm: null pointer");
+  EDET_CHECK(!ops || (iargs && fargs && luts), "edet_randaug_apply_norm: ops without iargs / fargs / luts");
+  EDET_CHECK((const void*)src != dst, "edet_randaug_apply_norm: in place (the geometric operations and Sharpness read neighbours)");
+  EDET_CHECK(batch > 0 && batch <= 65535 && height > 0 && width > 0, "edet_randaug_apply_norm: batch %d, image %d x %d", batch,
+             height, width);
+  EDET_CHECK((int64_t)height * width * 3 < (int64_t)1 << 31, "edet_randaug_apply_norm: image %d x %d too large", height, width);
+  for (int c = 0; c < 3; ++c)
+    EDET_CHECK(mean_std[3 + c] != 0.f && mean_std[3 + c] == mean_std[3 + c] && mean_std[c] == mean_std[c],
+               "edet_randaug_apply_norm: mean %g, std %g of channel %d", mean_std[c], mean_std[3 + c], c);
+  hipStream_t st = to_stream(stream);
+  if (out_dtype == OUT_U8) launch_apply_norm<uint8_t>(src, dst, batch, height, width, ops, iargs, fargs, luts, mean_std, st);
+  else if (out_dtype == EDET_F32) launch_apply_norm<float>(src, dst, batch, height, width, ops, iargs, fargs, luts, mean_std, st);
+  else if (out_dtype == EDET_BF16) launch_apply_norm<bf16_t>(src, dst, batch, height, width, ops, iargs, fargs, luts, mean_std, st);
+  else EDET_CHECK(false, "edet_randaug_apply_norm: bad out_dtype %d", out_dtype);
+  EDET_LAUNCH_CHECK("edet_randaug_apply_norm");
   return 0;
 }
 

@@ -54,6 +54,13 @@ whole.  With max_ratio > 1 each image is decoded at the smallest ratio at which 
 canvas (jpeg.choose_window_ratio); one that fits at no ratio is the decoder's TOO_LARGE.  Deliberate difference (5): the
 reference decodes the window at full size whatever its size; and the order of the draws is this project's, as for the crop in
 the step.  Without decode_crop nothing changes, the reader's state and the order of its records included.
+reader(..., decode_crop='legacy', crop_image_size=N): the same, with the LEGACY pipeline's window in place of the V2 sampler's
+-- preprocess_legacy.train_crop_window, the one function behind preprocess_legacy.legacy_train_rows: the box of area
+[0.08, 1], aspect ratio [3/4, 4/3], 10 attempts and min_object_covered 0.1, or the padded centre crop for training size N
+where the sampler hands back the whole image (preprocess_legacy.py:88-127) -- drawn from the header size on the same
+'window_rng' stream; the model is then TrainableModel(preprocessing='legacy', transformations='flip').  decode_crop=True
+keeps its sampler, stream and state.  A legacy reader's state carries 'window_sampler': 'legacy' beside the stream, and a
+state given to a reader with the other sampler raises: the stream never goes on silently under another sampler.
 
 Not built, raising ValueError('... is not built: ...'): every tfds-backed configuration (cifar10, cifar100, flowers,
 tfflowers, cars, imagenettfds: tensorflow_datasets is not available and its on-disk format is not read), imagenet21k (its
@@ -80,6 +87,7 @@ SPEC = (('image/encoded', 'bytes', 1), ('image/class/label', 'int64', 1))
 # an image whose header cannot be read has zeros in both
 HostBatch = collections.namedtuple('HostBatch', 'index images labels state windows image_sizes', defaults=(None, None))
 WINDOW_KEY = 'window_rng'
+SAMPLER_KEY = 'window_sampler'      # only in the state of a decode_crop='legacy' reader: which function draws from that stream
 
 # datasets.py:78-91; a slice is [start, stop] so that the table stays plain data (config.yaml)
 IMAGENET_CFG = dict(
@@ -161,8 +169,8 @@ class _Order(object):
   """dataloader.RecordOrder with the window generator's state next to its own: what the producer and HostReader know as the
   order.  rng None (no decode_crop): RecordOrder's state as it is."""
 
-  def __init__(self, order, rng):
-    self.order, self.rng = order, rng
+  def __init__(self, order, rng, sampler=None):
+    self.order, self.rng, self.sampler = order, rng, sampler      # sampler: None (the V2 box) or 'legacy'
 
   def next(self):
     return self.order.next()
@@ -175,6 +183,8 @@ class _Order(object):
     state = self.order.get_state()
     if self.rng is not None:
       state[WINDOW_KEY] = copy.deepcopy(self.rng.bit_generator.state)
+      if self.sampler is not None:
+        state[SAMPLER_KEY] = self.sampler
     return state
 
   def set_state(self, state):
@@ -182,6 +192,12 @@ class _Order(object):
       raise ValueError('this state has %s key %r and the reader was made with%s decode_crop: a state resumes a reader made the '
                        'same way' % (('the', WINDOW_KEY, 'out') if WINDOW_KEY in state else ('no', WINDOW_KEY, '')))
     state = dict(state)
+    sampler = state.pop(SAMPLER_KEY, None)
+    if sampler != self.sampler:
+      kind = lambda s: "decode_crop='legacy'" if s == 'legacy' else 'decode_crop=True'
+      raise ValueError('this state was saved by a reader made with %s and the reader was made with %s: the %r stream would go on '
+                       'under another sampler; a state resumes a reader made the same way' % (kind(sampler), kind(self.sampler),
+                                                                                                WINDOW_KEY))
     if self.rng is not None:
       self.rng.bit_generator.state = copy.deepcopy(state.pop(WINDOW_KEY))
     self.order.set_state(state)
@@ -191,14 +207,15 @@ class _Producer(dataloader._Producer):
   """The host half for classification records: dataloader._Producer's order, open files and thread body with the two-key
   parse in place of the detection decoder."""
 
-  def __init__(self, files, batch, shuffle, seed, num_classes, threads, verify, decode_crop=False):      # pylint: disable=super-init-not-called
+  def __init__(self, files, batch, shuffle, seed, num_classes, threads, verify, decode_crop=False, crop_image_size=None):      # pylint: disable=super-init-not-called
     self.files, self.batch = files, int(batch)
     self.drop_remainder, self.num_classes = True, int(num_classes)
     self.threads, self.verify = threads, verify
     self.open = collections.OrderedDict()
     self.views = {}
     self.order = _Order(dataloader.RecordOrder(len(files), self._has, shuffle, seed, repeat=shuffle),
-                        window_rng(seed) if decode_crop else None)
+                        window_rng(seed) if decode_crop else None, 'legacy' if decode_crop == 'legacy' else None)
+    self.legacy_size = int(crop_image_size) if decode_crop == 'legacy' else None
 
   def _error(self, pair, what, status=None):
     f, r = pair
@@ -225,11 +242,13 @@ class _Producer(dataloader._Producer):
       images.append(views[i][offset:offset + length])
     if self.order.rng is None:
       return HostBatch(index, images, labels, self.order.get_state())
-    from automl_amd import jpeg, v2_preprocessing
+    from automl_amd import jpeg, preprocess_legacy, v2_preprocessing
     sizes = jpeg.jpeg_sizes(images)
     windows = np.zeros((len(index), 4), np.int32)
     for i, (h, w) in enumerate(sizes):
-      if h >= 1 and w >= 1:      # (else: no draw; the decoder says what is wrong with the stream)
+      if h >= 1 and w >= 1 and self.legacy_size is not None:
+        windows[i] = preprocess_legacy.train_crop_window(self.order.rng, int(h), int(w), self.legacy_size)
+      elif h >= 1 and w >= 1:      # (else: no draw; the decoder says what is wrong with the stream)
         windows[i] = v2_preprocessing.sample_distorted_bounding_box(self.order.rng, int(h), int(w))
       else:
         sizes[i] = 0
@@ -357,26 +376,40 @@ class ImageNetInput(object):
       files = files[i::n]
     return files
 
-  def host_reader(self, batch_size, shard=None, depth=2, threads=None, verify=True, decode_crop=False):
+  @staticmethod
+  def _check_decode_crop(decode_crop, crop_image_size):
+    """decode_crop: False / True / 'legacy'; 'legacy' needs crop_image_size (the training size its centre-crop fallback is
+    made for), and nothing else takes one."""
+    if decode_crop not in (False, True, None, 'legacy'):
+      raise ValueError("decode_crop=%r: False, True or 'legacy'" % (decode_crop,))
+    if decode_crop == 'legacy':
+      if crop_image_size is None or int(crop_image_size) != crop_image_size or int(crop_image_size) < 1:
+        raise ValueError("decode_crop='legacy' needs crop_image_size, the training size (a positive integer): the centre-crop "
+                         'fallback of preprocess_legacy.py:110-127 depends on it; got %r' % (crop_image_size,))
+    elif crop_image_size is not None:
+      raise ValueError("crop_image_size belongs to decode_crop='legacy'")
+
+  def host_reader(self, batch_size, shard=None, depth=2, threads=None, verify=True, decode_crop=False, crop_image_size=None):
     batch = int(batch_size)
     if batch < 1:
       raise ValueError('batch_size %d < 1' % batch)
     if threads is not None and not 1 <= int(threads) <= tfrecord.MAX_THREADS:
       raise ValueError('threads %d outside 1 .. %d' % (threads, tfrecord.MAX_THREADS))
+    self._check_decode_crop(decode_crop, crop_image_size)
     if decode_crop and not self.is_training:
       raise ValueError('decode_crop is for training: evaluation takes the whole image or its centre crop (eval_rows)')
     producer = _Producer(self.files(shard), batch, self.is_training and not self.debug, self.seed, self.num_classes, threads,
-                         verify, bool(decode_crop))
+                         verify, 'legacy' if decode_crop == 'legacy' else bool(decode_crop), crop_image_size)
     producer.open_first()
     return dataloader.HostReader(producer, depth, False)
 
   def reader(self, batch_size, canvas=None, shard=None, depth=2, threads=None, fallback=None, verify=True, max_ratio=1,
-             decode_crop=False):
+             decode_crop=False, crop_image_size=None):
     if canvas is None or len(canvas) != 2:
       raise ValueError('canvas=(Hc, Wc) is needed: the slot every decoded image is written into (jpeg.JpegDecoder)')
     if max_ratio not in (1, 2, 4, 8):
       raise ValueError('max_ratio=%r: 1, 2, 4 or 8 (jpeg.JpegDecoder)' % (max_ratio,))
-    return DeviceReader(self.host_reader(batch_size, shard, depth, threads, verify, decode_crop), canvas, depth, threads,
-                        fallback, max_ratio, decode_crop)
+    return DeviceReader(self.host_reader(batch_size, shard, depth, threads, verify, decode_crop, crop_image_size), canvas, depth,
+                        threads, fallback, max_ratio, decode_crop)
 
   __call__ = reader

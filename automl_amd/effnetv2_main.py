@@ -8,7 +8,8 @@ The flags of efficientnetv2/cflags.py that mean something here keep their names:
 ``--hparam_str``, ``--data_dir``, ``--model_dir``, ``--mode``.  ``--canvas=HxW`` (the slot the reader's JPEG decoder writes
 every image into), ``--jpeg_max_ratio`` (1, 2, 4 or 8: an image larger than the canvas is decoded at the smallest
 tf.io.decode_jpeg ratio that fits it; default 1, full size only), ``--decode_crop`` (the training crop is drawn in the reader and only that window of each JPEG is
-decoded; the model then only flips), ``--dtype`` (default: bf16 with runtime.mixed_precision, else f32) and ``--seed`` (the model's, its input
+decoded; the model then only flips), ``--legacy_input`` (the reference's preprocess_legacy.py in front of the network, for the
+recipes whose data.augname starts with ``effnetv1_``: efficientnetv2-b0 .. b3, efficientnet-b0 .. b7), ``--dtype`` (default: bf16 with runtime.mixed_precision, else f32) and ``--seed`` (the model's, its input
 draws' and the reader's) are this project's own.
 
 The configuration is assembled as :121-125 does: ``base_config()`` -- hparams.base_config's train / eval / data / runtime
@@ -32,6 +33,13 @@ Refused with a reason, before a model or a reader exists: runtime.strategy 'tpu'
 base_config() restates it as None where the reference's default is 'tpu', which would refuse every run), ``--tpu*``,
 ``--use_tpu=true``, ``--export_to_tpu``, ``--sweeps``, a dataset configuration that is not built, an augname that
 TrainableModel refuses.  TensorBoard is left out.
+
+``--legacy_input``: a data.augname that starts with ``effnetv1_`` is then accepted; its remainder is the legacy pipeline's
+augment_name (``autoaug``, ``randaug``, or nothing for none) and the model is TrainableModel(preprocessing='legacy',
+augment_name=..., augname=None); ``--decode_crop`` then asks the reader for the legacy window (decode_crop='legacy' with the
+training size).  With the flag, an augname without the prefix is refused, and so is ``--decode_crop`` with a staged size
+schedule (the reader's centre-crop fallback is made for one training size and cannot follow the stages).  Without the flag
+everything is as before, the refusal of those names included.
 """
 import argparse
 import copy
@@ -109,6 +117,9 @@ def define_flags():
   ap.add_argument('--decode_crop', action='store_true',
                   help="draw the training crop in the reader and decode only that window of each JPEG "
                        "(tf.image.decode_and_crop_jpeg); the model is then built with transformations='flip'")
+  ap.add_argument('--legacy_input', action='store_true',
+                  help="the legacy EfficientNet input pipeline (preprocess_legacy.py: bicubic resize, AutoAugment v0, mean / "
+                       "stddev) for a recipe whose data.augname starts with 'effnetv1_'")
   ap.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help='storage dtype of the activations')
   ap.add_argument('--seed', type=int, default=0, help='seed of the model, its input draws and the reader')
   ap.add_argument('--lion_beta2', type=float, default=None, help='train.optimizer=lion: beta_2 (default 0.99)')
@@ -147,16 +158,29 @@ def build_config(flags):
     raise ValueError("runtime.strategy=%r is not built: classifier training is on one device ('tpu' has no counterpart and "
                      "'gpus' is data-parallel fit, which is not built); leave it out or set runtime.strategy=None" % (strategy,))
   effnetv2_datasets.get_dataset_class(config.data.ds_name)      # raises for a data set that is not built
-  if config.data.augname is not None:
+  if getattr(flags, 'legacy_input', False):
+    legacy_augment_name(config.data.augname)      # raises for a name without the prefix or with an unknown remainder
+  elif config.data.augname is not None:
     try:
       autoaugment.check_aug_name(config.data.augname)
     except ValueError as e:
       raise ValueError("%s -- the efficientnetv2-b* and efficientnet-b* recipes name 'effnetv1_autoaug' and the fine-tuning "
                        "configuration 'ft'; override it with --hparam_str=data.augname=randaug, or data.augname=None for no "
-                       'augmentation' % (e,))
+                       "augmentation; or, for an 'effnetv1_*' recipe, run its own legacy input pipeline with --legacy_input" % (e,))
   if config.train.loss_type not in (None, 'softmax'):
     raise ValueError('train.loss_type=%r is not built: train_step has the softmax loss' % (config.train.loss_type,))
   return config
+
+
+def legacy_augment_name(augname):
+  """data.augname of a legacy recipe -> TrainableModel's augment_name: 'effnetv1_autoaug' -> 'autoaug', 'effnetv1_randaug' ->
+  'randaug', 'effnetv1_' -> None (preprocessing.py:133-139 hands the remainder to preprocess_legacy)."""
+  from automl_amd import preprocess_legacy
+  name = str(augname)
+  if augname is None or not name.startswith('effnetv1_'):
+    raise ValueError("--legacy_input needs a data.augname that starts with 'effnetv1_' (the recipes of efficientnetv2-b0 .. b3 "
+                     'and efficientnet-b0 .. b7), this run has %r; without the flag the EfficientNetV2 pipeline runs' % (augname,))
+  return preprocess_legacy.check_augment_name(name[len('effnetv1_'):] or None)
 
 
 def _plain(value):
@@ -220,10 +244,14 @@ def build_model(flags, config, plan):
     raise ValueError('--lion_beta2 / --lion_wd need train.optimizer=lion, this run has %r' % (train.optimizer,))
   # --decode_crop: the reader has cropped already (get_dataset), the step takes the whole "image" and draws the flip
   crop = {'transformations': 'flip'} if getattr(flags, 'decode_crop', False) else {}
+  augname = data.augname
+  if getattr(flags, 'legacy_input', False):
+    crop.update(preprocessing='legacy', augment_name=legacy_augment_name(data.augname))
+    augname = None
   return effnetv2_train.TrainableModel(
       config.model.model_name, config.model.as_dict(), weight_decay=train.weight_decay, optimizer=train.optimizer,
       learning_rate=learning_rate, label_smoothing=train.label_smoothing, dtype=dtype, seed=flags.seed,
-      mixup_alpha=data.mixup_alpha, cutmix_alpha=data.cutmix_alpha, augname=data.augname,
+      mixup_alpha=data.mixup_alpha, cutmix_alpha=data.cutmix_alpha, augname=augname,
       ra_num_layers=data.ra_num_layers, ra_magnitude=15 if data.ram is None else data.ram, image_size=plan['train_size'],
       eval_image_size=plan['eval_size'], **lion, **crop)
 
@@ -234,6 +262,8 @@ def get_dataset(flags, config, plan, is_training):
   batch = config.train.batch_size if is_training else config.eval.batch_size
   ds = effnetv2_datasets.build_dataset_input(is_training, None, None, flags.data_dir, split, config.data, seed=flags.seed)
   crop = {'decode_crop': True} if is_training and getattr(flags, 'decode_crop', False) else {}
+  if crop and getattr(flags, 'legacy_input', False):
+    crop = {'decode_crop': 'legacy', 'crop_image_size': plan['train_size']}
   return ds(batch, canvas=flags.canvas, max_ratio=flags.jpeg_max_ratio, **crop)
 
 
@@ -257,6 +287,10 @@ def main(argv=None):
     raise ValueError('--model_dir is needed')
   config = build_config(flags)
   plan = plan_of(config)
+  if flags.legacy_input and flags.decode_crop and flags.mode == 'train' and config.train.stages:
+    raise ValueError('--legacy_input with --decode_crop and train.stages=%r: the reader draws the legacy window, whose centre-'
+                     'crop fallback is made for ONE training size, and cannot follow a staged size schedule; drop --decode_crop '
+                     'or set train.stages=0' % (config.train.stages,))
   from automl_amd import effnetv2_train, tf_checkpoint, train_lib, util_keras
   if 'train' in flags.mode:
     save_config(config, flags.model_dir)

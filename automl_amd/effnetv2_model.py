@@ -360,19 +360,21 @@ class V2Engine(layer_engine.LayerEngine):
     for dst, src, dt in ((self.ra_ops, ops, np.int32), (self.ra_iargs, iargs, np.int32), (self.ra_fargs, fargs, np.float32)):
       dst.copy_(torch.from_numpy(np.ascontiguousarray(src, dtype=dt).reshape(tuple(dst.shape))).pin_memory(), non_blocking=True)
 
-  def randaug_batch(self, images_u8, augment=True):
+  def randaug_batch(self, images_u8, augment=True, norm=None):
     """uint8 images [B, H, W, 3] -> the static network-input buffer (engine dtype), normalised (x - 128) / 128 by the last
     layer's launch: per layer edet_randaug_stats + edet_randaug_apply with the arguments of set_randaug_draws, ping-pong
-    through two uint8 buffers.  augment=False (test_step), or no layers: the normalising copy alone."""
+    through two uint8 buffers.  augment=False (test_step), or no layers: the normalising copy alone.  norm = (mean [3],
+    std [3]): the legacy pipeline's (x - mean) / std instead, by edet_randaug_apply_norm as the last launch."""
     from automl_amd import autoaugment
     b, (h, w) = self.batch, self.image_size
     assert images_u8.dtype == torch.uint8 and images_u8.is_contiguous() and tuple(images_u8.shape) == (b, h, w, 3), (
         images_u8.dtype, tuple(images_u8.shape))
     out = self.buf('randaug:images', (b, h, w, 3), self.tdtype)
     if not augment or self.ra_ops is None or self.ra_ops.shape[0] == 0:
-      return autoaugment.apply_layers(images_u8, out, None, None, None, None, None, self.stream)
+      return autoaugment.apply_layers(images_u8, out, None, None, None, None, None, self.stream, norm=norm)
     scratch = [self.buf('randaug:scratch%d' % k, (b, h, w, 3), torch.uint8) for k in range(min(int(self.ra_ops.shape[0]) - 1, 2))]
-    return autoaugment.apply_layers(images_u8, out, self.ra_ops, self.ra_iargs, self.ra_fargs, self.ra_luts, scratch, self.stream)
+    return autoaugment.apply_layers(images_u8, out, self.ra_ops, self.ra_iargs, self.ra_fargs, self.ra_luts, scratch, self.stream,
+                                    norm=norm)
 
   # ---- crop, resize and flip (efficientnetv2/preprocessing.py:22-70) on the device --------------------------------------
   crop_rows = None      # static int32 [B, 8] buffer of crop_batch (edet_crop_image_t rows), created by set_crop_rows
@@ -387,18 +389,19 @@ class V2Engine(layer_engine.LayerEngine):
     r = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32).reshape(b, 8)).pin_memory()
     self.crop_rows.copy_(r, non_blocking=True)
 
-  def crop_batch(self, raw_u8, to_u8):
+  def crop_batch(self, raw_u8, to_u8, method='bilinear', norm=None):
     """Decoded uint8 images on a common canvas [B, Hc, Wc, 3] -> this executor's image size with the rows of set_crop_rows:
     edet_crop_resize, the first launch of a step.  to_u8: into a static uint8 buffer (clipped and truncated,
     preprocessing.py:49-50) that randaug_batch reads next; else into the static network-input buffer in the engine's dtype,
-    normalised (v - 128) / 128."""
+    normalised (v - 128) / 128.  method='bicubic': edet_crop_resize_bicubic, whose float output is (v - mean) / std for
+    norm = (mean [3], std [3]) (the legacy pipeline, preprocess_legacy.py)."""
     from automl_amd import v2_preprocessing
     assert self.crop_rows is not None, 'crop_batch needs set_crop_rows first'
     b, (h, w) = self.batch, self.image_size
     assert raw_u8.dtype == torch.uint8 and raw_u8.is_contiguous() and raw_u8.dim() == 4 and raw_u8.shape[0] == b and \
         raw_u8.shape[3] == 3, (raw_u8.dtype, tuple(raw_u8.shape))
     out = self.buf('crop:u8', (b, h, w, 3), torch.uint8) if to_u8 else self.buf('crop:images', (b, h, w, 3), self.tdtype)
-    return v2_preprocessing.launch(raw_u8, self.crop_rows, out, self.stream)
+    return v2_preprocessing.launch(raw_u8, self.crop_rows, out, self.stream, method, norm)
 
   def l2_loss_eval(self, weight_decay):
     """The same L2 term for an evaluation pass (test_step, main_tf2.py:105-117), added to cls_sums[3] WITHOUT touching the

@@ -53,7 +53,10 @@ interrupted run continues bit for bit; ``ModelCheckpoint`` is ``train_lib``'s ca
 reader is automl_amd/effnetv2_datasets.py, the entry point automl_amd/effnetv2_main.py.
 
 Single GPU.  Not built, and raising or absent rather than ignored: data-parallel classifier training, ``conv_dropout``,
-AutoAugment v0 and ``ra_aa``, the legacy ``effnetv1_*`` preprocessing, the TF1 trainer's EMA-of-everything.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
+``ra_aa``, the ``ft*`` fine-tuning preprocessing, the TF1 trainer's EMA-of-everything.  The legacy ``effnetv1_*`` input
+pipeline (``preprocess_legacy.py``: bicubic crop-resize, AutoAugment v0 or RandAugment, mean / stddev normalisation) is built
+under keywords of its own, ``preprocessing='legacy'`` and ``augment_name``; ``augname`` keeps refusing the reference's
+spellings of it.  ``ema_decay`` is a constant-decay TFA MovingAverage shadow of the trainable variables (None, the
 reference's TF2 trainer, keeps none).
 """
 import json
@@ -65,6 +68,7 @@ import torch
 
 from automl_amd import autoaugment
 from automl_amd import effnetv2_model
+from automl_amd import preprocess_legacy
 from automl_amd import train_lib
 from automl_amd import util_keras
 from automl_amd import utils
@@ -154,6 +158,17 @@ def randaug_params(model_name):
   data = effnetv2_configs.get_model_config(model_name).as_dict().get('data') or {}
   ram = data.get('ram')
   return data.get('augname') or None, int(data.get('ra_num_layers') or 2), 15 if ram is None else ram
+
+
+def legacy_params(model_name):
+  """('autoaug' | 'randaug' | None, data.ra_num_layers, data.ram) of a named model whose recipe names the legacy input pipeline
+  (data.augname starts with 'effnetv1_': efficientnetv2-b0 .. b3, efficientnet-b0 .. b7; preprocessing.py:133-139) -- what
+  TrainableModel(preprocessing='legacy', augment_name=..., ra_num_layers=..., ra_magnitude=...) takes; None for every other
+  model.  The remainder of the name is the augmentation; an empty one means none."""
+  augname, layers, magnitude = randaug_params(model_name)
+  if not (augname or '').startswith('effnetv1_'):
+    return None
+  return preprocess_legacy.check_augment_name(augname[len('effnetv1_'):] or None), layers, magnitude
 
 
 IBASE = 128      # data.ibase of the reference's base configuration (hparams.py:284)
@@ -292,12 +307,19 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   canvas of any size (with their sizes) and crops, resizes and flips them on the device (`transformations`, the
   reference's 'crop|flip'; '' = the whole image, unflipped); test_step centre-crops and resizes them to eval_image_size
   (default: image_size).  The captured step is keyed on the canvas shape: a new one makes the next step eager and the one
-  after it captured again, so a fixed canvas (pad_batch(images, canvas)) keeps the graph."""
+  after it captured again, so a fixed canvas (pad_batch(images, canvas)) keeps the graph.
+  preprocessing: None (the default: nothing changes) or 'legacy' -- the reference's preprocess_legacy.py in front of the
+  network (automl_amd/preprocess_legacy.py; a named model's own recipe is legacy_params(model_name)): needs image_size (the
+  path starts from decoded canvases) and augname=None.  train_step then draws legacy_train_rows (with transformations='flip':
+  whole-image rows plus the flip draw, for a reader that already cut the windows), resizes with the bicubic kernel, augments
+  with augment_name -- None, 'autoaug' (AutoAugment v0) or 'randaug' (ra_num_layers, ra_magnitude), drawn from the generator
+  behind 'randaug_rng_state' -- and normalises with (x - MEAN_RGB) / STDDEV_RGB; test_step is the padded centre crop."""
 
   def __init__(self, model_name='efficientnetv2-s', model_config=None, name=None, weight_decay=0.0, optimizer='rmsprop',
                learning_rate=0.016, label_smoothing=0.0, ema_decay=None, momentum=0.9, use_graph=True, check_device_labels=False,
                mixup_alpha=0.0, cutmix_alpha=0.0, augname=None, ra_num_layers=2, ra_magnitude=15, image_size=None,
-               eval_image_size=None, transformations='crop|flip', lion_beta2=LION_BETA2, lion_wd=LION_WD, **kwargs):
+               eval_image_size=None, transformations='crop|flip', lion_beta2=LION_BETA2, lion_wd=LION_WD, preprocessing=None,
+               augment_name=None, **kwargs):
     super().__init__(model_name=model_name, model_config=model_config, include_top=True, name=name or model_name, **kwargs)
     optimizer = str(optimizer).lower()
     if optimizer not in OPTIMIZERS:
@@ -335,6 +357,23 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     self.transformations = 'crop|flip' if transformations is None else str(transformations)
     self._crop_rng = v2_preprocessing.crop_rng(self._seed)
     self._crop_forced = None
+    if preprocessing not in (None, 'legacy'):
+      raise ValueError("preprocessing %r: None or 'legacy'" % (preprocessing,))
+    self.preprocessing = preprocessing
+    self.augment_name = preprocess_legacy.check_augment_name(augment_name)
+    if preprocessing is None and self.augment_name is not None:
+      raise ValueError("augment_name=%r belongs to preprocessing='legacy'; the EfficientNetV2 pipeline's RandAugment is "
+                       "augname='randaug'" % (augment_name,))
+    if preprocessing == 'legacy':
+      if self.image_size is None:
+        raise ValueError("preprocessing='legacy' needs image_size: the legacy path starts from decoded canvases "
+                         '(preprocess_legacy.py:88-127)')
+      if self.augname is not None:
+        raise ValueError("preprocessing='legacy' needs augname=None, got %r: the legacy pipeline's augmentation is the "
+                         "keyword augment_name (None, 'autoaug' or 'randaug')" % (augname,))
+      if self.transformations not in ('crop|flip', 'flip'):
+        raise ValueError("preprocessing='legacy' takes transformations 'crop|flip' or 'flip' (windows already cut by the "
+                         'reader), got %r' % (self.transformations,))
     # fit / evaluate: float32 [4] device sums of cls_sums over the steps, by name
     self._sums_acc = {}
     self.fit_input = None        # the iterator fit is reading from (ModelCheckpoint saves its state)
@@ -359,9 +398,23 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     """One entry of progressive_stages: its image size, its RandAugment magnitude (when augname is set) and its mixup /
     cutmix alphas, from the next step on."""
     self.set_image_size(stage['image_size'])
-    if self.augname is not None:
+    if self._has_magnitude:
       self.set_randaug(stage['ra_magnitude'])
     self.set_mix_alphas(stage['mixup_alpha'], stage['cutmix_alpha'])
+
+  @property
+  def _augments(self):
+    """The step augments uint8 images on the device: augname (the V2 pipeline) or augment_name (the legacy one)."""
+    return self.augname is not None or self.augment_name is not None
+
+  @property
+  def _has_magnitude(self):
+    """A RandAugment magnitude is part of the step (AutoAugment's levels are its table's own)."""
+    return self.augname is not None or self.augment_name == 'randaug'
+
+  @property
+  def legacy(self):
+    return self.preprocessing == 'legacy'
 
   def force_crop_rows(self, rows):
     """Use these rows (v2_preprocessing.train_rows' int32 [batch, 8]) for every following train_step instead of drawing;
@@ -371,13 +424,15 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
   def set_randaug(self, magnitude):
     """A new RandAugment magnitude from the next step on (the reference ramps it per progressive-training stage,
     main_tf2.py:262-275); a float in [0, 20].  Only the argument buffers change: the captured step is kept."""
-    if self.augname is None:
-      raise ValueError('set_randaug on a model built without augname')
+    if not self._has_magnitude:
+      raise ValueError("set_randaug on a model built without augname (or, with preprocessing='legacy', without "
+                       "augment_name='randaug')")
     self.ra_magnitude = autoaugment.check_magnitude(magnitude)
 
   def force_randaug_draws(self, draws):
-    """Use these draws (autoaugment.randaug_draws' four arrays [ra_num_layers, batch]) for every following step instead of
-    drawing; None = draw again.  For tests and debugging."""
+    """Use these draws (autoaugment.randaug_draws' four arrays [ra_num_layers, batch]; with augment_name='autoaug'
+    autoaugment.autoaug_draws' three) for every following step instead of drawing; None = draw again.  For tests and
+    debugging."""
     self._ra_forced = draws
 
   def set_mix_alphas(self, mixup_alpha, cutmix_alpha):
@@ -493,7 +548,13 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
 
   # ---- the step ------------------------------------------------------------------------------------------------------
   def _step_body(self, eng, images, labels):
-    if self.image_size is not None:
+    if self.legacy:
+      # decoded uint8 canvases -> the training size by the bicubic kernel: uint8 for the augmentation, else normalised
+      norm = preprocess_legacy.NORM
+      images = eng.crop_batch(images, to_u8=self._augments, method='bicubic', norm=None if self._augments else norm)
+      if self._augments:
+        images = eng.randaug_batch(images, norm=norm)
+    elif self.image_size is not None:
       # decoded uint8 canvases -> the training size: uint8 for RandAugment, else the normalised network input
       images = eng.crop_batch(images, to_u8=self.augname is not None)
     if self.augname is not None:
@@ -557,7 +618,13 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       h, w = eng.image_size
       weights, boxes = draw_mix(self._mix_rng, eng.batch, h, w, self.mixup_alpha, self.cutmix_alpha)
       eng.set_mix_draws(weights, boxes, mix_split(eng.batch, self.mixup_alpha, self.cutmix_alpha))
-    if self.augname is not None:
+    if self.augment_name == 'autoaug':
+      h, w = eng.image_size
+      draws = self._ra_forced
+      if draws is None:
+        draws = autoaugment.autoaug_draws(self._ra_rng, eng.batch, 'v0')
+      eng.set_randaug_draws(*autoaugment.autoaug_args(draws, h, w, 'v0'))
+    elif self._augments:
       h, w = eng.image_size
       draws = self._ra_forced
       if draws is None:
@@ -565,7 +632,10 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       eng.set_randaug_draws(*autoaugment.randaug_args(draws, self.ra_magnitude, h, w))
     if self.image_size is not None:
       rows = self._crop_forced
-      if rows is None:
+      if rows is None and self.legacy:
+        rows = (preprocess_legacy.legacy_flip_rows(self._crop_rng, sizes) if self.transformations == 'flip' else
+                preprocess_legacy.legacy_train_rows(self._crop_rng, sizes, self.image_size))
+      elif rows is None:
         rows = v2_preprocessing.train_rows(self._crop_rng, sizes, self.transformations)
       eng.set_crop_rows(rows)
     if self.use_graph:
@@ -588,7 +658,10 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     if self.image_size is not None and images.dtype == torch.uint8:
       size = self.eval_image_size or self.image_size
     eng, images, labels = self._prepare((images, labels), crop_size=size)
-    if size is not None:
+    if size is not None and self.legacy:
+      eng.set_crop_rows(preprocess_legacy.legacy_eval_rows(self._raw_sizes(sizes, images), size))
+      images = eng.crop_batch(images, to_u8=False, method='bicubic', norm=preprocess_legacy.NORM)
+    elif size is not None:
       eng.set_crop_rows(v2_preprocessing.eval_rows(self._raw_sizes(sizes, images), size))
       images = eng.crop_batch(images, to_u8=False)
     elif images.dtype == torch.uint8:
@@ -612,7 +685,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
     state['iterations'] = self.iterations
     state['rng_state'] = self.engine._rng.get_state().cpu().numpy().copy()
     state['mix_rng_state'] = _pack_rng_state(self._mix_rng)
-    if self.augname is not None:
+    if self._augments:
       state['randaug_rng_state'] = _pack_rng_state(self._ra_rng)
     if self.image_size is not None:
       state['crop_rng_state'] = _pack_rng_state(self._crop_rng)
@@ -632,7 +705,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
       eng._rng.set_state(torch.as_tensor(state['rng_state'], dtype=torch.uint8))
     if 'mix_rng_state' in state:
       _unpack_rng_state(self._mix_rng, state['mix_rng_state'])
-    if self.augname is not None and 'randaug_rng_state' in state:
+    if self._augments and 'randaug_rng_state' in state:
       _unpack_rng_state(self._ra_rng, state['randaug_rng_state'])
     if self.image_size is not None and 'crop_rng_state' in state:
       _unpack_rng_state(self._crop_rng, state['crop_rng_state'])
@@ -644,7 +717,7 @@ class TrainableModel(effnetv2_model.EffNetV2Model):
             'cutmix_alpha': self.cutmix_alpha}
 
   def _in_stage(self, stage):
-    keys = ('image_size', 'mixup_alpha', 'cutmix_alpha') + (('ra_magnitude',) if self.augname is not None else ())
+    keys = ('image_size', 'mixup_alpha', 'cutmix_alpha') + (('ra_magnitude',) if self._has_magnitude else ())
     mine = self.current_stage()
     return all(float(stage[k]) == float(mine[k]) for k in keys)
 
@@ -832,7 +905,7 @@ def restore_train_state(model, path, reader=None):
   stage = meta.get('stage') or {}
   if model.image_size is not None and stage.get('image_size') is not None:
     model.set_image_size(stage['image_size'])
-  if model.augname is not None and 'ra_magnitude' in stage:
+  if model._has_magnitude and 'ra_magnitude' in stage:
     model.set_randaug(stage['ra_magnitude'])
   if 'mixup_alpha' in stage:
     model.set_mix_alphas(stage['mixup_alpha'], stage['cutmix_alpha'])

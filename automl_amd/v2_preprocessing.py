@@ -19,6 +19,7 @@ What cannot be pinned against TensorFlow here (it is not installed, and both pie
   where TensorFlow's own float32 evaluation lands on the other side of an integer the two taps' weights differ by one ulp's
   worth, never the taps' range.
 """
+import ctypes
 import math
 
 import numpy as np
@@ -57,10 +58,15 @@ def _round(v):
   return int(round(v))
 
 
-def sample_distorted_bounding_box(rng, height, width, area_range=(0.05, 1.0), aspect_ratio_range=(0.75, 1.33), max_attempts=100):
+def sample_distorted_bounding_box(rng, height, width, area_range=(0.05, 1.0), aspect_ratio_range=(0.75, 1.33), max_attempts=100,
+                                  min_object_covered=0.0):
   """tf.image.sample_distorted_bounding_box for the reference's call (preprocessing.py:32-37: no boxes,
   min_object_covered=0, use_image_if_no_bounding_boxes=True) -> (y, x, h, w) of the crop.  `rng`: a numpy Generator.
-  TensorFlow's generator stream and tie-breaking are not reproduced (module docstring)."""
+  TensorFlow's generator stream and tie-breaking are not reproduced (module docstring).
+  min_object_covered: the legacy pipeline's call (preprocess_legacy.py:88-98) hands the op ONE box, the whole image, and
+  0.1: a candidate covers the fraction (its area) / (the image's area) of that box, so one whose area is below
+  min_object_covered x the image's area is a failed attempt.  At the default 0 nothing changes: the same draws are consumed
+  and the same box returned."""
   height, width = int(height), int(width)
   if height < 1 or width < 1:
     raise ValueError('image %d x %d' % (height, width))
@@ -86,6 +92,8 @@ def sample_distorted_bounding_box(rng, height, width, area_range=(0.05, 1.0), as
       h -= 1
       w = _round(h * ratio)
     if w * h < min_area or w * h > max_area or w > width or h > height or w <= 0 or h <= 0:
+      continue
+    if w * h < min_object_covered * height * width:      # (never at the default 0)
       continue
     y = int(rng.integers(0, height - h + 1))
     x = int(rng.integers(0, width - w + 1))
@@ -161,20 +169,49 @@ def clamp_rows(rows, canvas_h, canvas_w):
   return out.astype(np.int32)
 
 
-def launch(raw, rows_dev, out, stream):
-  """edet_crop_resize on device tensors: raw uint8 [B, Hc, Wc, 3], rows int32 [B, 8], out [B, h, w, 3] uint8 / fp32 / bf16."""
+METHODS = ('bilinear', 'bicubic')
+
+
+def mean_std_array(norm):
+  """norm = (mean [3], std [3]) -> the six host floats edet_crop_resize_bicubic / edet_randaug_apply_norm read at the call
+  (a ctypes array; None stays None)."""
+  if norm is None:
+    return None
+  mean, std = (np.asarray(v, np.float32).reshape(-1) for v in norm)
+  if mean.shape != (3,) or std.shape != (3,) or not np.isfinite(mean).all() or not np.isfinite(std).all() or (std == 0).any():
+    raise ValueError('norm must be (mean [3], std [3]) of finite floats with no std 0, got %r' % (norm,))
+  return (ctypes.c_float * 6)(*[float(v) for v in np.concatenate([mean, std])])
+
+
+def launch(raw, rows_dev, out, stream, method='bilinear', norm=None):
+  """edet_crop_resize (method 'bilinear') or edet_crop_resize_bicubic ('bicubic', with norm = (mean, std) or None) on device
+  tensors: raw uint8 [B, Hc, Wc, 3], rows int32 [B, 8], out [B, h, w, 3] uint8 / fp32 / bf16."""
   b, hc, wc = int(raw.shape[0]), int(raw.shape[1]), int(raw.shape[2])
+  if method not in METHODS:
+    raise ValueError('method %r: one of %s' % (method, ', '.join(METHODS)))
+  if method == 'bicubic':
+    call('edet_crop_resize_bicubic', ptr(raw), b, hc, wc, ptr(rows_dev), ptr(out), int(out.shape[1]), int(out.shape[2]),
+         _OUT[out.dtype][0], mean_std_array(norm), stream, nbytes=out.numel() * out.element_size())
+    return out
+  if norm is not None:
+    raise ValueError("norm needs method='bicubic': the bilinear kernel's float output is (v - 128) / 128")
   # (nbytes: the bytes written; the bytes read are the crop areas, which only the device knows)
   call('edet_crop_resize', ptr(raw), b, hc, wc, ptr(rows_dev), ptr(out), int(out.shape[1]), int(out.shape[2]),
        _OUT[out.dtype][0], stream, nbytes=out.numel() * out.element_size())
   return out
 
 
-def crop_resize(raw, rows, out_size, out_dtype=None, out=None, stream=None):
+def crop_resize(raw, rows, out_size, out_dtype=None, out=None, stream=None, method='bilinear', norm=None):
   """Crop, resize and flip a canvas batch on the device: raw uint8 [B, Hc, Wc, 3] (numpy or torch), rows [B, 8] (train_rows /
   eval_rows; a device tensor is used as it is) -> [B, out_h, out_w, 3], uint8 (clipped and truncated, RandAugment's input)
   or, with out_dtype torch.float32 / torch.bfloat16, the normalised network input (v - 128) / 128.  out_size: an int or
-  (out_h, out_w)."""
+  (out_h, out_w).  method='bicubic': the legacy pipeline's tf.image.resize_bicubic (edet_crop_resize_bicubic); its float
+  output is (v - mean[c]) / std[c] for norm = (mean [3], std [3]), or the resized values as they are for norm=None."""
+  if method not in METHODS:
+    raise ValueError('method %r: one of %s' % (method, ', '.join(METHODS)))
+  if norm is not None and method != 'bicubic':
+    raise ValueError("norm needs method='bicubic': the bilinear kernel's float output is (v - 128) / 128")
+  mean_std_array(norm)
   if out_dtype not in _OUT:
     raise ValueError('out_dtype %r: None / torch.uint8, torch.float32 or torch.bfloat16' % (out_dtype,))
   x = torch.from_numpy(raw) if isinstance(raw, np.ndarray) else raw
@@ -195,4 +232,4 @@ def crop_resize(raw, rows, out_size, out_dtype=None, out=None, stream=None):
     out = torch.empty((b, oh, ow, 3), dtype=_OUT[out_dtype][1], device=x.device)
   elif tuple(out.shape) != (b, oh, ow, 3) or not out.is_contiguous() or out.dtype not in _OUT:
     raise ValueError('out must be a contiguous [%d, %d, %d, 3] uint8 / float32 / bfloat16 tensor' % (b, oh, ow))
-  return launch(x, r, out, torch.cuda.current_stream().cuda_stream if stream is None else stream)
+  return launch(x, r, out, torch.cuda.current_stream().cuda_stream if stream is None else stream, method, norm)

@@ -519,6 +519,14 @@ int edet_mix_labels(const int32_t* labels, int batch, int num_classes, int heigh
 int edet_randaug_stats(const uint8_t* src, int batch, int height, int width, const int32_t* ops, uint8_t* luts, void* stream);
 int edet_randaug_apply(const uint8_t* src, void* dst, int batch, int height, int width, const int32_t* ops,
                        const int32_t* iargs, const float* fargs, const uint8_t* luts, int out_dtype, void* stream);
+/* edet_randaug_apply_norm: edet_randaug_apply (the same kernel body) whose fp32 / bf16 conversion is the legacy pipeline's
+ * (efficientnetv2/preprocess_legacy.py:239-243): fp32 = (float(v) - mean[c]) / std[c], two individually rounded fp32
+ * operations with a true IEEE division; bf16 = that value rounded to nearest even.  mean_std: a HOST pointer to six floats
+ * {mean r, g, b, std r, g, b}, read at the call and passed to the kernel by value; never NULL, no std zero or NaN.
+ * EDET_U8 is edet_randaug_apply's output byte for byte. */
+int edet_randaug_apply_norm(const uint8_t* src, void* dst, int batch, int height, int width, const int32_t* ops,
+                            const int32_t* iargs, const float* fargs, const uint8_t* luts, int out_dtype, const float* mean_std,
+                            void* stream);
 /* The same two on a CANVAS batch: src (and dst, in its own element type) [batch][canvas_h][canvas_w][3]; image b is the
  * top-left sizes_dev[b] = {height, width} of its slot (int32 [batch][2], DEVICE memory), its row pitch canvas_w.  Every
  * height, width and pixel count above is then the image's own: the in-image test and the 128 fill of the geometric
@@ -551,6 +559,26 @@ typedef struct edet_crop_image { /* 32 bytes, one per image, read from DEVICE me
 } edet_crop_image_t;
 int edet_crop_resize(const uint8_t* raw, int batch, int canvas_h, int canvas_w, const edet_crop_image_t* per_image_dev,
                      void* out, int out_h, int out_w, int out_dtype, void* stream);
+/* edet_crop_resize_bicubic: the same contract (raw, per_image_dev and its clamps, the flip on the OUTPUT column, one launch
+ * that does not depend on the draws, the same limits) with tf.image.resize_bicubic of the crop in place of the bilinear
+ * resize (efficientnetv2/preprocess_legacy.py:80-127) -- TensorFlow's LEGACY bicubic: align_corners=False,
+ * half_pixel_centers=False, a 1024-entry coefficient table with a = -0.75.  Per axis, scale = float(crop_n) / float(out_n):
+ *   in_f = float(o) * scale; in = floor(in_f); delta = in_f - float(in); off = lrintf(delta * 1024.0f) (halves to even);
+ *   weights (T[2 off + 1], T[2 off], T[2 (1024 - off)], T[2 (1024 - off) + 1]) on the taps in - 1, in, in + 1, in + 2, each
+ *   clamped into [0, crop_n - 1] (the CROP's edges);
+ *   T[2i] = float(((a + 2) x - (a + 3)) x x + 1), T[2i + 1] = float(((a x' - 5a) x' + 8a) x' - 4a) for x = float(i / 1024.0),
+ *   x' = float(x + 1.0f), i = 0 .. 1024, the polynomials in double.  The 2050 floats are evaluated once by the HOST compiler
+ *   (constexpr) and lie in the library's code object: no call builds, allocates or copies a table.
+ * A value is formed vertically first: for each of the four tap columns c_k = p0 wy0 + p1 wy1 + p2 wy2 + p3 wy3, left to right
+ * in fp32, the pixels converted to float; then v = c0 wx0 + c1 wx1 + c2 wx2 + c3 wx3 the same way.  Results overshoot
+ * [0, 255].  EDET_U8 = clip(v, 0, 255) truncated (:168-169).  mean_std: a HOST pointer to six floats {mean r, g, b, std r, g,
+ * b}, read at the call and passed to the kernel by value: EDET_F32 = (v - mean[c]) / std[c], two individually rounded fp32
+ * operations with a true IEEE division, EDET_BF16 = that value rounded to nearest even; NULL = no normalisation (fp32 gets
+ * the resized values as they are, bf16 their rounding); uint8 never reads it.  This definition is written from TensorFlow's
+ * published resize_bicubic_op and is NOT pinned against TensorFlow (not installed where this project is tested); its numpy
+ * restatement tests/bicubic_ref.py is the definition, compared bit for bit. */
+int edet_crop_resize_bicubic(const uint8_t* raw, int batch, int canvas_h, int canvas_w, const edet_crop_image_t* per_image_dev,
+                             void* out, int out_h, int out_w, int out_dtype, const float* mean_std, void* stream);
 
 /* ---- mosaic augmentation (efficientdet/aug/mosaic.py) ----
  * raw uint8 [batch][canvas_h][canvas_w][3] as for edet_crop_resize; `groups` mosaics [groups][out_h][out_w][3] in one
