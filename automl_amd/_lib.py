@@ -88,6 +88,20 @@ class JpegImage(ctypes.Structure):
               ('first_block', ctypes.c_int32 * 3), ('total_blocks', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class JpegSegment(ctypes.Structure):
+  """edet_jpeg_segment_t: one restart interval of a scan in the scan arena (edet_jpeg_scan_prepare)."""
+  _fields_ = [('offset', ctypes.c_uint32), ('length', ctypes.c_uint32), ('first_unit', ctypes.c_uint32),
+              ('reserved', ctypes.c_uint32)]
+
+
+class JpegScan(ctypes.Structure):
+  """edet_jpeg_scan_t: one row of the device entropy decoder's per-image array (edet_jpeg_scan_prepare)."""
+  _fields_ = [('status', ctypes.c_int32), ('first_segment', ctypes.c_int32), ('segments', ctypes.c_int32),
+              ('first_unit', ctypes.c_int32), ('units', ctypes.c_int32), ('restart_interval', ctypes.c_int32),
+              ('mcus_w', ctypes.c_int32), ('mcus_h', ctypes.c_int32), ('blocks_per_mcu', ctypes.c_int32),
+              ('dc_table', ctypes.c_int32 * 3), ('ac_table', ctypes.c_int32 * 3), ('rounds', ctypes.c_int32)]
+
+
 class JpegWindow(ctypes.Structure):
   """edet_jpeg_window_t: one row of the window decode's second per-image array (edet_jpeg_entropy_decode_window)."""
   _fields_ = [('y', ctypes.c_int32), ('x', ctypes.c_int32), ('h', ctypes.c_int32), ('w', ctypes.c_int32),
@@ -261,6 +275,11 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int],
     'edet_jpeg_color_window': [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p],
+    'edet_jpeg_scan_prepare': [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t), c_int, c_int, c_int, c_int, c_void_p,
+                               ctypes.c_size_t, c_int, c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(ctypes.c_size_t), c_int],
+    'edet_jpeg_entropy_device': [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
     'edet_crc32c': [c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)],
     'edet_tfrecord_index': [c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, ctypes.c_size_t,
                             ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)],

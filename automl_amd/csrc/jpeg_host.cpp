@@ -18,13 +18,14 @@
 #include <vector>
 
 #include "../../include/edet_hip.h"
+#include "jpeg_entropy_impl.h"
 
 void edet_set_error(const char* fmt, ...);      // error.cpp (the stand-alone checker brings its own)
 
 namespace {
 
 constexpr int MAX_THREADS = 16;
-constexpr int LOOK_BITS = 10;
+using jpeg_entropy::LOOK_BITS;
 
 const uint8_t NATURAL[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -186,14 +187,11 @@ int check_scan(const Parsed& P, int td[3], int ta[3]) {
   return 0;
 }
 
-// jdhuff.c's derived table: a look-up for codes of up to LOOK_BITS bits, the canonical ranges for longer ones
-struct Huff {
-  uint16_t look[1 << LOOK_BITS];      // (length << 8) | symbol, 0 = no code of <= LOOK_BITS bits starts like this
-  int32_t mincode[17], count[17], valptr[17];
-  uint8_t vals[256];
-
+// jdhuff.c's derived table (jpeg_entropy_impl.h has the layout: the device decoder reads the same bytes)
+struct Huff : jpeg_entropy::HuffTable {
   bool build(const RawHuff& R, bool is_dc) {
     memset(look, 0, sizeof(look));
+    mincode[0] = count[0] = valptr[0] = pad = 0;
     memcpy(vals, R.vals, sizeof(vals));
     uint32_t code = 0;
     int k = 0;
@@ -418,13 +416,15 @@ void kept_grid(int components, int h_max, int v_max, int denom, int out_h, int o
   K.h = hi[1] - lo[1] + 1;
 }
 
-// All entry points: the headers, then the scans.  windows / wins NULL: the whole grid of every image is kept.  max_denom 1 and denoms NULL is the full-size decode; `scaled` says
-// whether the descriptor carries the denominator (the full-size entry point keeps writing 0 there).
-int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
-                   int max_denom, const int32_t* denoms, bool scaled, const int32_t* windows, edet_jpeg_window_t* wins,
-                   int16_t* coef_host, size_t coef_capacity, edet_jpeg_image_t* images_host, uint16_t* qtables_host,
-                   int32_t* status, int threads) {
-  if (!datas || !sizes || !coef_host || !images_host || !qtables_host || !status || batch < 1) {
+struct Job {
+  Parsed P;
+  int td[3], ta[3];
+  Kept K;
+};
+
+// the arguments every entry point checks; -> the worker threads to use, or -1 (the error is set)
+int check_args(const char* who, bool pointers, int batch, int max_denom, const int32_t* denoms, int threads) {
+  if (!pointers || batch < 1) {
     edet_set_error("%s: null pointer or batch %d < 1", who, batch);
     return -1;
   }
@@ -441,14 +441,14 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
   if (threads <= 0) threads = batch < MAX_THREADS ? batch : MAX_THREADS;
   if (threads > MAX_THREADS) threads = MAX_THREADS;
   if (threads > batch) threads = batch;
+  return threads;
+}
 
-  struct Job {
-    Parsed P;
-    int td[3], ta[3];
-    Kept K;
-  };
-  std::vector<Job> jobs((size_t)batch);
-  // the headers, one image after the other: the place of an image in the arena depends on the images in front of it
+// The headers of a batch, one image after the other: the place of an image in the arena depends on the images in front of
+// it.  Writes every descriptor, table and status; jobs[b] is what the scan of image b needs.
+void headers(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w, int max_denom,
+             const int32_t* denoms, bool scaled, const int32_t* windows, edet_jpeg_window_t* wins, size_t coef_capacity,
+             edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status, std::vector<Job>& jobs) {
   size_t next_block = 0;
   const size_t cap_blocks = coef_capacity / 64;
   for (int b = 0; b < batch; ++b) {
@@ -529,6 +529,35 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
     im.status = st;
     status[b] = st;
   }
+}
+
+// `work` on `threads` threads, the caller's among them
+template <class F>
+void run_parallel(int threads, F& work) {
+  if (threads == 1) {
+    work();
+    return;
+  }
+  std::vector<std::thread> pool;
+  pool.reserve((size_t)threads - 1);
+  for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+  work();
+  for (auto& t : pool) t.join();
+}
+
+// The three host entry points: the headers, then the scans.  windows / wins NULL: the whole grid of every image is kept.
+// max_denom 1 and denoms NULL is the full-size decode; `scaled` says whether the descriptor carries the denominator (the
+// full-size entry point keeps writing 0 there).
+int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
+                   int max_denom, const int32_t* denoms, bool scaled, const int32_t* windows, edet_jpeg_window_t* wins,
+                   int16_t* coef_host, size_t coef_capacity, edet_jpeg_image_t* images_host, uint16_t* qtables_host,
+                   int32_t* status, int threads) {
+  threads = check_args(who, datas && sizes && coef_host && images_host && qtables_host && status, batch, max_denom, denoms,
+                       threads);
+  if (threads < 0) return -1;
+  std::vector<Job> jobs((size_t)batch);
+  headers(datas, sizes, batch, canvas_h, canvas_w, max_denom, denoms, scaled, windows, wins, coef_capacity, images_host,
+          qtables_host, status, jobs);
 
   // the scans, in parallel: an image refused here keeps its place in the arena, unused
   std::atomic<int> next(0);
@@ -549,19 +578,174 @@ int entropy_decode(const char* who, const uint8_t* const* datas, const size_t* s
       }
     }
   };
-  if (threads == 1) {
-    work();
-  } else {
-    std::vector<std::thread> pool;
-    pool.reserve((size_t)threads - 1);
-    for (int t = 1; t < threads; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+  run_parallel(threads, work);
+  return 0;
+}
+
+// The scan of one image for the device decoder: its entropy-coded bytes, FF 00 stuffing removed, into arena[at, at + room),
+// one segment per restart interval, each at a 4-byte aligned offset and zero-padded to a whole word.  Segments end where
+// Bits::fill stops and the markers between them are checked as decode_scan checks them; nothing behind the last segment is
+// looked at.  -> 0, EDET_JPEG_MALFORMED (a restart marker missing or out of sequence) or EDET_JPEG_TOO_LARGE (no room).
+int copy_scan(const uint8_t* d, size_t n, size_t q, int nseg, uint8_t* arena, size_t at, size_t room,
+              edet_jpeg_segment_t* segs) {
+  const size_t end = at + room;
+  for (int j = 0; j < nseg; ++j) {
+    const size_t first = at;
+    for (;;) {
+      const uint8_t* ff = q < n ? (const uint8_t*)memchr(d + q, 0xFF, n - q) : nullptr;
+      const size_t run = (ff ? (size_t)(ff - d) : n) - q;
+      if (run > end - at) return EDET_JPEG_TOO_LARGE;
+      memcpy(arena + at, d + q, run);
+      at += run;
+      q += run;
+      if (!ff || !(q + 1 < n && d[q + 1] == 0)) break;      // the end of the data, or a marker: q stays on its 0xFF
+      if (at >= end) return EDET_JPEG_TOO_LARGE;
+      arena[at++] = 0xFF;
+      q += 2;
+    }
+    const size_t length = at - first;
+    if (length >= ((size_t)1 << 28) || first > (size_t)UINT32_MAX) return EDET_JPEG_TOO_LARGE;      // (bit positions are 32-bit)
+    while (at & 3) {
+      if (at >= end) return EDET_JPEG_TOO_LARGE;
+      arena[at++] = 0;
+    }
+    segs[j].offset = (uint32_t)first;
+    segs[j].length = (uint32_t)length;
+    segs[j].first_unit = 0;      // (the caller's, once every length is known)
+    segs[j].reserved = 0;
+    if (j + 1 < nseg) {
+      if (q >= n || d[q] != 0xFF) return EDET_JPEG_MALFORMED;
+      while (q < n && d[q] == 0xFF) ++q;
+      if (q >= n || d[q] != 0xD0 + (j & 7)) return EDET_JPEG_MALFORMED;
+      ++q;
+    }
   }
   return 0;
 }
 
 }  // namespace
+
+extern "C" int edet_jpeg_scan_prepare(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
+                                      int max_denom, const int32_t* denoms, size_t coef_capacity, int subseq_bits,
+                                      uint8_t* scan_host, size_t scan_capacity, edet_jpeg_segment_t* segments_host,
+                                      size_t segment_capacity, size_t unit_capacity, uint8_t* tables_host,
+                                      edet_jpeg_scan_t* scans_host, edet_jpeg_image_t* images_host, uint16_t* qtables_host,
+                                      int32_t* status, size_t* used, int threads) {
+  const char* who = "edet_jpeg_scan_prepare";
+  threads = check_args(who, datas && sizes && scan_host && segments_host && tables_host && scans_host && images_host &&
+                                qtables_host && status && used, batch, max_denom, denoms, threads);
+  if (threads < 0) return -1;
+  if (subseq_bits < 64 || subseq_bits > 8192 || subseq_bits % 32 != 0 || ((uintptr_t)scan_host & 3) != 0) {
+    edet_set_error("%s: subseq_bits %d is not a multiple of 32 in 64 .. 8192, or scan_host is not 4-byte aligned", who, subseq_bits);
+    return -1;
+  }
+  std::vector<Job> jobs((size_t)batch);
+  // (max_denom 1 without denoms: edet_jpeg_entropy_decode's descriptors; otherwise edet_jpeg_entropy_decode_scaled's)
+  headers(datas, sizes, batch, canvas_h, canvas_w, max_denom, denoms, max_denom != 1 || denoms, nullptr, nullptr, coef_capacity,
+          images_host, qtables_host, status, jobs);
+  auto refuse = [&](int b, int st) {
+    memset(&images_host[b], 0, sizeof(images_host[b]));
+    memset(&scans_host[b], 0, sizeof(scans_host[b]));
+    memset(qtables_host + (size_t)b * 256, 0, 256 * sizeof(uint16_t));
+    images_host[b].status = st;
+    status[b] = st;
+  };
+  // the tables, and each image's room in the arenas: what is left of the file behind SOS bounds its scan, so the place of an
+  // image does not wait for the walk over the image in front of it
+  memset(tables_host, 0, (size_t)batch * EDET_JPEG_TABLES * EDET_JPEG_TABLE_BYTES);
+  std::vector<size_t> scan_at((size_t)batch), scan_room((size_t)batch);
+  size_t next_byte = 0, next_seg = 0;
+  for (int b = 0; b < batch; ++b) {
+    edet_jpeg_image_t& im = images_host[b];
+    edet_jpeg_scan_t& sc = scans_host[b];
+    memset(&sc, 0, sizeof(sc));
+    if (im.status) continue;
+    const Job& J = jobs[(size_t)b];
+    const int nc = im.components;
+    Huff* tables = reinterpret_cast<Huff*>(tables_host + (size_t)b * EDET_JPEG_TABLES * EDET_JPEG_TABLE_BYTES);
+    int slots = 0, cls_of[EDET_JPEG_TABLES], id_of[EDET_JPEG_TABLES];
+    bool built = true;
+    for (int c = 0; c < nc && built; ++c) {
+      for (int cls = 0; cls < 2 && built; ++cls) {      // 0: DC, 1: AC; components that name one table share its slot
+        const int id = cls ? J.ta[c] : J.td[c];
+        int s = 0;
+        while (s < slots && !(cls_of[s] == cls && id_of[s] == id)) ++s;
+        if (s == slots) {
+          built = tables[s].build(J.P.huff[cls][id], cls == 0);
+          cls_of[s] = cls;
+          id_of[s] = id;
+          ++slots;
+        }
+        (cls ? sc.ac_table : sc.dc_table)[c] = s;
+      }
+    }
+    if (!built) {
+      memset(tables, 0, (size_t)EDET_JPEG_TABLES * EDET_JPEG_TABLE_BYTES);
+      refuse(b, EDET_JPEG_MALFORMED);
+      continue;
+    }
+    const int64_t mcus = (int64_t)J.K.full_w * J.K.full_h;
+    const int ri = J.P.info.restart_interval;
+    const int64_t nseg = ri ? (mcus + ri - 1) / ri : 1;
+    const size_t room = ((sizes[b] - J.P.scan) + 4 * (size_t)nseg + 15) & ~(size_t)15;
+    if ((size_t)nseg > segment_capacity - next_seg || next_seg > segment_capacity || room > scan_capacity - next_byte ||
+        next_byte > scan_capacity || next_byte + room > (size_t)INT32_MAX) {
+      memset(tables, 0, (size_t)EDET_JPEG_TABLES * EDET_JPEG_TABLE_BYTES);
+      refuse(b, EDET_JPEG_TOO_LARGE);
+      continue;
+    }
+    sc.first_segment = (int32_t)next_seg;
+    sc.segments = (int32_t)nseg;
+    sc.restart_interval = ri;
+    sc.mcus_w = J.K.full_w;
+    sc.mcus_h = J.K.full_h;
+    sc.blocks_per_mcu = im.h_max * im.v_max + (nc == 3 ? 2 : 0);
+    scan_at[(size_t)b] = next_byte;
+    scan_room[(size_t)b] = room;
+    next_byte += room;
+    next_seg += (size_t)nseg;
+  }
+  // the scans, in parallel
+  std::atomic<int> next(0);
+  std::vector<int> scan_status((size_t)batch, 0);
+  auto work = [&]() {
+    for (;;) {
+      const int b = next.fetch_add(1);
+      if (b >= batch) return;
+      if (images_host[b].status) continue;
+      const edet_jpeg_scan_t& sc = scans_host[b];
+      scan_status[(size_t)b] = copy_scan(datas[b], sizes[b], jobs[(size_t)b].P.scan, sc.segments, scan_host, scan_at[(size_t)b],
+                                         scan_room[(size_t)b], segments_host + sc.first_segment);
+    }
+  };
+  run_parallel(threads, work);
+  // the units, which need every length
+  size_t next_unit = 0;
+  for (int b = 0; b < batch; ++b) {
+    edet_jpeg_scan_t& sc = scans_host[b];
+    if (images_host[b].status) continue;
+    int st = scan_status[(size_t)b];
+    size_t units = 0;
+    for (int j = 0; !st && j < sc.segments; ++j) {
+      edet_jpeg_segment_t& sg = segments_host[sc.first_segment + j];
+      sg.first_unit = (uint32_t)units;
+      units += jpeg_entropy::units_of(8 * sg.length, (uint32_t)subseq_bits);
+    }
+    if (!st && (units > unit_capacity - next_unit || next_unit + units > (size_t)INT32_MAX)) st = EDET_JPEG_TOO_LARGE;
+    if (st) {
+      memset(tables_host + (size_t)b * EDET_JPEG_TABLES * EDET_JPEG_TABLE_BYTES, 0, (size_t)EDET_JPEG_TABLES * EDET_JPEG_TABLE_BYTES);
+      refuse(b, st);
+      continue;
+    }
+    sc.first_unit = (int32_t)next_unit;
+    sc.units = (int32_t)units;
+    next_unit += units;
+  }
+  used[0] = next_byte;
+  used[1] = next_seg;
+  used[2] = next_unit;
+  return 0;
+}
 
 extern "C" int edet_jpeg_entropy_decode(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h,
                                         int canvas_w, int16_t* coef_host, size_t coef_capacity,

@@ -327,18 +327,35 @@ class HostReader(object):
 class DeviceReader(object):
   """Iterator over the raw batches of the module's docstring: HostReader's batches through the reader's own JpegDecoder."""
 
-  def __init__(self, host, files, is_training, canvas, depth, threads, fallback, fake):
+  def __init__(self, host, files, is_training, canvas, depth, threads, fallback, fake, jpeg_entropy='host'):
     self._host, self._files, self._is_training, self._canvas = host, files, is_training, (int(canvas[0]), int(canvas[1]))
     self._depth, self._threads, self._fallback, self._fake = depth, threads, fallback, fake
+    self._entropy = jpeg_entropy
     self._decoders = {}
+    self._issued = {}      # device entropy: per decoder and set of arenas, (batch number, HostBatch.index) of its last batch
+    self._count = 0
     self._first = None
 
   def _decoder(self, batch):
     from automl_amd import jpeg
     if batch not in self._decoders:      # the reader's batch, and the short last one where it is kept
+      mode = {} if self._entropy == 'host' else {'entropy': self._entropy}
       self._decoders[batch] = jpeg.JpegDecoder(batch, self._canvas[0], self._canvas[1], depth=self._depth,
-                                               threads=None if self._threads is None else min(int(self._threads), batch))
+                                               threads=None if self._threads is None else min(int(self._threads), batch), **mode)
+      self._issued[batch] = [None] * self._decoders[batch].depth
     return self._decoders[batch]
+
+  def _check_scans(self, batch, ahead=0):
+    """Device entropy: a stream damaged inside its scan is found on the device, behind decode()'s back.  Asked here, for the
+    batch that last used the set of arenas the next decode() takes, where decode() waits for that set anyway."""
+    dec = self._decoders[batch]
+    at = (dec._next + ahead) % dec.depth
+    failed = dec.scan_failures(ahead)
+    if failed and self._issued[batch][at] is not None:
+      number, index = self._issued[batch][at]
+      self._issued[batch][at] = None
+      raise ValueError('batch %d: the scan of image %s is malformed or truncated (found on the device, behind decode): %s'
+                       % (number, failed, ['%s record %d' % (self._files[index[i][0]], index[i][1]) for i in failed]))
 
   def __iter__(self):
     return self
@@ -346,9 +363,20 @@ class DeviceReader(object):
   def __next__(self):
     if self._first is not None:
       return self._first
-    hb = next(self._host)
     try:
-      raw, sizes = self._decoder(len(hb.images)).decode(hb.images, fallback=self._fallback)
+      hb = next(self._host)
+    except StopIteration:
+      for batch in self._decoders if self._entropy == 'device' else ():      # the batches still in flight
+        for ahead in range(self._decoders[batch].depth):
+          self._check_scans(batch, ahead)
+      raise
+    dec = self._decoder(len(hb.images))
+    if self._entropy == 'device':
+      self._check_scans(len(hb.images))
+      self._issued[len(hb.images)][dec._next] = (self._count, hb.index)
+    self._count += 1
+    try:
+      raw, sizes = dec.decode(hb.images, fallback=self._fallback)
     except ValueError as e:
       raise ValueError('%s; the batch holds %s' % (e, ['%s record %d' % (self._files[f], r) for f, r in hb.index]))
     if self._is_training:
@@ -374,7 +402,11 @@ class InputReader(object):
   """dataloader.py:236-460.  reader(params, ...) -- also reader_obj(params, ...), as the reference calls it -- returns the
   iterator of raw batches; host_reader(params, ...) the host half alone (HostBatch, no device)."""
 
-  def __init__(self, file_pattern, is_training, use_fake_data=False, max_instances_per_image=None, debug=False):
+  def __init__(self, file_pattern, is_training, use_fake_data=False, max_instances_per_image=None, debug=False,
+               jpeg_entropy='host'):
+    if jpeg_entropy not in ('host', 'device'):
+      raise ValueError("jpeg_entropy=%r: 'host' or 'device' (jpeg.JpegDecoder's entropy=)" % (jpeg_entropy,))
+    self._jpeg_entropy = jpeg_entropy
     self._file_pattern = file_pattern
     self._is_training = bool(is_training)
     self._use_fake_data = bool(use_fake_data)
@@ -418,6 +450,7 @@ class InputReader(object):
     if canvas is None or len(canvas) != 2:
       raise ValueError('canvas=(Hc, Wc) is needed: the slot every decoded image is written into (jpeg.JpegDecoder)')
     host = self.host_reader(params, batch_size, shard, depth, threads, verify)
-    return DeviceReader(host, host.files, self._is_training, canvas, depth, threads, fallback, self._use_fake_data)
+    return DeviceReader(host, host.files, self._is_training, canvas, depth, threads, fallback, self._use_fake_data,
+                        self._jpeg_entropy)
 
   __call__ = reader

@@ -29,6 +29,14 @@ is decoded at.  The host stage stores only the blocks the window needs -- the ke
 (csrc/jpeg_window.hip: edet_jpeg_color_window) all work on the kept area alone.  The result is the full decode's
 [y:y + h, x:x + w] byte for byte (tests/jpeg_window_ref.py).  JpegDecoder(windowed=True).decode(windows=...) takes one window
 per image; decode_and_crop_jpeg is the one-file form.
+
+Huffman decode on the device: JpegDecoder(entropy='device') moves the entropy stage behind the bus as well.  The host keeps the
+marker walk and one byte-copy pass over each scan (edet_jpeg_scan_prepare: stuffing removed, cut into segments at the restart
+markers), the device decodes the Huffman stream with a self-synchronising parallel decoder (csrc/jpeg_entropy.hip, one
+workgroup per image, units of subseq_bits bits that re-decode until each starts where its predecessor ended) and writes the
+very coefficient arena the host stage writes; the compressed scan crosses the bus instead of its coefficients.  Header-level
+refusals are known on the host as before; a stream damaged INSIDE its scan is only found on the device (scan_status,
+decode(check_scan=True)).  Restated in tests/jpeg_entropy_ref.py.  entropy='host' stays the default.
 """
 import collections
 import ctypes
@@ -56,6 +64,10 @@ KINDS = ('baseline', 'extended', 'progressive', 'other')
 MAX_THREADS = 16
 IMAGE_BYTES = ctypes.sizeof(_lib.JpegImage)      # 80
 WINDOW_BYTES = ctypes.sizeof(_lib.JpegWindow)    # 48
+SCAN_BYTES = ctypes.sizeof(_lib.JpegScan)        # 64
+SEGMENT_BYTES = ctypes.sizeof(_lib.JpegSegment)  # 16
+TABLES, TABLE_BYTES, UNIT_WORDS = 6, 2512, 8     # EDET_JPEG_TABLES, EDET_JPEG_TABLE_BYTES, EDET_JPEG_UNIT_WORDS
+ENTROPIES = ('host', 'device')
 
 JpegInfo = collections.namedtuple('JpegInfo', 'height width components precision kind restart_interval sof h_samp v_samp '
                                               'quant_id comp_id jfif adobe_transform')
@@ -291,6 +303,43 @@ def entropy_decode_window(datas, canvas_h, canvas_w, max_ratio, ratios, windows,
        _host(images), _host(wins), _host(qtables), _host(status), int(threads))
 
 
+def check_subseq_bits(subseq_bits):
+  subseq_bits = int(subseq_bits)
+  if subseq_bits < 64 or subseq_bits > 8192 or subseq_bits % 32:
+    raise ValueError('subseq_bits=%r: a multiple of 32 from 64 to 8192' % (subseq_bits,))
+  return subseq_bits
+
+
+def scan_prepare(datas, canvas_h, canvas_w, max_ratio, ratios, coef_capacity, subseq_bits, scan, segments, unit_capacity, tables,
+                 scans, images, qtables, status, threads=0):
+  """edet_jpeg_scan_prepare on host arrays (numpy or CPU tensors), as entropy_decode_scaled: scan uint8 [scan capacity],
+  segments uint8 [segment capacity * 16], tables uint8 [B * 6 * 2512], scans uint8 [B * 64]; coef_capacity counts the int16
+  elements of the coefficient arena the device will write.  -> (scan bytes, segments, units) in use.  Needs no device."""
+  n, _keep, ptrs, sizes = _streams(datas)      # (_keep: alive until the call returns)
+  forced = _forced(ratios, n)
+
+  def count(a):
+    return int(a.size if isinstance(a, np.ndarray) else a.numel())
+  used = (ctypes.c_size_t * 3)()
+  call('edet_jpeg_scan_prepare', ptrs, sizes, n, int(canvas_h), int(canvas_w), int(max_ratio),
+       None if forced is None else ctypes.addressof(forced), int(coef_capacity), int(subseq_bits), _host(scan), count(scan),
+       _host(segments), count(segments) // SEGMENT_BYTES, int(unit_capacity), _host(tables), _host(scans), _host(images),
+       _host(qtables), _host(status), used, int(threads))
+  return int(used[0]), int(used[1]), int(used[2])
+
+
+def scan_descriptors(scans, batch):
+  """The per-image scan array as a list of _lib.JpegScan (copies)."""
+  raw = scans.tobytes() if isinstance(scans, np.ndarray) else scans.numpy().tobytes()
+  return [_lib.JpegScan.from_buffer_copy(raw, i * SCAN_BYTES) for i in range(batch)]
+
+
+def segment_rows(segments, count):
+  """The first `count` rows of the segment table as a list of _lib.JpegSegment (copies)."""
+  raw = segments.tobytes() if isinstance(segments, np.ndarray) else segments.numpy().tobytes()
+  return [_lib.JpegSegment.from_buffer_copy(raw, i * SEGMENT_BYTES) for i in range(count)]
+
+
 def window_descriptors(wins, batch):
   """The per-image window array as a list of _lib.JpegWindow (copies)."""
   raw = wins.tobytes() if isinstance(wins, np.ndarray) else wins.numpy().tobytes()
@@ -323,6 +372,31 @@ class _Slot(object):
     self.done = None        # behind the kernels that read the device arenas
 
 
+class _DeviceSlot(object):
+  """One set of arenas of the device entropy mode: the pinned scan arena with its segment, table and scan-descriptor arrays in
+  the place of the pinned coefficients, their device copies, the unit and DC scratch, and the statuses the device reports."""
+
+  def __init__(self, batch, blocks, scan_bytes, segments, units, device):
+    def pair(count, dtype=torch.uint8):
+      return torch.zeros(count, dtype=dtype).pin_memory(), torch.zeros(count, dtype=dtype, device=device)
+    self.scan_host, self.scan = pair(scan_bytes)
+    self.segments_host, self.segments = pair(segments * SEGMENT_BYTES)
+    self.tables_host, self.tables = pair(batch * TABLES * TABLE_BYTES)
+    self.scans_host, self.scans = pair(batch * SCAN_BYTES)
+    self.images_host, self.images = pair(batch * IMAGE_BYTES)
+    self.qtables_host = torch.zeros((batch, 4, 64), dtype=torch.int16).pin_memory()      # uint16 bits
+    self.qtables = torch.zeros((batch, 4, 64), dtype=torch.int16, device=device)
+    self.status = np.zeros(batch, np.int32)      # the host's: header-level refusals
+    self.scan_status_host, self.scan_status = pair(batch, torch.int32)      # the device's: those, and damaged scans
+    self.units = torch.empty(units * UNIT_WORDS, dtype=torch.int32, device=device)
+    self.dc = torch.empty(blocks, dtype=torch.int16, device=device)
+    self.coef = torch.empty(blocks * 64, dtype=torch.int16, device=device)
+    self.planes = torch.empty(blocks * 64, dtype=torch.uint8, device=device)
+    self.unit_capacity = units
+    self.copied = None
+    self.done = None
+
+
 class JpegDecoder(object):
   """Decodes batches of `batch` JPEG files into a canvas_h x canvas_w canvas each.  Allocates once: `depth` sets of pinned
   host arenas (coefficients, descriptors, quantisation tables), their device copies and the plane scratch, each sized for
@@ -337,11 +411,30 @@ class JpegDecoder(object):
 
   windowed=True: decode(windows=...) is allowed, and the arenas are sized for windows -- worst_window_blocks(canvas) in the
   place of worst_blocks(canvas), under the same rule for max_ratio and coef_blocks: a window that fits the canvas can lie in
-  an image of any size, and keeps at most that many blocks at full size."""
+  an image of any size, and keeps at most that many blocks at full size.
+
+  entropy='device': the Huffman stage runs on the device (edet_jpeg_scan_prepare, edet_jpeg_entropy_device).  Per set the
+  pinned coefficient arena and its copy give way to a pinned scan arena of scan_bytes bytes (default 64 per block of
+  coef_blocks, half the pinned memory it replaces), a segment table of 64 rows per image plus one per eight blocks, the tables
+  and scan descriptors, and on the device the unit scratch (32 bytes per unit: 8 scan_bytes / subseq_bits units and one more per
+  segment) and two bytes of DC scratch per block.  A batch whose scans, segments or units do not fit gives TOO_LARGE for the
+  image that no longer fits, on the host.  subseq_bits: the bits of a unit, a multiple of 32 from 64 to 8192; smaller units
+  are more parallel and need more rounds to synchronise (LABNOTES has the measurements behind the default).  Every max_ratio
+  works, since the coefficients do not depend on it; windowed=True does not (ValueError): a window needs the DC predictors of
+  blocks it does not keep.  entropy='host', the default, allocates and calls exactly what it always did."""
 
   def __init__(self, batch, canvas_h, canvas_w, device='cuda:0', threads=None, depth=2, max_ratio=1, coef_blocks=None,
-               windowed=False):
+               windowed=False, entropy='host', subseq_bits=4096, scan_bytes=None):
     batch, canvas_h, canvas_w, depth = int(batch), int(canvas_h), int(canvas_w), int(depth)
+    if entropy not in ENTROPIES:
+      raise ValueError("entropy=%r: 'host' or 'device'" % (entropy,))
+    if entropy == 'device' and windowed:
+      raise ValueError("windowed=True needs entropy='host': the device entropy decoder does not skip blocks outside a window")
+    subseq_bits = check_subseq_bits(subseq_bits)
+    if scan_bytes is not None and entropy != 'device':
+      raise ValueError("scan_bytes= needs entropy='device'")
+    if scan_bytes is not None and not 16 <= int(scan_bytes) < 2 ** 31:
+      raise ValueError('scan_bytes %d outside 16 .. 2^31 - 1' % scan_bytes)
     if max_ratio not in RATIOS:
       raise ValueError('max_ratio=%r: 1, 2, 4 or 8' % (max_ratio,))
     if batch < 1 or batch > 65535:
@@ -374,11 +467,22 @@ class JpegDecoder(object):
                            'edet_jpeg_color): there is no CPU fall-back')
     _lib.load()
     self.batch, self.canvas_h, self.canvas_w, self.threads, self.depth = batch, canvas_h, canvas_w, threads, depth
-    self._slots = [_Slot(batch, self.blocks, self.device, self.windowed) for _ in range(depth)]
+    self.entropy, self.subseq_bits = entropy, subseq_bits
+    if entropy == 'device':
+      scan_bytes = 64 * self.blocks if scan_bytes is None else int(scan_bytes)
+      if scan_bytes >= 2 ** 31:
+        raise ValueError('batch %d of %d x %d canvases: a scan arena of 2^31 bytes or more; pass scan_bytes=' % (batch, canvas_h, canvas_w))
+      self.scan_bytes = (scan_bytes + 15) // 16 * 16
+      self.segments = 64 * batch + self.blocks // 8
+      units = 8 * self.scan_bytes // subseq_bits + self.segments
+      self._slots = [_DeviceSlot(batch, self.blocks, self.scan_bytes, self.segments, units, self.device) for _ in range(depth)]
+    else:
+      self._slots = [_Slot(batch, self.blocks, self.device, self.windowed) for _ in range(depth)]
     self._next = 0
+    self._last = None      # the set of the most recent decode
 
   def decode(self, contents, out=None, sizes_out=None, fallback=None, stream=None, ratios=None, ratios_out=None,
-             windows=None):
+             windows=None, check_scan=False):
     """contents: `batch` JPEG files as bytes -> (raw uint8 [B, Hc, Wc, 3] on the device, sizes int32 [B, 2] = (height,
     width) on the host): exactly pad_batch(decoded images, (Hc, Wc)).  out / sizes_out: where to write them (out a
     contiguous device tensor; every byte of it is written, so it needs no clearing).  A refused stream raises ValueError
@@ -395,7 +499,12 @@ class JpegDecoder(object):
     window belongs to one ratio.  Each canvas holds its window at the top-left, zero elsewhere, and sizes its (h, w).  A window
     outside its image is refused like a stream (status WINDOW); so is one larger than the canvas (TOO_LARGE), while the image
     around it may be of any size.  A stream that goes to `fallback` comes back WHOLE, uncropped, with the fallback image's
-    size.  windows=None calls the entry points it always did."""
+    size.  windows=None calls the entry points it always did.
+    check_scan (entropy='device' only; it changes nothing in host mode, where the scan is decoded before the call returns):
+    False, the default -- the call does not wait for the device, so a stream damaged inside its scan (a truncated file, a bad
+    code, too few blocks) is NOT reported here: its canvas comes out all zero, sizes_out keeps its header size, and
+    scan_status() tells afterwards.  True -- the call waits for the batch and then behaves as the host mode does: ValueError
+    with the index and the reason, or the `fallback` image copied in."""
     if len(contents) != self.batch:
       raise ValueError('%d files for a decoder of batch %d' % (len(contents), self.batch))
     b, hc, wc = self.batch, self.canvas_h, self.canvas_w
@@ -426,9 +535,15 @@ class JpegDecoder(object):
     scaled = self.max_ratio > 1 or windows is not None
     slot = self._slots[self._next]
     self._next = (self._next + 1) % self.depth
+    self._last = slot
     if slot.copied is not None:
       slot.copied.synchronize()      # the device has read this set's pinned arenas
-    if windows is not None:
+    used_scan = None
+    if self.entropy == 'device':
+      used_scan = scan_prepare(contents, hc, wc, self.max_ratio, ratios, self.blocks * 64, self.subseq_bits, slot.scan_host,
+                               slot.segments_host, slot.unit_capacity, slot.tables_host, slot.scans_host, slot.images_host,
+                               slot.qtables_host, slot.status, self.threads)
+    elif windows is not None:
       entropy_decode_window(contents, hc, wc, self.max_ratio, ratios, windows, slot.coef_host, slot.images_host,
                             slot.windows_host, slot.qtables_host, slot.status, self.threads)
       wdesc = window_descriptors(slot.windows_host, b)
@@ -446,11 +561,7 @@ class JpegDecoder(object):
         if fallback is None:
           why = self._reason(contents[i], d.status, None if ratios is None else ratios[i], windows is not None)
           raise ValueError('contents[%d] is not decoded: %s (status %d)' % (i, why, d.status))
-        img = fallback(contents[i])
-        img = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
-        if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or \
-            not (1 <= img.shape[0] <= hc and 1 <= img.shape[1] <= wc):
-          raise ValueError('fallback(contents[%d]) must be uint8 [h, w, 3] inside the %d x %d canvas' % (i, hc, wc))
+        img = self._fallback_image(fallback, contents[i], i)
         filled[i] = img
         sizes_out[i] = (img.shape[0], img.shape[1])
       else:
@@ -461,7 +572,15 @@ class JpegDecoder(object):
     with torch.cuda.device(self.device), torch.cuda.stream(st):
       if slot.done is not None:
         st.wait_event(slot.done)      # (a device-side wait: the set's last kernels may have run on another stream)
-      if used:
+      if used_scan is not None:
+        nbytes, nseg = used_scan[0], used_scan[1] * SEGMENT_BYTES
+        if nbytes:
+          slot.scan[:nbytes].copy_(slot.scan_host[:nbytes], non_blocking=True)
+        if nseg:
+          slot.segments[:nseg].copy_(slot.segments_host[:nseg], non_blocking=True)
+        slot.tables.copy_(slot.tables_host, non_blocking=True)
+        slot.scans.copy_(slot.scans_host, non_blocking=True)
+      elif used:
         slot.coef[:used * 64].copy_(slot.coef_host[:used * 64], non_blocking=True)
       slot.images.copy_(slot.images_host, non_blocking=True)
       slot.qtables.copy_(slot.qtables_host, non_blocking=True)
@@ -470,6 +589,11 @@ class JpegDecoder(object):
       slot.copied = torch.cuda.Event()
       slot.copied.record(st)
       raw = st.cuda_stream
+      if used_scan is not None:
+        # the descriptor of an image the device refuses gets its status THERE, in front of the two kernels below
+        call('edet_jpeg_entropy_device', ptr(slot.scan), self.scan_bytes, ptr(slot.segments), self.segments, ptr(slot.tables),
+             ptr(slot.scans), ptr(slot.images), b, self.subseq_bits, ptr(slot.units), slot.unit_capacity, ptr(slot.dc),
+             ptr(slot.coef), self.blocks * 64, ptr(slot.scan_status), raw)
       call('edet_jpeg_idct_scaled' if scaled else 'edet_jpeg_idct', ptr(slot.coef), ptr(slot.images), ptr(slot.qtables), b,
            most, ptr(slot.planes), self.blocks * 64, raw)
       if windows is not None:
@@ -478,17 +602,88 @@ class JpegDecoder(object):
       else:
         call('edet_jpeg_color_scaled' if scaled else 'edet_jpeg_color', ptr(slot.planes), ptr(slot.images), b, hc, wc,
              self.blocks * 64, ptr(out), raw)
+      if used_scan is not None:
+        slot.scan_status_host.copy_(slot.scan_status, non_blocking=True)
       slot.done = torch.cuda.Event()
       slot.done.record(st)
       for i, img in filled.items():
         out[i, :img.shape[0], :img.shape[1]].copy_(img, non_blocking=True)
+      if used_scan is not None and check_scan:
+        slot.done.synchronize()
+        found = slot.scan_status_host.numpy()
+        for i in range(b):
+          if found[i] and not desc[i].status:      # damaged inside the scan: its canvas is zero
+            if fallback is None:
+              raise ValueError('contents[%d] is not decoded: %s (status %d)' % (i, REASONS.get(int(found[i]), '?'), found[i]))
+            img = self._fallback_image(fallback, contents[i], i)
+            sizes_out[i] = (img.shape[0], img.shape[1])
+            if ratios_out is not None:
+              ratios_out[i] = 1
+            out[i, :img.shape[0], :img.shape[1]].copy_(img, non_blocking=True)
     return out, sizes_out
+
+  def _fallback_image(self, fallback, content, i):
+    img = fallback(content)
+    img = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
+    if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or \
+        not (1 <= img.shape[0] <= self.canvas_h and 1 <= img.shape[1] <= self.canvas_w):
+      raise ValueError('fallback(contents[%d]) must be uint8 [h, w, 3] inside the %d x %d canvas' % (i, self.canvas_h, self.canvas_w))
+    return img
+
+  def scan_status(self, wait=True):
+    """The int32 [batch] statuses of the most recent decode(): 0, or the reason an image's canvas holds no decoded pixels.  In
+    the device entropy mode these come from the device and include the streams damaged inside their scans, which decode()
+    without check_scan does not report; wait=True waits for that batch, wait=False returns None while it is still running.
+    In host mode they are the host stage's.  None before the first decode()."""
+    slot = self._last
+    if slot is None:
+      return None
+    if self.entropy != 'device':
+      return slot.status.copy()
+    if slot.done is None:      # (a decode() that raised in front of its launches)
+      return None
+    if wait:
+      slot.done.synchronize()
+    elif not slot.done.query():
+      return None
+    return slot.scan_status_host.numpy().copy()
+
+  def scan_failures(self, ahead=0):
+    """entropy='device': the indices of the images the DEVICE refused (streams damaged inside their scans) in the batch that
+    last used the set of arenas the next decode() will use -- `ahead` further decodes on -- as a list; [] for a set not used
+    yet, and in host mode.  Waits for that batch, which the next decode() on that set does anyway before it writes the set's
+    pinned arenas; a reader calls this in front of decode() to learn, `depth` batches late, what decode() could not tell."""
+    slot = self._slots[(self._next + int(ahead)) % self.depth]
+    if self.entropy != 'device' or slot.done is None:
+      return []
+    slot.done.synchronize()
+    found = slot.scan_status_host.numpy()
+    return [i for i in range(self.batch) if found[i] and not slot.status[i]]
+
+  def scan_rounds(self):
+    """entropy='device': the int32 [batch] rounds the device ran per image of the most recent decode() (round 0 included; 0
+    for an image it did not decode).  Waits for that batch and copies the descriptors back: a measurement aid."""
+    if self.entropy != 'device' or self._last is None:
+      return None
+    self._last.done.synchronize()
+    return np.array([d.rounds for d in scan_descriptors(self._last.scans.cpu(), self.batch)], np.int32)
 
   def _reason(self, content, status, forced=None, windowed=False):
     """REASONS[status]; for TOO_LARGE with max_ratio > 1 it says which of the two limits the image met."""
     if windowed and status == TOO_LARGE:
       return ('a crop window larger than the %d x %d canvas, or no room left in the coefficient arena of coef_blocks=%d blocks'
               % (self.canvas_h, self.canvas_w, self.blocks))
+    if status == TOO_LARGE and self.entropy == 'device':
+      try:
+        info = jpeg_info(content)
+        ratio = forced if forced is not None else choose_ratio(info.height, info.width, self.canvas_h, self.canvas_w, self.max_ratio)
+        h, w = scaled_size(info.height, info.width, ratio) if ratio else (self.canvas_h + 1, 0)
+        if h <= self.canvas_h and w <= self.canvas_w:
+          return ('no room left for this %d x %d image in the scan arena of scan_bytes=%d bytes, its %d segments or its units, or '
+                  'in the coefficient arena of coef_blocks=%d blocks; raise them or pass fallback='
+                  % (info.height, info.width, self.scan_bytes, self.segments, self.blocks))
+      except ValueError:
+        pass
     if status != TOO_LARGE or self.max_ratio == 1:
       return REASONS.get(int(status), '?')
     try:
@@ -506,11 +701,14 @@ class JpegDecoder(object):
                                                                                               info.width))
 
 
-def decode_jpeg(contents, channels=3, ratio=1):
+def decode_jpeg(contents, channels=3, ratio=1, entropy='host'):
   """tf.io.decode_jpeg(contents, channels, ratio) with its defaults otherwise -> uint8 [ceil(height / ratio), ceil(width /
   ratio), 3] on the device.  channels: 0 (the file's own; a greyscale file still comes out replicated, as
-  decode_image(channels=3) gives it) or 3.  ratio: 1, 2, 4 or 8, libjpeg's reduced-size decode.  A stream that is not decoded
-  raises ValueError naming the reason."""
+  decode_image(channels=3) gives it) or 3.  ratio: 1, 2, 4 or 8, libjpeg's reduced-size decode.  entropy: 'host' or 'device', where the
+  Huffman stage runs (JpegDecoder); the result is the same.  A stream that is not decoded raises ValueError naming the reason
+  (the device mode waits for the device to say so: check_scan=True)."""
+  if entropy not in ENTROPIES:
+    raise ValueError("entropy=%r: 'host' or 'device'" % (entropy,))
   if channels not in (0, 3):
     raise ValueError('channels=%r: 0 or 3 (a greyscale file is replicated to three channels)' % (channels,))
   if ratio not in RATIOS:
@@ -518,12 +716,15 @@ def decode_jpeg(contents, channels=3, ratio=1):
   info = jpeg_info(contents)
   if info.height < 1 or info.width < 1:
     raise ValueError('contents is not decoded: %s (status %d)' % (REASONS[MALFORMED], MALFORMED))
+  mode = {} if entropy == 'host' else {'entropy': entropy}
+  # (a scan of noise at quality 100 can outgrow 64 bytes a block: the file itself bounds it)
+  room = {} if entropy == 'host' else {'scan_bytes': _buffer(contents)[2] + 64}
   if ratio == 1:
-    raw, _ = JpegDecoder(1, info.height, info.width, depth=1).decode([contents])
+    raw, _ = JpegDecoder(1, info.height, info.width, depth=1, **mode, **room).decode([contents], **({'check_scan': True} if mode else {}))
   else:
     h, w = scaled_size(info.height, info.width, ratio)
-    raw, _ = JpegDecoder(1, h, w, depth=1, max_ratio=ratio, coef_blocks=worst_blocks(info.height, info.width)).decode(
-        [contents], ratios=[ratio])
+    raw, _ = JpegDecoder(1, h, w, depth=1, max_ratio=ratio, coef_blocks=worst_blocks(info.height, info.width), **mode,
+                         **room).decode([contents], ratios=[ratio], **({'check_scan': True} if mode else {}))
   return raw[0]
 
 

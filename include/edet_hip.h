@@ -1114,6 +1114,82 @@ int edet_jpeg_entropy_decode_window(const uint8_t* const* datas, const size_t* s
 int edet_jpeg_color_window(const uint8_t* planes, const edet_jpeg_image_t* images_dev, const edet_jpeg_window_t* windows_dev,
                            int batch, int canvas_h, int canvas_w, size_t plane_capacity, uint8_t* raw, void* stream);
 
+/* ---- JPEG Huffman decode on the device (JpegDecoder(entropy='device')) ---------------------------------------------------
+ * The entropy stage moved behind the bus: the host keeps the marker walk and ONE byte-copy pass over each scan
+ * (edet_jpeg_scan_prepare, csrc/jpeg_host.cpp), the device decodes the Huffman stream with a self-synchronising parallel
+ * decoder (edet_jpeg_entropy_device, csrc/jpeg_entropy.hip) and writes the coefficient arena edet_jpeg_idct[_scaled] read,
+ * bit for bit what edet_jpeg_entropy_decode[_scaled] write.  What crosses the bus is the compressed scan, not its
+ * coefficients.  The per-unit code is one text for host and device (csrc/jpeg_entropy_impl.h); restated in
+ * tests/jpeg_entropy_ref.py.
+ * Segments and units.  A SEGMENT is the entropy-coded data of one restart interval (the whole scan without DRI) with the
+ * FF 00 stuffing removed, at a 4-byte aligned offset of the scan arena, zero-padded to a whole word.  A UNIT is one
+ * subsequence of subseq_bits bits (a multiple of 32 in 64 .. 8192) of one segment; the last may be shorter.
+ * The decoder's state at a bit position is (p, b, k): the bit, the block inside the MCU, the zigzag position (0: a DC symbol
+ * is next); (0, 0, 0) at a segment's start.  decode_unit(state, unit end) decodes whole symbols until p >= unit end and
+ * returns the end state and the blocks completed; an absent code, or one that runs past the segment, stops it at (segment
+ * end, 0, 0).  Round 0 decodes every unit from (unit start, 0, 0); in round r a unit whose predecessor's end state differs
+ * from the start state it last used decodes again from it; unit 0 of a segment starts from the truth, so after at most
+ * `units` rounds every unit starts where the serial decode passes, whatever the speculative units did.  A prefix sum of the
+ * completed blocks gives every unit its first block, segment j starts at block j restart_interval blocks_per_mcu, a last pass
+ * writes the AC values and the DC differences, and a segmented prefix sum per component (32-bit, wrapping; low 16 bits
+ * stored) turns the differences into the host stage's predictors. */
+#define EDET_JPEG_TABLES 6          /* derived Huffman tables per image: a DC and an AC table for each of three components */
+#define EDET_JPEG_TABLE_BYTES 2512  /* one of them: look uint16 [1024], mincode, count, valptr int32 [17], vals uint8 [256], pad */
+#define EDET_JPEG_UNIT_WORDS 8      /* uint32 words of device scratch per unit                                                */
+typedef struct edet_jpeg_segment { /* 16 bytes, one per restart interval */
+  uint32_t offset;               /* of its first byte in the scan arena, a multiple of 4                                    */
+  uint32_t length;               /* in bytes, stuffing removed; below 2^28                                                  */
+  uint32_t first_unit;           /* its first unit among the image's units                                                  */
+  uint32_t reserved;
+} edet_jpeg_segment_t;
+typedef struct edet_jpeg_scan { /* 64 bytes, one per image: written by edet_jpeg_scan_prepare, read from DEVICE memory */
+  int32_t status;                /* 0; edet_jpeg_entropy_device: EDET_JPEG_MALFORMED for a scan it refused                  */
+  int32_t first_segment, segments; /* the image's rows of the segment table: ceil(MCUs / restart_interval), or 1            */
+  int32_t first_unit, units;     /* the image's units of the unit scratch; the sum of its segments' units                   */
+  int32_t restart_interval;      /* MCUs per segment, 0: one segment                                                        */
+  int32_t mcus_w, mcus_h;        /* the file's MCU grid                                                                     */
+  int32_t blocks_per_mcu;        /* h_max v_max + 2, or 1                                                                   */
+  int32_t dc_table[3], ac_table[3]; /* per component: its slot 0 .. 5 among the image's tables                              */
+  int32_t rounds;                /* 0; edet_jpeg_entropy_device: the rounds it ran for this image (round 0 included)        */
+} edet_jpeg_scan_t;
+/* edet_jpeg_scan_prepare (host, blocks until done; no device call): edet_jpeg_entropy_decode_scaled's streams, canvas,
+ * max_denom, denoms, images_host, qtables_host, status and threads, and the same walk, frame check, scan check and Huffman
+ * table build, so every header-level refusal comes back here with the status it always had; the descriptors and
+ * quantisation tables are those of edet_jpeg_entropy_decode_scaled for the same batch (with max_denom 1 and denoms NULL:
+ * edet_jpeg_entropy_decode's, `reserved` 0), first_block placed against coef_capacity (int16 elements of the DEVICE arena)
+ * by the same rule.  Then one pass over the entropy-coded bytes per image, in parallel over images: copied into scan_host
+ * with the stuffing removed and cut into segments -- a segment ends at an FF that 00 does not follow, fill FFs are skipped,
+ * the marker behind segment j must be RST(j mod 8), else EDET_JPEG_MALFORMED; nothing behind the last segment is looked at.
+ * An image's room in scan_host is what is left of its file behind SOS plus 4 bytes per segment, rounded up to 16, so
+ * placement does not depend on the walk.  scans_host [batch], segments_host [segment_capacity] and tables_host [batch]
+ * [EDET_JPEG_TABLES][EDET_JPEG_TABLE_BYTES] (components that name one table share a slot; unused slots zero) are written;
+ * an image whose scan, segments or units do not fit scan_capacity (bytes, below 2^31), segment_capacity or unit_capacity is
+ * EDET_JPEG_TOO_LARGE.  A refused image has a zero descriptor, zero tables and a zero scan row.  A stream damaged INSIDE a
+ * segment is not found here: the device finds it.  used[3] receives the bytes of scan_host, the segments and the units in
+ * use.  Fails (-1) for what edet_jpeg_entropy_decode_scaled fails for, a bad subseq_bits or a scan_host not 4-byte aligned.
+ * edet_jpeg_entropy_device (device, one launch, one workgroup per image; every wait is a workgroup barrier): the arrays above
+ * in DEVICE memory -- scan_dev [scan_bytes], segments_dev [segment_count], tables_dev, scans_dev, images_dev -- -> coef, in
+ * the layout and with the values of the host stage: natural order, not dequantised, padding blocks included, the image's
+ * block range zeroed first.  units_dev: uint32 [unit_capacity][EDET_JPEG_UNIT_WORDS] scratch; dc_dev: uint16 [coef_capacity
+ * / 64] scratch.  An image whose descriptor carries a status is left alone.  A segment that completes fewer blocks than its
+ * share -- min(restart_interval, MCUs left) blocks_per_mcu -- makes its image EDET_JPEG_MALFORMED: images_dev[b].status and
+ * scans_dev[b].status are set (so the inverse DCT and colour kernels, launched behind this one, zero its canvas slot), its
+ * coefficients stay zero.  Blocks a segment decodes behind its share are dropped.  status_dev int32 [batch] receives every
+ * image's status.  Nothing is trusted: descriptors, segment rows and table entries are checked against the capacities passed
+ * here before they index anything, and an image that fails is EDET_JPEG_MALFORMED.  Loops: a unit decodes at most subseq_bits
+ * + 31 symbols; at most `units` rounds; every other loop runs over the image's units, segments, MCUs or blocks.  coef
+ * 16-byte aligned, scan_dev and the others 4-byte aligned; batch <= 65535. */
+int edet_jpeg_scan_prepare(const uint8_t* const* datas, const size_t* sizes, int batch, int canvas_h, int canvas_w,
+                           int max_denom, const int32_t* denoms, size_t coef_capacity, int subseq_bits, uint8_t* scan_host,
+                           size_t scan_capacity, edet_jpeg_segment_t* segments_host, size_t segment_capacity,
+                           size_t unit_capacity, uint8_t* tables_host, edet_jpeg_scan_t* scans_host,
+                           edet_jpeg_image_t* images_host, uint16_t* qtables_host, int32_t* status, size_t* used, int threads);
+int edet_jpeg_entropy_device(const uint8_t* scan_dev, size_t scan_bytes, const edet_jpeg_segment_t* segments_dev,
+                             size_t segment_count, const uint8_t* tables_dev, edet_jpeg_scan_t* scans_dev,
+                             edet_jpeg_image_t* images_dev, int batch, int subseq_bits, uint32_t* units_dev,
+                             size_t unit_capacity, uint16_t* dc_dev, int16_t* coef, size_t coef_capacity, int32_t* status_dev,
+                             void* stream);
+
 /* ---- TFRecord input (dataloader.py:404-460 reads TFRecord shards of tf.train.Example; object_detection/
  * tf_example_decoder.py:30-169 names the keys) -- HOST only, csrc/tfrecord_host.cpp: plain C++, no device call.  Every input
  * is a (pointer, length) pair into the caller's memory, every output a caller-allocated array with a stated capacity; nothing

@@ -19,6 +19,11 @@ grids and edet_jpeg_color_window (csrc/jpeg_window.hip): `--window` or `--window
 v2_preprocessing.sample_distorted_bounding_box from a fixed seed (at --ratio above 1: its covering output window),
 `--window whole` takes the whole image through the same path.  The canvas stays the whole output's size.  window_area is the
 mean share of the output's pixels the windows cover, kept_blocks the mean share of the file's blocks stored and copied.
+`--entropy device` measures JpegDecoder(entropy='device') on the same batch, full size only: host_ms is then
+edet_jpeg_scan_prepare (the marker walk and the byte-copy pass) at 1, 4 and 16 threads, copy_ms the copies of the scan arena,
+its segment, table and descriptor arrays, entropy_ms edet_jpeg_entropy_device alone at `--subseq_bits`, with `rounds` read
+back from the scan descriptors after the run; the other keys keep their meaning.  The host mode measured in the same run is
+the yardstick.
 No ratio between two timings is asserted: the numbers are the result."""
 import argparse
 import io
@@ -57,6 +62,85 @@ def events(fn, launches, reps):
   return stats(times)
 
 
+def main_device(args, data, rgb, h, w, out):
+  """--entropy device: the keys of main(), with edet_jpeg_scan_prepare as the host stage and the entropy kernel beside the two
+  others."""
+  b = args.batch
+  datas = [data] * b
+  dec = jpeg.JpegDecoder(b, h, w, threads=args.threads, depth=2, entropy='device', subseq_bits=args.subseq_bits,
+                         scan_bytes=b * ((len(data) + 79) // 16 * 16))
+  slot = dec._slots[0]
+  out['entropy'], out['subseq_bits'] = 'device', args.subseq_bits
+  used = None
+
+  def host_stage(threads):
+    return jpeg.scan_prepare(datas, h, w, 1, None, dec.blocks * 64, args.subseq_bits, slot.scan_host, slot.segments_host,
+                             slot.unit_capacity, slot.tables_host, slot.scans_host, slot.images_host, slot.qtables_host,
+                             slot.status, threads)
+  out['host_ms'] = {}
+  for threads in (1, 4, 16):
+    times = []
+    for _ in range(args.reps + 1):
+      t0 = time.perf_counter()
+      used = host_stage(threads)
+      times.append((time.perf_counter() - t0) * 1e3)
+    out['host_ms'][str(threads)] = dict(stats(times[1:]), images_per_s=round(b / (float(np.median(times[1:])) * 1e-3), 1))
+  assert not slot.status.any()
+  desc = jpeg.descriptors(slot.images_host, b)
+  most = max(d.total_blocks for d in desc)
+  nbytes, nseg = used[0], used[1] * jpeg.SEGMENT_BYTES
+  out['scan_bytes'], out['segments'], out['units'] = used
+  out['copied_bytes'] = nbytes + nseg + slot.tables_host.numel() + slot.scans_host.numel() + slot.images_host.numel() + \
+      slot.qtables_host.numel() * 2
+  out['blocks_per_image'] = most
+
+  def copy():
+    slot.scan[:nbytes].copy_(slot.scan_host[:nbytes], non_blocking=True)
+    slot.segments[:nseg].copy_(slot.segments_host[:nseg], non_blocking=True)
+    slot.tables.copy_(slot.tables_host, non_blocking=True)
+    slot.scans.copy_(slot.scans_host, non_blocking=True)
+    slot.images.copy_(slot.images_host, non_blocking=True)
+    slot.qtables.copy_(slot.qtables_host, non_blocking=True)
+  raw = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dec.device)
+  st = torch.cuda.current_stream().cuda_stream
+  copy()
+  torch.cuda.synchronize()
+  out['copy_ms'] = events(copy, 1, args.reps)
+  out['copy_GBps'] = round(out['copied_bytes'] / (out['copy_ms']['median_ms'] * 1e-3) / 1e9, 1)
+  out['entropy_ms'] = events(lambda: call('edet_jpeg_entropy_device', ptr(slot.scan), dec.scan_bytes, ptr(slot.segments),
+                                          dec.segments, ptr(slot.tables), ptr(slot.scans), ptr(slot.images), b, args.subseq_bits,
+                                          ptr(slot.units), slot.unit_capacity, ptr(slot.dc), ptr(slot.coef), dec.blocks * 64,
+                                          ptr(slot.scan_status), st), args.launches, args.reps)
+  rounds = [d.rounds for d in jpeg.scan_descriptors(slot.scans.cpu(), b)]
+  assert not slot.scan_status.cpu().numpy().any()
+  out['rounds'] = {'min': int(min(rounds)), 'max': int(max(rounds))}
+  out['units_per_image'] = used[2] // b
+  out['idct_ms'] = events(lambda: call('edet_jpeg_idct', ptr(slot.coef), ptr(slot.images), ptr(slot.qtables), b, most,
+                                       ptr(slot.planes), dec.blocks * 64, st), args.launches, args.reps)
+  out['color_ms'] = events(lambda: call('edet_jpeg_color', ptr(slot.planes), ptr(slot.images), b, h, w, dec.blocks * 64,
+                                        ptr(raw), st), args.launches, args.reps)
+  if rgb is not None:
+    assert np.array_equal(raw[b - 1].cpu().numpy(), rgb), 'the decoded batch differs from the fixture'
+  else:      # any other file: the host mode is the yardstick
+    want = jpeg.JpegDecoder(1, h, w, depth=1).decode([data])[0]
+    assert torch.equal(raw[b - 1], want[0]), 'the device entropy mode differs from the host mode'
+  sizes = np.zeros((b, 2), np.int32)
+  for _ in range(2):
+    dec.decode(datas, out=raw, sizes_out=sizes)
+  torch.cuda.synchronize()
+  times = []
+  for _ in range(args.reps):
+    t0 = time.perf_counter()
+    for _ in range(args.batches):
+      dec.decode(datas, out=raw, sizes_out=sizes)
+    torch.cuda.synchronize()
+    times.append((time.perf_counter() - t0) * 1e3 / args.batches)
+  assert not dec.scan_status().any()
+  out['end_to_end'] = dict(stats(times), threads=args.threads, depth=2, batches_per_rep=args.batches,
+                           images_per_s=round(b / (float(np.median(times)) * 1e-3), 1))
+  print(json.dumps(out))
+
+
 def main(args):
   if args.file:
     data = open(args.file, 'rb').read()
@@ -78,6 +162,11 @@ def main(args):
   file_blocks = jpeg.worst_blocks(h, w)
   h, w = jpeg.scaled_size(h, w, ratio)      # the canvas: the output, exactly
   out['canvas'] = [h, w]
+  if args.entropy == 'device':
+    if scaled:
+      sys.exit('--entropy device is measured at full size: no --ratio, --max_ratio or --window with it')
+    return main_device(args, data, rgb, h, w, out)
+  out['entropy'] = 'host'
   windows = None
   if args.window:
     from automl_amd import v2_preprocessing
@@ -196,6 +285,8 @@ if __name__ == '__main__':
   ap.add_argument('--window', nargs='?', const='sampled', default='', choices=['sampled', 'whole'],
                   help='decode a crop window of every image: sampled (sample_distorted_bounding_box, the default) or whole')
   ap.add_argument('--window_seed', type=int, default=0)
+  ap.add_argument('--entropy', default='host', choices=['host', 'device'], help="where the Huffman stage runs (JpegDecoder's entropy=)")
+  ap.add_argument('--subseq_bits', type=int, default=4096, help='--entropy device: the bits of a unit')
   ap.add_argument('--batch', type=int, default=128)
   ap.add_argument('--threads', type=int, default=16)
   ap.add_argument('--reps', type=int, default=7)
