@@ -190,6 +190,12 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p],
     'edet_box_loss_eval': [c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                            ctypes.c_size_t, c_int, c_void_p],
+    'edet_iou_loss': [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    'edet_box_iou_loss': [c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p,
+                          c_void_p, c_int64, c_int, c_float],
+    'edet_box_iou_loss_eval': [c_void_p, c_int, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                               ctypes.c_size_t, c_int, c_void_p, c_void_p, c_int64, c_int],
     'edet_l2_loss': [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p],
     'edet_opt_l2_norms': [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p],
     'edet_opt_clip_factors': [c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],

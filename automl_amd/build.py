@@ -10,7 +10,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.path.join(_HERE, 'libedet_hip.so')
 # Jobs start in this order.  dw_march.hip and mbconv_fused.hip take longest by far (40-50 s each): they stay among the first
 # eight, so that a machine with eight cores starts them at once.
-SOURCES = ['pw_gemm.hip', 'pw_big.hip', 'pw_glds.hip', 'pw_tile_bwd.hip', 'conv.hip', 'conv_halo.hip', 'dwconv.hip', 'dw_march.hip', 'mbconv_fused.hip', 'pw_stream_fwd.hip', 'pw_stream_dgrad.hip', 'pw_stream_wgrad.hip', 'pw_stream_fused.hip', 'stem.hip', 'bn.hip', 'se.hip', 'reduce.hip', 'fuse.hip', 'det_loss.hip', 'optimizer.hip', 'softmax_xent.hip', 'tensor_ops.hip', 'mix.hip', 'randaug.hip', 'crop_resize.hip', 'crop_bicubic.hip', 'mosaic.hip', 'gridmask.hip', 'det_autoaug.hip', 'coco_eval.hip', 'wbf.hip', 'det_eval.hip', 'postprocess.hip', 'labeling.hip', 'preprocess.hip', 'jpeg.hip', 'jpeg_scaled.hip', 'jpeg_window.hip', 'jpeg_entropy.hip', 'error.cpp', 'jpeg_host.cpp', 'tfrecord_host.cpp', 'plan_file.cpp', 'net_runtime.cpp']
+SOURCES = ['pw_gemm.hip', 'pw_big.hip', 'pw_glds.hip', 'pw_tile_bwd.hip', 'conv.hip', 'conv_halo.hip', 'dwconv.hip', 'dw_march.hip', 'mbconv_fused.hip', 'pw_stream_fwd.hip', 'pw_stream_dgrad.hip', 'pw_stream_wgrad.hip', 'pw_stream_fused.hip', 'stem.hip', 'bn.hip', 'se.hip', 'reduce.hip', 'fuse.hip', 'det_loss.hip', 'iou_loss.hip', 'optimizer.hip', 'softmax_xent.hip', 'tensor_ops.hip', 'mix.hip', 'randaug.hip', 'crop_resize.hip', 'crop_bicubic.hip', 'mosaic.hip', 'gridmask.hip', 'det_autoaug.hip', 'coco_eval.hip', 'wbf.hip', 'det_eval.hip', 'postprocess.hip', 'labeling.hip', 'preprocess.hip', 'jpeg.hip', 'jpeg_scaled.hip', 'jpeg_window.hip', 'jpeg_entropy.hip', 'error.cpp', 'jpeg_host.cpp', 'tfrecord_host.cpp', 'plan_file.cpp', 'net_runtime.cpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result']
 # files that restate float32 numpy / TensorFlow expressions operation by operation (argmax ties, 1e-6 parities):
@@ -21,7 +21,7 @@ EXTRA_FLAGS = {'labeling.hip': ['-ffp-contract=off'], 'preprocess.hip': ['-ffp-c
                'mosaic.hip': ['-ffp-contract=off'],
                'gridmask.hip': ['-ffp-contract=off'], 'det_autoaug.hip': ['-ffp-contract=off'],
                'coco_eval.hip': ['-ffp-contract=off'], 'wbf.hip': ['-ffp-contract=off'],
-               'det_eval.hip': ['-ffp-contract=off']}
+               'det_eval.hip': ['-ffp-contract=off'], 'iou_loss.hip': ['-ffp-contract=off']}
 
 
 def _stale(target, deps):

@@ -3,6 +3,7 @@
 //
 // Reference: efficientdet/tf2/train_lib.py:357-406 (FocalLoss), :409-437 (BoxLoss / Keras Huber),
 // :493-604 (_detection_loss), :686-732 (test_step).
+#include "iou_impl.h"
 #include "rowmap_impl.h"
 
 #include <cfloat>
@@ -205,28 +206,69 @@ __global__ __launch_bounds__(THREADS) void k_focal_eval(const T* __restrict__ lo
   focal_body<T, G15, LS, false>(logits, ld, tgt, positions, na, nc, alpha, gamma, inv_norm_h, norm_scale, nullptr, nullptr, sums, part, m, half_ls);
 }
 
-template <typename T, bool GRAD>
+// acc + v * s and acc + v * s1 * s2 with every product rounded (no contraction: the evaluation kernel's sum is the training
+// kernel's bit for bit, whatever else each instantiation computes)
+__device__ __forceinline__ float iou_add_scaled(float acc, float v, float s) {
+#pragma clang fp contract(off)
+  const float t = v * s;
+  return acc + t;
+}
+__device__ __forceinline__ float iou_add_scaled2(float acc, float v, float s1, float s2) {
+#pragma clang fp contract(off)
+  const float t = v * s1 * s2;
+  return acc + t;
+}
+
+// The IoU loss of a workgroup (box_body<.., IOU = true>): the loss_tail of a second sum, with an LDS array of its own so that
+// it may follow loss_tail without a barrier in between.  part: the workgroup's slot of the ordered partial column, else the
+// kernel runs as ONE workgroup and adds into the destination itself.
+__device__ __forceinline__ void iou_tail(float acc, float* part, float* sum_dst) {
+  __shared__ float wsum_iou[THREADS / 64];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((tid & 63) == 0) wsum_iou[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    float t = 0.f;
+    for (int w = 0; w < THREADS / 64; ++w) t += wsum_iou[w];
+    if (part) part[blockIdx.x] = t; else *sum_dst += t;
+  }
+}
+
+// What the IoU loss adds to the arguments of the box kernels (train_lib.py:440-464, :580-600): the level's first anchor row
+// [ymin, xmin, ymax, xmax] (row (p mod hw) * A + a belongs to position p, anchor a), the type (iou_impl.h), the weight of its
+// gradient and the partial column of its sum.
+struct IouArgs { const float* anchors; int64_t hw; int type; float grad_scale; float* part; };
+
+// IOU: the thread's 8-channel chunk is two whole anchors (j0 % 8 == 0, four channels each; j < nch cuts the last chunk to one
+// for an odd number of anchors).  Where some target component of an anchor is non-zero, iou_decoded adds its loss to a second
+// sum (sums[3]) and its gradient, times inv_norm * grad_scale, to the Huber gradient in fp32: dbox is rounded and written
+// once, dbias sums what was written.  IOU = false is the kernel as it was, instruction for instruction.
+template <typename T, bool GRAD, bool IOU = false>
 __device__ __forceinline__ void box_body(const T* out, int ld, const float* tgt, int64_t positions, int nch,
                                          float delta, float inv_norm_h, float grad_scale, const float* norm_scale,
-                                         T* dbox, float* dbias, float* sums, float* part, RowMap m) {
+                                         T* dbox, float* dbias, float* sums, float* part, RowMap m, IouArgs iou = IouArgs{}) {
   const float inv_norm = norm_scale ? inv_norm_h * norm_scale[0] : inv_norm_h;
   const int tid = threadIdx.x;
   const int cv = tid % m.tpr, rr = tid / m.tpr;
   const int j0 = cv * 8;
   const bool ok = j0 < ld;
-  float loss_acc = 0.f, db[8];
+  float loss_acc = 0.f, iou_acc = 0.f, db[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) db[e] = 0.f;
   if (ok) {
     for (int64_t p = (int64_t)blockIdx.x * m.rpp + rr; p < positions; p += (int64_t)gridDim.x * m.rpp) {
-      float x[8], g[8];
+      float x[8], g[8], tg[8];
       load8<T>(out + p * ld + j0, x);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int j = j0 + e;
         g[e] = 0.f;
+        if (IOU) tg[e] = 0.f;
         if (j < nch) {
           const float t = tgt[p * nch + j];
+          if (IOU) tg[e] = t;
           if (t != 0.f) {
             const float err = x[e] - t;
             const float ae = fabsf(err);
@@ -235,13 +277,37 @@ __device__ __forceinline__ void box_body(const T* out, int ld, const float* tgt,
             if (GRAD) g[e] = (quad ? err : (err > 0.f ? delta : -delta)) * inv_norm * grad_scale;
           }
         }
-        if (GRAD) db[e] += g[e];
+        if (GRAD && !IOU) db[e] += g[e];
+      }
+      if (IOU) {
+        const int64_t arow = (p % iou.hw) * (nch >> 2) + (j0 >> 2);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const float tq[4] = {tg[4 * q], tg[4 * q + 1], tg[4 * q + 2], tg[4 * q + 3]};
+          if (tq[0] != 0.f || tq[1] != 0.f || tq[2] != 0.f || tq[3] != 0.f) {      // (never true past nch: tg is 0 there)
+            const float4 av = *reinterpret_cast<const float4*>(iou.anchors + (arow + q) * 4);
+            const float a[4] = {av.x, av.y, av.z, av.w};
+            const float xq[4] = {x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
+            float dx[4];
+            const float l = iou_decoded<GRAD>(a, xq, tq, iou.type, dx);
+            iou_acc = iou_add_scaled(iou_acc, l, inv_norm);
+            if (GRAD) {
+#pragma unroll
+              for (int k = 0; k < 4; ++k) g[4 * q + k] = iou_add_scaled2(g[4 * q + k], dx[k], inv_norm, iou.grad_scale);
+            }
+          }
+        }
+        if (GRAD) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) db[e] += g[e];
+        }
       }
       if (GRAD) store8<T>(dbox + p * ld + j0, g);
     }
   }
   extern __shared__ float red[];  // [THREADS * 8]
   loss_tail<GRAD>(loss_acc, db, ok, nch, m, red, part, &sums[1], dbias);
+  if (IOU) iou_tail(iou_acc, iou.part, &sums[3]);
 }
 
 template <typename T>
@@ -260,6 +326,26 @@ __global__ __launch_bounds__(THREADS) void k_box_eval(const T* __restrict__ out,
   box_body<T, false>(out, ld, tgt, positions, nch, delta, inv_norm_h, 0.f, norm_scale, nullptr, nullptr, sums, part, m);
 }
 
+// the box kernels with the IoU loss fused in: one pass over the outputs and the targets, the Huber sum to sums[1] as k_box /
+// k_box_eval form it, the IoU sum to sums[3]
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_box_iou(const T* __restrict__ out, int ld,
+                                                    const float* __restrict__ tgt, int64_t positions, int nch,
+                                                    float delta, float inv_norm_h, float grad_scale,
+                                                    const float* __restrict__ norm_scale,
+                                                    T* __restrict__ dbox, float* dbias, float* sums, float* part, RowMap m,
+                                                    IouArgs iou) {
+  box_body<T, true, true>(out, ld, tgt, positions, nch, delta, inv_norm_h, grad_scale, norm_scale, dbox, dbias, sums, part, m, iou);
+}
+template <typename T>
+__global__ __launch_bounds__(THREADS) void k_box_iou_eval(const T* __restrict__ out, int ld,
+                                                         const float* __restrict__ tgt, int64_t positions, int nch,
+                                                         float delta, float inv_norm_h,
+                                                         const float* __restrict__ norm_scale, float* sums, float* part, RowMap m,
+                                                         IouArgs iou) {
+  box_body<T, false, true>(out, ld, tgt, positions, nch, delta, inv_norm_h, 0.f, norm_scale, nullptr, nullptr, sums, part, m, iou);
+}
+
 // inv_out[0] = 1 / (sum_i mean_num_positives[i] + 1): one wave, lanes in a fixed order (the counts are integers: exact)
 __global__ __launch_bounds__(64) void k_loss_normalizer(const float* __restrict__ mnp, int n, float* __restrict__ inv_out) {
   float s = 0.f;
@@ -274,7 +360,8 @@ __global__ __launch_bounds__(64) void k_loss_normalizer(const float* __restrict_
 // passes, at most `cap` workgroups; ordered partial rows [g][1 + nch] -- the TRAINING row width, whoever asks -- when the
 // workspace holds them, else ONE workgroup that adds into the destinations itself.
 struct LossGrid { RowMap m; int g; float* part; size_t lds; };
-inline LossGrid loss_grid(int ld, int64_t positions, int nch, int64_t cap, void* workspace, size_t workspace_bytes) {
+// extra: further one-float columns behind the g rows (the IoU sum of edet_box_iou_loss: g more floats).
+inline LossGrid loss_grid(int ld, int64_t positions, int nch, int64_t cap, void* workspace, size_t workspace_bytes, int extra = 0) {
   LossGrid L;
   L.m = row_map(ld);
   L.lds = (size_t)THREADS * 8 * sizeof(float);
@@ -282,7 +369,7 @@ inline LossGrid loss_grid(int ld, int64_t positions, int nch, int64_t cap, void*
   g = (g + 3) / 4;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
-  L.part = (workspace && workspace_bytes >= (size_t)g * (1 + nch) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
+  L.part = (workspace && workspace_bytes >= (size_t)g * (1 + nch + extra) * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
   L.g = L.part ? (int)g : 1;
   return L;
 }
@@ -422,6 +509,69 @@ extern "C" int edet_box_loss_eval(const void* box_out, int ld, const float* box_
   });
   if (L.part && edet_reduce_partials2(L.part, L.g, 1, nullptr, 0, &sums[1], to_stream(stream)) != 0) return -2;
   EDET_LAUNCH_CHECK("edet_box_loss_eval");
+  return 0;
+}
+
+// ---- the box loss with the IoU loss fused in (tf2/train_lib.py:440-464, :580-600).  The grid of edet_box_loss for the same
+// shape; the partial rows [nch | 1] of edet_box_loss followed by a column of g IoU sums, each added in row order by
+// edet_reduce_partials2: sums[1] and, with iou_grad_scale = 0, dbox and dbias are edet_box_loss's bit for bit.  A workspace too
+// small for rows and column: ONE workgroup.  No atomics anywhere.
+namespace {
+inline int iou_args_check(const char* who, const float* anchors, int64_t positions, int nch, int64_t hw, int iou_type) {
+  EDET_CHECK(anchors && ((uintptr_t)anchors & 15) == 0, "%s: anchors must be a 16-byte aligned device pointer", who);
+  EDET_CHECK(nch % 4 == 0, "%s: nch %d is no multiple of 4", who, nch);
+  EDET_CHECK(hw >= 1 && positions % hw == 0, "%s: positions %lld are no multiple of hw %lld", who, (long long)positions, (long long)hw);
+  EDET_CHECK(iou_type >= 0 && iou_type < IOU_TYPES, "%s: bad iou_type %d", who, iou_type);
+  return 0;
+}
+}  // namespace
+
+extern "C" int edet_box_iou_loss(const void* box_out, int ld, const float* box_targets,
+                                 int64_t positions, int nch, float delta, float inv_normalizer,
+                                 float grad_scale, const float* norm_scale_dev, void* dbox, float* dbias,
+                                 float* sums, void* workspace, size_t workspace_bytes, int dtype, void* stream,
+                                 const float* anchors, int64_t hw, int iou_type, float iou_grad_scale) {
+  EDET_CHECK(box_out && box_targets && dbox && sums, "edet_box_iou_loss: null pointer");
+  EDET_CHECK(ld % 8 == 0 && nch >= 1 && ld >= nch && ld <= 2048 && positions >= 0, "edet_box_iou_loss: bad ld %d", ld);
+  EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_box_iou_loss: bad dtype %d", dtype);
+  EDET_CHECK(delta > 0.f && delta <= FLT_MAX, "edet_box_iou_loss: delta %g must be positive and finite", (double)delta);
+  if (iou_args_check("edet_box_iou_loss", anchors, positions, nch, hw, iou_type) != 0) return -1;
+  if (positions == 0) return 0;
+  const LossGrid L = loss_grid(ld, positions, nch, BOX_GRID_CAP, workspace, workspace_bytes, 1);
+  float* part_iou = L.part ? L.part + (size_t)L.g * (1 + nch) : nullptr;
+  const IouArgs iou{anchors, hw, iou_type, iou_grad_scale, part_iou};
+  (void)dtype_dispatch(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    edet_launch(k_box_iou<T>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const T*)box_out, ld, box_targets, positions, nch, delta,
+                inv_normalizer, grad_scale, norm_scale_dev, (T*)dbox, dbias, sums, L.part, L.m, iou);
+  });
+  if (L.part && edet_reduce_partials2(L.part, L.g, 1 + nch, dbias, nch, &sums[1], to_stream(stream)) != 0) return -2;
+  if (L.part && edet_reduce_partials2(part_iou, L.g, 1, nullptr, 0, &sums[3], to_stream(stream)) != 0) return -2;
+  EDET_LAUNCH_CHECK("edet_box_iou_loss");
+  return 0;
+}
+
+extern "C" int edet_box_iou_loss_eval(const void* box_out, int ld, const float* box_targets,
+                                      int64_t positions, int nch, float delta, float inv_normalizer,
+                                      const float* norm_scale_dev, float* sums, void* workspace, size_t workspace_bytes,
+                                      int dtype, void* stream, const float* anchors, int64_t hw, int iou_type) {
+  EDET_CHECK(box_out && box_targets && sums, "edet_box_iou_loss_eval: null pointer");
+  EDET_CHECK(ld % 8 == 0 && nch >= 1 && ld >= nch && ld <= 2048 && positions >= 0, "edet_box_iou_loss_eval: bad ld %d", ld);
+  EDET_CHECK(dtype == EDET_BF16 || dtype == EDET_F32, "edet_box_iou_loss_eval: bad dtype %d", dtype);
+  EDET_CHECK(delta > 0.f && delta <= FLT_MAX, "edet_box_iou_loss_eval: delta %g must be positive and finite", (double)delta);
+  if (iou_args_check("edet_box_iou_loss_eval", anchors, positions, nch, hw, iou_type) != 0) return -1;
+  if (positions == 0) return 0;
+  const LossGrid L = loss_grid(ld, positions, nch, BOX_GRID_CAP, workspace, workspace_bytes, 1);
+  float* part_iou = L.part ? L.part + L.g : nullptr;
+  const IouArgs iou{anchors, hw, iou_type, 0.f, part_iou};
+  (void)dtype_dispatch(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    edet_launch(k_box_iou_eval<T>, dim3(L.g), dim3(THREADS), L.lds, to_stream(stream), (const T*)box_out, ld, box_targets, positions, nch,
+                delta, inv_normalizer, norm_scale_dev, sums, L.part, L.m, iou);
+  });
+  if (L.part && edet_reduce_partials2(L.part, L.g, 1, nullptr, 0, &sums[1], to_stream(stream)) != 0) return -2;
+  if (L.part && edet_reduce_partials2(part_iou, L.g, 1, nullptr, 0, &sums[3], to_stream(stream)) != 0) return -2;
+  EDET_LAUNCH_CHECK("edet_box_iou_loss_eval");
   return 0;
 }
 

@@ -39,6 +39,7 @@ class EfficientDetNet(object):
 
   MAX_ENGINES = 2      # activation buffers of that many (batch, image size) shapes stay allocated
   _lion = None         # optimizer='lion': {'beta_2':, 'wd':} for the engines (train_lib.EfficientDetNetTrain.set_lion)
+  _iou_loss = None     # (type, weight) of BoxIouLoss for the engines (train_lib.EfficientDetNetTrain.set_iou_loss)
 
   def _ensure_engine(self, batch, height, width):
     """The executor for this batch / image shape.  Buffers are per shape (static shapes); the variables, the
@@ -51,7 +52,8 @@ class EfficientDetNet(object):
       arena = self.engine.arena if self.engine is not None else None
       e = engine_lib.Engine(self.config, batch, (height, width), dtype=self._dtype, device=self._device,
                             seed=self._seed, params=self._init_params, stochastic_depth=self._stochastic_depth,
-                            arena=arena, **({'lion': self._lion} if self._lion else {}))
+                            arena=arena, **({'lion': self._lion} if self._lion else {}),
+                            **({'iou_loss': self._iou_loss} if self._iou_loss else {}))
       if self._init_ema and arena is None:
         e.arena.set_ema_params(self._init_ema)      # shadows restored before the model was built (util_keras.restore_ckpt)
         self._init_ema = None

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from automl_amd import _lib
+from automl_amd import iou_utils
 from automl_amd import netspec as netspec_lib
 from automl_amd._lib import ACT_NONE, ACT_SWISH, EDET_BF16, RS_IDENTITY, RS_POOL, RS_UP2, call, ptr
 from automl_amd.layer_engine import BN, LayerEngine, ParamArena, Raw, Update, View, capture_graph, lion_options  # noqa: F401
@@ -21,8 +22,14 @@ class Engine(LayerEngine):
   """Builds buffers for (config, batch, image size, dtype) and runs forward / backward / update."""
 
   def __init__(self, config, batch_size, image_size=None, dtype='bf16', device='cuda:0', seed=0,
-               params=None, spec=None, stochastic_depth=True, arena=None, lion=None):
+               params=None, spec=None, stochastic_depth=True, arena=None, lion=None, iou_loss=None):
     self.config = config
+    # iou_loss = (type, weight): BoxIouLoss (tf2/train_lib.py:440-464, :580-600) fused into the box-loss pass -- loss_backward and
+    # loss_only launch edet_box_iou_loss[_eval] in the place of edet_box_loss[_eval]; None: exactly the launches without it
+    self.iou_loss = None
+    if iou_loss is not None:
+      kind, weight = iou_loss
+      self.iou_loss = (iou_utils.iou_type_id(kind), str(kind), float(weight))
     # optimizer = 'adam' (train_lib.py:183-186: beta_1 = momentum, Keras defaults for what the reference does not set),
     # 'lion' (lion/lion_tf2.py's Lion in the optimizer's place: beta_1 = momentum by the same convention; beta_2 and wd are
     # no configuration keys and come in `lion`, a dict, with the reference's defaults), anything else Keras SGD
@@ -436,6 +443,7 @@ class Engine(LayerEngine):
     normalizer, norm_dev, levels = self._loss_front(labels, self.hyper[2:])
     na = self.spec.num_anchors
     ls = float(getattr(c, 'label_smoothing', 0.0) or 0.0)
+    anchors, anchor_row = (self._iou_anchors(), 0) if self.iou_loss is not None else (None, 0)
     for r, rb, ct, bt in levels:
       if ls:      # FocalLoss(label_smoothing), train_lib.py:400-402
         call('edet_focal_loss_smooth', ptr(r.data), r.ld, ptr(ct), r.rows, na, c.num_classes, c.alpha, c.gamma, ls,
@@ -448,9 +456,15 @@ class Engine(LayerEngine):
              ptr(self.loss_sums), *self._ws(), self.dtype, self.stream,
              nbytes=2 * r.rows * r.c * self.esize)
       r.grad_written = True
-      call('edet_box_loss', ptr(rb.data), rb.ld, ptr(bt), rb.rows, 4 * na, c.delta, 1.0 / (normalizer * 4.0),
-           float(c.box_loss_weight), norm_dev, ptr(rb.ensure_grad()), ptr(self.grad('box_net/box-predict/bias')),
-           ptr(self.loss_sums), *self._ws(), self.dtype, self.stream)
+      box_args = (ptr(rb.data), rb.ld, ptr(bt), rb.rows, 4 * na, c.delta, 1.0 / (normalizer * 4.0),
+                  float(c.box_loss_weight), norm_dev, ptr(rb.ensure_grad()), ptr(self.grad('box_net/box-predict/bias')),
+                  ptr(self.loss_sums), *self._ws(), self.dtype, self.stream)
+      if self.iou_loss is None:
+        call('edet_box_loss', *box_args)
+      else:
+        hw = rb.rows // self.batch
+        call('edet_box_iou_loss', *box_args, anchors.data_ptr() + 16 * anchor_row, hw, self.iou_loss[0], self.iou_loss[2])
+        anchor_row += hw * na
       rb.grad_written = True
     self.backward()
 
@@ -467,15 +481,45 @@ class Engine(LayerEngine):
     normalizer, norm_dev, levels = self._loss_front(labels, self.eval_inv_norm)
     na = self.spec.num_anchors
     ls = float(getattr(c, 'label_smoothing', 0.0) or 0.0)
+    anchors, anchor_row = (self._iou_anchors(), 0) if self.iou_loss is not None else (None, 0)
     for r, rb, ct, bt in levels:
       call('edet_focal_loss_eval', ptr(r.data), r.ld, ptr(ct), r.rows, na, c.num_classes, c.alpha, c.gamma, ls,
            1.0 / normalizer, norm_dev, ptr(sums), *self._ws(), _lib.EDET_F32 if r.data.dtype == torch.float32 else EDET_BF16,
            self.stream, nbytes=r.rows * r.c * r.data.element_size())
-      call('edet_box_loss_eval', ptr(rb.data), rb.ld, ptr(bt), rb.rows, 4 * na, c.delta, 1.0 / (normalizer * 4.0), norm_dev,
-           ptr(sums), *self._ws(), _lib.EDET_F32 if rb.data.dtype == torch.float32 else EDET_BF16, self.stream)
+      box_args = (ptr(rb.data), rb.ld, ptr(bt), rb.rows, 4 * na, c.delta, 1.0 / (normalizer * 4.0), norm_dev,
+                  ptr(sums), *self._ws(), _lib.EDET_F32 if rb.data.dtype == torch.float32 else EDET_BF16, self.stream)
+      if self.iou_loss is None:
+        call('edet_box_loss_eval', *box_args)
+      else:
+        hw = rb.rows // self.batch
+        call('edet_box_iou_loss_eval', *box_args, anchors.data_ptr() + 16 * anchor_row, hw, self.iou_loss[0])
+        anchor_row += hw * na
     seg_l2 = self.buf('eval:seg_l2', (self.nseg * _lib.OPT_SPLIT,), torch.float32)
     call('edet_l2_loss', ptr(self.params_flat), ptr(self.seg_offsets), ptr(self.seg_flags), self.nseg, float(c.weight_decay),
          ptr(seg_l2), sums.data_ptr() + 8, self.stream)
+
+  def _iou_anchors(self):
+    """The anchor table [sum over the levels of h * w * A, 4] fp32 of this engine's image size on its device, in the order
+    of anchors.Anchors.boxes (level, y, x, anchor): the cached table of postprocess._anchor_boxes.  A level's first row is
+    the running sum of h * w * A; every row of the box outputs is paired with its own anchor whatever the batch size."""
+    from automl_amd import postprocess
+    c = self.config
+    a = postprocess._anchor_boxes({'min_level': c.min_level, 'max_level': c.max_level, 'num_scales': c.num_scales,
+                                   'aspect_ratios': c.aspect_ratios, 'anchor_scale': c.anchor_scale,
+                                   'image_size': tuple(self.image_size)}, self.device)
+    rows = sum(bv.raw.rows // self.batch for bv in self.box_views) * self.spec.num_anchors
+    if a.shape[0] != rows:
+      raise ValueError('the IoU loss pairs %d box outputs per image with %d anchors' % (rows, a.shape[0]))
+    return a
+
+  def _with_iou(self, s, values):
+    """loss_values / eval_loss_values with the IoU loss on: 'box_iou_loss' = sums[3], folded into det_loss and loss
+    (train_lib.py:592-601); the values as they are with it off."""
+    if self.iou_loss is None:
+      return values
+    det = float(s.dtype.type(values['det_loss']) + s.dtype.type(self.iou_loss[2]) * s[3])
+    values.update({'box_iou_loss': float(s[3]), 'det_loss': det, 'loss': det + float(s[2])})
+    return values
 
   @property
   def eval_sums(self):
@@ -490,8 +534,8 @@ class Engine(LayerEngine):
     s = self.eval_sums.detach().cpu().numpy()
     c = self.config
     det = float(s[0] + c.box_loss_weight * s[1])
-    return {'cls_loss': float(s[0]), 'box_loss': float(s[1]), 'det_loss': det, 'reg_l2_loss': float(s[2]),
-            'loss': det + float(s[2])}
+    return self._with_iou(s, {'cls_loss': float(s[0]), 'box_loss': float(s[1]), 'det_loss': det, 'reg_l2_loss': float(s[2]),
+                              'loss': det + float(s[2])})
 
   def backward(self):
     """The base pass; with set_overlap_reduce, every range of the arena is handed to the reduce as soon as the tape entry
@@ -615,17 +659,30 @@ class Engine(LayerEngine):
     """LOSS_KEYS of a step on the device, for a caller that sums them over steps without reading them (train_lib's fit and
     evaluate): sums = loss_sums or eval_sums [cls, box, L2, -] -> out float32 [5], formed in float32 with the roundings
     loss_values makes on the host -- box_loss_weight * box rounded, then added to cls; det + L2 -- so a value read from
-    `out` is the float32 of the one loss_values reports.  Small torch launches on the current stream; nothing waits."""
+    `out` is the float32 of the one loss_values reports.  Small torch launches on the current stream; nothing waits.
+    With the IoU loss on, sums = [cls, box, L2, iou] and out is float32 [6] (loss_keys): iou_loss_weight * iou, rounded, is
+    added to det before L2 is, and the sixth entry is box_iou_loss."""
     torch.mul(sums[1:2], float(self.config.box_loss_weight), out=out[2:3])
     out[2:3].add_(sums[0:1])
     out[0:2].copy_(sums[0:2])
     out[3:4].copy_(sums[2:3])
+    if self.iou_loss is not None:      # out [6]: det += iou_loss_weight * box_iou_loss (rounded), the value itself last
+      torch.mul(sums[3:4], self.iou_loss[2], out=out[5:6])
+      out[2:3].add_(out[5:6])
+      torch.add(out[2:3], sums[2:3], out=out[4:5])
+      out[5:6].copy_(sums[3:4])
+      return out
     torch.add(out[2:3], sums[2:3], out=out[4:5])
     return out
+
+  @property
+  def loss_keys(self):
+    """The names of loss_vector's entries: LOSS_KEYS, and 'box_iou_loss' behind them with the IoU loss on."""
+    return self.LOSS_KEYS + (('box_iou_loss',) if self.iou_loss is not None else ())
 
   def loss_values(self):
     s = self.loss_sums.detach().cpu().numpy()
     c = self.config
     det = float(s[0] + c.box_loss_weight * s[1])
-    return {'cls_loss': float(s[0]), 'box_loss': float(s[1]), 'det_loss': det, 'reg_l2_loss': float(s[2]),
-            'loss': det + float(s[2]), 'gradient_norm': float(self.gnorm.item())}
+    return self._with_iou(s, {'cls_loss': float(s[0]), 'box_loss': float(s[1]), 'det_loss': det, 'reg_l2_loss': float(s[2]),
+                              'loss': det + float(s[2]), 'gradient_norm': float(self.gnorm.item())})

@@ -730,6 +730,11 @@ def record_network(net, images, labels=None, path='efficientdet.plan', learning_
   with (torch.cuda.use_mem_pool(pool) if fresh else contextlib.nullcontext()):
     eng = net._ensure_engine(b, h, w)
     assert eng.sync_bn is None and eng._overlap_reduce is None, 'plans record the default step structure'
+    # The recorder takes any entry point a pass calls, by its ctypes signature: edet_box_iou_loss would be recorded without a
+    # word, with the cached anchor table as one more buffer that neither the network-level C ABI nor the plan tests know of.
+    if getattr(eng, 'iou_loss', None) is not None:
+      raise ValueError('recording a plan of a model with the IoU loss on (set_iou_loss) is not built: plans record the '
+                       'detection loss without BoxIouLoss')
     images = net._to_device_images(images, eng)
     dl = None
     if labels is not None:

@@ -77,7 +77,20 @@ def define_flags():
   ap.add_argument('--lion_beta2', type=float, default=None, help='--hparams=optimizer=lion: beta_2 (default 0.99)')
   ap.add_argument('--lion_wd', type=float, default=None,
                   help='--hparams=optimizer=lion: the decoupled weight decay wd (default 0), on every variable')
+  ap.add_argument('--iou_loss_type', default=None, choices=['iou', 'giou', 'diou', 'ciou'],
+                  help='adds BoxIouLoss of this type to the detection loss (not --hparams=iou_loss_type, which is refused)')
+  ap.add_argument('--iou_loss_weight', type=float, default=None,
+                  help='--iou_loss_type: its weight in det_loss (default: the configuration key iou_loss_weight, 1.0)')
   return ap
+
+
+def iou_loss_of(flags):
+  """--iou_loss_type / --iou_loss_weight -> EfficientDetNetTrain's `iou_loss` keyword; a weight without a type is refused."""
+  if flags.iou_loss_type is None:
+    if flags.iou_loss_weight is not None:
+      raise ValueError('--iou_loss_weight needs --iou_loss_type')
+    return None
+  return {'type': flags.iou_loss_type, 'weight': flags.iou_loss_weight}
 
 
 def lion_of(flags, config):
@@ -172,7 +185,8 @@ def main(argv=None):
   steps_per_epoch = config.steps_per_epoch
   model = train_lib.EfficientDetNetTrain(config=config, dtype=flags.dtype, seed=flags.tf_random_seed or 0,
                                          steps_per_epoch=steps_per_epoch, global_batch_size=flags.batch_size,
-                                         use_graph=not flags.debug, lion=lion_of(flags, config))
+                                         use_graph=not flags.debug, lion=lion_of(flags, config),
+                                         iou_loss=iou_loss_of(flags))
   latest = tf_checkpoint.latest_checkpoint(flags.model_dir) if os.path.isdir(flags.model_dir) else None
 
   if flags.mode == 'eval':

@@ -24,6 +24,7 @@ from automl_amd import det_autoaugment
 from automl_amd import det_input
 from automl_amd import efficientdet_net
 from automl_amd import engine as engine_lib
+from automl_amd import iou_utils
 from automl_amd import layer_engine
 from automl_amd import utils
 
@@ -144,18 +145,22 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
   """
 
   def __init__(self, *args, steps_per_epoch=1000, global_batch_size=None, process_group=None,
-               use_dist=False, use_graph=False, sync_bn=False, overlap_grad_reduce=None, lion=None, **kwargs):
+               use_dist=False, use_graph=False, sync_bn=False, overlap_grad_reduce=None, lion=None, iou_loss=None,
+               **kwargs):
     """use_graph: capture the whole step (forward, loss, backward, L2/clip, update: ~1600 kernel launches)
     into a hipGraph at the second call for a given batch shape and replay it afterwards; inputs are
     copied into static device buffers (input_buffers() exposes them for in-place filling), learning
     rate / EMA decay / loss normalizer travel through a small device vector.  With data parallelism the
     gradient all-reduce stays an eager RCCL call between two captured halves.
     lion: with config.optimizer = 'lion', dict(beta_2=0.99, wd=0.0) -- lion_tf2.Lion's two arguments that are no
-    configuration keys (see set_lion)."""
+    configuration keys (see set_lion).
+    iou_loss: dict(type='ciou', weight=None) -- BoxIouLoss added to the detection loss (see set_iou_loss)."""
     super().__init__(*args, **kwargs)
     self._check_training_options(self.config)
     if lion is not None:
       self.set_lion(**lion)
+    if iou_loss is not None:
+      self.set_iou_loss(**iou_loss)
     # sync_bn: cross-replica BatchNorm statistics (the reference's --strategy=gpus / tpu BatchNorm classes,
     # utils.py:166-266): two small all-reduces per BatchNorm layer and step, eager launches only.
     self.sync_bn = sync_bn
@@ -227,6 +232,31 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
                                            current.get('wd', layer_engine.LION_WD))
     self._lion = {'beta_2': beta_2, 'wd': wd}
 
+  def set_iou_loss(self, type, weight=None):      # pylint: disable=redefined-builtin
+    """Switches BoxIouLoss (tf2/train_lib.py:440-464, :580-600) on: type 'iou', 'giou', 'diou' or 'ciou' (iou_utils.py), added to
+    det_loss with `weight` (None: config.iou_loss_weight, 1.0) and reported as 'box_iou_loss'; type=None switches it off.
+    The configuration key iou_loss_type keeps raising: this is its switch.  Every row of the box outputs is decoded with its own
+    anchor; the gradient is the reference's as TensorFlow executes it (CIoU's v is a constant of the backward pass).  The
+    type and the weight are arguments of launches an engine makes (and of a step it has captured), so once an engine exists
+    they are fixed: build a new model for other values."""
+    if self.engine is not None:
+      raise ValueError('set_iou_loss after the first engine was made: the type and the weight are arguments of the loss kernels '
+                       'it launches (and of a step it has captured); set them before the first step, or build a new model')
+    if type is None:
+      self._iou_loss = None
+      return
+    iou_utils.iou_type_id(type)      # an unknown type raises the reference's message
+    if weight is None:
+      weight = getattr(self.config, 'iou_loss_weight', 1.0)
+    weight = float(weight)
+    if not np.isfinite(weight):
+      raise ValueError('set_iou_loss: weight %r is not finite' % (weight,))
+    self._iou_loss = (str(type), weight)
+
+  def _loss_keys(self):
+    """Engine.LOSS_KEYS, and 'box_iou_loss' behind them with the IoU loss on (Engine.loss_keys, without an engine)."""
+    return engine_lib.Engine.LOSS_KEYS + (('box_iou_loss',) if self._iou_loss is not None else ())
+
   @property
   def update(self):
     """The update description of this model's engines (layer_engine.Update), from the configuration alone: no device."""
@@ -274,10 +304,13 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
   @staticmethod
   def _check_training_options(c):
     """The train step here is the reference's default one (train_lib.py:606-684 with the d0..d7x settings); options
-    that would change its arithmetic and are not built raise instead of being ignored."""
+    that would change its arithmetic and are not built raise instead of being ignored.  BoxIouLoss itself is built, behind the
+    constructor's iou_loss= and set_iou_loss: the configuration key iou_loss_type is not its switch and keeps raising."""
     unsupported = []
     if getattr(c, 'iou_loss_type', None):
-      unsupported.append('iou_loss_type=%r (BoxIouLoss, train_lib.py:440-466)' % c.iou_loss_type)
+      unsupported.append('iou_loss_type=%r as a configuration key (BoxIouLoss, train_lib.py:440-466, is switched on with '
+                         'EfficientDetNetTrain(..., iou_loss=dict(type=%r)) or set_iou_loss; train.py: --iou_loss_type)'
+                         % (c.iou_loss_type, c.iou_loss_type))
     if str(getattr(c, 'optimizer', 'sgd')).lower() not in ('sgd', 'adam', 'lion'):
       unsupported.append("optimizer=%r (the reference has 'sgd' and 'adam', train_lib.py:180-188; 'lion' is lion/lion_tf2.py's)"
                          % c.optimizer)
@@ -720,7 +753,8 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
     in-place add into the accumulator, in step order.  first: the accumulator starts at zero.  Nothing is read."""
     if name not in self._loss_acc:
       dev = sums.device
-      self._loss_acc[name] = (torch.zeros(5, dtype=torch.float32, device=dev), torch.zeros(5, dtype=torch.float32, device=dev))
+      n = len(self._loss_keys())
+      self._loss_acc[name] = (torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev))
     acc, vec = self._loss_acc[name]
     if first:
       acc.zero_()
@@ -734,11 +768,11 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
   def _mean_losses(self, acc, steps, prefix=''):
     """Keras' Mean: total / count, both float32, the total summed on the device in step order."""
     mean = self._read_losses(acc) / np.float32(steps)
-    return {prefix + k: float(mean[i]) for i, k in enumerate(engine_lib.Engine.LOSS_KEYS)}
+    return {prefix + k: float(mean[i]) for i, k in enumerate(self._loss_keys())}
 
   def evaluate(self, x, steps=None):
     """tf.keras.Model.evaluate over test_step: x = an iterable of the raw batches test_step_raw takes; -> the means of its five
-    values over `steps` batches (all of them for None), accumulated on the device and read ONCE, at the end.  Like test_step
+    values (six with the IoU loss on: box_iou_loss) over `steps` batches (all of them for None), accumulated on the device and read ONCE, at the end.  Like test_step
     it moves nothing of the training state."""
     acc, n = None, 0
     for batch in x:
@@ -760,7 +794,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
 
     The loop does not wait for the device per step.  After a step its loss values are added, on the step's stream, into a
     float32 device accumulator (_accumulate); the epoch's logs are accumulator / steps in float32 -- Keras' Mean with the sum
-    in step order -- for loss, cls_loss, box_loss, det_loss, reg_l2_loss, plus learning_rate of the last step.  The waits
+    in step order -- for loss, cls_loss, box_loss, det_loss, reg_l2_loss (and box_iou_loss with the IoU loss on), plus learning_rate of the last step.  The waits
     are the reader's arena event, the one read at the end of an epoch, a batch-level callback that ACCESSES a device value of
     its logs (LazyLogs: the running means of the epoch), and a checkpoint.
 
@@ -798,7 +832,7 @@ class EfficientDetNetTrain(efficientdet_net.EfficientDetNet):
         acc = self._accumulate('fit', self.engine.loss_sums, steps == 0)
         steps += 1
         if batch_level:
-          blogs = LazyLogs({'learning_rate': lr, 'step': self.iterations}, engine_lib.Engine.LOSS_KEYS,
+          blogs = LazyLogs({'learning_rate': lr, 'step': self.iterations}, self._loss_keys(),
                            lambda acc=acc, steps=steps: self._mean_losses(acc, steps))
           for fn in batch_level:
             fn(steps - 1, blogs)
@@ -958,6 +992,21 @@ def lion_difference(theirs, mine):
   return ['lion %s %r, this model %r' % (k, theirs.get(k), mine[k]) for k in ('beta_2', 'wd') if theirs.get(k) != mine[k]]
 
 
+def iou_loss_identity(model):
+  """What a training-state file carries of the IoU loss: {'type':, 'weight':}; None with it off (and the file is as without)."""
+  iou = getattr(model, '_iou_loss', None)
+  return {'type': iou[0], 'weight': float(iou[1])} if iou else None
+
+
+def iou_loss_difference(theirs, mine):
+  """The differences between a file's 'iou_loss' entry and this model's, worded for restore_train_state's refusal."""
+  if theirs == mine:
+    return []
+  if theirs is None or mine is None:
+    return ['iou_loss %r, this model %r' % (theirs, mine)]
+  return ['iou_loss %s %r, this model %r' % (k, theirs.get(k), mine[k]) for k in ('type', 'weight') if theirs.get(k) != mine[k]]
+
+
 def save_train_state(model, path, reader=None):
   """Writes <ckpt prefix>.train_state.npz next to a checkpoint: get_optimizer_state() in full (velocity, ema, the second slot
   under its key, iterations, moving_normalizer, input_rng_state), the stochastic-depth generator's state of every engine the
@@ -969,6 +1018,8 @@ def save_train_state(model, path, reader=None):
   meta.update(_model_identity(model))
   if meta['optimizer'] == 'lion':
     meta['lion'] = lion_identity(model.update)
+  if iou_loss_identity(model) is not None:
+    meta['iou_loss'] = iou_loss_identity(model)
   for k, v in state.items():
     if k in _SLOT_KEYS or k == 'input_rng_state':
       arrays[k] = np.asarray(v)
@@ -1013,6 +1064,8 @@ def restore_train_state(model, path, reader=None):
           if meta.get(k) != mine[k]]
   if not diff and mine['optimizer'] == 'lion':
     diff = lion_difference(meta.get('lion'), lion_identity(model.update))
+  if not diff:
+    diff = iou_loss_difference(meta.get('iou_loss'), iou_loss_identity(model))
   if diff:
     raise ValueError('%s is the training state of another model: the file has %s' % (path, '; '.join(diff)))
   state = {k: arrays[k] for k in _SLOT_KEYS + ('input_rng_state',) if k in arrays}

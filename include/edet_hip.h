@@ -447,6 +447,38 @@ int edet_box_loss_eval(const void* box_out, int ld, const float* box_targets,
 int edet_l2_loss(const float* params, const int64_t* seg_offsets, const int32_t* seg_flags, int nseg,
                  float weight_decay, float* seg_l2, float* l2_out, void* stream);
 
+/* ---- the IoU / GIoU / DIoU / CIoU box loss (efficientdet/iou_utils.py; train_lib.py:440-464, :580-600) --------------------
+ * iou_type: 0 iou, 1 giou, 2 diou, 3 ciou.  The gradient is the reference's as TensorFlow executes it: the aspect-ratio term v
+ * of ciou is a constant of the backward pass (its tf.custom_gradient reaches the target's size only), alpha is differentiated
+ * through iou; ties of maximum / minimum go to the first argument as the reference writes them; divide_no_nan has zero
+ * gradient where its denominator is 0; squared lengths are sums of squares (zero gradient at the zero vector).
+ *
+ * edet_iou_loss: iou_utils.iou_loss on decoded fp32 boxes [rows][k][ymin, xmin, ymax, xmax] (16-byte aligned):
+ * loss_out[r] = sum over the k anchors of m * (1 - metric), m = the target has positive height and width;
+ * dpred_out (may be NULL) [rows][4k] = d loss_out[r] / d pred_boxes[r].  One launch.
+ *
+ * edet_box_iou_loss / edet_box_iou_loss_eval: edet_box_loss / edet_box_loss_eval with the IoU loss fused into the same pass.
+ * anchors: the level's first anchor row [ymin, xmin, ymax, xmax] fp32 (16-byte aligned), row (p mod hw) * (nch / 4) + a for
+ * position p and anchor a; hw divides positions.  The outputs and the targets of an anchor are decoded with that anchor
+ * (anchors.py:30-58), each decoded coordinate of both boxes times (its raw target component != 0); an anchor whose four targets
+ * are 0 does no arithmetic.  sums[3] += sum of the anchors' losses * inv_normalizer [* norm_scale_dev[0]]; sums[1] as
+ * edet_box_loss, bit for bit.  dbox = Huber gradient * inv_norm * grad_scale + IoU gradient * inv_norm * iou_grad_scale, added
+ * in fp32 and rounded to the storage type once; dbias += its column sums.  With iou_grad_scale = 0 and finite inputs dbox and
+ * dbias are edet_box_loss's bit for bit.  The grid of edet_box_loss; workspace: [workgroups][1 + nch] + [workgroups] floats,
+ * else ONE workgroup.  No atomics: the same bits on every run.  edet_box_iou_loss_eval adds to sums[1] and sums[3] what
+ * edet_box_iou_loss adds, bit for bit, and writes nothing else.  */
+int edet_iou_loss(const float* pred_boxes, const float* target_boxes, int64_t rows, int k, int iou_type,
+                  float* loss_out, float* dpred_out, void* stream);
+int edet_box_iou_loss(const void* box_out, int ld, const float* box_targets,
+                      int64_t positions, int nch, float delta, float inv_normalizer,
+                      float grad_scale, const float* norm_scale_dev, void* dbox, float* dbias, float* sums,
+                      void* workspace, size_t workspace_bytes, int dtype, void* stream,
+                      const float* anchors, int64_t hw, int iou_type, float iou_grad_scale);
+int edet_box_iou_loss_eval(const void* box_out, int ld, const float* box_targets,
+                           int64_t positions, int nch, float delta, float inv_normalizer,
+                           const float* norm_scale_dev, float* sums, void* workspace, size_t workspace_bytes,
+                           int dtype, void* stream, const float* anchors, int64_t hw, int iou_type);
+
 /* ---- EfficientNetV2 classifier loss and head dropout (efficientnetv2/main_tf2.py:89-117,199-207) ----
  * edet_softmax_xent: tf.keras.losses.CategoricalCrossentropy(label_smoothing, from_logits=True) with the default mean over
  * the batch (main_tf2.py:201-202), its gradient, and the counts behind TopKCategoricalAccuracy(k=1) / (k=5) (:203-206), in
